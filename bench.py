@@ -11,7 +11,11 @@ state_dict surface (pretrained 003_cracker_box weights are not available offline
 N>1: weak scaling, 64 pairs per GPU, weights broadcast once from rank 0 over RCCL.  `python bench.py --gpus N`
 launches its own N ranks (torch.distributed.run, one per GPU) when it is not already running under a launcher.
 
-The JSON line carries, besides the contract fields:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times exactly K steps of the headline path
+(two lanes, see --streams) and prints the result line: metric, value, unit, ms_per_step, higher_is_better, dtype and the
+configuration.  `--dump-outputs DIR` writes what the last timed step computed (trans.npy, rot.npy float32; pose.npy float64).
+Everything else is measured only with `--full`; the JSON line then also carries:
+  single_stream the same steps strictly one after the other on one stream (re-run with more steps if shorter than 1 s)
   roofline      executed MFMA flops of the 3x3 conv family / its HIP-event time / 157.3 TF (frac <= 1); the
                 algorithmic (direct-convolution) rate is reported beside it as effective_vs_direct
   parity        the TIMED batch checked against the CPU oracle: all pairs, pre-processing bit-exact, (trans, rot)
@@ -21,8 +25,9 @@ The JSON line carries, besides the contract fields:
                 synthetic tracking problem with ground truth and trained stand-in weights, under both normaliser regimes -- ADD / ADD-S
                 AUC of both tracks -- and 300 on the random-init stand-in, each with the oracle-vs-itself control)
   cpu_baseline  the oracle timed on this box's host cores (bounded sample)
+  alt_precision / alt_algorithm   the f16x3 mode and the direct kernels on the same inputs
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--stage full|net]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--stage full|net] [--dump-outputs DIR] [--full]
 """
 import argparse
 import contextlib
@@ -30,6 +35,7 @@ import json
 import math
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -45,7 +51,8 @@ NET_TOL, POSE_TOL = 1e-4, 1e-5        # north-star tolerances (BASELINE.json)
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` outside a launcher: become `torch.distributed.run --nproc-per-node N bench.py ...`."""
+    """`python bench.py --gpus N` outside a launcher: run `torch.distributed.run --nproc-per-node N bench.py ...` as a child
+    process and exit with its status."""
     import torch
     ndev = torch.cuda.device_count()
     if ndev < args.gpus and not args.dry_run_gloo:
@@ -60,7 +67,7 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % args.gpus,
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -101,8 +108,15 @@ def main():
                          "default: those tracks are unrelated after 5-20 frames whatever the implementation (1,000 frames x 3 seeds x every "
                          "control: profiles/r06_free_run.json)")
     ap.add_argument("--exact-steps", action="store_true",
-                    help="never extend the timed region beyond --steps (default: a region shorter than 1 s is re-run "
-                         "with enough steps and BOTH are reported)")
+                    help="--full: never extend the single-stream region beyond --steps (default: a region shorter than 1 s is "
+                         "re-run with enough steps and BOTH are reported; the headline always times exactly --steps steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: single-stream region, roofline and per-launch "
+                         "times, oracle parity, pipelined verification, the f16x3 and direct-kernel legs, cpu_baseline, track, "
+                         "tracker_batch (the --no-* / --track-frames / --free-frames options select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/{trans,rot}.npy (float32) "
+                         "and DIR/pose.npy (float64), rank 0")
     ap.add_argument("--layers", action="store_true", help="print the per-launch time breakdown to stderr")
     ap.add_argument("--dry-run-gloo", action="store_true",
                     help="NOT a measurement: the same self-launch, rank logic, barriers, weight-blob broadcast (the real packed "
@@ -236,6 +250,7 @@ def main():
         eng.preprocess(cropsA, inA); eng.preprocess(cropsB, inB)
 
     pending = []   # [(gathered poses, work)] of the previous step
+    last_pose = [poseB]   # the pose buffer the latest single-stream step wrote
 
     def step():
         if args.stage == "full":
@@ -258,6 +273,7 @@ def main():
         # C2, overlapped: step k writes pose buffer k % 2; its all-gather runs on the RCCL stream while
         # step k+1 computes into the other buffer; the gather of step k-1 is retired first
         buf = poseB if len(pending) == 0 or pending[-1][2] is poseB_alt else poseB_alt
+        last_pose[0] = buf
         eng.infer(inA, inB, nb, se3.NHWC, trans, rot, poseA, buf)
         while pending:
             pending.pop(0)[1].wait()
@@ -300,17 +316,19 @@ def main():
     def timed_region(steps):
         """Warm-up is done by the caller.  Times exactly `steps` steps; if that region is shorter than
         MIN_TIMED_SECONDS it is timed AGAIN with enough steps to exceed it (every rank takes the same decision from
-        the max-over-ranks time).  Returns (dt, steps_timed, short) with short = (dt, steps) of the first region or None."""
+        the max-over-ranks time).  Returns (dt, steps_timed, short, slots, first) with short = (dt, steps) of the first region
+        or None and first = (dt, this rank's time) of the first region: exactly `steps` steps."""
         slots = min(steps, 64)
         eng.profile_enable(slots)
         dt = timed_loop(steps)
+        first = (dt, local_dt[0])
         if args.exact_steps or dt >= min_timed:
-            return dt, steps, None, slots
+            return dt, steps, None, slots, first
         more = min(20000, int(math.ceil(steps * min_timed * 1.1 / dt)))
         slots = min(more, 64)
         eng.profile_enable(slots)
         dt2 = timed_loop(more)
-        return dt2, more, (dt, steps), slots
+        return dt2, more, (dt, steps), slots, first
 
     # ---- throughput mode: successive steps alternate over the lanes of the PipelinedEngine --------------------------
     lane_out = [(torch.empty((nb, 3), device=dev), torch.empty((nb, 3), device=dev), torch.empty_like(poseA)) for _ in range(lanes)]
@@ -365,15 +383,84 @@ def main():
             dtp = float(t_.item())
         return dtp
 
-    for _ in range(args.warmup):
-        step()
-    dt, steps_timed, short, slots = timed_region(args.steps)
-    per_rank = [nb * steps_timed / local_dt[0]]
-    if use_dist:
-        t = torch.tensor([per_rank[0]], dtype=torch.float64, device=dev)
+    def rates_of_ranks(rate):
+        """this rank's pairs/s -> every rank's, in rank order"""
+        if not use_dist:
+            return [rate]
+        t = torch.tensor([rate], dtype=torch.float64, device=dev)
         allr = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(allr, t)
-        per_rank = [float(x.item()) for x in allr]
+        return [float(x.item()) for x in allr]
+
+    def host_copies(outs):
+        """what a step computed, (trans, rot, pose), as host arrays"""
+        sync()
+        return [x.detach().cpu().numpy() for x in outs]
+
+    def result_line(dt_h, per_rank_h, outs_h):
+        """the headline fields of the JSON line: exactly --steps steps timed in dt_h seconds (rank 0 prints it)"""
+        assert os.environ.get("SE3TN_NOCHECK") or all(np.isfinite(x).all() for x in outs_h), "non-finite outputs"
+        if args.dump_outputs:
+            dump_outputs(np, args.dump_outputs, outs_h)
+        value = world * nb * args.steps / dt_h
+        out = {
+            "metric": "RGB-D pair inferences/sec (176x176)", "value": round(value, 1), "unit": "pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt_h / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+            "steps_timed": args.steps, "timed_seconds": round(dt_h, 4),
+            # `value`: K complete steps of one batch each, successive steps alternating over `lanes` HIP streams / activation
+            # workspaces (PipelinedEngine) -- throughput of the job, not 1 / latency of a step.  With --full, `single_stream`: the
+            # same steps strictly one after the other on one stream; the roofline / layers_ms blocks are measured in THAT region
+            # (kernel durations undisturbed by a concurrent lane).
+            "steps_in_flight": lanes if pipelined_headline else 1,
+            "config": {"workload": "configs[1]: batch=%d synthetic 176x176 RGB-D pairs per GPU, random-init Se3TrackNet "
+                                   "(reference state_dict surface), stage=%s" % (nb, args.stage),
+                       "pairs_per_gpu": nb, "global_batch": world * nb, "stage": args.stage,
+                       "frames": "pinned host memory, uploaded per step (PCIe-inclusive)" if args.host_frames else "resident in HBM",
+                       "parallelism": "frame-sharded x%d, RCCL weight broadcast at start-up, pose all-gather %s; per GPU the steps "
+                                      "alternate over %d HIP stream(s)" %
+                                      (world, "every step (overlapped)" if args.gather_every_step else "once per timed region", lanes)},
+            "rccl_ranks": dist.get_world_size() if use_dist else 1,
+            "backend": dist.get_backend() if use_dist else None,
+            "per_rank_pairs_per_s": [round(v, 1) for v in per_rank_h],
+            "tflops_total": round(value * FLOP_PER_PAIR / 1e12, 2),
+        }
+        if DRY:
+            out["dry_run"] = ("gloo on CPU, every kernel stubbed out: `value`, `roofline` and `layers_ms` are NOT measurements; this "
+                              "line only shows that the N-rank launch, broadcast, gather and reporting path runs")
+        return out
+
+    # the headline: exactly --steps steps, pipelined over the lanes when there are several, else one step after the other
+    pipelined_headline = lanes > 1 and args.stage == "full"
+    if not args.full:
+        if pipelined_headline:
+            for _ in range(max(args.warmup, 2 * lanes)):
+                step_pipelined()
+            dt_h = timed_loop_pipelined(args.steps)
+            outs_h = lane_out[last_lane[0]]
+        else:
+            for _ in range(args.warmup):
+                step()
+            dt_h = timed_loop(args.steps)
+            outs_h = (trans, rot, last_pose[0])
+        per_rank_h = rates_of_ranks(nb * args.steps / local_dt[0])
+        outs_h = host_copies(outs_h)
+        if rank == 0:
+            print(json.dumps(result_line(dt_h, per_rank_h, outs_h)))
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: the single-stream region (roofline, parity), then the headline region and the other legs ----
+    for _ in range(args.warmup):
+        step()
+    dt, steps_timed, short, slots, first = timed_region(args.steps)
+    per_rank = rates_of_ranks(nb * steps_timed / local_dt[0])
+    if not pipelined_headline:
+        dt_h, per_rank_h = first[0], rates_of_ranks(nb * args.steps / first[1])
+        outs_h = host_copies((trans, rot, last_pose[0]))
 
     dry_checks = None
     if DRY and use_dist:
@@ -468,17 +555,13 @@ def main():
 
     # ---- the headline when lanes > 1: the same steps pipelined over the lanes (each step is still one batch of nb pairs) ----
     pipelined = None
-    if lanes > 1 and args.stage == "full":
+    if pipelined_headline:
         for _ in range(max(args.warmup, 2 * lanes)):
             step_pipelined()
-        steps_p = steps_timed if args.exact_steps else int(math.ceil(steps_timed * 1.25))   # also >= 1 s at the higher rate
+        steps_p = args.steps
         dtp = timed_loop_pipelined(steps_p)
-        pr = [nb * steps_p / local_dt[0]]
-        if use_dist:
-            t = torch.tensor([pr[0]], dtype=torch.float64, device=dev)
-            allr = [torch.zeros_like(t) for _ in range(world)]
-            dist.all_gather(allr, t)
-            pr = [float(x.item()) for x in allr]
+        pr = rates_of_ranks(nb * steps_p / local_dt[0])
+        dt_h, per_rank_h, outs_h = dtp, pr, host_copies(lane_out[last_lane[0]])
         same = all(torch.equal(o[0], trans_main) and torch.equal(o[1], rot_main) and torch.equal(o[2], pose_main) for o in lane_out)
         n_verify = 16 * lanes
         n_bad = verify_pipelined(n_verify, (trans_main, rot_main, pose_main))
@@ -574,33 +657,10 @@ def main():
 
     if rank == 0:
         value_single = world * nb * steps_timed / dt
-        value = pipelined["value"] if pipelined else value_single
-        out = {
-            "metric": "RGB-D pair inferences/sec (176x176)", "value": round(value, 1), "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": pipelined["ms_per_step"] if pipelined else round(dt / steps_timed * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "steps_timed": pipelined["steps_timed"] if pipelined else steps_timed,
-            "timed_seconds": pipelined["timed_seconds"] if pipelined else round(dt, 4),
-            # `value`: K complete steps of one batch each, successive steps alternating over `lanes` HIP streams / activation
-            # workspaces (PipelinedEngine) -- throughput of the job, not 1 / latency of a step.  `single_stream`: the same K
-            # steps strictly one after the other on one stream; the roofline / layers_ms blocks are measured in THAT region
-            # (kernel durations undisturbed by a concurrent lane).
-            "steps_in_flight": lanes if pipelined else 1,
+        out = result_line(dt_h, per_rank_h, outs_h)
+        out.update({
             "single_stream": {"value": round(value_single, 1), "ms_per_step": round(dt / steps_timed * 1e3, 4),
                               "timed_seconds": round(dt, 4), "steps_timed": steps_timed},
-            "config": {"workload": "configs[1]: batch=%d synthetic 176x176 RGB-D pairs per GPU, random-init Se3TrackNet "
-                                   "(reference state_dict surface), stage=%s" % (nb, args.stage),
-                       "pairs_per_gpu": nb, "global_batch": world * nb, "stage": args.stage,
-                       "frames": "pinned host memory, uploaded per step (PCIe-inclusive)" if args.host_frames else "resident in HBM",
-                       "parallelism": "frame-sharded x%d, RCCL weight broadcast at start-up, pose all-gather %s; per GPU the steps "
-                                      "alternate over %d HIP stream(s)" %
-                                      (world, "every step (overlapped)" if args.gather_every_step else "once per timed region", lanes)},
-            "rccl_ranks": dist.get_world_size() if use_dist else 1,
-            "backend": dist.get_backend() if use_dist else None,
-            "per_rank_pairs_per_s": pipelined["per_rank_pairs_per_s"] if pipelined else [round(v, 1) for v in per_rank],
-            "tflops_total": round(value * FLOP_PER_PAIR / 1e12, 2),
             "roofline": {"bound": "mfma",
                          "kernel": "3x3 conv family, 10 convs/step on exact-f32 v_mfma_f32_32x32x2_f32: direct implicit GEMM "
                                    "(conv3x3_slab_kernel, conv3x3_gather_s2_kernel)" +
@@ -630,10 +690,8 @@ def main():
                                         "frac_pipelined": (round((executed_per_pair + 2 * 194281472) * nb / (pipelined["ms_per_step"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)
                                                            if pipelined else None)}},
             "layers_ms": {n: round(ms, 4) for n, ms in layers},
-        }
+        })
         if DRY:
-            out["dry_run"] = ("gloo on CPU, every kernel stubbed out: `value`, `roofline` and `layers_ms` are NOT measurements; this "
-                              "line only shows that the N-rank launch, broadcast, gather and reporting path runs")
             out["dry_run_checks"] = dry_checks
         if pipelined:
             out["pipelined"] = pipelined
@@ -641,8 +699,9 @@ def main():
             out["requested_steps_region"] = {"steps": short[1], "seconds": round(short[0], 4),
                                              "ms_per_step": round(short[0] / short[1] * 1e3, 4),
                                              "value": round(world * nb * short[1] / short[0], 1),
-                                             "note": "the --steps region (single stream) was shorter than %.1f s; `single_stream` and "
-                                                     "`value` come from regions of steps_timed steps timed right after it" % MIN_TIMED_SECONDS}
+                                             "note": "the --steps region (single stream) was shorter than %.1f s; `single_stream` "
+                                                     "comes from a region of single_stream.steps_timed steps timed right after it"
+                                                     % MIN_TIMED_SECONDS}
         if parity is not None:
             parity.pop("_oracle", None)
             out["parity"] = parity
@@ -778,6 +837,16 @@ class DryPipelinedEngine:
         if name.startswith("set_"):
             return lambda *a, **k: None
         raise AttributeError(name)
+
+
+def dump_outputs(np, out_dir, outs):
+    """--dump-outputs: what the last timed step returned to its caller, the whole batch (a few kB): trans / rot [nb, 3] float32,
+    pose [nb, 4, 4] float64"""
+    os.makedirs(out_dir, exist_ok=True)
+    trans, rot, pose = outs
+    np.save(os.path.join(out_dir, "trans.npy"), np.ascontiguousarray(trans, np.float32))
+    np.save(os.path.join(out_dir, "rot.npy"), np.ascontiguousarray(rot, np.float32))
+    np.save(os.path.join(out_dir, "pose.npy"), np.ascontiguousarray(pose, np.float64).reshape(-1, 4, 4))
 
 
 def compare_with_oracle(np, orc, trans, rot, pose):

@@ -6,7 +6,7 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-parity --track-frames 0 --exact-steps --streams 1"
+CMD="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-parity --track-frames 0 --exact-steps --streams 1"
 cd /tmp
 SE3TN_NO_ALT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $CMD > $OUT/bench_traced.json 2> $OUT/trace.err
 # the PMC passes run the default float32 configuration only (SE3TN_NO_ALT: no f16x3 / direct-kernel legs): per-step byte totals are

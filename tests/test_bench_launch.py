@@ -1,5 +1,5 @@
 """CPU: bench.py's N > 1 launch path, end to end, with the gloo backend and the kernels stubbed out (`--dry-run-gloo`):
-the self-launch (os.execve into torch.distributed.run), the driver's own launch line, the rank logic (barriers, max over
+the self-launch (a child torch.distributed.run process), the driver's own launch line, the rank logic (barriers, max over
 ranks, per-rank rates), the broadcast of the REAL packed weight blob, the pose all-gather, and stdout == exactly one JSON
 line.  The GPU box has one GPU, so this is the only place the N > 1 branches of bench.py execute before the driver's
 8-GPU node (VERDICT r2 missing #2)."""
@@ -44,7 +44,7 @@ def _check(out, n):
 
 @pytest.mark.timeout(600)
 def test_self_launch_two_ranks_gloo_dry_run():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run-gloo", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run-gloo", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     chk = _check(_one_json_line(r.stdout), 2)
@@ -55,7 +55,7 @@ def test_self_launch_two_ranks_gloo_dry_run():
 @pytest.mark.timeout(900)
 def test_self_launch_eight_ranks_gloo_dry_run():
     """the rank count of the driver's scaling node (BASELINE configs[3]: 8 x 64 = 512 pairs): the launch path has counted to eight"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-run-gloo", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-run-gloo", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, env=dict(_env(), OMP_NUM_THREADS="1"), cwd=ROOT, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]
     chk = _check(_one_json_line(r.stdout), 8)
@@ -70,12 +70,33 @@ def test_driver_launch_line_two_ranks_gloo_dry_run():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run-gloo", "--gather-every-step"]
+           "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run-gloo", "--gather-every-step", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _one_json_line(r.stdout)
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["dry_run_checks"]["gather_ok"]
     assert "every step" in out["config"]["parallelism"]
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_exactly_the_requested_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full): one JSON line with the headline fields, exactly --steps timed steps, none of the --full blocks,
+    and --dump-outputs writes the last step's outputs"""
+    dump = str(tmp_path / "out")
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run-gloo", "--steps", "7", "--warmup", "1",
+                        "--dump-outputs", dump], capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=540)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _one_json_line(r.stdout)
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in out
+    assert out["steps"] == out["steps_timed"] == 7 and out["ms_per_step"] > 0
+    for k in ("single_stream", "roofline", "layers_ms", "pipelined", "parity", "alt_precision", "cpu_baseline", "track"):
+        assert k not in out
+    import numpy as np
+    trans, rot, pose = (np.load(os.path.join(dump, n + ".npy")) for n in ("trans", "rot", "pose"))
+    assert trans.shape == rot.shape == (64, 3) and trans.dtype == rot.dtype == np.float32
+    assert pose.shape == (64, 4, 4) and pose.dtype == np.float64
+    assert (pose[:, 3, 3] == 1.0).all()         # DryEngine.infer marks rank 0's poses with rank + 1
 
 
 def test_missing_gpus_is_reported_unmeasured_not_extrapolated():
@@ -107,7 +128,7 @@ def test_rccl_path_of_bench_at_world_size_one(every_step):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
-           "--track-frames", "0"]
+           "--track-frames", "0", "--full"]
     if every_step:
         cmd.append("--gather-every-step")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=840)

@@ -1,7 +1,7 @@
 """`object_width` derived from a model file (predict.py:131-142): the product's load_model_points -> voxel_down_sample ->
 compute_obj_max_width against a SECOND, independent implementation (a dict of voxels filled point by point; the diameter by brute
-force over every pair of down-sampled points) on the reference's own object_models/bunny/1.ply (11,159 vertices; present in the
-build container only) and on a fixture mesh.  trimesh.load / open3d themselves are absent offline: oracle/pin_open3d.py turns this
+force over every pair of down-sampled points) on the reference's own object_models/bunny/1.ply (11,159 vertices; stored gzipped as
+tests/golden/bunny.ply.gz) and on a fixture mesh.  trimesh.load / open3d themselves are absent offline: oracle/pin_open3d.py turns this
 restated rule into a pinned one on first contact (tests/test_pinned_third_party.py)."""
 import os
 
@@ -10,7 +10,7 @@ import pytest
 
 from oracle import fixtures as Fx
 
-BUNNY = "/root/reference/object_models/bunny/1.ply"
+BUNNY_GZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bunny.ply.gz")
 
 
 @pytest.fixture(scope="module")
@@ -53,10 +53,11 @@ def _check(U, pts):
     return len(ds), w
 
 
-def test_object_width_of_the_references_bunny(U):
-    if not os.path.isfile(BUNNY):
-        pytest.skip("the reference tree (object_models/bunny/1.ply) is only present in the build container")
-    pts = U.load_model_points(BUNNY)
+def test_object_width_of_the_references_bunny(U, tmp_path):
+    import gzip
+    bunny = tmp_path / "1.ply"                  # the reference's file, byte for byte
+    bunny.write_bytes(gzip.decompress(open(BUNNY_GZ, "rb").read()))
+    pts = U.load_model_points(str(bunny))
     assert pts.shape == (11159, 3) and pts.dtype == np.float64
     # `property float`: the values are float32 numbers (as trimesh / plyfile return them), held in float64
     assert np.array_equal(pts, pts.astype(np.float32).astype(np.float64))
