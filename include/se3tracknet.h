@@ -277,6 +277,34 @@ int se3tn_on_track_batch(se3tn_ctx* ctx, se3tn_mesh* mesh, int n, const double* 
                          const uint8_t* const* rgb, const uint16_t* const* depth, int H, int W, uint8_t* rgbA_dev,
                          uint16_t* depthA_dev, double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu, void* stream);
 
+/* ---- n different objects in one camera frame, ONE call ------------------------------------------------------------ */
+/* se(3)-TrackNet is trained per object (its own weights, mean / std and normalisers: one context each); a frame shows several objects.
+ * se3tn_on_track_objects runs the loop body of se3tn_on_track for n objects of ONE camera frame (host rgb uint8 [H,W,3], depth uint16
+ * [H,W] millimetres), each with its own model:
+ *   objects[i].model  the context whose bound weights, se3tn_set_normalization mean / std and se3tn_set_normalizers tn / rn object i
+ *                     uses (read only; no weights are copied).  A model may appear several times and `ctx` may be one of them;
+ *   objects[i].mesh   vertex-colour mesh of the VispyRenderer route (not textured);
+ *   objects[i].object_width_mm, prev_poses [n,16] row-major.
+ * `ctx` runs the call: its workspaces, staging, streams, offset rule and raster rule.  Image A of all n objects comes out of FOUR
+ * rasteriser launches (grid.y = object, each instance with its own mesh), the frame's n crop windows go up in one copy, and the network
+ * runs in chunks of at most 5 objects, ALWAYS through the batch 1-5 kernel family (whatever ctx's Winograd / trunk settings): every
+ * kernel of that family works image by image, here with each image's own weights, so object i gets exactly the bits se3tn_on_track on
+ * its own model context gives it -- whatever n, the chunking, the order or the company.  Outputs (host) as se3tn_on_track_batch:
+ * pose_out [n,16], trans_out / rot_out [n,3] and bbox_vu [n,4,2] (may be NULL); rgbA_dev / depthA_dev optional device [n,176,176,3] /
+ * [n,176,176].  1 <= n <= se3tn_max_batch(ctx).  SYNCHRONOUS on `stream`, refused inside a stream capture; the first call (a larger n,
+ * mesh or frame) allocates.
+ * SE3TN_E_ARG: n out of range, a NULL or textured mesh, a pose with z <= 0 or not finite.  SE3TN_E_STATE: a model without weights or
+ * normalisation, on another device, with another packed size, offset rule or raster rule than ctx; ctx in SE3TN_PREC_F16X3, with the
+ * small kernels off or with se3tn_keep_intermediates on.  The context stays usable after a refusal. */
+typedef struct se3tn_object {
+  const se3tn_ctx* model;   /* weights (bound blob), mean / std, trans / rot normalisers of this object */
+  se3tn_mesh* mesh;         /* vertex-colour mesh (VispyRenderer route)                              */
+  double object_width_mm;
+} se3tn_object;
+int se3tn_on_track_objects(se3tn_ctx* ctx, int n, const se3tn_object* objects, const double* prev_poses, const double K[9],
+                           const uint8_t* rgb, const uint16_t* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev,
+                           double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu, void* stream);
+
 /* ---- live-camera front end: depth hole filling ---------------------------------------------------- */
 /* Utils.py:455-514 `fill_depth` as predict_ros.py:38-41 applies it to every depth frame before on_track:
  *     depth = fill_depth(depth_mm / 1e3, max_depth, extrapolate, blur_type);  out_mm = (depth * 1000).astype(uint16)

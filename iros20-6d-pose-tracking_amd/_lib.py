@@ -32,6 +32,11 @@ class Crop(C.Structure):
                 ("z_offset_mm", C.c_double), ("stats", C.c_int32), ("_pad", C.c_int32)]
 
 
+class Object(C.Structure):
+    """se3tn_object (include/se3tracknet.h): one object of se3tn_on_track_objects."""
+    _fields_ = [("model", C.c_void_p), ("mesh", C.c_void_p), ("object_width_mm", C.c_double)]
+
+
 # the same record as a numpy dtype, for building many descriptors without a Python loop
 import numpy as _np
 CROP_DTYPE = _np.dtype([("rgb", "<u8"), ("depth", "<u8"), ("H", "<i4"), ("W", "<i4"), ("left", "<i4"), ("top", "<i4"),
@@ -89,6 +94,8 @@ _SIGS = {
                                  C.POINTER(C.c_int32), C.c_void_p]),
     "se3tn_on_track_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_on_track_objects": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Object), C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_render": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_fill_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,

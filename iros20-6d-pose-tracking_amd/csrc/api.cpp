@@ -116,6 +116,11 @@ struct se3tn_ctx {
   unsigned long long* tb_zbuf = nullptr;
   uint8_t *tb_rgbA = nullptr, *tb_stage_host = nullptr, *tb_stage_dev = nullptr, *tb_out_host = nullptr, *tb_out_dev = nullptr;
   uint16_t* tb_depthA = nullptr;
+  // se3tn_on_track_objects: rasteriser scratch of up to mo_cap instances of up to mo_V vertices / mo_F triangles (several meshes per launch)
+  int mo_cap = 0, mo_V = 0, mo_F = 0;
+  float4* mo_vpost = nullptr;
+  int4* mo_vsnap = nullptr;
+  int *mo_big = nullptr, *mo_clipq = nullptr;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive / splitk_sem before the next one
   int* tail_arrive = nullptr;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
   int* tail_flag = nullptr; int tail_seq = 0;   // set around se3tn_on_track's infer: the tail kernel stores tail_seq to this (mapped) word
@@ -427,6 +432,8 @@ void se3tn_destroy(se3tn_ctx* c) {
     for (void* b : {(void*)c->tb_inst_host, (void*)c->tb_out_host, (void*)c->tb_stage_host})
       if (b) (void)hipHostFree(b);
     for (void* b : {(void*)c->tb_inst_dev, (void*)c->tb_zbuf, (void*)c->tb_rgbA, (void*)c->tb_depthA, (void*)c->tb_out_dev, (void*)c->tb_stage_dev})
+      if (b) (void)hipFree(b);
+    for (void* b : {(void*)c->mo_vpost, (void*)c->mo_vsnap, (void*)c->mo_big, (void*)c->mo_clipq})
       if (b) (void)hipFree(b);
     if (c->fd_buf) (void)hipFree(c->fd_buf);
     for (int s = 0; s < c->slots; ++s)
@@ -1313,8 +1320,9 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
 
 // ---- n tracks per call -------------------------------------------------------------------------------------------------------
 // start-up allocations of se3tn_on_track_batch (first call, a larger n, a larger mesh or frame)
+// (m == nullptr: the context's part only -- se3tn_on_track_objects keeps the rasteriser scratch itself)
 static int reserve_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, size_t stage_bytes) {
-  if (n <= c->tb_cap && n <= m->batch_cap && stage_bytes <= c->tb_stage_bytes) return SE3TN_OK;
+  if (n <= c->tb_cap && (!m || n <= m->batch_cap) && stage_bytes <= c->tb_stage_bytes) return SE3TN_OK;
   DeviceGuard dg(c->device);
   if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
   HIPCHK(hipDeviceSynchronize());
@@ -1335,7 +1343,7 @@ static int reserve_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, size_t stage_
     HIPCHK(hipMalloc((void**)&c->tb_out_dev, (size_t)cap * 160));
     c->tb_cap = cap;
   }
-  if (n > m->batch_cap) {
+  if (m && n > m->batch_cap) {
     for (void* b : {(void*)m->b_vpost, (void*)m->b_vsnap, (void*)m->b_big, (void*)m->b_clipq})
       if (b) HIPCHK(hipFree(b));
     m->b_vpost = nullptr; m->b_vsnap = nullptr; m->b_big = nullptr; m->b_clipq = nullptr; m->batch_cap = 0;
@@ -1487,6 +1495,236 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
       for (double& v : tb_acc) v = 0;
     }
   }
+  std::memcpy(pose_out, c->tb_out_host, (size_t)n * 128);
+  if (trans_out) std::memcpy(trans_out, c->tb_out_host + (size_t)n * 128, (size_t)n * 12);
+  if (rot_out) std::memcpy(rot_out, c->tb_out_host + (size_t)n * 140, (size_t)n * 12);
+  if (bbox_vu) std::memcpy(bbox_vu, vu.data(), sizeof(int32_t) * 8 * (size_t)n);
+  return SE3TN_OK;
+}
+
+// ---- n objects (n models) in one camera frame per call ------------------------------------------------------------------------------
+// rasteriser scratch for n instances of meshes of up to V vertices / F triangles (se3tn_on_track_objects; grown at first use)
+static int reserve_objects_raster(se3tn_ctx* c, int n, int V, int F) {
+  if (n <= c->mo_cap && V <= c->mo_V && F <= c->mo_F) return SE3TN_OK;
+  DeviceGuard dg(c->device);
+  if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+  HIPCHK(hipDeviceSynchronize());
+  for (void* b : {(void*)c->mo_vpost, (void*)c->mo_vsnap, (void*)c->mo_big, (void*)c->mo_clipq})
+    if (b) HIPCHK(hipFree(b));
+  c->mo_vpost = nullptr; c->mo_vsnap = nullptr; c->mo_big = nullptr; c->mo_clipq = nullptr; c->mo_cap = 0;
+  const int cap = n > c->max_batch ? n : c->max_batch;
+  V = V > c->mo_V ? V : c->mo_V;
+  F = F > c->mo_F ? F : c->mo_F;
+  c->mo_V = 0; c->mo_F = 0;
+  HIPCHK(hipMalloc((void**)&c->mo_vpost, sizeof(float4) * (size_t)V * cap));
+  HIPCHK(hipMalloc((void**)&c->mo_vsnap, sizeof(int4) * (size_t)V * cap));
+  HIPCHK(hipMalloc((void**)&c->mo_big, sizeof(int) * (size_t)(1 + F) * cap));
+  HIPCHK(hipMalloc((void**)&c->mo_clipq, sizeof(int) * (size_t)(1 + F) * cap));
+  c->mo_cap = cap; c->mo_V = V; c->mo_F = F;
+  return SE3TN_OK;
+}
+
+// The network on k <= 5 pairs of (possibly) k models, through the batch 1-5 family chosen EXPLICITLY -- not through infer_launch's
+// predicates: stem + pool in one launch, the four trunk convs (conv64_small), the five 128 .. 512-channel convs as channel slices
+// (+ conv_reduce), the tail on the last conv's partial sums.  That is the sequence se3tn_infer runs for one pair of a default context;
+// every kernel of it works image by image in a layer-fixed order, and here image i reads its parameters ip.off[i] floats from W.
+static int infer_small_objects(se3tn_ctx* c, const float* W, const ImgParams& ip, const float* A, const float* B, int k, float* trans,
+                               float* rot, const double* poseA, double* poseB, hipStream_t st) {
+  const BlobLayout& L = c->L;
+  HIPCHK(launch_stem_pool_small_multi(A, B, W + L.stem_w, W + L.stem_b, c->pool, k, ip.off, st));
+  auto conv = [&](ConvId id, const float* in, int in_ld, int in_gs, const float* res, int res_ld, int res_gs, float* out, int out_ld,
+                  int out_gs, int hin, int stride, int epi, bool skip_reduce, const char* name) -> int {
+    const Conv3& s = conv_specs()[id];
+    ConvArgs a{};
+    a.in = in; a.w = W + L.conv_w[id]; a.bias = W + L.conv_b[id]; a.res = res; a.out = out;
+    a.part = c->part; a.part_bytes = c->part_bytes; a.small_ok = 1; a.skip_reduce = skip_reduce ? 1 : 0;
+    a.in_ld = in_ld; a.res_ld = res_ld; a.out_ld = out_ld;
+    a.H = hin; a.W = hin; a.Ho = (hin - 1) / stride + 1; a.Wo = a.Ho;
+    a.M = k * a.Ho * a.Wo;
+    a.groups = s.groups;
+    a.in_gs = in_gs; a.res_gs = res_gs; a.out_gs = out_gs; a.bias_gs = s.cout;
+    a.w_gs = (long long)conv3_words(s.cin, s.cout);
+    a.per_img = 1;
+    std::memcpy(a.img_off, ip.off, sizeof(a.img_off));
+    const hipError_t e = launch_conv_small(a, s.cin, s.cout, stride, epi, st);
+    return e == hipSuccess ? SE3TN_OK : hipfail(e, name);
+  };
+  int rc;
+  if ((rc = conv(L64_1, c->pool, 128, 64, nullptr, 0, 0, c->t64, 128, 64, S2, 1, 0, false, "conv64 A2.conv1|B2.conv1"))) return rc;
+  if ((rc = conv(L64_2, c->t64, 128, 64, c->pool, 128, 64, c->q64, 128, 64, S2, 1, 1, false, "conv64 A2.conv2|B2.conv2"))) return rc;
+  if ((rc = conv(L64_3, c->q64 + 64, 128, 0, nullptr, 0, 0, c->t64 + 64, 128, 0, S2, 1, 0, false, "conv64 B3.conv1"))) return rc;
+  if ((rc = conv(L64_4, c->t64 + 64, 128, 0, c->q64 + 64, 128, 0, c->q64 + 64, 128, 0, S2, 1, 1, false, "conv64 B3.conv2"))) return rc;
+  if ((rc = conv(LAB1, c->q64, 128, 0, nullptr, 0, 0, c->ab, 256, 0, S2, 2, 2, false, "convAB1 s2"))) return rc;
+  if ((rc = conv(LAB2_1, c->ab, 256, 0, nullptr, 0, 0, c->ab_t, 256, 0, S3, 1, 0, false, "convAB2.conv1"))) return rc;
+  if ((rc = conv(LAB2_2, c->ab_t, 256, 0, c->ab, 256, 0, c->ab, 256, 0, S3, 1, 1, false, "convAB2.conv2"))) return rc;
+  if ((rc = conv(LH1, c->ab, 256, 0, nullptr, 0, 0, c->head, 1024, 0, S3, 2, 2, false, "trans|rot conv1 s2"))) return rc;
+  if ((rc = conv(LH2_1, c->head, 1024, 512, nullptr, 0, 0, c->head_t, 1024, 512, S4, 1, 0, false, "trans|rot conv2.conv1"))) return rc;
+  // the last head conv leaves its 8 partial-sum slices to the tail (conv_slices_small_count(512, 1, S4) == 8)
+  if ((rc = conv(LH2_2, c->head_t, 1024, 512, c->head, 1024, 512, c->head, 1024, 512, S4, 1, 1, true, "trans|rot conv2.conv2"))) return rc;
+  c->head_final = nullptr;   // (not materialised)
+  c->last_fast = false;
+  const int M = k * S4 * S4;
+  HIPCHK(launch_tail_parts(c->part, 8, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head, 1024, W + L.fc_w, W + L.fc_b, c->logits, trans,
+                           rot, poseA, poseB, 0.0, 0.0, k, st, c->fcpart, c->tail_arrive, nullptr, 0, 16, &ip));
+  return SE3TN_OK;
+}
+
+int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const double* prev_poses, const double K[9], const uint8_t* rgb,
+                           const uint16_t* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev, double* pose_out, float* trans_out,
+                           float* rot_out, int32_t* bbox_vu, void* stream) {
+  if (!c || c->device < 0 || !objs || !prev_poses || !K || !rgb || !depth || H < 1 || W < 1 || !pose_out)
+    return fail(SE3TN_E_ARG, "se3tn_on_track_objects: bad argument");
+  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_on_track_objects: n outside [1, max_batch]");
+  if (c->prec != SE3TN_PREC_F32)
+    return fail(SE3TN_E_STATE, "se3tn_on_track_objects: ctx is in SE3TN_PREC_F16X3 (the batch 1-5 kernel family is float32)");
+  if (!c->small_kernels) return fail(SE3TN_E_STATE, "se3tn_on_track_objects: ctx has the batch 1-5 kernels switched off (se3tn_set_small_kernels)");
+  if (c->keep_intermediates) return fail(SE3TN_E_STATE, "se3tn_on_track_objects: ctx keeps intermediates (se3tn_keep_intermediates)");
+  if (stream_is_capturing((hipStream_t)stream)) return fail(SE3TN_E_STATE, "se3tn_on_track_objects: synchronous call, not capturable");
+  const std::string who = "se3tn_on_track_objects: object ";
+  int maxV = 0, maxF = 0;
+  for (int i = 0; i < n; ++i) {
+    const se3tn_object& o = objs[i];
+    const std::string id = who + std::to_string(i);
+    if (!o.mesh) return fail(SE3TN_E_ARG, id + ": null mesh");
+    if (o.mesh->tex || o.mesh->uv) return fail(SE3TN_E_ARG, id + ": textured mesh (the full-frame renderer's route: se3tn_on_track per object)");
+    if (!(o.object_width_mm > 0)) return fail(SE3TN_E_ARG, id + ": object width must be > 0");
+    const se3tn_ctx* m = o.model;
+    if (!m) return fail(SE3TN_E_ARG, id + ": null model");
+    if (!m->blob) return fail(SE3TN_E_STATE, id + ": model has no weights (se3tn_upload_weights / se3tn_bind_weights)");
+    if (!m->have_norm) return fail(SE3TN_E_STATE, id + ": model has no normalisation (se3tn_set_normalization)");
+    if (m->device != c->device) return fail(SE3TN_E_STATE, id + ": model lives on another device than ctx");
+    if (m->L.total != c->L.total) return fail(SE3TN_E_STATE, id + ": model's packed size differs from ctx's");
+    if (m->offset_rule != c->offset_rule) return fail(SE3TN_E_STATE, id + ": model's offset rule differs from ctx's (se3tn_set_offset_rule)");
+    if (m->raster_sub_bits != c->raster_sub_bits) return fail(SE3TN_E_STATE, id + ": model's raster rule differs from ctx's (se3tn_set_raster_rule)");
+    if (((uintptr_t)m->blob - (uintptr_t)objs[0].model->blob) % sizeof(float) != 0)
+      return fail(SE3TN_E_STATE, id + ": model's weight blob is not float-aligned to the others'");
+    maxV = o.mesh->V > maxV ? o.mesh->V : maxV;
+    maxF = o.mesh->F > maxF ? o.mesh->F : maxF;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // pass 1 (host float64): the windows of every object (predict.py:231-235 / :201-206) and its staged sub-image of the frame
+  std::vector<int32_t> win(8 * (size_t)n), vu(8 * (size_t)n);
+  std::vector<size_t> off_rgb(n), off_d(n);
+  std::vector<int> geo(4 * (size_t)n);
+  const size_t norm_off = (((size_t)n * 128) + 255) & ~(size_t)255;              // the poses in front, then mean | std per object
+  size_t bytes = norm_off + ((((size_t)n * 128) + 255) & ~(size_t)255);
+  for (int i = 0; i < n; ++i) {
+    const double* P = prev_poses + 16 * (size_t)i;
+    int32_t* wB = &win[8 * (size_t)i];
+    int32_t* wA = wB + 4;
+    const double wd = objs[i].object_width_mm;
+    if (!(P[11] > 0) || !bbox_window(P, K, wd, 1000.0, wB, &vu[8 * (size_t)i]) || !bbox_window(P, K, wd, -1000.0, wA, nullptr))
+      return fail(SE3TN_E_ARG, who + std::to_string(i) + ": pose is not in front of the camera (z <= 0 or not finite)");
+    if (wB[2] <= wB[0] || wB[3] <= wB[1]) return fail(SE3TN_E_ARG, who + std::to_string(i) + ": empty crop window");
+    int x0 = wB[0] > 0 ? wB[0] : 0, x1 = wB[2] < W ? wB[2] : W;
+    int y0 = wB[1] > 0 ? wB[1] : 0, y1 = wB[3] < H ? wB[3] : H;
+    int sw = x1 - x0, sh = y1 - y0;
+    if (sw <= 0 || sh <= 0) { sw = sh = -1; x0 = wB[0] - 8; y0 = wB[1] - 8; }   // the window misses the frame: a 1 x 1 zero sub-image
+    geo[4 * i] = x0; geo[4 * i + 1] = y0; geo[4 * i + 2] = sw; geo[4 * i + 3] = sh;
+    const size_t px = sw > 0 ? (size_t)sw * sh : 1;
+    off_rgb[i] = bytes; bytes += (px * 3 + 63) & ~(size_t)63;
+    off_d[i] = bytes;   bytes += (px * 2 + 63) & ~(size_t)63;
+  }
+  if (int rc = reserve_track_batch(c, nullptr, n, bytes)) return rc;
+  if (int rc = reserve_objects_raster(c, n, maxV, maxF)) return rc;
+  if (c->rearm_counters) {   // (as se3tn_infer: a launch sequence that failed half-way may have left the tail's counters non-zero)
+    HIPCHK(hipMemsetAsync(c->tail_arrive, 0, sizeof(int) * c->max_batch, st));
+    c->rearm_counters = false;
+  }
+  // image A of all n objects: FOUR launches (grid.y = object), every instance with its own mesh
+  uint8_t* rA = rgbA_dev ? rgbA_dev : c->tb_rgbA;
+  uint16_t* dA = depthA_dev ? depthA_dev : c->tb_depthA;
+  RasterArgs ra{};
+  raster_common(ra, c, objs[0].mesh, rA, dA);
+  ra.rw = RES; ra.rh = RES; ra.mode = 0;
+  ra.vpost = c->mo_vpost; ra.vsnap = c->mo_vsnap; ra.big = c->mo_big; ra.clipq = c->mo_clipq; ra.zbuf = c->tb_zbuf;
+  ra.V = maxV; ra.F = maxF; ra.inst_mesh = 1;
+  for (int i = 0; i < n; ++i) {
+    RasterArgs one{};
+    if (!vispy_uniforms(one, prev_poses + 16 * (size_t)i, K, &win[8 * (size_t)i + 4]))
+      return fail(SE3TN_E_ARG, who + std::to_string(i) + ": singular pose");
+    const se3tn_mesh* m = objs[i].mesh;
+    RasterInstance& I = c->tb_inst_host[i];
+    std::memcpy(I.PV, one.PV, sizeof(I.PV));
+    std::memcpy(I.light, one.light, sizeof(I.light));
+    I._pad = 0.f; I.dA = one.dA; I.dB = one.dB;
+    I.verts = m->verts; I.normals = m->normals; I.colors = m->colors; I.faces = m->faces; I.V = m->V; I.F = m->F;
+  }
+  HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, sizeof(RasterInstance) * n, hipMemcpyHostToDevice, st));
+  ra.inst = c->tb_inst_dev;
+  HIPCHK(launch_raster(ra, st, n));
+  // the poses, every object's mean | std and the frame's n windows: staged through pinned memory while the rasteriser runs, ONE copy
+  uint8_t* hp = c->tb_stage_host;
+  std::memcpy(hp, prev_poses, (size_t)n * 128);
+  double* norm_h = (double*)(hp + norm_off);
+  for (int i = 0; i < n; ++i) {
+    std::memcpy(norm_h + 16 * (size_t)i, objs[i].model->mean, 8 * sizeof(double));
+    std::memcpy(norm_h + 16 * (size_t)i + 8, objs[i].model->stdv, 8 * sizeof(double));
+  }
+  for (int i = 0; i < n; ++i) {
+    const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
+    if (sw < 0) { std::memset(hp + off_rgb[i], 0, 3); std::memset(hp + off_d[i], 0, 2); continue; }
+    for (int y = 0; y < sh; ++y) {
+      std::memcpy(hp + off_rgb[i] + (size_t)y * sw * 3, rgb + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
+      std::memcpy(hp + off_d[i] + (size_t)y * sw * 2, depth + (size_t)(y0 + y) * W + x0, (size_t)sw * 2);
+    }
+  }
+  HIPCHK(hipMemcpyAsync(c->tb_stage_dev, hp, bytes, hipMemcpyHostToDevice, c->trk_copy_stream));
+  HIPCHK(hipEventRecord(c->trk_copy_event, c->trk_copy_stream));
+  HIPCHK(hipStreamWaitEvent(st, c->trk_copy_event, 0));
+  // both crops of every object, each normalised with its own model's mean / std (the device table staged above); up to 32 objects
+  // (64 descriptors) per launch: images A into inA, images B into inB
+  const size_t img_floats = (size_t)IN_P * IN_P * 4;
+  int rc = SE3TN_OK;
+  for (int g0 = 0; g0 < n && rc == SE3TN_OK; g0 += CropArgs::MAX / 2) {
+    const int kg = n - g0 < CropArgs::MAX / 2 ? n - g0 : CropArgs::MAX / 2;
+    CropArgs a;
+    std::memcpy(a.mean, c->mean, sizeof(a.mean));
+    std::memcpy(a.stdv, c->stdv, sizeof(a.stdv));
+    for (int j = 0; j < kg; ++j) {
+      const int i = g0 + j;
+      const double z_mm = prev_poses[16 * (size_t)i + 11] * 1000;
+      se3tn_crop& ca = a.c[j];
+      ca.rgb = rA + (size_t)i * RES * RES * 3; ca.depth = dA + (size_t)i * RES * RES; ca.H = RES; ca.W = RES;
+      ca.left = 0; ca.top = 0; ca.right = RES; ca.bottom = RES; ca.z_offset_mm = z_mm; ca.stats = 0; ca._pad = 0;
+      se3tn_crop& cb = a.c[kg + j];
+      const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
+      const int32_t* wB = &win[8 * (size_t)i];
+      cb.rgb = c->tb_stage_dev + off_rgb[i]; cb.depth = (const uint16_t*)(c->tb_stage_dev + off_d[i]);
+      cb.H = sw < 0 ? 1 : sh; cb.W = sw < 0 ? 1 : sw;
+      cb.left = wB[0] - x0; cb.top = wB[1] - y0; cb.right = wB[2] - x0; cb.bottom = wB[3] - y0;
+      cb.z_offset_mm = z_mm; cb.stats = 1; cb._pad = 0;
+    }
+    a.n = 2 * kg; a.n_first = kg;
+    a.out = c->inA + (size_t)g0 * img_floats; a.out2 = c->inB + (size_t)g0 * img_floats; a.padded = 1; a.split = 0;
+    a.overflow = c->overflow; a.offset_rule = c->offset_rule;
+    a.norm = (const double*)(c->tb_stage_dev + norm_off) + 16 * (size_t)g0;
+    if (const hipError_t e = launch_preprocess(a, st)) rc = hipfail(e, "launch_preprocess");
+  }
+  c->in_split[0] = c->in_split[1] = 0;
+  // the network, chunks of at most 5 objects; image j of a chunk reads its model's blob at off[j] floats from the chunk's first blob
+  float* trans_d = (float*)(c->tb_out_dev + (size_t)n * 128);
+  float* rot_d = trans_d + 3 * (size_t)n;
+  for (int i0 = 0; i0 < n && rc == SE3TN_OK; i0 += SE3TN_SLICES_SMALL_MAX_N) {
+    const int k = n - i0 < SE3TN_SLICES_SMALL_MAX_N ? n - i0 : SE3TN_SLICES_SMALL_MAX_N;
+    const float* W0 = objs[i0].model->blob;
+    ImgParams ip{};
+    for (int j = 0; j < k; ++j) {
+      const se3tn_ctx* m = objs[i0 + j].model;
+      ip.off[j] = (long long)(((intptr_t)m->blob - (intptr_t)W0) / (intptr_t)sizeof(float));
+      ip.tn[j] = m->tn;
+      ip.rn[j] = m->rn;
+    }
+    rc = infer_small_objects(c, W0, ip, c->inA + (size_t)i0 * img_floats, c->inB + (size_t)i0 * img_floats, k, trans_d + 3 * (size_t)i0,
+                             rot_d + 3 * (size_t)i0, (const double*)c->tb_stage_dev + 16 * (size_t)i0, (double*)c->tb_out_dev + 16 * (size_t)i0, st);
+  }
+  if (rc != SE3TN_OK) {
+    c->rearm_counters = true;
+    (void)hipStreamSynchronize(c->trk_copy_stream);   // the staged frame may still be travelling
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(c->tb_out_host, c->tb_out_dev, (size_t)n * 152, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   std::memcpy(pose_out, c->tb_out_host, (size_t)n * 128);
   if (trans_out) std::memcpy(trans_out, c->tb_out_host + (size_t)n * 128, (size_t)n * 12);
   if (rot_out) std::memcpy(rot_out, c->tb_out_host + (size_t)n * 140, (size_t)n * 12);

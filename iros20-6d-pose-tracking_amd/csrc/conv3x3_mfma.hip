@@ -440,7 +440,9 @@ __device__ __forceinline__ void store_partial(float* p, const float4 v) {
 }
 
 // one float4 of the output: the slices' partial sums added in a FIXED order, then bias / residual / activation
-template <int EPI, int MM, int OUTF, int RESF>
+// PI (mixed-model batch, conv_slices_small only): the bias of output row m's image, img_off[m / (Ho Wo)] floats from a.bias -- a
+// per-lane index here (a workgroup may straddle two images), so the offset is selected from the table, not indexed
+template <int EPI, int MM, int OUTF, int RESF, bool PI = false>
 __device__ __forceinline__ void reduce_element(const ConvArgs& a, const float* src, size_t slice_stride, int g, int m, int c) {
   float4 v = *reinterpret_cast<const float4*>(src);
 #pragma unroll 8
@@ -453,7 +455,15 @@ __device__ __forceinline__ void reduce_element(const ConvArgs& a, const float* s
     v.x *= w.x; v.y *= w.y; v.z *= w.z; v.w *= w.w;
   }
   const size_t opix = (size_t)padded_index(m, a.Ho * a.Wo, a.Wo);
-  const float4 b = *reinterpret_cast<const float4*>(a.bias + (size_t)g * a.bias_gs + c);
+  const float* bias = a.bias;
+  if (PI) {
+    const int im = m / (a.Ho * a.Wo);
+    long long o = a.img_off[0];
+#pragma unroll
+    for (int k = 1; k < SMALL_MAX_IMG; ++k) o = im == k ? a.img_off[k] : o;
+    bias += o;
+  }
+  const float4 b = *reinterpret_cast<const float4*>(bias + (size_t)g * a.bias_gs + c);
   float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
   if (EPI == 1) {
     const float* res = a.res + (size_t)g * a.res_gs;
@@ -468,14 +478,14 @@ __device__ __forceinline__ void reduce_element(const ConvArgs& a, const float* s
   }
 }
 
-template <int EPI, int MM, int OUTF, int RESF>
+template <int EPI, int MM, int OUTF, int RESF, bool PI = false>
 __global__ __launch_bounds__(256) void conv_reduce_kernel(const ConvArgs a, int cout, int total) {
   const int idx = blockIdx.x * 256 + threadIdx.x;  // (group, m, c4)
   if (idx >= total) return;
   const int q4 = cout >> 2;
   const int c = (idx % q4) * 4, t = idx / q4;
   const int g = t / a.M, m = t % a.M;
-  reduce_element<EPI, MM, OUTF, RESF>(a, a.part + ((size_t)g * a.M + m) * cout + c, (size_t)a.groups * a.M * cout, g, m, c);
+  reduce_element<EPI, MM, OUTF, RESF, PI>(a, a.part + ((size_t)g * a.M + m) * cout + c, (size_t)a.groups * a.M * cout, g, m, c);
 }
 
 // The reduction INSIDE the split-K launch (a.sem != nullptr): the grid carries, after the conv workgroups, a.rpt reduce
@@ -751,10 +761,10 @@ static hipError_t launch_gather(const ConvArgs& a, hipStream_t st) {
   return launch_gather_nw<CIN, EPI, MM, OUTF, 4>(a, st);
 }
 
-template <int EPI, int MM, int OUTF, int RESF>
+template <int EPI, int MM, int OUTF, int RESF, bool PI = false>
 static void launch_reduce(const ConvArgs& a, int cout, hipStream_t st) {
   const int total = a.groups * a.M * (cout / 4);
-  hipLaunchKernelGGL((conv_reduce_kernel<EPI, MM, OUTF, RESF>), dim3((total + 255) / 256), dim3(256), 0, st, a, cout, total);
+  hipLaunchKernelGGL((conv_reduce_kernel<EPI, MM, OUTF, RESF, PI>), dim3((total + 255) / 256), dim3(256), 0, st, a, cout, total);
 }
 
 // the fused reduction's reduce workgroups: at most this many per launch (the launch holds 512 workgroup slots: 2 per compute unit)
@@ -925,6 +935,37 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
   if (stride == 2 && cin == 128 && epi == 2) return launch_gather<128, 2>(a, st);
   if (stride == 2 && cin == 256 && epi == 2) return launch_gather<256, 2>(a, st);
   return hipErrorInvalidValue;
+}
+
+// The batch 1-5 family with no predicate to fall through: the caller (se3tn_on_track_objects: mixed-model batches, whose bits must
+// equal each model's batch-1 run) has chosen it, so a shape or batch it does not cover is an error, not another algorithm.
+hipError_t launch_conv_small(const ConvArgs& a0, int cin, int cout, int stride, int epi, hipStream_t st) {
+  ConvArgs a = a0;
+  if (a.fast || a.Ho * a.Wo <= 0 || a.M % (a.Ho * a.Wo) != 0) return hipErrorInvalidValue;
+  const int n = a.M / (a.Ho * a.Wo);
+  if (n < 1 || n > SE3TN_SLICES_SMALL_MAX_N) return hipErrorInvalidValue;
+  if (cin == 64 && cout == 64 && stride == 1 && a.W == 44 && a.H == 44 && epi != 2) {
+    if (n > SE3TN_CONV64_SMALL_MAX_N) return hipErrorInvalidValue;
+    return launch_conv64_small(a, n, epi, st);
+  }
+  const int sl = conv_slices_small_count(cin, stride, a.H);
+  if (sl <= 0 || !a.part || (size_t)sl * a.groups * a.M * cout * sizeof(float) > a.part_bytes) return hipErrorInvalidValue;
+  a.slices = sl;
+  a.tiles_n = cout / 32;
+  a.sem = nullptr;
+  hipError_t e = launch_conv_slices_small(a, cin, stride, st);
+  if (e != hipSuccess) return e;
+  if (a.skip_reduce) return hipSuccess;
+  if (a.per_img) {
+    if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
+    else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
+    else launch_reduce<2, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
+  } else {
+    if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
+    else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
+    else launch_reduce<2, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
+  }
+  return hipGetLastError();
 }
 
 }  // namespace se3tn

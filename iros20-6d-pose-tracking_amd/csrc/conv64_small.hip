@@ -131,7 +131,8 @@ struct C64Run<-1> {
 
 // grid: (121 tiles, n images, groups) workgroups of 256 threads (no division by a run-time value in the index arithmetic: this
 // kernel lives for 4 us); EPI 0 = bias + ReLU, 1 = bias + residual + ReLU
-template <int EPI>
+// PI: per-image weights / bias at a.img_off[img] (mixed-model batch); false = the single-model kernel
+template <int EPI, bool PI>
 __global__ __launch_bounds__(256, 1) void conv64_small_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -140,7 +141,8 @@ __global__ __launch_bounds__(256, 1) void conv64_small_kernel(const ConvArgs a) 
   const int ty = tile / 11, tx = tile - ty * 11;
   constexpr int Wp = S2 + 2;                            // 46
   const float* __restrict__ in = a.in + (size_t)g * a.in_gs + ((size_t)(img * Wp + ty * 4) * Wp + tx * 4) * a.in_ld;   // patch origin (padded)
-  const float* __restrict__ wgt = a.w + (size_t)g * a.w_gs;
+  const long long woff = PI ? a.img_off[img] : 0;     // (img = blockIdx.y: a scalar load)
+  const float* __restrict__ wgt = a.w + woff + (size_t)g * a.w_gs;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
 
   // ---- request everything: the patch (576 16-byte slots: pixel = slot >> 4, physical column = slot & 15) ...
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void conv64_small_kernel(const ConvArgs a) 
   const int ho = ty * 4 + (f.pix >> 2), wo = tx * 4 + (f.pix & 3);
   const size_t opix = ((size_t)img * Wp + ho + 1) * Wp + wo + 1;
   float4 v = make_float4(acc0[0] + acc1[0], acc0[1] + acc1[1], acc0[2] + acc1[2], acc0[3] + acc1[3]);
-  const float4 bias = *reinterpret_cast<const float4*>(a.bias + (size_t)g * a.bias_gs + c);
+  const float4 bias = *reinterpret_cast<const float4*>(a.bias + woff + (size_t)g * a.bias_gs + c);
   float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
   if (EPI == 1) r = *reinterpret_cast<const float4*>(a.res + (size_t)g * a.res_gs + opix * a.res_ld + c);
   v = apply_epilogue<EPI>(v, bias, r);
@@ -193,10 +195,12 @@ __global__ __launch_bounds__(256, 1) void conv64_small_kernel(const ConvArgs a) 
 }
 
 hipError_t launch_conv64_small(const ConvArgs& a, int n, int epi, hipStream_t st) {
-  static PerDeviceOnce attr0, attr1;
-  auto k0 = conv64_small_kernel<0>;
-  auto k1 = conv64_small_kernel<1>;
-  bool* done = (epi == 1 ? attr1 : attr0).current();
+  static PerDeviceOnce attr[4];
+  const bool pi = a.per_img != 0;
+  auto k0 = pi ? conv64_small_kernel<0, true> : conv64_small_kernel<0, false>;
+  auto k1 = pi ? conv64_small_kernel<1, true> : conv64_small_kernel<1, false>;
+  if (pi && n > SMALL_MAX_IMG) return hipErrorInvalidValue;
+  bool* done = attr[(epi == 1 ? 1 : 0) + (pi ? 2 : 0)].current();
   if (!(done && *done)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(epi == 1 ? k1 : k0), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)C64_LDS_BYTES);

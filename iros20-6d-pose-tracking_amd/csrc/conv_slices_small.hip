@@ -190,7 +190,8 @@ struct CsRun<G, -1> {
 // -- partial tiles written through to memory with sc1 stores, a ticket per output tile, the last arriver reads the SLICES tiles back
 // with sc1 loads, adds them in slice order and applies the epilogue: 210 us per forward against 183 us with the separate launch.
 // Three dependent round trips to the memory side (store acknowledgements, ticket, read-back) cost more than a launch boundary.
-template <int CHUNKS, int STRIDE, int PPMAX, int WO, int SLICES, int NT>
+// PI: per-image weights at a.img_off[img] (mixed-model batch); false = the single-model kernel
+template <int CHUNKS, int STRIDE, int PPMAX, int WO, int SLICES, int NT, bool PI>
 __global__ __launch_bounds__(256, 1) void conv_slices_small_kernel(const ConvArgs a) {
   using G = CsGeom<CHUNKS, PPMAX>;
   constexpr int HW = WO * WO, TPI = (HW + 127) / 128, H = STRIDE * WO, Wp = H + 2, cout = NT * 32;
@@ -206,7 +207,8 @@ __global__ __launch_bounds__(256, 1) void conv_slices_small_kernel(const ConvArg
   const size_t pix0 = ((size_t)img * (H + 2) + (size_t)oy0 * STRIDE) * Wp;
   const float* __restrict__ in = a.in + (size_t)g * a.in_gs + pix0 * a.in_ld + (size_t)sl * CHUNKS * 32;
   // panels [chunk][tap][cout][32] of group g; this workgroup's rows nt * 32 .. + 31 of chunks sl * CHUNKS ..
-  const float* __restrict__ wgt = a.w + (size_t)g * a.w_gs + ((size_t)sl * CHUNKS * 9 * cout + (size_t)nt * 32) * 32;
+  const long long woff = PI ? a.img_off[img] : 0;          // (img from blockIdx.y: a scalar load)
+  const float* __restrict__ wgt = a.w + woff + (size_t)g * a.w_gs + ((size_t)sl * CHUNKS * 9 * cout + (size_t)nt * 32) * 32;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
 
   static_assert(G::schedule_ok(), "a K-step would wait for a weight tile that has not been requested");
@@ -270,9 +272,12 @@ static hipError_t launch_cs(const ConvArgs& a, hipStream_t st) {
   constexpr int HW = WO * WO, TPI = (HW + 127) / 128;
   if (a.Ho != WO || a.Wo != WO || a.H != STRIDE * WO || a.W != STRIDE * WO || a.tiles_n != NT || a.slices != SLICES || a.M % HW != 0)
     return hipErrorInvalidValue;
-  static PerDeviceOnce attr;
-  auto kern = conv_slices_small_kernel<CHUNKS, STRIDE, PPMAX, WO, SLICES, NT>;
-  bool* done = attr.current();
+  static PerDeviceOnce attr[2];
+  const bool pi = a.per_img != 0;
+  if (pi && a.M / HW > SMALL_MAX_IMG) return hipErrorInvalidValue;
+  auto kern = pi ? conv_slices_small_kernel<CHUNKS, STRIDE, PPMAX, WO, SLICES, NT, true>
+                 : conv_slices_small_kernel<CHUNKS, STRIDE, PPMAX, WO, SLICES, NT, false>;
+  bool* done = attr[pi ? 1 : 0].current();
   if (!(done && *done)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
     if (e != hipSuccess) return e;

@@ -65,6 +65,8 @@ hipError_t launch_to_padded_input(const float* in, float* out, int n, int nchw, 
 // reference: the depth offset (data_augmentation.py:137-140) as ONE float32 operation with the scalar cast to float32 first
 // (SE3TN_OFFSET_RULE_NUMPY1: value-based casting, every NumPy the reference runs on) or in float64 rounded once (NUMPY2, NEP 50);
 // (x - mean)/std in f64 then stored as f32 (:160-164, :182-187: array operands, float64 under both).
+// TAB: mean / std per crop from the device table a.norm (several models' crops in one launch); false = the kernel-argument pair
+template <bool TAB>
 __global__ __launch_bounds__(256) void preprocess_kernel(const CropArgs a) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= RES * RES) return;
@@ -95,6 +97,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const CropArgs a) {
   if (invalid) d = 2000.f;
   const double* mean = a.mean + 4 * c.stats;
   const double* sd = a.stdv + 4 * c.stats;
+  if (TAB) {   // (i = blockIdx.y: the row is uniform over the workgroup)
+    const double* row = a.norm + (size_t)(i < a.n_first ? i : i - a.n_first) * 16;
+    mean = row + 4 * c.stats;
+    sd = row + 8 + 4 * c.stats;
+  }
   float4 o;
   o.x = (float)(((double)r - mean[0]) / sd[0]);
   o.y = (float)(((double)g - mean[1]) / sd[1]);
@@ -113,7 +120,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const CropArgs a) {
 }
 
 hipError_t launch_preprocess(const CropArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(preprocess_kernel, dim3((RES * RES + 255) / 256, a.n), dim3(256), 0, st, a);
+  if (a.norm) hipLaunchKernelGGL(preprocess_kernel<true>, dim3((RES * RES + 255) / 256, a.n), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(preprocess_kernel<false>, dim3((RES * RES + 255) / 256, a.n), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -258,13 +266,16 @@ hipError_t launch_tail(const float* head, const float* fc_w, const float* fc_b, 
 // reads cost 7.7 us (16 compute units cannot pull 4 MB fast enough); as 64 workgroups of 16 channels 2.2 us.  So: 64 workgroups per
 // pair (2 heads x 32 slices of 16 channels); thread (pg, col) = pixels pg and pg + 64 x channels 4 col .. 4 col + 3 (16 + 2 loads, all in
 // flight); pixel groups, then columns, added in a fixed order; fcpart[pair][head][32][3]; the last arriver finishes as above.
-template <int CH, int SLICES>      // channels per workgroup (16 | 32), partial-sum slices
+// PI (mixed-model batch): pair i's bias / fc_w / fc_b lie img.off[i] floats from the pointers and its pose update takes img.tn[i] /
+// img.rn[i] (i from blockIdx.x: scalar loads); false = the single-model kernel, which ignores `img`
+template <int CH, int SLICES, bool PI = false>      // channels per workgroup (16 | 32), partial-sum slices
 __global__ __launch_bounds__(256) void tail_parts_kernel(const float* __restrict__ part, size_t slice_stride, int M,
                                                          const float* __restrict__ bias, const float* __restrict__ res, int res_ld,
                                                          const float* __restrict__ fc_w, const float* __restrict__ fc_b,
                                                          float* __restrict__ logits, float* __restrict__ trans, float* __restrict__ rot,
                                                          const double* __restrict__ poseA, double* __restrict__ poseB, double tn, double rn,
-                                                         float* __restrict__ fcpart, int* __restrict__ arrive, int* done_flag, int done_seq) {
+                                                         float* __restrict__ fcpart, int* __restrict__ arrive, int* done_flag, int done_seq,
+                                                         const ImgParams img) {
   constexpr int COLS = CH / 4, PGS = 256 / COLS, NSL = 512 / CH, WGS = 2 * NSL;   // float4 columns, pixel groups, slices per head
   constexpr int HW = S4 * S4, PPT = (HW + PGS - 1) / PGS;                         // pixels per thread: 2 | 4
   __shared__ float4 psum[PGS][COLS];
@@ -275,6 +286,11 @@ __global__ __launch_bounds__(256) void tail_parts_kernel(const float* __restrict
   const int hd = slw / NSL, c0 = (slw - hd * NSL) * CH;
   const int t = threadIdx.x, col = t % COLS, pg = t / COLS;
   const int c = c0 + col * 4;
+  if (PI) {
+    const long long o = img.off[i];
+    bias += o; fc_w += o; fc_b += o;
+    tn = img.tn[i]; rn = img.rn[i];
+  }
   const float4 b = *reinterpret_cast<const float4*>(bias + hd * 512 + c);
   // every load of this thread first (PPT x (SLICES + 1), all in flight), then the sums in slice order
   float4 v[PPT][SLICES], r[PPT];
@@ -370,14 +386,19 @@ __global__ __launch_bounds__(256) void tail_parts_kernel(const float* __restrict
 hipError_t launch_tail_parts(const float* part, int slices, size_t slice_stride, int M, const float* bias, const float* res, int res_ld,
                              const float* fc_w, const float* fc_b, float* logits, float* trans, float* rot, const double* poseA,
                              double* poseB, double tn, double rn, int n, hipStream_t st, float* fcpart, int* arrive, int* done_flag,
-                             int done_seq, int ch) {
+                             int done_seq, int ch, const ImgParams* img) {
   if (slices != 8 || (ch != 16 && ch != 32)) return hipErrorInvalidValue;
-  if (ch == 16)
+  ImgParams none{};
+  if (img) {
+    if (ch != 16 || n > SMALL_MAX_IMG) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((tail_parts_kernel<16, 8, true>), dim3(n * 64), dim3(256), 0, st, part, slice_stride, M, bias, res, res_ld, fc_w,
+                       fc_b, logits, trans, rot, poseA, poseB, tn, rn, fcpart, arrive, done_flag, done_seq, *img);
+  } else if (ch == 16)
     hipLaunchKernelGGL((tail_parts_kernel<16, 8>), dim3(n * 64), dim3(256), 0, st, part, slice_stride, M, bias, res, res_ld, fc_w, fc_b,
-                       logits, trans, rot, poseA, poseB, tn, rn, fcpart, arrive, done_flag, done_seq);
+                       logits, trans, rot, poseA, poseB, tn, rn, fcpart, arrive, done_flag, done_seq, none);
   else
     hipLaunchKernelGGL((tail_parts_kernel<32, 8>), dim3(n * 32), dim3(256), 0, st, part, slice_stride, M, bias, res, res_ld, fc_w, fc_b,
-                       logits, trans, rot, poseA, poseB, tn, rn, fcpart, arrive, done_flag, done_seq);
+                       logits, trans, rot, poseA, poseB, tn, rn, fcpart, arrive, done_flag, done_seq, none);
   return hipGetLastError();
 }
 

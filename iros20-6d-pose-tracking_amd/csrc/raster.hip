@@ -50,6 +50,10 @@ __device__ __forceinline__ RasterArgs raster_instance(const RasterArgs& a0) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) a.light[k] = I->light[k];
     a.dA = I->dA; a.dB = I->dB;
+    if (a0.inst_mesh) {   // several meshes in one launch: this instance's own (strides below stay those of the largest V / F)
+      a.verts = I->verts; a.normals = I->normals; a.colors = I->colors; a.faces = I->faces;
+      a.V = I->V; a.F = I->F;
+    }
     const size_t px = (size_t)a0.rw * a0.rh;
     a.vpost += b * a0.V; a.vsnap += b * a0.V;
     a.zbuf += b * px;

@@ -132,6 +132,20 @@ constexpr int IN_PAD = 3;
 constexpr int IN_P = RES + 2 * IN_PAD;  // 182
 constexpr int IN_SLACK_ROWS = 6;
 constexpr int SE3TN_SPLITK_MAX_TILES = 1024;   // output tiles (m tile x group x n tile) of a split-K launch with the fused reduction
+// batch 1-5 kernel family: most pairs a launch takes (stem + pool, trunk convs, channel-slice convs, and so the per-image tables below)
+#ifndef SE3TN_SLICES_SMALL_MAX_N
+#define SE3TN_SLICES_SMALL_MAX_N 5   // up to this many pairs the 128 .. 512-channel convs take conv_slices_small_kernel (0: never)
+#endif
+constexpr int SMALL_MAX_IMG = 5;
+static_assert(SE3TN_SLICES_SMALL_MAX_N <= SMALL_MAX_IMG, "the per-image tables hold SMALL_MAX_IMG entries");
+// Mixed-model launches of the batch 1-5 family (se3tn_on_track_objects): image i of a launch reads every weight / bias / FC tensor
+// img_off[i] floats away from the launch's own pointers (all blobs share one layout, so one offset per image serves every tensor),
+// and its pose update takes tn[i] / rn[i].  The offset is looked up once per workgroup from the image index of blockIdx (a scalar
+// load); the kernels take it through a template switch, so the single-model instantiations are the code they were.
+struct ImgParams {
+  long long off[SMALL_MAX_IMG];
+  double tn[SMALL_MAX_IMG], rn[SMALL_MAX_IMG];
+};
 struct ConvArgs {
   const float* in;    // padded NHWC, `in_ld` floats per pixel; channel offset already applied
   const float* w;     // packed panels of group 0
@@ -161,6 +175,9 @@ struct ConvArgs {
   const float* wscale;
   int* overflow;
   int fast;
+  // mixed-model batch (batch 1-5 family only): per_img != 0 => image i reads w / bias at img_off[i] floats from them (ImgParams)
+  int per_img = 0;
+  long long img_off[SMALL_MAX_IMG] = {};
 };
 
 // Winograd F(m x m,3x3) path of the stride-1 256/512-channel convs at large batch (wino_mfma.hip)
@@ -214,6 +231,9 @@ struct CropArgs {  // one launch handles up to MAX crops
   int split;    // f16x3 mode: a pixel is stored as 4 x f16 hi | 4 x f16 lo (same 16 bytes)
   int offset_rule;  // SE3TN_OFFSET_RULE_*: how `depth -= z` rounds (NumPy 1.x: one float32 operation; NumPy 2: float64, rounded once)
   int* overflow;
+  // nullptr: every crop normalises with mean / stdv above.  Otherwise a DEVICE table [n_first][16] (mean[8] | std[8] per object):
+  // crop i normalises with row (i < n_first ? i : i - n_first) -- several models' crops in one launch (se3tn_on_track_objects)
+  const double* norm = nullptr;
 };
 
 static_assert(sizeof(CropArgs) <= 4096, "CropArgs travels as kernel arguments: HIP's limit is 4 KB");
@@ -268,12 +288,16 @@ hipError_t launch_stem_pool_small(const float* inA, const float* inB, const floa
 // the 64 -> 64 trunk convs at batch 1-5 without a K split (conv64_small.hip)
 hipError_t launch_conv64_small(const ConvArgs& a, int n, int epi, hipStream_t st);
 // the 128 .. 512-channel convs at batch 1-5: 128 pixels x 32 couts x one channel slice with all nine taps per workgroup
-// (conv_slices_small.hip); partial sums for conv_reduce_kernel
-#ifndef SE3TN_SLICES_SMALL_MAX_N
-#define SE3TN_SLICES_SMALL_MAX_N 5   // up to this many pairs the 128 .. 512-channel convs take conv_slices_small_kernel (0: never)
-#endif
+// (conv_slices_small.hip); partial sums for conv_reduce_kernel (SE3TN_SLICES_SMALL_MAX_N: above)
 int conv_slices_small_count(int cin, int stride, int H);
 hipError_t launch_conv_slices_small(const ConvArgs& a, int cin, int stride, hipStream_t st);
+// one conv of the batch 1-5 family, chosen explicitly (no fall-back): conv64_small for the 64-channel trunk, otherwise
+// conv_slices_small + conv_reduce_kernel (a.skip_reduce: the caller consumes the partial sums).  hipErrorInvalidValue when the
+// family has no kernel for the shape or the batch (conv3x3_mfma.hip)
+hipError_t launch_conv_small(const ConvArgs& a, int cin, int cout, int stride, int epi, hipStream_t st);
+// stem + max-pool with a per-image weight offset table (ImgParams::off; nullptr = the single-model kernel)
+hipError_t launch_stem_pool_small_multi(const float* inA, const float* inB, const float* w, const float* bias, float* pool, int n,
+                                        const long long* img_off, hipStream_t st);
 hipError_t launch_tail(const float* head, const float* fc_w, const float* fc_b, float* logits,
                        float* trans, float* rot, const double* poseA, double* poseB, double tn,
                        double rn, int n, hipStream_t st, float* fcpart, int* arrive, int* done_flag = nullptr, int done_seq = 0);
@@ -281,7 +305,7 @@ hipError_t launch_tail(const float* head, const float* fc_w, const float* fc_b, 
 hipError_t launch_tail_parts(const float* part, int slices, size_t slice_stride, int M, const float* bias, const float* res, int res_ld,
                              const float* fc_w, const float* fc_b, float* logits, float* trans, float* rot, const double* poseA,
                              double* poseB, double tn, double rn, int n, hipStream_t st, float* fcpart, int* arrive, int* done_flag = nullptr,
-                             int done_seq = 0, int ch = 16);
+                             int done_seq = 0, int ch = 16, const ImgParams* img = nullptr);
 // padded [n,h+2,w+2,c] NHWC interior -> [n,c,h,w]
 // split != 0: the source holds split rows (32 f16 hi | 32 f16 lo per 32-channel chunk)
 hipError_t launch_padded_nhwc_to_nchw(const float* in, float* out, int n, int h, int w, int c, int split,
@@ -295,6 +319,10 @@ struct RasterInstance {
   float light[3];
   float _pad;
   double dA, dB;
+  // RasterArgs::inst_mesh != 0 (several meshes in one launch, se3tn_on_track_objects): this instance's mesh and its counts
+  const float *verts, *normals, *colors;
+  const int* faces;
+  int V, F;
 };
 struct RasterArgs {
   const RasterInstance* inst;  // nullptr: one instance, uniforms below.  Otherwise instance b = blockIdx.y takes PV / light / dA / dB from
@@ -323,6 +351,8 @@ struct RasterArgs {
   int tw, th, tlevels;
   unsigned tex_off[16];  // byte offset of every mip level
   float kd[3];           // base colour factor (mtl Kd)
+  int inst_mesh = 0;     // batched launch: 1 = every instance brings its own mesh (RasterInstance verts .. F); V / F above are then
+                         // the LARGEST counts (grid and scratch strides), and threads past their own instance's counts exit
 };
 hipError_t launch_raster(const RasterArgs& a, hipStream_t st, int instances = 1);
 

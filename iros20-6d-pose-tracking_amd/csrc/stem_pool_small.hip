@@ -44,6 +44,7 @@ struct StemPoolArgs {
   const float* bias;    // [2][64]
   float* pool;          // [n,46,46,128] zero-bordered, branch A in channels 0-63, B in 64-127
   int n;
+  long long img_off[SMALL_MAX_IMG];   // PI: image i's w / bias lie img_off[i] floats from w / bias (ImgParams)
 };
 
 // tap (r, s) of weight slot e (weights.cpp: pack_stem)
@@ -112,6 +113,7 @@ __device__ __forceinline__ void sp_mma(const float4 (&w)[SP_GROUPS], const SpOpe
   }
 }
 
+template <bool PI>   // PI: per-image weights (mixed-model batch); false = the single-model kernel
 __global__ __launch_bounds__(256) void stem_pool_small_kernel(const StemPoolArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[SP_PATCH_BYTES + 81 * 64 * 4];
   float* patch = reinterpret_cast<float*>(smem);
@@ -124,6 +126,7 @@ __global__ __launch_bounds__(256) void stem_pool_small_kernel(const StemPoolArgs
   const int R0 = ti == 0 ? 0 : 8 * ti - 1, C0 = tj == 0 ? 0 : 8 * tj - 1;   // first stem row / column of the 9 x 9 window
   const float* __restrict__ in = a.in[br] + ((size_t)img * SP_IP * SP_IP + (size_t)(2 * R0) * SP_IP + 2 * C0) * 4;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(patch));
+  const long long woff = PI ? a.img_off[img] : 0;   // (img = blockIdx.y: a scalar load)
 
   // ---- the 23 x 23 input patch (529 pixels of 16 bytes), as it lies
 #pragma unroll
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(256) void stem_pool_small_kernel(const StemPoolArgs
   const int kk = lane >> 4;
   float4 w[SP_GROUPS];
   {
-    const float* wp = a.w + ((size_t)br * 64 + wid * 16 + (lane & 15)) * SP_WROW + kk * 4;
+    const float* wp = a.w + woff + ((size_t)br * 64 + wid * 16 + (lane & 15)) * SP_WROW + kk * 4;
 #pragma unroll
     for (int g = 0; g < SP_GROUPS - 1; ++g) w[g] = *reinterpret_cast<const float4*>(wp + g * 16);
     w[SP_GROUPS - 1] = kk == 0 ? *reinterpret_cast<const float4*>(wp + (SP_GROUPS - 1) * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(256) void stem_pool_small_kernel(const StemPoolArgs
   for (int g = 0; g < SP_GROUPS; ++g)
     off[g] = kk == 0 ? sp_slot_off(4 * g) : kk == 1 ? sp_slot_off(4 * g + 1) : kk == 2 ? sp_slot_off(4 * g + 2) : sp_slot_off(4 * g + 3);
   const int c = wid * 16 + (lane >> 4) * 4;              // the four couts this lane ends with
-  const float4 bias = *reinterpret_cast<const float4*>(a.bias + br * 64 + c);
+  const float4 bias = *reinterpret_cast<const float4*>(a.bias + woff + br * 64 + c);
   SP_TRACE(1)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -229,9 +232,20 @@ extern "C" int se3tn_debug_trace_stem(unsigned long long* out) {
 
 hipError_t launch_stem_pool_small(const float* inA, const float* inB, const float* w, const float* bias, float* pool, int n,
                                   hipStream_t st) {
-  StemPoolArgs a;
+  StemPoolArgs a{};
   a.in[0] = inA; a.in[1] = inB; a.w = w; a.bias = bias; a.pool = pool; a.n = n;
-  hipLaunchKernelGGL(stem_pool_small_kernel, dim3(121, n, 2), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(stem_pool_small_kernel<false>, dim3(121, n, 2), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_stem_pool_small_multi(const float* inA, const float* inB, const float* w, const float* bias, float* pool, int n,
+                                        const long long* img_off, hipStream_t st) {
+  if (!img_off) return launch_stem_pool_small(inA, inB, w, bias, pool, n, st);
+  if (n < 1 || n > SMALL_MAX_IMG) return hipErrorInvalidValue;
+  StemPoolArgs a{};
+  a.in[0] = inA; a.in[1] = inB; a.w = w; a.bias = bias; a.pool = pool; a.n = n;
+  for (int i = 0; i < n; ++i) a.img_off[i] = img_off[i];
+  hipLaunchKernelGGL(stem_pool_small_kernel<true>, dim3(121, n, 2), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

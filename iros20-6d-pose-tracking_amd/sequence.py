@@ -242,6 +242,60 @@ def get_results_ycb(tracker, ycb_dir, class_id, out_dir, seq_ids=YCB_TEST_SEQUEN
     return done
 
 
+def get_results_ycb_objects(trackers_by_class, ycb_dir, out_dirs_by_class, seq_ids=YCB_TEST_SEQUENCES, max_frames=None,
+                            multi_tracker=None):
+    """Extension: get_results_ycb (GT initialisation) for SEVERAL classes at once, the way a YCB-Video frame shows them.  Within each
+    sequence every listed class that has pose_gt/<class_id>/ advances together, frame by frame, through ONE
+    ``MultiTracker.on_track`` call per frame (se3tn_on_track_objects: each class with its own tracker's weights, normalisation and
+    mesh), and every frame is read once.  Per class the files written are exactly those of
+    ``get_results_ycb(trackers_by_class[c], ycb_dir, c, out_dirs_by_class[c], seq_ids, max_frames)``: the library gives every object
+    the bits its own tracker gives it.  multi_tracker: factory ``trackers -> object with on_track(prev_poses, rgb, depth)`` (default
+    MultiTracker on the trackers' device).  Returns {class_id: {seq_id: n_poses}}."""
+    classes = list(trackers_by_class)
+    if set(classes) != set(out_dirs_by_class):
+        raise ValueError("trackers_by_class and out_dirs_by_class must name the same classes")
+    if multi_tracker is None:
+        from .tracker import MultiTracker
+
+        def multi_tracker(trackers):
+            return MultiTracker(trackers, device=int(trackers[0].engine.device))
+    multis = {}
+    done = {c: {} for c in classes}
+    root = os.path.join(ycb_dir, "data_organized")
+    for seq_dir in sorted(glob.glob(os.path.join(root, "*"))):
+        present = [c for c in classes if os.path.isdir(os.path.join(seq_dir, "pose_gt", str(c)))]
+        if not present:
+            continue
+        seq_id = int(os.path.basename(seq_dir))
+        if seq_ids is not None and seq_id not in seq_ids:
+            continue
+        rgb_files = sorted(glob.glob(os.path.join(seq_dir, "color", "*")))
+        depth_files = sorted(glob.glob(os.path.join(seq_dir, "depth_filled", "*")))
+        prev = []
+        for c in present:
+            gt_files = sorted(glob.glob(os.path.join(seq_dir, "pose_gt", str(c), "*")))
+            assert len(rgb_files) == len(depth_files) == len(gt_files) > 0, "incomplete sequence directory %s" % seq_dir
+            prev.append(np.loadtxt(gt_files[0]))
+        n = len(rgb_files) if max_frames is None else min(len(rgb_files), max_frames)
+        key = tuple(present)
+        if key not in multis:
+            multis[key] = multi_tracker([trackers_by_class[c] for c in present])
+        mt = multis[key]
+        pred = [[p] for p in prev]
+        for i in range(1, n):
+            poses = mt.on_track(np.stack(prev), read_rgb(rgb_files[i]), read_depth_mm(depth_files[i]))
+            prev = [np.array(p, np.float64) for p in poses]
+            for k, p in enumerate(prev):
+                pred[k].append(p)
+        for k, c in enumerate(present):
+            sdir = os.path.join(out_dirs_by_class[c], "seq%d" % seq_id)
+            os.makedirs(sdir, exist_ok=True)
+            for i, p in enumerate(pred[k]):
+                np.savetxt(os.path.join(sdir, "%07d.txt" % i), p)
+            done[c][seq_id] = len(pred[k])
+    return done
+
+
 def eval_one_class(res_dir, ycb_dir, class_id):
     """eval_ycb.py:67-119: ADD / ADD-S AUC (x100) of the keyframe poses found under res_dir/seq*/,
     against <ycb_dir>/data_organized/%04d/pose_gt/<class_id>/%06d.txt, with the class's

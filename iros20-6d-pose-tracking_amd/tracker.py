@@ -326,3 +326,88 @@ class Tracker:
         self.last_prediction = dict(trans=trans_h, rot=rot_h, bbox=np.stack(bboxes), rgbA=keep[0::4], depthA=keep[1::4])
         self.frame_cnt += 1
         return out
+
+
+class MultiTracker:
+    """Extension: several DIFFERENT objects in one camera frame, one library call per frame.  se(3)-TrackNet is trained per object
+    (every YCB-Video class has its own weights, mean / std, normalisers and mesh: one ``Tracker`` each); a frame shows several of
+    them.  ``on_track(prev_poses, rgb, depth)`` advances all of them through se3tn_on_track_objects: image A of every object in four
+    rasteriser launches, the frame's crop windows in one upload, the network in chunks of <= 5 objects on the batch 1-5 kernel family
+    with every object reading its own tracker's weights -- object i gets exactly the bits ``trackers[i].on_track`` gives it.
+    The trackers are used as they are (their weights, normalisation and meshes stay where they live; nothing is copied); they must
+    render image A with the built-in vertex-colour rasteriser.  The MultiTracker owns one executing ``Engine`` of
+    max_batch = len(trackers) (workspaces, staging)."""
+
+    def __init__(self, trackers, device=0):
+        from .renderer import HipRenderer
+        import ctypes as C
+        from ._lib import Object
+        trackers = list(trackers)
+        if not trackers:
+            raise ValueError("MultiTracker: no trackers")
+        for i, t in enumerate(trackers):
+            if not isinstance(t.renderer, HipRenderer) or t.renderer.full_frame:
+                raise ValueError("MultiTracker: tracker %d does not render image A with the built-in vertex-colour rasteriser (an "
+                                 "injected or full-frame renderer): track it with its own on_track" % i)
+            if int(t.engine.device) != int(device):
+                raise ValueError("MultiTracker: tracker %d lives on device %d, not %d" % (i, t.engine.device, device))
+            if not np.array_equal(np.asarray(t.K, np.float64), np.asarray(trackers[0].K, np.float64)):
+                raise ValueError("MultiTracker: tracker %d has another camera matrix than tracker 0 (one camera frame per call)" % i)
+        self.trackers = trackers
+        self.n = len(trackers)
+        self.engine = Engine(device, self.n)
+        self.K = np.ascontiguousarray(trackers[0].K, np.float64)
+        self._dev = "cuda:%d" % device
+        self._objs = (Object * self.n)(*[Object(t.engine._h.value, t.renderer._m.value, float(t.object_width)) for t in trackers])
+        self._rgbA = torch.empty((self.n, 176, 176, 3), dtype=torch.uint8, device=self._dev)
+        self._depthA = torch.empty((self.n, 176, 176), dtype=torch.int16, device=self._dev)
+        self._C = C
+        self.last_prediction = None
+        self.frame_cnt = 0
+
+    def on_track(self, prev_poses, rgb, depth, rgbA_out=None, depthA_out=None, bbox_out=None):
+        """prev_poses: n 4x4 poses (object i = trackers[i]); rgb HxWx3 uint8, depth HxW millimetres: ONE camera frame.
+        Returns [n,4,4] float64.  rgbA_out / depthA_out: optional device tensors uint8 [n,176,176,3] / 16-bit [n,176,176] that receive
+        the images A (default: the MultiTracker's own, kept in last_prediction); bbox_out: optional host int32 [n,4,2] array that
+        receives compute_bbox's corners."""
+        C = self._C
+        from ._lib import check
+        from .engine import _stream_ptr
+        n = self.n
+        poses = np.ascontiguousarray(np.asarray(prev_poses, np.float64).reshape(-1, 16))
+        if poses.shape[0] != n:
+            raise ValueError("MultiTracker.on_track: %d poses for %d objects" % (poses.shape[0], n))
+        rgb = rgb if (type(rgb) is np.ndarray and rgb.dtype == np.uint8 and rgb.flags.c_contiguous) else np.ascontiguousarray(rgb, dtype=np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("rgb must be HxWx3 uint8")
+        dep = depth if (type(depth) is np.ndarray and depth.dtype == np.uint16 and depth.flags.c_contiguous
+                        and depth.shape == rgb.shape[:2]) else _depth_u16(depth, rgb)
+        rA, dA = self._rgbA, self._depthA
+        if rgbA_out is not None:
+            if tuple(rgbA_out.shape) != (n, 176, 176, 3) or rgbA_out.dtype != torch.uint8 or not rgbA_out.is_cuda or not rgbA_out.is_contiguous():
+                raise ValueError("rgbA_out must be a contiguous device uint8 tensor [n,176,176,3]")
+            rA = rgbA_out
+        if depthA_out is not None:
+            if tuple(depthA_out.shape) != (n, 176, 176) or depthA_out.element_size() != 2 or not depthA_out.is_cuda or not depthA_out.is_contiguous():
+                raise ValueError("depthA_out must be a contiguous 16-bit device tensor [n,176,176]")
+            dA = depthA_out
+        bb = bbox_out if bbox_out is not None else np.empty((n, 4, 2), np.int32)
+        if bb.shape != (n, 4, 2) or bb.dtype != np.int32 or not bb.flags.c_contiguous:
+            raise ValueError("bbox_out must be a contiguous int32 array [n,4,2]")
+        # the call runs under the trackers' offset / raster rules (the library refuses models whose rules differ from the executing ctx's)
+        t0 = self.trackers[0].engine
+        self.engine.set_offset_rule(t0.get_offset_rule())
+        self.engine.set_raster_rule(t0.get_raster_rule())
+        out = np.empty((n, 16), np.float64)
+        tr, ro = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        check(self.engine.lib.se3tn_on_track_objects(
+            self.engine._h, n, self._objs, C.c_void_p(poses.ctypes.data), self.K.ctypes.data_as(C.POINTER(C.c_double)),
+            C.c_void_p(rgb.ctypes.data), C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]), C.c_void_p(rA.data_ptr()),
+            C.c_void_p(dA.data_ptr()), C.c_void_p(out.ctypes.data), C.c_void_p(tr.ctypes.data), C.c_void_p(ro.ctypes.data),
+            C.c_void_p(bb.ctypes.data), _stream_ptr()), "se3tn_on_track_objects")
+        self.last_prediction = dict(trans=tr, rot=ro, bbox=bb, rgbA=list(rA), depthA=list(dA))
+        self.frame_cnt += 1
+        return out.reshape(n, 4, 4)
+
+    def close(self):
+        self.engine.close()
