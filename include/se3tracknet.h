@@ -289,7 +289,10 @@ int se3tn_on_track_batch(se3tn_ctx* ctx, se3tn_mesh* mesh, int n, const double* 
  * rasteriser launches (grid.y = object, each instance with its own mesh), the frame's n crop windows go up in one copy, and the network
  * runs in chunks of at most 5 objects, ALWAYS through the batch 1-5 kernel family (whatever ctx's Winograd / trunk settings): every
  * kernel of that family works image by image, here with each image's own weights, so object i gets exactly the bits se3tn_on_track on
- * its own model context gives it -- whatever n, the chunking, the order or the company.  Outputs (host) as se3tn_on_track_batch:
+ * its own model context gives it while that context runs one pair through the same family (its default) -- whatever n, the chunking,
+ * the order or the company.  A model context set to take another route at one pair (se3tn_set_winograd / se3tn_set_trunk_winograd
+ * thresholds of 1, se3tn_set_small_kernels(0), SE3TN_PREC_F16X3, developer switches) gets other bits from se3tn_on_track, within
+ * float32 tolerance.  Outputs (host) as se3tn_on_track_batch:
  * pose_out [n,16], trans_out / rot_out [n,3] and bbox_vu [n,4,2] (may be NULL); rgbA_dev / depthA_dev optional device [n,176,176,3] /
  * [n,176,176].  1 <= n <= se3tn_max_batch(ctx).  SYNCHRONOUS on `stream`, refused inside a stream capture; the first call (a larger n,
  * mesh or frame) allocates.
@@ -332,7 +335,10 @@ int se3tn_pose_update_host(const double poseA[16], const float trans[3], const f
  * names: "inA" "inB" [n,182,182,4] (3-pixel zero border), "stem" [n,88,88,128]; the conv activations carry a one-pixel
  * zero border: "pool" "t64" "q64" [n,46,46,128] (channels 0-63 branch A, 64-127 branch B),
  * "ab" "ab_t" [n,24,24,256], "head" "head_t" [n,13,13,1024] (0-511 trans, 512-1023 rot).
- * dims = {H, W, C} as stored (borders included). */
+ * dims = {H, W, C} as stored (borders included).  A stage the last se3tn_infer (or se3tn_on_track_objects, or the graph it
+ * replayed) did NOT write is refused with SE3TN_E_STATE instead of handing out an older call's data: "stem" after the batch 1-5
+ * stem + pool kernel, "ab_t" / "head_t" / "head" after the fused Winograd blocks, "head" when the tail added the last head conv's
+ * partial sums itself (see se3tn_keep_intermediates).  "inA" / "inB" are always handed out (se3tn_preprocess fills them too). */
 int se3tn_debug_buffer(se3tn_ctx* ctx, const char* name, const float** ptr, int32_t dims[3]);
 /* The fused Winograd blocks (batches of n >= the se3tn_set_winograd threshold) keep the activation between a
  * residual block's two convolutions in LDS and reduce the heads' last activation in registers: "ab_t", "head_t"

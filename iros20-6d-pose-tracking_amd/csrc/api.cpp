@@ -46,8 +46,11 @@ struct GraphEntry {
   GraphKey key;
   hipGraphExec_t exec = nullptr;  // null: seen once (run eagerly, which also sets the kernels' LDS attributes)
   bool fast = false;
-  const float* head_final = nullptr;
+  unsigned written = 0;   // the stages the captured sequence writes (se3tn_ctx::written)
 };
+// the activation buffers se3tn_debug_buffer hands out, as bits of se3tn_ctx::written
+enum : unsigned { STAGE_STEM = 1, STAGE_POOL = 2, STAGE_T64 = 4, STAGE_Q64 = 8, STAGE_AB = 16, STAGE_AB_T = 32, STAGE_HEAD = 64,
+                  STAGE_HEAD_T = 128 };
 
 struct se3tn_ctx {
   int device = -1, max_batch = 0;
@@ -65,7 +68,7 @@ struct se3tn_ctx {
   float *head = nullptr, *head_t = nullptr;     // [mb,13,13,1024]
   float* head_f = nullptr;                      // f16x3 mode: float32 output of the last head conv (the
                                                 // in-place residual update cannot change format)
-  const float* head_final = nullptr;            // what the tail of the last infer read
+  unsigned written = 0;                         // STAGE_* the last infer wrote (the others hold older data: se3tn_debug_buffer refuses them)
   float* logits = nullptr;                      // [mb,6]
   float* fcpart = nullptr;                      // [mb,2,<=32,3] partial FC dot products (fused Winograd tail: 8 slices per head; tail_kernel 8; tail_parts_kernel 32)
   bool keep_intermediates = false;              // se3tn_keep_intermediates: fused blocks also store ab_t / head_t / head
@@ -685,6 +688,18 @@ static const char* algo_name(const char* name, int tile, bool fused_block = fals
   }
   return it->second.c_str();
 }
+// ... and the direct family's: "convAB1 s2 [slices]", "[split-K]", "[slab f16x3]" (keyed by the literal's address: no string work on a hit)
+static const char* direct_name(const char* name, const ConvRoute& r, bool fast) {
+  static const char* const tags[] = {"", "conv64 small", "slices", "split-K", "slab", "gather"};
+  if (r.algo < ConvRoute::SMALL64 || r.algo > ConvRoute::GATHER) return name;
+  static std::mutex mu;
+  static std::map<std::pair<const char*, int>, std::string> names;
+  std::lock_guard<std::mutex> lk(mu);
+  auto key = std::make_pair(name, (int)r.algo * 2 + (fast ? 1 : 0));
+  auto it = names.find(key);
+  if (it == names.end()) it = names.emplace(key, std::string(name) + " [" + tags[r.algo] + (fast ? " f16x3]" : "]")).first;
+  return it->second.c_str();
+}
 
 static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int layout, float* trans, float* rot,
                         const double* poseA, double* poseB, void* stream);
@@ -736,7 +751,7 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
         return fail(SE3TN_E_STATE, "se3tn_infer: the input buffers were filled under a different precision mode");
       HIPCHK(hipGraphLaunch(g.exec, st));
       c->last_fast = g.fast;
-      c->head_final = g.head_final;
+      c->written = g.written;
       return SE3TN_OK;
     }
     // second sighting: capture
@@ -750,7 +765,7 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
     (void)hipGraphDestroy(graph);
     if (e2 != hipSuccess) { g.exec = nullptr; return hipfail(e2, "hipGraphInstantiate"); }
     g.fast = c->last_fast;
-    g.head_final = c->head_final;
+    g.written = c->written;
     HIPCHK(hipGraphLaunch(g.exec, st));
     return SE3TN_OK;
   }
@@ -805,9 +820,12 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   const SplitLayout& SL = c->SL;
   const bool fast = c->prec == SE3TN_PREC_F16X3;  // both the big-tile and the split-K kernels
   c->last_fast = fast;
+  c->written = 0;          // (until this sequence has been enqueued in full)
+  unsigned written = STAGE_POOL | STAGE_T64 | STAGE_Q64 | STAGE_AB;   // every route writes these; the others are added where they are
   // batch 1-2 (the per-frame regime): stem + max-pool of both branches in ONE launch of 16-pool-pixel tiles; the 88 x 88 x 128 stem
   // map is not stored, so a caller who asked for the intermediates gets the batch-64 pair
   const bool small_stem = c->small_kernels && !want_split && !c->keep_intermediates && n <= SE3TN_STEM_SMALL_MAX_N;
+  if (!small_stem) written |= STAGE_STEM;
   if (small_stem) {
     HIPCHK(launch_stem_pool_small(A, B, W + L.stem_w, W + L.stem_b, c->pool, n, st));
     HIPCHK((hipError_t)prof_mark(c, st, "stem7x7 + maxpool [small tiles]", false));
@@ -823,14 +841,17 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     HIPCHK((hipError_t)prof_mark(c, st, "maxpool3x3s2", false));
   }
 
-  bool skip_reduce = false;   // set around the last head conv when tail_parts_kernel consumes its partial sums
+  bool skip_reduce = false;   // set around the last head conv: tail_parts_kernel MAY consume its partial sums (what happened: `route`)
+  ConvRoute route;            // the algorithm the last conv() took
   auto conv = [&](ConvId id, const float* in, int in_ld, int in_gs, const float* res, int res_ld, int res_gs,
                   float* out, int out_ld, int out_gs, int hin, int stride, int epi, const char* name) -> int {
     const Conv3& s = conv_specs()[id];
     const int ws = wino_slot(id);
     const int wtile = tile_for(c, n, ws >= 2 ? 1 : 0);
     const bool u_ready = wtile == 6 ? (c->wino_u6[0] && c->wino6_blob == c->blob) : (c->wino_tile_derived == wtile);
+    route = ConvRoute{};
     if (ws >= 0 && !fast && c->wino_min_batch > 0 && n >= c->wino_min_batch && c->wino_v && u_ready) {
+      route.algo = ConvRoute::WINO;
       WinoArgs w{};
       w.in = in; w.U = wtile == 6 ? c->wino_u6[ws] : c->wino_u[ws]; w.bias = W + L.conv_b[id]; w.res = res; w.out = out;
       w.V = c->wino_v; w.Mw = c->wino_m;
@@ -848,6 +869,7 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     }
     if (id <= L64_4 && !fast && wino64_pays(c, n, s.groups) && c->wino64_blob == c->blob && stride == 1 && hin == S2 && epi != 2) {
       const int slot64 = (int)id - (int)L64_1;
+      route.algo = ConvRoute::WINO64;
       hipError_t e = launch_wino64(in, in_ld, in_gs, c->wino64_u[slot64], (long long)16 * s.cin * s.cout, W + L.conv_b[id], s.cout, res,
                                    res_ld, res_gs, out, out_ld, out_gs, n, s.groups, epi, c->trunk_kernel, st);
       if (e != hipSuccess) return hipfail(e, name);
@@ -872,9 +894,9 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     a.groups = s.groups;
     a.in_gs = in_gs; a.res_gs = res_gs; a.out_gs = out_gs; a.bias_gs = s.cout;
     a.w_gs = (long long)conv3_words(s.cin, s.cout);
-    hipError_t e = launch_conv3x3(a, s.cin, s.cout, stride, epi, st);
+    hipError_t e = launch_conv3x3(a, s.cin, s.cout, stride, epi, st, &route);
     if (e != hipSuccess) return hipfail(e, name);
-    return prof_mark(c, st, name, true);
+    return prof_mark(c, st, c->prof ? direct_name(name, route, fast) : name, true);
   };
   int rc;
   // 64-channel trunk: pool = a0|b0 ; t64 scratch ; q64 = a1|b1 -> a1|b2 (== torch.cat((a,b),1))
@@ -928,40 +950,42 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   // traffic) and lose to the direct f16x3 kernels (0.247 vs 0.220 ms at batch 64); the 512-channel heads win (0.349 vs 0.427 ms)
   if (block_ok(0) && !fast) {
     if ((rc = block(LAB2_1, LAB2_2, c->ab, c->ab_t, 256, 0, S3, nullptr, "convAB2.conv1", "convAB2.conv2"))) return rc;
+    if (c->keep_intermediates) written |= STAGE_AB_T;
   } else {
     if ((rc = conv(LAB2_1, c->ab, 256, 0, nullptr, 0, 0, c->ab_t, 256, 0, S3, 1, 0, "convAB2.conv1"))) return rc;
     if ((rc = conv(LAB2_2, c->ab_t, 256, 0, c->ab, 256, 0, c->ab, 256, 0, S3, 1, 1, "convAB2.conv2"))) return rc;
+    written |= STAGE_AB_T;
   }
   if ((rc = conv(LH1, c->ab, 256, 0, nullptr, 0, 0, c->head, 1024, 0, S3, 2, 2, "trans|rot conv1 s2"))) return rc;
   if (block_ok(1)) {
     TailArgs tl{W + L.fc_w, W + L.fc_b, c->logits, c->fcpart, trans, rot, poseA, poseB, c->tn, c->rn};
     if ((rc = block(LH2_1, LH2_2, c->head, c->head_t, 1024, 512, S4, &tl, "trans|rot conv2.conv1",
                     "trans|rot conv2.conv2 + avgpool+fc+tanh+pose"))) return rc;
-    c->head_final = fast ? c->head_f : c->head;
+    if (c->keep_intermediates) written |= STAGE_HEAD_T | STAGE_HEAD;
   } else {
     if ((rc = conv(LH2_1, c->head, 1024, 512, nullptr, 0, 0, c->head_t, 1024, 512, S4, 1, 0, "trans|rot conv2.conv1"))) return rc;
+    written |= STAGE_HEAD_T;
     float* head_out = fast ? c->head_f : c->head;
-    // batch 1-5 (conv_slices_small: 8 partial-sum slices per output): the tail adds the slices itself -- no conv_reduce launch, the
-    // final head map is not written (se3tn_keep_intermediates keeps the old sequence).  Same predicate as launch_conv3x3's.
-    const bool parts_tail = !fast && c->small_kernels && c->tail_parts && !c->keep_intermediates && c->part && n <= SE3TN_SLICES_SMALL_MAX_N &&
-                            conv_slices_small_count(512, 1, S4) == 8 &&
-                            (size_t)8 * 2 * n * S4 * S4 * 512 * sizeof(float) <= c->part_bytes && !c->splitk_fused;
-    skip_reduce = parts_tail;
+    // batch 1-5 (conv_slices_small: 8 partial-sum slices per output) may leave the slices to the tail -- no conv_reduce launch, the final
+    // head map not written (se3tn_keep_intermediates keeps it).  Whether it did is what launch_conv3x3 reports: any other route the conv
+    // takes (Winograd, split-K, ...) writes head_out and ignores the permission.
+    skip_reduce = c->tail_parts && !c->keep_intermediates;
     rc = conv(LH2_2, c->head_t, 1024, 512, c->head, 1024, 512, head_out, 1024, 512, S4, 1, 1, "trans|rot conv2.conv2");
     skip_reduce = false;
     if (rc) return rc;
-    if (parts_tail) {
-      c->head_final = nullptr;     // (not materialised in this configuration)
+    if (route.algo == ConvRoute::SLICES && !route.reduced) {
       const int M = n * S4 * S4;
-      HIPCHK(launch_tail_parts(c->part, 8, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head, 1024, W + L.fc_w, W + L.fc_b, c->logits, trans,
-                               rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart, c->tail_arrive, c->tail_flag, c->tail_seq, c->tail_parts_ch));
+      HIPCHK(launch_tail_parts(c->part, route.slices, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head, 1024, W + L.fc_w, W + L.fc_b,
+                               c->logits, trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart, c->tail_arrive, c->tail_flag, c->tail_seq,
+                               c->tail_parts_ch));
       HIPCHK((hipError_t)prof_mark(c, st, "tail slices+avgpool+fc+tanh+pose", false));
     } else {
-      c->head_final = head_out;
+      written |= STAGE_HEAD;
       HIPCHK(launch_tail(head_out, W + L.fc_w, W + L.fc_b, c->logits, trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart, c->tail_arrive, c->tail_flag, c->tail_seq));
       HIPCHK((hipError_t)prof_mark(c, st, "tail avgpool+fc+tanh+pose", false));
     }
   }
+  c->written = written;
   if (c->prof) c->slot_launches[slot] = c->n_launch;
   return SE3TN_OK;
 }
@@ -976,14 +1000,17 @@ const float* se3tn_logits(se3tn_ctx* c) { return c ? c->logits : nullptr; }
 
 int se3tn_debug_buffer(se3tn_ctx* c, const char* name, const float** ptr, int32_t dims[3]) {
   if (!c || !name || !ptr || !dims) return fail(SE3TN_E_ARG, "se3tn_debug_buffer: bad argument");
-  struct { const char* n; const float* p; int h, w, ch; } t[] = {
-      {"inA", c->inA, IN_P, IN_P, 4},    {"inB", c->inB, IN_P, IN_P, 4},     {"stem", c->stem, S1, S1, 128},
-      {"pool", c->pool, S2 + 2, S2 + 2, 128},    {"t64", c->t64, S2 + 2, S2 + 2, 128},
-      {"q64", c->q64, S2 + 2, S2 + 2, 128},      {"ab", c->ab, S3 + 2, S3 + 2, 256},
-      {"ab_t", c->ab_t, S3 + 2, S3 + 2, 256},    {"head", c->head_final ? c->head_final : c->head, S4 + 2, S4 + 2, 1024},
-      {"head_t", c->head_t, S4 + 2, S4 + 2, 1024}};
+  struct { const char* n; const float* p; int h, w, ch; unsigned stage; } t[] = {   // (stage 0: the inputs, whoever filled them)
+      {"inA", c->inA, IN_P, IN_P, 4, 0},    {"inB", c->inB, IN_P, IN_P, 4, 0},     {"stem", c->stem, S1, S1, 128, STAGE_STEM},
+      {"pool", c->pool, S2 + 2, S2 + 2, 128, STAGE_POOL},    {"t64", c->t64, S2 + 2, S2 + 2, 128, STAGE_T64},
+      {"q64", c->q64, S2 + 2, S2 + 2, 128, STAGE_Q64},       {"ab", c->ab, S3 + 2, S3 + 2, 256, STAGE_AB},
+      {"ab_t", c->ab_t, S3 + 2, S3 + 2, 256, STAGE_AB_T},    {"head", c->last_fast ? c->head_f : c->head, S4 + 2, S4 + 2, 1024, STAGE_HEAD},
+      {"head_t", c->head_t, S4 + 2, S4 + 2, 1024, STAGE_HEAD_T}};
   for (auto& e : t)
     if (std::strcmp(e.n, name) == 0) {
+      if (e.stage && !(c->written & e.stage))
+        return fail(SE3TN_E_STATE, std::string("se3tn_debug_buffer: \"") + name + "\" was not written by the last se3tn_infer (its route keeps "
+                                   "that stage on chip or never forms it; se3tn_keep_intermediates makes it written)");
       *ptr = e.p; dims[0] = e.h; dims[1] = e.w; dims[2] = e.ch;
       return SE3TN_OK;
     }
@@ -1531,6 +1558,7 @@ static int reserve_objects_raster(se3tn_ctx* c, int n, int V, int F) {
 static int infer_small_objects(se3tn_ctx* c, const float* W, const ImgParams& ip, const float* A, const float* B, int k, float* trans,
                                float* rot, const double* poseA, double* poseB, hipStream_t st) {
   const BlobLayout& L = c->L;
+  c->written = 0;
   HIPCHK(launch_stem_pool_small_multi(A, B, W + L.stem_w, W + L.stem_b, c->pool, k, ip.off, st));
   auto conv = [&](ConvId id, const float* in, int in_ld, int in_gs, const float* res, int res_ld, int res_gs, float* out, int out_ld,
                   int out_gs, int hin, int stride, int epi, bool skip_reduce, const char* name) -> int {
@@ -1561,7 +1589,7 @@ static int infer_small_objects(se3tn_ctx* c, const float* W, const ImgParams& ip
   if ((rc = conv(LH2_1, c->head, 1024, 512, nullptr, 0, 0, c->head_t, 1024, 512, S4, 1, 0, false, "trans|rot conv2.conv1"))) return rc;
   // the last head conv leaves its 8 partial-sum slices to the tail (conv_slices_small_count(512, 1, S4) == 8)
   if ((rc = conv(LH2_2, c->head_t, 1024, 512, c->head, 1024, 512, c->head, 1024, 512, S4, 1, 1, true, "trans|rot conv2.conv2"))) return rc;
-  c->head_final = nullptr;   // (not materialised)
+  c->written = STAGE_POOL | STAGE_T64 | STAGE_Q64 | STAGE_AB | STAGE_AB_T | STAGE_HEAD_T;   // (not the stem map, not the final head map)
   c->last_fast = false;
   const int M = k * S4 * S4;
   HIPCHK(launch_tail_parts(c->part, 8, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head, 1024, W + L.fc_w, W + L.fc_b, c->logits, trans,

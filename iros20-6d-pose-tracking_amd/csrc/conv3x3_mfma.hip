@@ -856,11 +856,16 @@ static int pick_slices(const ConvArgs& a, int cin, int cout, int big_tile_rows, 
                                      // 8.6k -> 9.6k / 10.2k -> 11.0k / 10.8k -> 11.2k pairs/s at 3 / 4 / 5 pairs (one stream)
 #endif
 // (SE3TN_SLICES_SMALL_MAX_N: se3tn_internal.h)
-hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int epi, hipStream_t st) {
+hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int epi, hipStream_t st, ConvRoute* route) {
   ConvArgs a = a0;
+  ConvRoute unused;
+  ConvRoute& r = route ? *route : unused;
+  r = ConvRoute{};
   if (!a.fast && cin == 64 && cout == 64 && stride == 1 && a.W == 44 && a.H == 44 && epi != 2 && a.M % (44 * 44) == 0 &&
-      a.M / (44 * 44) <= SE3TN_CONV64_SMALL_MAX_N && a.small_ok)
+      a.M / (44 * 44) <= SE3TN_CONV64_SMALL_MAX_N && a.small_ok) {
+    r.algo = ConvRoute::SMALL64;
     return launch_conv64_small(a, a.M / (44 * 44), epi, st);
+  }
   // batch 1-5, float32: the wide convs as one round of 128-pixel x 32-cout x channel-slice workgroups (conv_slices_small.hip)
   if (!a.fast && a.small_ok && a.part && a.Ho * a.Wo > 0 && a.M % (a.Ho * a.Wo) == 0 && a.M / (a.Ho * a.Wo) <= SE3TN_SLICES_SMALL_MAX_N) {
     const int sl = conv_slices_small_count(cin, stride, a.H);
@@ -868,9 +873,14 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
       a.slices = sl;
       a.tiles_n = cout / 32;
       a.sem = nullptr;
+      r.algo = ConvRoute::SLICES;
+      r.slices = sl;
       hipError_t e = launch_conv_slices_small(a, cin, stride, st);
       if (e != hipSuccess) return e;
-      if (a.skip_reduce) return hipSuccess;              // (the tail adds the slices: kernels_misc.hip tail_parts_kernel)
+      if (a.skip_reduce) {                               // (the tail adds the slices: kernels_misc.hip tail_parts_kernel)
+        r.reduced = false;
+        return hipSuccess;
+      }
       if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
       else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
       else launch_reduce<2, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
@@ -879,6 +889,8 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
   }
   a.slices = pick_slices(a, cin, cout, stride == 1 ? 256 : 128, cout >= 128 ? 128 : 64);
   if (a.slices > 0) {
+    r.algo = ConvRoute::SPLITK;
+    r.slices = a.slices;
     a.tiles_n = cout >= 128 ? cout / 128 : 1;
     if (a.fast) {  // f16x3: split rows everywhere, float32 out of the last head conv (cin 512, residual)
       const int outf = (cin == 512 && epi == 1) ? FMT_F32 : FMT_SPLIT;
@@ -896,6 +908,7 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
     if (cin == 512 && stride == 1) return launch_splitk<512, 1, 2, MM_F32>(a, epi, FMT_F32, FMT_F32, st);
     return hipErrorInvalidValue;
   }
+  r.algo = stride == 1 ? ConvRoute::SLAB : ConvRoute::GATHER;   // (the big-tile kernels: slab at stride 1, gather at stride 2)
   if (a.fast) {
     // f16x3 mode (se3tn_set_precision): every 3x3 conv runs on the f16 matrix cores with split-row
     // operands; the max-pool produces the first split-row tensor, the last conv of the heads writes

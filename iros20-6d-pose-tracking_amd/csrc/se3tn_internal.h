@@ -265,8 +265,15 @@ hipError_t launch_stem(const float* inA, const float* inB, const float* w, const
                        const float* wscale, float* out, int n, hipStream_t st);
 // split_out != 0: write split rows (f16 hi | f16 lo) for the f16x3 mode
 hipError_t launch_maxpool(const float* in, float* out, int n, int split_out, hipStream_t st);
-// conv3x3: cin/cout/stride select the instantiation; epi: 0 bias+relu, 1 bias+res+relu, 2 bias+selu
-hipError_t launch_conv3x3(const ConvArgs& a, int cin, int cout, int stride, int epi, hipStream_t st);
+// conv3x3: cin/cout/stride select the instantiation; epi: 0 bias+relu, 1 bias+res+relu, 2 bias+selu.
+// route (optional out): the algorithm it took -- what the caller decides the next launch from (a.skip_reduce is a permission)
+struct ConvRoute {
+  enum Algo { NONE = 0, SMALL64, SLICES, SPLITK, SLAB, GATHER, WINO, WINO64 };   // (WINO / WINO64: set by the caller's own routes)
+  Algo algo = NONE;
+  int slices = 0;      // partial-sum slices left in a.part (SLICES / SPLITK)
+  bool reduced = true; // false: the output map was NOT written, the partial sums were left to the caller (a.skip_reduce)
+};
+hipError_t launch_conv3x3(const ConvArgs& a, int cin, int cout, int stride, int epi, hipStream_t st, ConvRoute* route = nullptr);
 // Winograd F(m x m,3x3): U = G g G^T (float64, rounded once) from the packed direct weights
 // [chunk][9][cout][32] -> [chunk][(m+2)^2][cout][32]; launch_wino_conv = input transform + nf x groups
 // batched MFMA GEMMs + output transform with the conv epilogue (epi 0 | 1)

@@ -109,10 +109,13 @@ def _conv_bn_selu(sd, name, x, stride):
     return F.selu(_bn(sd, name + ".1", x))
 
 
-def _basic_block(sd, name, x):
-    # ResnetBasicBlock.forward  network_modules.py:103-120 (no downsample, stride 1)
+def _basic_block(sd, name, x, mid=None):
+    # ResnetBasicBlock.forward  network_modules.py:103-120 (no downsample, stride 1); mid: list that receives the activation
+    # between the two convolutions
     out = F.conv2d(x, sd[name + ".conv1.weight"], sd[name + ".conv1.bias"], padding=1)
     out = F.relu(_bn(sd, name + ".bn1", out))
+    if mid is not None:
+        mid.append(out)
     out = F.conv2d(out, sd[name + ".conv2.weight"], sd[name + ".conv2.bias"], padding=1)
     out = _bn(sd, name + ".bn2", out)
     return F.relu(out + x)
@@ -120,34 +123,39 @@ def _basic_block(sd, name, x):
 
 @torch.no_grad()
 def forward(sd, A, B, intermediates=False):
-    """Se3TrackNet.forward (se3_tracknet.py:81-112). A,B: float32 [N,4,H,W] NCHW.
-    Returns dict(trans,rot[,feature,trans_logit,rot_logit, per-stage tensors])."""
+    """Se3TrackNet.forward (se3_tracknet.py:81-112). A,B: float32 [N,4,H,W] NCHW (or float64 with a float64 state dict).
+    Returns dict(trans,rot[,feature,trans_logit,rot_logit, per-stage tensors]); the per-stage tensors include the activations
+    between the two convolutions of the blocks convA2 / convB3 / convAB2 / <head>_conv2 ("A2_t", "B3_t", "ab_t", "<head>_t")."""
     out = {}
+    mid = [] if intermediates else None
     a = _conv_bn_selu(sd, "convA1", A, 2)
     if intermediates: out["stemA"] = a
     a = F.max_pool2d(a, 3, 2, 1)
     if intermediates: out["poolA"] = a
-    a = _basic_block(sd, "convA2", a)
+    a = _basic_block(sd, "convA2", a, mid)
     b = _conv_bn_selu(sd, "convB1", B, 2)
     if intermediates: out["stemB"] = b
     b = F.max_pool2d(b, 3, 2, 1)
+    if intermediates: out["poolB"] = b
     b = _basic_block(sd, "convB2", b)
-    b = _basic_block(sd, "convB3", b)
+    b = _basic_block(sd, "convB3", b, mid)
     ab = torch.cat((a, b), 1).contiguous()
     if intermediates: out["cat"] = ab
     ab = _conv_bn_selu(sd, "convAB1", ab, 2)
     if intermediates: out["ab1"] = ab
-    ab = _basic_block(sd, "convAB2", ab)
+    ab = _basic_block(sd, "convAB2", ab, mid)
     out["feature"] = ab
     for head in ("trans", "rot"):
         h = _conv_bn_selu(sd, head + "_conv1", ab, 2)
         if intermediates: out[head + "_c1"] = h
-        h = _basic_block(sd, head + "_conv2", h)
+        h = _basic_block(sd, head + "_conv2", h, mid)
         if intermediates: out[head + "_c2"] = h
         h = F.adaptive_avg_pool2d(h, 1).reshape(A.shape[0], -1)
         logit = F.linear(h, sd[head + "_out.0.weight"], sd[head + "_out.0.bias"])
         out[head + "_logit"] = logit
         out[head] = torch.tanh(logit).contiguous()
+    if intermediates:
+        out["A2_t"], out["B3_t"], out["ab_t"], out["trans_t"], out["rot_t"] = mid
     return out
 
 

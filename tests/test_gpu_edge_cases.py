@@ -253,10 +253,14 @@ def test_on_track_batch_one_call_equals_the_stepwise_path(se3, n):
     for i in range(n):
         assert np.array_equal(g["rgbA"][i], lw["rgbA"][i].cpu().numpy()) and np.array_equal(g["depthA"][i], lw["depthA"][i].cpu().numpy()), i
         assert (g["depthA"][i] != 0).sum() > 500
-    # and per pair the single-frame call (batch-1 kernels: other summation order, same tolerance class as on_track's own batch test)
+    # and per pair the single-frame call: at 1-5 pairs one kernel family that works image by image, so the same bits (what the header,
+    # tests/test_c_host.py and get_results_ycb(lockstep=True) rely on); above 5 pairs other kernels, another summation order
     trk.one_call = True
     one = np.stack([trk.on_track(poses[i], rgbs[i], deps[i]) for i in range(min(n, 5))])
-    assert np.abs(one - got[:len(one)]).max() < 1e-6
+    if n <= 5:
+        assert np.array_equal(one, got[:len(one)])
+    else:
+        assert np.abs(one - got[:len(one)]).max() < 1e-6
 
 
 def test_on_track_refuses_poses_that_have_no_crop_window(se3):

@@ -118,6 +118,30 @@ def test_order_and_company_do_not_matter(se3, trackers):
     assert_same(got[3], single(trks[1], poses[4], rgb, depth), "other pose")
 
 
+def test_a_model_context_off_the_default_one_pair_route(se3, models):
+    """The bit-equality contract holds while the model context runs one pair through the batch 1-5 family (its default): under
+    se3tn_set_winograd(1, 2) se3tn_on_track on that context takes the F(2x2) blocks and the plain tail -- other bits, the same
+    tolerance -- while se3tn_on_track_objects still runs the family (the bits of the default route).  At the parent commit the
+    single-object call under this setting read stale partial sums in its tail (wrong trans / rot / pose)."""
+    rgb, depth, poses = frame_and_poses(2, seed=23)
+    trks = [make_tracker(se3, models, "random", "sphere", 130.0), make_tracker(se3, models, "5deg", "ellipsoid", 150.0)]
+    base = [single(t, poses[i], rgb, depth) for i, t in enumerate(trks)]
+    trks[0].engine.set_winograd(1, 2)
+    got = multi(se3, trks, poses, rgb, depth)
+    for i in range(2):
+        assert_same(got[i], base[i], ("default-route bits", i))
+    off = single(trks[0], poses[0], rgb, depth)
+    assert not np.array_equal(off["trans"], base[0]["trans"]) or not np.array_equal(off["rot"], base[0]["rot"])
+    for k in ("trans", "rot"):
+        assert np.abs(off[k] - base[0][k]).max() < 3e-5, k
+    assert np.abs(off["pose"] - base[0]["pose"]).max() < 1e-5
+    sd, mean, std, tn, rn = models["random"]
+    want, aux = O.on_track(sd, poses[0], rgb, depth, off["rgbA"], off["depthA"].view(np.uint16), trks[0].K, trks[0].object_width, mean,
+                           std, tn, rn)
+    assert np.abs(off["trans"] - aux["trans"]).max() < 2e-5 and np.abs(off["rot"] - aux["rot"]).max() < 2e-5
+    assert np.abs(off["pose"] - want).max() < 1e-5
+
+
 def test_against_the_oracle_per_object(se3, trackers, models):
     rgb, depth, poses = frame_and_poses(5, seed=3)
     trks = trackers[:5]

@@ -1,0 +1,402 @@
+"""GPU: every route se3tn_infer can take, against a FLOAT64 evaluation of the network.
+
+se3tn_infer picks an algorithm per layer from the public switches (se3tn_set_winograd / _trunk_winograd / _small_kernels /
+_keep_intermediates / _precision / _normalizers / _enable_graphs) and the create-time developer switches (SE3TN_WINOGRAD_FUSE,
+SE3TN_TAIL_PARTS, SE3TN_SPLITK_FUSED, SE3TN_WINOGRAD_AUTO_TILE_AB2 / _HEADS).  Each case of CASES is one combination, run at the
+batch sizes around its switch points.  Per (case, n):
+  * one call on another window of the 72-pair pool first, so that a route which reads the previous call's buffers fails;
+  * the checked call: EVERY pair's logits against float64 within the case's tolerance class, every composed pose within 1e-5;
+  * the profile names of that call: the algorithm the route table (`expected`) names ran for each conv and for the tail;
+  * every stage se3tn_debug_buffer hands out against the float64 intermediates (first and last pair of the call), and the stages it
+    refuses are exactly the ones the route does not write.
+Bit identity: SE3TN_SPLITK_FUSED=1 against 0, and graph replay (non-default stream, third call) against the eager call."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import fixtures as Fx
+from oracle import se3_oracle as O
+
+POOL = 72
+POSE_TOL = 1e-5
+ACT_RTOL = 2e-5
+# logit bound against float64 per route class, fixed before the first measurement: upper bounds taken from the documented rounding of
+# each algorithm (e.g. 1.3e-5 logit rounding of F(6x6) heads, tile_for in api.cpp), all well inside the 1e-4 north star
+CLASS_TOL = {"f32 direct": 1e-5, "F(2x2)/F(4x4)": 2e-5, "F(6x6)": 5e-5, "f16x3": 5e-5}
+# activations: |err| <= ACT_RTOL |ref| + scale x max |ref|, scale per algorithm (tests/test_gpu_parity.py's bounds)
+STAGE_SCALE = {"small": 5e-6, "direct": 5e-6, "f16x3": 5e-6, "trunk F2": 2e-5, "F2": 2e-5, "F4": 6e-5, "F6": 1.5e-4}
+WORST = {}   # class -> worst |d logit| against float64 over the cases run (printed by the last test)
+CUS = 256    # compute units of an MI355X: the fused trunk kernel runs only in rounds of them that are full enough
+TILE_AUTO, TILE_6_4, TILE6_MIN, HEADS6_MAX_ROT = 46, 64, 14, 0.2   # include/se3tracknet.h (checked against _lib in the fixture)
+DEG = np.pi / 180
+LAYERS = [("trunk1", "conv64 A2.conv1|B2.conv1"), ("trunk2", "conv64 A2.conv2|B2.conv2"), ("trunk3", "conv64 B3.conv1"),
+          ("trunk4", "conv64 B3.conv2"), ("ab1", "convAB1 s2"), ("ab2.1", "convAB2.conv1"), ("ab2.2", "convAB2.conv2"),
+          ("h1", "trans|rot conv1 s2"), ("h2.1", "trans|rot conv2.conv1"), ("h2.2", "trans|rot conv2.conv2")]
+STAGES = ("stem", "pool", "t64", "q64", "ab", "ab_t", "head", "head_t")
+S15 = [1, 2, 3, 4, 5]
+EVERY_N = [1, 2, 3, 4, 5, 6, 7, 13, 14, 15, 17, 18, 33, 34, 64, 72]   # 5/6: batch 1-5 family | Winograd; 14: AUTO -> F(6x6); 18/34: trunk
+
+
+def case(cid, ns, env=None, ops=(), graph=False, twin=None):
+    return dict(id=cid, ns=ns, env=env or {}, ops=list(ops), graph=graph, twin=twin)
+
+
+SPLITK = {"SE3TN_SPLITK_FUSED": "1"}
+CASES = [case("default", EVERY_N),
+         case("small-off", S15, ops=[("small", 0)]),
+         case("keep", S15 + [6, 14], ops=[("keep", 1)])]
+CASES += [case("wino1-F%s-keep%d" % (name, keep), S15 + [6, 14], ops=[("wino", 1, tile), ("keep", keep)])
+          for name, tile in (("2", 2), ("4", 4), ("6", 6), ("6_4", TILE_6_4), ("auto", TILE_AUTO)) for keep in (0, 1)]
+CASES += [case("fuse0-F%d" % tile, [1, 3, 5, 8, 20], env={"SE3TN_WINOGRAD_FUSE": "0"}, ops=[("wino", 1, tile)]) for tile in (4, 6)]
+CASES += [case("tail-parts%s" % v, S15, env={"SE3TN_TAIL_PARTS": v}) for v in ("0", "2")]
+CASES += [case("splitk-fused", S15, env=SPLITK, twin={}),
+          case("splitk-fused-small-off", S15, env=SPLITK, ops=[("small", 0)], twin={}),
+          case("splitk-fused-direct", [6, 9, 13], env=SPLITK, ops=[("wino", 0, 0)], twin={}),
+          case("trunk1-fill0", S15 + [8], ops=[("trunk", 1, 0)]),
+          case("direct", EVERY_N, ops=[("wino", 0, 0), ("trunk", 0, 0)]),
+          case("auto-rot0.3", [14], ops=[("norm", 0.03, 0.3)]),
+          case("auto-rot0.1", [14], ops=[("norm", 0.03, 0.1)]),
+          case("auto-tile-ab2-4-heads-6", [6, 14], env={"SE3TN_WINOGRAD_AUTO_TILE_AB2": "4", "SE3TN_WINOGRAD_AUTO_TILE_HEADS": "6"}),
+          case("f16x3", [1, 5, 6, 14, 64], ops=[("f16",)]),
+          case("graph-wino1-F2", [1, 3, 5], ops=[("wino", 1, 2)], graph=True),
+          case("graph-tail-parts", [1, 3, 5], graph=True)]
+
+
+# ---- the route table: what se3tn_infer must run for a configuration ----------------------------------------------------------------
+def _tile_for(cfg, n, which):
+    """Winograd tile of the 256-channel block (which 0) / the heads (1): include/se3tracknet.h, se3tn_set_winograd"""
+    t = cfg["tile"]
+    if t in (2, 4):
+        return t
+    if cfg["f16"]:
+        return 4
+    if t == 6:
+        return 6
+    if t == TILE_6_4:
+        return 6 if which == 0 else 4
+    if cfg["ovr"][which]:
+        return cfg["ovr"][which]
+    if n < TILE6_MIN:
+        return 4
+    return 6 if which == 0 or cfg["rn"] <= HEADS6_MAX_ROT else 4
+
+
+def expected(cfg, n):
+    """(algorithm per conv + "stem" + "tail", {stage: written}) of one call of n pairs"""
+    f16 = cfg["f16"]
+    small = cfg["small"] and not f16 and n <= 5
+    plain = "small" if small else ("f16x3" if f16 else "direct")
+    wino = cfg["wmin"] > 0 and n >= cfg["wmin"]
+    r = {"stem": "small" if small and not cfg["keep"] else "big"}
+    for key, groups in zip(("trunk1", "trunk2", "trunk3", "trunk4"), (2, 2, 1, 1)):
+        wgs = 4 * n * groups
+        fused = not f16 and cfg["tmin"] > 0 and n >= cfg["tmin"] and 100 * wgs >= cfg["tfill"] * -(-wgs // CUS) * CUS
+        r[key] = "trunk F2" if fused else plain
+    r["ab1"] = r["h1"] = plain
+    block = {}
+    for which, convs in ((0, ("ab2.1", "ab2.2")), (1, ("h2.1", "h2.2"))):
+        t = _tile_for(cfg, n, which)
+        block[which] = cfg["fuse"] and wino and (t == 4 or (t == 6 and not f16)) and not (which == 0 and f16)
+        for k in convs:
+            r[k] = ("F%d block" % t) if block[which] else (("F%d" % t) if wino and not f16 else plain)
+    r["tail"] = "fused" if block[1] else ("parts" if r["h2.2"] == "small" and cfg["tail_parts"] and not cfg["keep"] else "tail")
+    written = {"stem": r["stem"] == "big", "pool": True, "t64": True, "q64": True, "ab": True,
+               "ab_t": not block[0] or cfg["keep"], "head_t": not block[1] or cfg["keep"],
+               "head": (block[1] and cfg["keep"]) or (not block[1] and r["tail"] != "parts")}
+    return r, written
+
+
+def tol_class(cfg, r):
+    if cfg["f16"]:
+        return "f16x3"
+    tags = " ".join(r.values())
+    if "F6" in tags:
+        return "F(6x6)"
+    return "F(2x2)/F(4x4)" if ("F2" in tags or "F4" in tags) else "f32 direct"
+
+
+def _tag(name):
+    if "[fused F(2x2)]" in name:
+        return "trunk F2"
+    m = re.search(r"\[F\((\d)x\1\)\]", name)
+    if m:
+        return ("F%s block" % m.group(1)) if "fused block" in name else "F" + m.group(1)
+    m = re.search(r"\[(conv64 small|slices|split-K|slab|gather)( f16x3)?\]", name)
+    if m is None:
+        return "untagged: " + name
+    return "f16x3" if m.group(2) else ("small" if m.group(1) in ("conv64 small", "slices") else "direct")
+
+
+def actual(names):
+    """the route of a profiled call, from its launch names"""
+    r = {}
+    for key, prefix in LAYERS:
+        hits = [nm for nm in names if nm == prefix or nm.startswith(prefix + " ")]
+        assert len(hits) == 1, (key, names)
+        r[key] = _tag(hits[0])
+    r["stem"] = "small" if any(nm.startswith("stem7x7 + maxpool") for nm in names) else "big"
+    r["tail"] = ("parts" if any(nm.startswith("tail slices") for nm in names) else
+                 "tail" if any(nm.startswith("tail avgpool") for nm in names) else "fused")
+    return r
+
+
+# ---- reference ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def se3():
+    import se3tracknet_amd
+    L = se3tracknet_amd._lib
+    assert (L.WINOGRAD_TILE_AUTO, L.WINOGRAD_TILE_6_4, L.WINOGRAD_TILE6_MIN_BATCH) == (TILE_AUTO, TILE_6_4, TILE6_MIN)
+    assert L.WINOGRAD_HEADS_TILE6_MAX_ROT == HEADS6_MAX_ROT
+    return se3tracknet_amd
+
+
+@pytest.fixture(scope="module")
+def ref():
+    """one seeded state dict, 72 input pairs, their logits in float64 (the yardstick) and in float32 (its noise floor)"""
+    sd = O.make_state_dict(21)
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    A, B = Fx.net_inputs(2100, POOL)
+    lg64, lg32 = [], []
+    for i in range(0, POOL, 8):
+        o64 = O.forward(sd64, A[i:i + 8].double(), B[i:i + 8].double())
+        o32 = O.forward(sd, A[i:i + 8], B[i:i + 8])
+        lg64.append(torch.cat([o64["trans_logit"], o64["rot_logit"]], 1))
+        lg32.append(torch.cat([o32["trans_logit"], o32["rot_logit"]], 1))
+    lg64, lg32 = torch.cat(lg64).numpy(), torch.cat(lg32).numpy()
+    floor = float(np.abs(lg32 - lg64).max())
+    print("float32 oracle vs float64: max |d logit| %.2e over %d pairs (the noise floor of the float32 yardstick)" % (floor, POOL))
+    return dict(sd=sd, sd64=sd64, A=A, B=B, Ac=A.cuda(), Bc=B.cuda(), lg64=lg64, floor=floor, poseA=Fx.pose(9, (0.03, -0.02, 0.7)),
+                stages={})
+
+
+def _stage_ref(ref, i):
+    """float64 stage maps of pair i in the layout of se3tn_debug_buffer's channels (NCHW)"""
+    if i not in ref["stages"]:
+        o = O.forward(ref["sd64"], ref["A"][i:i + 1].double(), ref["B"][i:i + 1].double(), intermediates=True)
+        cat = lambda a, b: torch.cat([o[a], o[b]], 1)
+        ref["stages"][i] = {"stem": cat("stemA", "stemB"), "pool": cat("poolA", "poolB"), "t64": cat("A2_t", "B3_t"), "q64": o["cat"],
+                            "ab": o["feature"], "ab_t": o["ab_t"], "head": cat("trans_c2", "rot_c2"), "head_t": cat("trans_t", "rot_t")}
+    return ref["stages"][i]
+
+
+def _close(name, got, want, rtol, atol, scale_atol=0.0):
+    got = got.double(); want = want.double()
+    err = (got - want).abs()
+    tol = atol + scale_atol * float(want.abs().max()) + rtol * want.abs()
+    worst = float((err - tol).max())
+    assert worst <= 0, "%s: max abs err %.3e (max |ref| %.3e), exceeds tol by %.3e" % (name, float(err.max()), float(want.abs().max()), worst)
+
+
+def _nchw(t, border):
+    if border:
+        assert float(t[:, 0].abs().max()) == 0 and float(t[:, -1].abs().max()) == 0            # borders stay zero
+        assert float(t[:, :, 0].abs().max()) == 0 and float(t[:, :, -1].abs().max()) == 0
+        t = t[:, border:-border, border:-border]
+    return t.permute(0, 3, 1, 2).contiguous()
+
+
+def _windows(n):
+    """(previous call, checked call): pool indices; slot j of the two calls never holds the same pair"""
+    s = (11 * n + 5) % (POOL - n + 1)
+    chk = list(range(s, s + n))
+    return [POOL - 1 - i for i in chk], chk
+
+
+class _Runner:
+    """se3tn_infer on pool pairs through fixed buffers (a captured graph replays with the same pointers)"""
+    def __init__(self, se3, eng, ref, n_max):
+        self.se3, self.eng, self.ref = se3, eng, ref
+        self.A = torch.empty((n_max, 4, 176, 176), device="cuda")
+        self.B = torch.empty_like(self.A)
+        self.trans = torch.empty((n_max, 3), device="cuda")
+        self.rot = torch.empty_like(self.trans)
+        self.pA = torch.from_numpy(np.tile(ref["poseA"].reshape(1, 16), (n_max, 1))).cuda()
+        self.pB = torch.empty_like(self.pA)
+
+    def __call__(self, idx):
+        n = len(idx)
+        ii = torch.tensor(idx, device="cuda")
+        self.A[:n].copy_(self.ref["Ac"][ii]); self.B[:n].copy_(self.ref["Bc"][ii])
+        self.eng.infer(self.A, self.B, n, self.se3.NCHW, self.trans, self.rot, self.pA, self.pB)
+        return self.eng.logits(n).cpu().numpy(), self.pB[:n].cpu().numpy().reshape(n, 4, 4)
+
+
+def _engine(se3, ref, env, ops, n_max):
+    saved = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)                  # read by se3tn_create
+    try:
+        eng = se3.Engine(0, n_max)
+        eng.load_state_dict(ref["sd"])
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    wmin, tile = eng.get_winograd()
+    tmin, tfill = eng.get_trunk_winograd()
+    ovr = [int(env.get(k, "0")) for k in ("SE3TN_WINOGRAD_AUTO_TILE_AB2", "SE3TN_WINOGRAD_AUTO_TILE_HEADS")]
+    cfg = dict(wmin=wmin, tile=tile, tmin=tmin, tfill=tfill, small=eng.get_small_kernels(), keep=False, f16=False, tn=0.03, rn=5 * DEG,
+               fuse=env.get("SE3TN_WINOGRAD_FUSE", "1") != "0", tail_parts=env.get("SE3TN_TAIL_PARTS", "1") != "0",
+               ovr=[v if v in (4, 6) else 0 for v in ovr])
+    for op in ops:
+        if op[0] == "wino":
+            eng.set_winograd(op[1], op[2])
+            cfg["wmin"] = op[1]
+            cfg["tile"] = op[2] or cfg["tile"]
+        elif op[0] == "trunk":
+            eng.set_trunk_winograd(op[1], op[2])
+            cfg["tmin"], cfg["tfill"] = op[1], op[2]
+        elif op[0] == "small":
+            eng.set_small_kernels(bool(op[1]))
+            cfg["small"] = bool(op[1])
+        elif op[0] == "keep":
+            eng.keep_intermediates(bool(op[1]))
+            cfg["keep"] = bool(op[1])
+        elif op[0] == "norm":
+            eng.set_normalizers(op[1], op[2])
+            cfg["tn"], cfg["rn"] = op[1], op[2]
+        elif op[0] == "f16":
+            eng.set_precision(se3._lib.PREC_F16X3)
+            cfg["f16"] = True
+    return eng, cfg
+
+
+def _readable(se3, eng, n):
+    """stage -> the device map [n,H,W,C] se3tn_debug_buffer hands out, or None where it refuses"""
+    out = {}
+    for s in STAGES:
+        try:
+            out[s] = eng.debug_buffer(s, n)
+        except se3._lib.Se3tnError as e:
+            assert "not written" in str(e), (s, str(e))
+            out[s] = None
+    return out
+
+
+def _check(se3, eng, run, ref, cfg, n, cid):
+    pre, chk = _windows(n)
+    run(pre)
+    eng.profile_enable(1)
+    try:
+        lg, pose = run(chk)
+        names = [nm for nm, _ in eng.profile_launches(0)]
+    finally:
+        eng.profile_enable(0)
+    want_r, written = expected(cfg, n)
+    cls = tol_class(cfg, want_r)
+    err = np.abs(lg.astype(np.float64) - ref["lg64"][chk])
+    e = float(err.max())
+    WORST[cls] = max(WORST.get(cls, 0.0), e)
+    assert e <= CLASS_TOL[cls], "%s n=%d: max |d logit| vs float64 %.3e > %.0e (%s), pair %d" % (
+        cid, n, e, CLASS_TOL[cls], cls, chk[int(err.max(1).argmax())])
+    for j, i in enumerate(chk):
+        want = O.process_predict(ref["poseA"], np.tanh(ref["lg64"][i, :3]), np.tanh(ref["lg64"][i, 3:]), cfg["tn"], cfg["rn"])
+        d = float(np.abs(pose[j] - want).max())
+        assert d <= POSE_TOL, "%s n=%d pair %d: |d pose| %.3e" % (cid, n, i, d)
+    got_r = actual(names)
+    assert got_r == want_r, "%s n=%d: route %s, expected %s (%s)" % (cid, n, got_r, want_r, names)
+    # the stages: handed out exactly where this call wrote them, and then equal to float64
+    maps = _readable(se3, eng, n)
+    got_w = {s: maps[s] is not None for s in STAGES}
+    assert got_w == written, "%s n=%d: readable stages %s, written by the route %s" % (cid, n, got_w, written)
+    sc = lambda keys: max(STAGE_SCALE[want_r[k].replace(" block", "")] for k in keys)
+    sc_trunk, sc_all = sc(("trunk1", "trunk2", "trunk3", "trunk4")), sc([k for k, _ in LAYERS])
+    for s, t in maps.items():
+        if t is None or (cfg["f16"] and s != "head"):   # (f16x3: every map but the last head map holds split rows)
+            continue
+        for j in sorted({0, n - 1}):
+            got = _nchw(t[j:j + 1].cpu(), 0 if s == "stem" else 1)
+            want = _stage_ref(ref, chk[j])[s]
+            _close("%s n=%d %s pair %d" % (cid, n, s, chk[j]), got, want, ACT_RTOL, 1e-5 if s in ("stem", "pool") else 0,
+                   sc_trunk if s in ("stem", "pool", "t64", "q64") else sc_all)
+    return lg, pose, got_w
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
+def test_route_vs_float64(se3, ref, case):
+    n_max = max(case["ns"])
+    eng, cfg = _engine(se3, ref, case["env"], case["ops"], n_max)
+    twin = _engine(se3, ref, case["twin"], case["ops"], n_max)[0] if case["twin"] is not None else None
+    try:
+        run = _Runner(se3, eng, ref, n_max)
+        run_twin = _Runner(se3, twin, ref, n_max) if twin else None
+        for n in case["ns"]:
+            lg, pose, got_w = _check(se3, eng, run, ref, cfg, n, case["id"])
+            if twin:   # SE3TN_SPLITK_FUSED: "bitwise the same results" as the separate reduce launch
+                pre, chk = _windows(n)
+                run_twin(pre)
+                lg_t, pose_t = run_twin(chk)
+                assert np.array_equal(lg, lg_t) and np.array_equal(pose, pose_t), (case["id"], n)
+            if case["graph"]:   # graph replay: first call eager, second captured, third replayed -- the eager bits
+                pre, chk = _windows(n)
+                s = torch.cuda.Stream()
+                with torch.cuda.stream(s):
+                    eng.enable_graphs(True)
+                    try:
+                        run(pre)
+                        run(chk[::-1])
+                        lg_g, pose_g = run(chk)
+                        w_g = {k: v is not None for k, v in _readable(se3, eng, n).items()}
+                    finally:
+                        eng.enable_graphs(False)
+                torch.cuda.synchronize()
+                assert np.array_equal(lg_g, lg) and np.array_equal(pose_g, pose), (case["id"], n)
+                assert w_g == got_w, (case["id"], n, w_g, got_w)
+    finally:
+        eng.close()
+        if twin:
+            twin.close()
+
+
+class _Render:
+    """synthetic image A per render call (kept for the oracle)"""
+    def __init__(self):
+        self.log = []
+
+    def render(self, ob2cam, K, window):
+        self.log.append(Fx.synthetic_render(130 + len(self.log), ob2cam[2, 3]))
+        return self.log[-1]
+
+
+def test_tracker_on_track_and_batch_with_winograd_tile2_from_one_pair(se3):
+    """Tracker.on_track / on_track_batch(3) on a context with se3tn_set_winograd(1, 2): the per-frame batch runs the F(2x2) blocks
+    conv by conv and the plain tail (at the parent commit the tail read stale partial sums here)."""
+    sd = O.make_state_dict(0, head_gain=0.01)
+    mean, std = Fx.mean_std(0)
+    rend = _Render()
+    trk = se3.Tracker(Fx.DATASET_INFO, mean, std, {"state_dict": sd}, renderer=rend, max_samples=3)
+    trk.engine.set_winograd(1, 2)
+    tol = CLASS_TOL["F(2x2)/F(4x4)"]
+    args = (trk.K, trk.object_width, mean, std, trk.trans_normalizer, trk.rot_normalizer)
+    P = Fx.pose(3)
+    for f in range(3):
+        rgb, depth = Fx.synthetic_frame(30 + f)
+        got = trk.on_track(P, rgb, depth)
+        want, o = O.on_track(sd, P, rgb, depth, *rend.log[-1], *args)
+        lp = trk.last_prediction
+        assert np.abs(lp["trans"][0] - o["trans"]).max() < tol and np.abs(lp["rot"][0] - o["rot"]).max() < tol, f
+        assert np.abs(got - want).max() < POSE_TOL, f
+        P = got
+    poses = [Fx.pose(40 + i, (0.03 * i - 0.03, 0.01, 0.7 + 0.05 * i)) for i in range(3)]
+    frames = [Fx.synthetic_frame(50 + i) for i in range(3)]
+    k0 = len(rend.log)
+    bat = trk.on_track_batch(poses, [f[0] for f in frames], [f[1] for f in frames])
+    lp = trk.last_prediction
+    for i in range(3):
+        want, o = O.on_track(sd, poses[i], *frames[i], *rend.log[k0 + i], *args)
+        assert np.abs(lp["trans"][i] - o["trans"]).max() < tol and np.abs(lp["rot"][i] - o["rot"]).max() < tol, i
+        assert np.abs(bat[i] - want).max() < POSE_TOL, i
+
+
+def test_zz_report_worst_logit_error_per_class(ref):
+    """(runs last) the worst |d logit| against float64 per tolerance class over the cases above, beside the float32 oracle's own error"""
+    print("float32 oracle vs float64: %.2e" % ref["floor"])
+    for cls, bound in CLASS_TOL.items():
+        print("%-14s worst |d logit| vs float64 %s (bound %.0e)" % (cls, "%.2e" % WORST[cls] if cls in WORST else "not run", bound))
+        assert WORST.get(cls, 0.0) <= bound
