@@ -249,6 +249,23 @@ int se3tn_get_raster_rule(const se3tn_ctx* ctx);
 int se3tn_mesh_set_texture(se3tn_mesh* mesh, const float* uv, const uint8_t* rgb, int tw, int th, const float kd[3]);
 int se3tn_render_frame(se3tn_ctx* ctx, se3tn_mesh* mesh, const double ob_in_cam[16], const double K[9], int W, int H,
                        uint8_t* rgb, uint16_t* depth, void* stream);
+/* The same render restricted to a rectangle of the frame: rect = {x0, y0, x1, y1}, columns [x0, x1) and rows [y0, y1) in OpenCV
+ * image coordinates (row 0 = top).  The vertices go through the full W x H projection; the z-buffer, the coverage loops and the
+ * shading cover the rectangle only.  rgb_sub uint8 [y1-y0, x1-x0, 3] and depth_sub uint16 [y1-y0, x1-x0] (device, tightly packed,
+ * top-down) receive the sub-image: every byte equals the same pixel of se3tn_render_frame.  Stream-ordered and capturable like
+ * se3tn_render_frame; the z-buffer holds (x1-x0) (y1-y0) keys: reserved by se3tn_reserve(ctx, H, W) for every rectangle of such a
+ * frame, else grown on the first call (inside a stream capture: SE3TN_E_STATE).  SE3TN_E_ARG: an empty rectangle, one that is not
+ * inside [0, W) x [0, H), H > 2048. */
+int se3tn_render_frame_rect(se3tn_ctx* ctx, se3tn_mesh* mesh, const double ob_in_cam[16], const double K[9], int W, int H,
+                            const int32_t rect[4], uint8_t* rgb_sub, uint16_t* depth_sub, void* stream);
+/* Which renderer se3tn_on_track / se3tn_on_track_batch use for image A of this mesh:
+ *   SE3TN_ROUTE_WINDOW (default, also for a mesh with a texture attached)  the VispyRenderer route: se3tn_render at the y-flipped window;
+ *   SE3TN_ROUTE_FRAME   the pyrender route (predict.py:209-213): the full-frame render cropped with the plain compute_bbox window.
+ * se3tn_mesh_get_route returns the route, or -1 for a NULL mesh. */
+#define SE3TN_ROUTE_WINDOW 0
+#define SE3TN_ROUTE_FRAME 1
+int se3tn_mesh_set_route(se3tn_mesh* mesh, int route);
+int se3tn_mesh_get_route(const se3tn_mesh* mesh);
 
 /* ---- one frame of Tracker.on_track in ONE call -------------------------------------------------------- */
 /* predict.py:217-296 for samples == 1, with the model mesh rendered by this library: compute_bbox (host float64) -> image A
@@ -258,7 +275,16 @@ int se3tn_render_frame(se3tn_ctx* ctx, se3tn_mesh* mesh, const double ob_in_cam[
  * rgbA_dev / depthA_dev: optional device buffers (uint8 [176,176,3], uint16 [176,176]) that receive image A (NULL: internal).
  * Outputs are host memory: pose_out = the 4x4 float64 estimate (row-major); trans_out / rot_out [3] (may be NULL) the network's
  * tanh outputs; bbox_vu [4][2] (may be NULL) compute_bbox's corners.  SYNCHRONOUS on `stream` (as predict.py:275-276 is); the first
- * call (or a larger frame) allocates the staging buffers.  Same arithmetic as se3tn_render + se3tn_preprocess x2 + se3tn_infer. */
+ * call (or a larger frame) allocates the staging buffers.  Same arithmetic as se3tn_render + se3tn_preprocess x2 + se3tn_infer.
+ * A mesh on SE3TN_ROUTE_FRAME (se3tn_mesh_set_route) takes predict.py:209-213 instead: compute_bbox -> rectangle = crop window
+ * intersected with the frame (se3tn_frame_rect) -> se3tn_render_frame_rect of that rectangle at prev_pose -> image A (the sub-image
+ * with the window shifted by the rectangle's origin) and the camera frame cropped in ONE launch -> network as above.  A window that
+ * misses the frame gives an all-zero image A.  rgbA_dev / depthA_dev then receive the 176 x 176 crop_bbox of the render (what
+ * se3tn_crop_raw gives on the full-frame render), written by the same launch.  Same arithmetic as se3tn_render_frame +
+ * se3tn_preprocess x2 + se3tn_infer.  H > 2048 is refused on this route (as se3tn_render_frame does).  On this route the first call
+ * (or a larger frame) also allocates a z-buffer and a sub-image for a WHOLE H x W frame (13 bytes per pixel, 4 MB at 480 x 640), so
+ * that a moving window never re-allocates; they are the route's own, beside what se3tn_reserve holds for se3tn_render_frame
+ * (se3tn_on_track_batch sizes the same buffers by pairs x the largest rectangle of the call instead). */
 int se3tn_on_track(se3tn_ctx* ctx, se3tn_mesh* mesh, const double prev_pose[16], const double K[9], double object_width_mm,
                    const uint8_t* rgb, const uint16_t* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev,
                    double pose_out[16], float trans_out[3], float rot_out[3], int32_t bbox_vu[8], void* stream);
@@ -272,7 +298,8 @@ int se3tn_on_track(se3tn_ctx* ctx, se3tn_mesh* mesh, const double prev_pose[16],
  * uint16 [H,W] frames of one size (the same pointer may repeat).  rgbA_dev / depthA_dev: optional device buffers
  * [n,176,176,3] / [n,176,176] that receive the images A (NULL: internal).  Outputs (host): pose_out [n,16], trans_out / rot_out
  * [n,3] (may be NULL), bbox_vu [n,4,2] (may be NULL).  n <= max_batch of se3tn_create.  SYNCHRONOUS on `stream`; the first call
- * (a larger n, mesh or frame) allocates. */
+ * (a larger n, mesh or frame) allocates.  A mesh on SE3TN_ROUTE_FRAME: as se3tn_on_track describes, the n rectangles rendered in the
+ * same FOUR launches (one mesh and texture pyramid, z-buffers and sub-images sized by the largest rectangle of the call). */
 int se3tn_on_track_batch(se3tn_ctx* ctx, se3tn_mesh* mesh, int n, const double* prev_poses, const double K[9], double object_width_mm,
                          const uint8_t* const* rgb, const uint16_t* const* depth, int H, int W, uint8_t* rgbA_dev,
                          uint16_t* depthA_dev, double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu, void* stream);
@@ -296,7 +323,7 @@ int se3tn_on_track_batch(se3tn_ctx* ctx, se3tn_mesh* mesh, int n, const double* 
  * pose_out [n,16], trans_out / rot_out [n,3] and bbox_vu [n,4,2] (may be NULL); rgbA_dev / depthA_dev optional device [n,176,176,3] /
  * [n,176,176].  1 <= n <= se3tn_max_batch(ctx).  SYNCHRONOUS on `stream`, refused inside a stream capture; the first call (a larger n,
  * mesh or frame) allocates.
- * SE3TN_E_ARG: n out of range, a NULL or textured mesh, a pose with z <= 0 or not finite.  SE3TN_E_STATE: a model without weights or
+ * SE3TN_E_ARG: n out of range, a NULL or textured mesh or one on SE3TN_ROUTE_FRAME, a pose with z <= 0 or not finite.  SE3TN_E_STATE: a model without weights or
  * normalisation, on another device, with another packed size, offset rule or raster rule than ctx; ctx in SE3TN_PREC_F16X3, with the
  * small kernels off or with se3tn_keep_intermediates on.  The context stays usable after a refusal. */
 typedef struct se3tn_object {
@@ -326,6 +353,11 @@ int se3tn_fill_depth(se3tn_ctx* ctx, const uint16_t* depth_mm, int H, int W, dou
  * row-major 3x3, width in mm; out_vu[8] = 4 x (v,u) int32, np.round (half-to-even). */
 int se3tn_compute_bbox(const double pose[16], const double K[9], double object_width_mm,
                        int32_t out_vu[8]);
+/* The rectangle the SE3TN_ROUTE_FRAME route renders for this pose: compute_bbox's crop window (left, top, right, bottom = min / max of
+ * the corners) intersected with the H x W frame, rect = {x0, y0, x1, y1} as se3tn_render_frame_rect takes it -- the size of the
+ * sub-image, for callers that bring their own buffers.  A window that misses the frame is reported as the empty rectangle
+ * {0, 0, 0, 0} (return value SE3TN_OK).  SE3TN_E_ARG: z <= 0 or a pose that is not finite, width <= 0, H or W < 1. */
+int se3tn_frame_rect(const double pose[16], const double K[9], double object_width_mm, int H, int W, int32_t rect[4]);
 /* datasets.py:159-175 processPredict on the host. */
 int se3tn_pose_update_host(const double poseA[16], const float trans[3], const float rot[3],
                            double trans_normalizer, double rot_normalizer, double poseB[16]);

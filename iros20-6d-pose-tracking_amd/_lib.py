@@ -18,6 +18,7 @@ WINOGRAD_TILE_6_4, WINOGRAD_HEADS_TILE6_MAX_ROT = 64, 0.2     # F(6x6) 256-chann
 TRUNK_WINOGRAD_DEFAULT_MIN_BATCH, TRUNK_WINOGRAD_DEFAULT_MIN_FILL = 8, 55   # as include/se3tracknet.h (tests/test_host_abi.py)
 OFFSET_RULE_NUMPY1, OFFSET_RULE_NUMPY2 = 0, 1   # as include/se3tracknet.h: rounding of OffsetDepth's float64-scalar subtraction
 BLUR_NONE, BLUR_BILATERAL, BLUR_GAUSSIAN = 0, 1, 2
+ROUTE_WINDOW, ROUTE_FRAME = 0, 1   # as include/se3tracknet.h: the renderer se3tn_on_track uses for a mesh's image A
 RES = 176
 
 
@@ -89,6 +90,11 @@ _SIGS = {
     "se3tn_mesh_set_texture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "se3tn_render_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_render_frame_rect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int,
+                                          C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_mesh_set_route": (C.c_int, [C.c_void_p, C.c_int]),
+    "se3tn_mesh_get_route": (C.c_int, [C.c_void_p]),
+    "se3tn_frame_rect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "se3tn_on_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                  C.POINTER(C.c_int32), C.c_void_p]),

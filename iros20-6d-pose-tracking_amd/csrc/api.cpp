@@ -119,6 +119,12 @@ struct se3tn_ctx {
   unsigned long long* tb_zbuf = nullptr;
   uint8_t *tb_rgbA = nullptr, *tb_stage_host = nullptr, *tb_stage_dev = nullptr, *tb_out_host = nullptr, *tb_out_dev = nullptr;
   uint16_t* tb_depthA = nullptr;
+  // SE3TN_ROUTE_FRAME meshes (se3tn_on_track, se3tn_on_track_batch): the rendered rectangles [64 zero bytes | rgb of every pair | depth of
+  // every pair] and, for the batch, their z-buffers -- fr_px pixels in all (pairs x the largest rectangle of the call), grown at need.
+  // The 64 bytes in front are zeroed at allocation and never written: the 1 x 1 image A of a window that misses the frame
+  uint8_t* fr_sub = nullptr;
+  unsigned long long* fr_zbuf = nullptr;
+  size_t fr_px = 0;
   // se3tn_on_track_objects: rasteriser scratch of up to mo_cap instances of up to mo_V vertices / mo_F triangles (several meshes per launch)
   int mo_cap = 0, mo_V = 0, mo_F = 0;
   float4* mo_vpost = nullptr;
@@ -172,6 +178,7 @@ struct se3tn_mesh {
   int tw = 0, th = 0, tlevels = 0;
   unsigned tex_off[16] = {};
   float kd[3] = {1.f, 1.f, 1.f};
+  int route = SE3TN_ROUTE_WINDOW;   // se3tn_mesh_set_route: the renderer se3tn_on_track / _batch use for image A
 };
 
 // Init-time entry points that allocate or launch (plane derivation, workspace growth) run on the CONTEXT's device whatever device the
@@ -339,7 +346,7 @@ static bool stream_is_capturing(hipStream_t st) {
 
 extern "C" {
 
-const char* se3tn_version(void) { return "se3tracknet-gfx950 0.5.0 (blob v7)"; }
+const char* se3tn_version(void) { return "se3tracknet-gfx950 0.6.0 (blob v7)"; }
 const char* se3tn_last_error(void) { return g_err.c_str(); }
 
 int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
@@ -439,6 +446,8 @@ void se3tn_destroy(se3tn_ctx* c) {
     for (void* b : {(void*)c->mo_vpost, (void*)c->mo_vsnap, (void*)c->mo_big, (void*)c->mo_clipq})
       if (b) (void)hipFree(b);
     if (c->fd_buf) (void)hipFree(c->fd_buf);
+    if (c->fr_sub) (void)hipFree(c->fr_sub);
+    if (c->fr_zbuf) (void)hipFree(c->fr_zbuf);
     for (int s = 0; s < c->slots; ++s)
       for (auto& e : c->evs[s]) (void)hipEventDestroy(e);
   }
@@ -626,7 +635,9 @@ int se3tn_set_normalizers(se3tn_ctx* c, double tn, double rn) {
 
 float* se3tn_input_buffer(se3tn_ctx* c, int which) { return !c ? nullptr : (which == 0 ? c->inA : c->inB); }
 
-int se3tn_preprocess(se3tn_ctx* c, const se3tn_crop* crops, int n, float* out, void* stream) {
+// se3tn_preprocess; raw_rgb / raw_depth non-null: crop i also leaves its raw pixels (crop_bbox alone) as image i of [n,176,176,3] /
+// [n,176,176] (image A of the full-frame route: se3tn_on_track_batch)
+static int preprocess_impl(se3tn_ctx* c, const se3tn_crop* crops, int n, float* out, uint8_t* raw_rgb, uint16_t* raw_depth, void* stream) {
   if (!c || c->device < 0 || !crops || !out || n < 0) return fail(SE3TN_E_ARG, "se3tn_preprocess: bad argument");
   if (!c->have_norm) return fail(SE3TN_E_STATE, "se3tn_preprocess: call se3tn_set_normalization first");
   // the context's own input buffers hold max_batch images: more crops would run past them
@@ -652,9 +663,15 @@ int se3tn_preprocess(se3tn_ctx* c, const se3tn_crop* crops, int n, float* out, v
     if (a.padded) c->in_split[out == c->inA ? 0 : 1] = a.split;
     a.out = out + (size_t)i0 * (a.padded ? IN_P * IN_P : RES * RES) * 4;
     a.out2 = nullptr; a.n_first = a.n;
+    a.raw_rgb = raw_rgb ? raw_rgb + (size_t)i0 * RES * RES * 3 : nullptr;
+    a.raw_depth = raw_rgb ? raw_depth + (size_t)i0 * RES * RES : nullptr;
     HIPCHK(launch_preprocess(a, (hipStream_t)stream));
   }
   return SE3TN_OK;
+}
+
+int se3tn_preprocess(se3tn_ctx* c, const se3tn_crop* crops, int n, float* out, void* stream) {
+  return preprocess_impl(c, crops, n, out, nullptr, nullptr, stream);
 }
 
 int se3tn_crop_raw(se3tn_ctx* c, const se3tn_crop* k, uint8_t* rgb_out, uint16_t* depth_out, void* stream) {
@@ -1186,6 +1203,85 @@ int se3tn_render(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[16], const 
   return SE3TN_OK;
 }
 
+// ---- the pyrender-style renderer (offscreen_renderer.py:48-83): full frame, or a rectangle of it -------------------------------
+// material and the projection of mode 1: pyrender's IntrinsicsCamera at W x H (GL clip space, y up) times cvcam_in_glcam . ob_in_cam,
+// formed in float64 and uploaded as ONE float32 matrix; the vertex shader multiplies it with the position
+static void frame_uniforms(RasterArgs& a, const se3tn_mesh* m, const double ob_in_cam[16], const double K[9], int W, int H) {
+  a.rw = W; a.rh = H; a.mode = 1;
+  a.uv = m->uv; a.tex = m->tex; a.tw = m->tw; a.th = m->th; a.tlevels = m->tlevels;
+  for (int i = 0; i < 16; ++i) a.tex_off[i] = m->tex_off[i];
+  a.kd[0] = m->kd[0]; a.kd[1] = m->kd[1]; a.kd[2] = m->kd[2];
+  const double n = R_NEAR_D, f = R_FAR_D;
+  double P[4][4] = {{2.0 * K[0] / W, 0.0, 1.0 - 2.0 * K[2] / W, 0.0},
+                    {0.0, 2.0 * K[4] / H, 2.0 * K[5] / H - 1.0, 0.0},
+                    {0.0, 0.0, (f + n) / (n - f), 2.0 * f * n / (n - f)},
+                    {0.0, 0.0, -1.0, 0.0}};
+  const double sgn[4] = {1.0, -1.0, -1.0, 1.0};
+  for (int r = 0; r < 4; ++r)
+    for (int q = 0; q < 4; ++q) {
+      double acc = 0.0;
+      for (int k = 0; k < 4; ++k) acc += P[r][k] * (sgn[k] * ob_in_cam[4 * k + q]);
+      a.PV[4 * r + q] = (float)acc;
+    }
+}
+// rect = {x0, y0, x1, y1} in OpenCV image coordinates -> the scissor in GL window coordinates (row 0 at the bottom)
+static void rect_to_scissor(const int32_t rect[4], int H, int s[4]) {
+  s[0] = rect[0]; s[1] = H - rect[3]; s[2] = rect[2]; s[3] = H - rect[1];
+}
+// crop window (left, top, right, bottom) intersected with the frame; false: they do not meet (rect = {0, 0, 0, 0})
+static bool window_rect(const int32_t win[4], int H, int W, int32_t rect[4]) {
+  const int32_t x0 = win[0] > 0 ? win[0] : 0, x1 = win[2] < W ? win[2] : W;
+  const int32_t y0 = win[1] > 0 ? win[1] : 0, y1 = win[3] < H ? win[3] : H;
+  if (x1 <= x0 || y1 <= y0) { rect[0] = rect[1] = rect[2] = rect[3] = 0; return false; }
+  rect[0] = x0; rect[1] = y0; rect[2] = x1; rect[3] = y1;
+  return true;
+}
+// sub-images and z-buffers of the SE3TN_ROUTE_FRAME calls for `px` pixels in all (never inside a capture: the callers are synchronous)
+static int reserve_frame_route(se3tn_ctx* c, size_t px) {
+  if (px <= c->fr_px) return SE3TN_OK;
+  DeviceGuard dg(c->device);
+  if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+  HIPCHK(hipDeviceSynchronize());
+  if (c->fr_sub) HIPCHK(hipFree(c->fr_sub));
+  if (c->fr_zbuf) HIPCHK(hipFree(c->fr_zbuf));
+  c->fr_sub = nullptr; c->fr_zbuf = nullptr; c->fr_px = 0;
+  HIPCHK(hipMalloc((void**)&c->fr_sub, 64 + ((px * 3 + 63) & ~(size_t)63) + px * 2 + 64));
+  HIPCHK(hipMalloc((void**)&c->fr_zbuf, sizeof(unsigned long long) * px));
+  HIPCHK(hipMemset(c->fr_sub, 0, 64));
+  c->fr_px = px;
+  return SE3TN_OK;
+}
+
+int se3tn_mesh_set_route(se3tn_mesh* m, int route) {
+  if (!m || (route != SE3TN_ROUTE_WINDOW && route != SE3TN_ROUTE_FRAME)) return fail(SE3TN_E_ARG, "se3tn_mesh_set_route: bad argument");
+  m->route = route;
+  return SE3TN_OK;
+}
+int se3tn_mesh_get_route(const se3tn_mesh* m) { return m ? m->route : -1; }
+
+int se3tn_render_frame_rect(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[16], const double K[9], int W, int H, const int32_t rect[4],
+                            uint8_t* rgb_sub, uint16_t* depth_sub, void* stream) {
+  if (!c || c->device < 0 || !m || !ob_in_cam || !K || !rect || !rgb_sub || !depth_sub || W < 1 || H < 1)
+    return fail(SE3TN_E_ARG, "se3tn_render_frame_rect: bad argument");
+  if (H > 2048) return fail(SE3TN_E_ARG, "se3tn_render_frame_rect: frames of more than 2048 rows are not supported");
+  if (rect[2] <= rect[0] || rect[3] <= rect[1]) return fail(SE3TN_E_ARG, "se3tn_render_frame_rect: empty rectangle");
+  if (rect[0] < 0 || rect[1] < 0 || rect[2] > W || rect[3] > H) return fail(SE3TN_E_ARG, "se3tn_render_frame_rect: rectangle outside the frame");
+  const size_t px = (size_t)(rect[2] - rect[0]) * (size_t)(rect[3] - rect[1]);
+  if (px > c->zbuf_px) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
+    if (stream_is_capturing((hipStream_t)stream))
+      return fail(SE3TN_E_STATE, "se3tn_render_frame_rect: z-buffer too small for this rectangle inside a stream capture: call se3tn_reserve(ctx, H, W) first");
+    if (int rc = reserve_zbuf(c, px)) return rc;
+  }
+  RasterArgs a{};
+  raster_common(a, c, m, rgb_sub, depth_sub);
+  frame_uniforms(a, m, ob_in_cam, K, W, H);
+  int s[4];
+  rect_to_scissor(rect, H, s);
+  a.scissor = 1; a.sx0 = s[0]; a.sy0 = s[1]; a.sx1 = s[2]; a.sy1 = s[3]; a.spx = (int)px;
+  HIPCHK(launch_raster(a, (hipStream_t)stream));
+  return SE3TN_OK;
+}
+
 // np.round: round half to even
 static double round_half_even(double x) { return std::nearbyint(x); }
 
@@ -1259,7 +1355,31 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
   // image A first: its four launches run on the device while the host stages the frame
   uint8_t* rA = rgbA_dev ? rgbA_dev : c->trk_rgbA;
   uint16_t* dA = depthA_dev ? depthA_dev : c->trk_depthA;
-  if (int rc = se3tn_render(c, m, prev_pose, K, winA, rA, dA, stream)) return rc;
+  const bool frame_route = m->route == SE3TN_ROUTE_FRAME;
+  int32_t rectA[4] = {0, 0, 0, 0};
+  bool missA = false;
+  size_t subA_d_off = 0;   // frame route: offset of the sub-image's depth in c->fr_sub
+  if (frame_route) {
+    // predict.py:209-213: the full-frame render cropped with the SAME window as the camera frame -- only the rectangle of the frame
+    // the window covers is rendered (every byte of it as se3tn_render_frame gives it)
+    if (H > 2048) return fail(SE3TN_E_ARG, "se3tn_on_track: frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
+    if (int rc = reserve_frame_route(c, (size_t)H * W)) return rc;
+    missA = !window_rect(winB, H, W, rectA);
+    if (!missA) {
+      const size_t px = (size_t)(rectA[2] - rectA[0]) * (size_t)(rectA[3] - rectA[1]);
+      subA_d_off = 64 + ((px * 3 + 63) & ~(size_t)63);
+      RasterArgs ra{};
+      raster_common(ra, c, m, c->fr_sub + 64, (uint16_t*)(c->fr_sub + subA_d_off));
+      ra.zbuf = c->fr_zbuf;
+      frame_uniforms(ra, m, prev_pose, K, W, H);
+      int s[4];
+      rect_to_scissor(rectA, H, s);
+      ra.scissor = 1; ra.sx0 = s[0]; ra.sy0 = s[1]; ra.sx1 = s[2]; ra.sy1 = s[3]; ra.spx = (int)px;
+      HIPCHK(launch_raster(ra, st));
+    }
+  } else if (int rc = se3tn_render(c, m, prev_pose, K, winA, rA, dA, stream)) {
+    return rc;
+  }
   const double t1 = trace ? now() : 0.0;
   // only the part of the frame the window covers travels: rows / columns [y0, y1) x [x0, x1) into pinned memory, ONE copy
   // with the pose in front, on a copy stream of its own (beside the rasteriser, not behind it).  crop_bbox's canvas is zero
@@ -1295,6 +1415,16 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
   se3tn_crop& ca = a.c[0];
   ca.rgb = rA; ca.depth = dA; ca.H = RES; ca.W = RES; ca.left = 0; ca.top = 0; ca.right = RES; ca.bottom = RES;
   ca.z_offset_mm = z_mm; ca.stats = 0; ca._pad = 0;
+  if (frame_route) {
+    // image A = the rendered rectangle with the window shifted by its origin (a window that misses the frame: the 1 x 1 zero image in
+    // front of the buffer, which the shifted window does not touch); the same launch writes its raw crop = Tracker.render_window
+    const int ox = missA ? winB[0] - 8 : rectA[0], oy = missA ? winB[1] - 8 : rectA[1];
+    ca.rgb = missA ? c->fr_sub : c->fr_sub + 64;
+    ca.depth = missA ? (const uint16_t*)(c->fr_sub + 32) : (const uint16_t*)(c->fr_sub + subA_d_off);
+    ca.H = missA ? 1 : rectA[3] - rectA[1]; ca.W = missA ? 1 : rectA[2] - rectA[0];
+    ca.left = winB[0] - ox; ca.top = winB[1] - oy; ca.right = winB[2] - ox; ca.bottom = winB[3] - oy;
+    if (rgbA_dev || depthA_dev) { a.raw_rgb = rA; a.raw_depth = dA; }   // (the one not given goes to the internal buffer)
+  }
   se3tn_crop& cb = a.c[1];
   cb.rgb = c->trk_dev + 256; cb.depth = (const uint16_t*)(c->trk_dev + d_off); cb.H = sh; cb.W = sw;
   cb.left = winB[0] - x0; cb.top = winB[1] - y0; cb.right = winB[2] - x0; cb.bottom = winB[3] - y0;
@@ -1436,21 +1566,51 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   // image A of all n poses: the instance table goes up on the launch stream, then FOUR launches (grid.y = pose)
   uint8_t* rA = rgbA_dev ? rgbA_dev : c->tb_rgbA;
   uint16_t* dA = depthA_dev ? depthA_dev : c->tb_depthA;
+  // SE3TN_ROUTE_FRAME (predict.py:209-213): per pair the rectangle of the full-frame render its crop window covers -- geo above, the
+  // same rectangle as the staged part of the camera frame.  Z-buffers and sub-images are sized by the largest rectangle of the call
+  const bool frame_route = m->route == SE3TN_ROUTE_FRAME;
+  size_t maxpx = 0, fr_d_off = 0;
+  if (frame_route) {
+    if (H > 2048) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
+    for (int i = 0; i < n; ++i)
+      if (geo[4 * i + 2] > 0) maxpx = std::max(maxpx, (size_t)geo[4 * i + 2] * (size_t)geo[4 * i + 3]);
+    const size_t need = maxpx ? (size_t)n * maxpx : 1, cap = (size_t)n * H * W;
+    // windows change from frame to frame: grow with half as much again in hand (never past n whole frames)
+    if (need > c->fr_px)
+      if (int rc = reserve_frame_route(c, std::max(need, std::min(need + need / 2, cap)))) return rc;
+    fr_d_off = 64 + (((size_t)n * maxpx * 3 + 63) & ~(size_t)63);
+  }
   RasterArgs ra{};
   raster_common(ra, c, m, rA, dA);
   ra.rw = RES; ra.rh = RES; ra.mode = 0;
-  ra.vpost = m->b_vpost; ra.vsnap = m->b_vsnap; ra.big = m->b_big; ra.clipq = m->b_clipq; ra.zbuf = c->tb_zbuf;
+  if (frame_route) {
+    frame_uniforms(ra, m, prev_poses, K, W, H);   // material, frame size (the matrix comes from the instance table)
+    ra.rgb = c->fr_sub + 64; ra.depth = (uint16_t*)(c->fr_sub + fr_d_off);
+    ra.scissor = 1; ra.spx = (int)maxpx;
+  }
+  ra.vpost = m->b_vpost; ra.vsnap = m->b_vsnap; ra.big = m->b_big; ra.clipq = m->b_clipq; ra.zbuf = frame_route ? c->fr_zbuf : c->tb_zbuf;
   for (int i = 0; i < n; ++i) {
     RasterArgs one{};
-    if (!vispy_uniforms(one, prev_poses + 16 * (size_t)i, K, &win[8 * (size_t)i + 4])) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: singular pose");
     RasterInstance& I = c->tb_inst_host[i];
+    if (frame_route) {
+      frame_uniforms(one, m, prev_poses + 16 * (size_t)i, K, W, H);
+      const int32_t r[4] = {geo[4 * i], geo[4 * i + 1], geo[4 * i] + geo[4 * i + 2], geo[4 * i + 1] + geo[4 * i + 3]};
+      if (geo[4 * i + 2] > 0) rect_to_scissor(r, H, I.rect);
+      // the window misses the frame: an empty rectangle.  The instance still runs its vertex / triangle / queue workgroups (one grid
+      // for all instances) and writes nothing: a few microseconds wasted on a case a tracker does not stay in
+      else I.rect[0] = I.rect[1] = I.rect[2] = I.rect[3] = 0;
+    } else if (!vispy_uniforms(one, prev_poses + 16 * (size_t)i, K, &win[8 * (size_t)i + 4])) {
+      return fail(SE3TN_E_ARG, "se3tn_on_track_batch: singular pose");
+    }
     std::memcpy(I.PV, one.PV, sizeof(I.PV));
     std::memcpy(I.light, one.light, sizeof(I.light));
     I._pad = 0.f; I.dA = one.dA; I.dB = one.dB;
   }
-  HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, sizeof(RasterInstance) * n, hipMemcpyHostToDevice, st));
-  ra.inst = c->tb_inst_dev;
-  HIPCHK(launch_raster(ra, st, n));
+  if (!frame_route || maxpx > 0) {
+    HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, sizeof(RasterInstance) * n, hipMemcpyHostToDevice, st));
+    ra.inst = c->tb_inst_dev;
+    HIPCHK(launch_raster(ra, st, n));
+  }
   const double t1 = trace ? now() : 0.0;
   // the frames' windows: staged through pinned memory while the rasteriser runs, ONE copy with the poses in front
   uint8_t* hp = c->tb_stage_host;
@@ -1496,12 +1656,20 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
     se3tn_crop& cb = crops[(size_t)n + i];
     const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
     const int32_t* wB = &win[8 * (size_t)i];
+    if (frame_route) {   // image A = the rendered rectangle under the window shifted by its origin (a miss: the 1 x 1 zero image)
+      ca.rgb = sw < 0 ? c->fr_sub : c->fr_sub + 64 + (size_t)i * maxpx * 3;
+      ca.depth = sw < 0 ? (const uint16_t*)(c->fr_sub + 32) : (const uint16_t*)(c->fr_sub + fr_d_off) + (size_t)i * maxpx;
+      ca.H = sw < 0 ? 1 : sh; ca.W = sw < 0 ? 1 : sw;
+      ca.left = wB[0] - x0; ca.top = wB[1] - y0; ca.right = wB[2] - x0; ca.bottom = wB[3] - y0;
+    }
     cb.rgb = c->tb_stage_dev + off_rgb[i]; cb.depth = (const uint16_t*)(c->tb_stage_dev + off_d[i]);
     cb.H = sw < 0 ? 1 : sh; cb.W = sw < 0 ? 1 : sw;
     cb.left = wB[0] - x0; cb.top = wB[1] - y0; cb.right = wB[2] - x0; cb.bottom = wB[3] - y0;
     cb.z_offset_mm = z_mm; cb.stats = 1; cb._pad = 0;
   }
-  int rc = se3tn_preprocess(c, crops.data(), n, c->inA, stream);
+  // frame route: the crops of image A also leave their raw pixels (crop_bbox of the render = Tracker.render_window) in rgbA_dev / depthA_dev
+  const bool rawA = frame_route && (rgbA_dev || depthA_dev);
+  int rc = preprocess_impl(c, crops.data(), n, c->inA, rawA ? rA : nullptr, rawA ? dA : nullptr, stream);
   if (rc == SE3TN_OK) rc = se3tn_preprocess(c, crops.data() + n, n, c->inB, stream);
   float* trans_d = (float*)(c->tb_out_dev + (size_t)n * 128);
   float* rot_d = trans_d + 3 * (size_t)n;
@@ -1615,6 +1783,7 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     const std::string id = who + std::to_string(i);
     if (!o.mesh) return fail(SE3TN_E_ARG, id + ": null mesh");
     if (o.mesh->tex || o.mesh->uv) return fail(SE3TN_E_ARG, id + ": textured mesh (the full-frame renderer's route: se3tn_on_track per object)");
+    if (o.mesh->route != SE3TN_ROUTE_WINDOW) return fail(SE3TN_E_ARG, id + ": mesh on SE3TN_ROUTE_FRAME (se3tn_on_track per object)");
     if (!(o.object_width_mm > 0)) return fail(SE3TN_E_ARG, id + ": object width must be > 0");
     const se3tn_ctx* m = o.model;
     if (!m) return fail(SE3TN_E_ARG, id + ": null model");
@@ -1794,24 +1963,7 @@ int se3tn_render_frame(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[16], 
   if (H > 2048) return fail(SE3TN_E_ARG, "se3tn_render_frame: frames of more than 2048 rows are not supported");
   RasterArgs a{};
   raster_common(a, c, m, rgb, depth);
-  a.rw = W; a.rh = H; a.mode = 1;
-  a.uv = m->uv; a.tex = m->tex; a.tw = m->tw; a.th = m->th; a.tlevels = m->tlevels;
-  for (int i = 0; i < 16; ++i) a.tex_off[i] = m->tex_off[i];
-  a.kd[0] = m->kd[0]; a.kd[1] = m->kd[1]; a.kd[2] = m->kd[2];
-  // pyrender's IntrinsicsCamera projection at W x H (GL clip space, y up) times cvcam_in_glcam . ob_in_cam, formed in float64 and
-  // uploaded as ONE float32 matrix; the vertex shader multiplies it with the position
-  const double n = R_NEAR_D, f = R_FAR_D;
-  double P[4][4] = {{2.0 * K[0] / W, 0.0, 1.0 - 2.0 * K[2] / W, 0.0},
-                    {0.0, 2.0 * K[4] / H, 2.0 * K[5] / H - 1.0, 0.0},
-                    {0.0, 0.0, (f + n) / (n - f), 2.0 * f * n / (n - f)},
-                    {0.0, 0.0, -1.0, 0.0}};
-  const double sgn[4] = {1.0, -1.0, -1.0, 1.0};
-  for (int r = 0; r < 4; ++r)
-    for (int q = 0; q < 4; ++q) {
-      double acc = 0.0;
-      for (int k = 0; k < 4; ++k) acc += P[r][k] * (sgn[k] * ob_in_cam[4 * k + q]);
-      a.PV[4 * r + q] = (float)acc;
-    }
+  frame_uniforms(a, m, ob_in_cam, K, W, H);
   HIPCHK(launch_raster(a, (hipStream_t)stream));
   return SE3TN_OK;
 }
@@ -1885,6 +2037,17 @@ int se3tn_compute_bbox(const double pose[16], const double K[9], double width, i
     out_vu[2 * i + 0] = (int32_t)round_half_even(v);
     out_vu[2 * i + 1] = (int32_t)round_half_even(u);
   }
+  return SE3TN_OK;
+}
+
+int se3tn_frame_rect(const double pose[16], const double K[9], double width, int H, int W, int32_t rect[4]) {
+  if (!pose || !K || !rect || H < 1 || W < 1 || !(width > 0)) return fail(SE3TN_E_ARG, "se3tn_frame_rect: bad argument");
+  int32_t win[4];
+  if (!(pose[11] > 0) || !std::isfinite(pose[3]) || !std::isfinite(pose[7]) || !std::isfinite(pose[11]) ||
+      !bbox_window(pose, K, width, 1000.0, win, nullptr))
+    return fail(SE3TN_E_ARG, "se3tn_frame_rect: pose is not in front of the camera (z <= 0 or not finite)");
+  if (win[2] <= win[0] || win[3] <= win[1]) return fail(SE3TN_E_ARG, "se3tn_frame_rect: empty crop window");
+  (void)window_rect(win, H, W, rect);
   return SE3TN_OK;
 }
 

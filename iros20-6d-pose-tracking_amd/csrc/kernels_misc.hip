@@ -86,6 +86,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const CropArgs a) {
     r = (float)px[0]; g = (float)px[1]; b = (float)px[2];
     d = (float)c.depth[q];
   }
+  if (a.raw_rgb != nullptr && i < a.n_first) {   // (uniform over the launch / the workgroup; the values are exact integers)
+    uint8_t* rr = a.raw_rgb + ((size_t)i * RES * RES + p) * 3;
+    rr[0] = (uint8_t)r; rr[1] = (uint8_t)g; rr[2] = (uint8_t)b;
+    a.raw_depth[(size_t)i * RES * RES + p] = (uint16_t)d;
+  }
   const bool invalid = (d <= 100.f) || (d >= 2000.f);
   const double z = c.z_offset_mm;
   if (a.offset_rule == SE3TN_OFFSET_RULE_NUMPY1) {

@@ -29,6 +29,11 @@
 // linearised to camera z.  Coverage, depth and vertex colours follow the same rules exactly; the texture FILTER is float32
 // arithmetic here (the GL implementation filters in 16-bit fixed point): textured colours agree to a few / 255.
 //
+// Scissored form of the second mode (a.scissor != 0, se3tn_render_frame_rect): the vertices go through the FULL-frame projection, but the
+// z-buffer, its clear, every coverage loop and the resolve cover only the rectangle [sx0, sx1) x [sy0, sy1) of GL window coordinates,
+// and the output is that rectangle as a tightly packed sub-image.  Keys, plane equations and the texture level of detail are evaluated
+// at ABSOLUTE window coordinates, so every byte equals the same pixel of the full-frame render; the scissor only bounds the loops.
+//
 // Four launches: vertices -> clip / window space (+ z-buffer / queue clears); one thread per triangle scatters (z | triangle id) keys;
 // raster_queue_kernel: large bounding boxes by one wave per triangle, triangles crossing the frustum clipped and their outline walked
 // by one wave; one thread per pixel re-derives the plane equations of the winning triangle, interpolates and shades.
@@ -54,12 +59,14 @@ __device__ __forceinline__ RasterArgs raster_instance(const RasterArgs& a0) {
       a.verts = I->verts; a.normals = I->normals; a.colors = I->colors; a.faces = I->faces;
       a.V = I->V; a.F = I->F;
     }
-    const size_t px = (size_t)a0.rw * a0.rh;
+    const size_t px = a0.scissor ? (size_t)a0.spx : (size_t)a0.rw * a0.rh;
+    if (a0.scissor) { a.sx0 = I->rect[0]; a.sy0 = I->rect[1]; a.sx1 = I->rect[2]; a.sy1 = I->rect[3]; }
     a.vpost += b * a0.V; a.vsnap += b * a0.V;
     a.zbuf += b * px;
     a.big += b * (size_t)(1 + a0.F); a.clipq += b * (size_t)(1 + a0.F);
     a.rgb += b * px * 3; a.depth += b * px;
   }
+  if (!a0.scissor) { a.sx0 = 0; a.sy0 = 0; a.sx1 = a.rw; a.sy1 = a.rh; }   // the whole window
   return a;
 }
 
@@ -67,7 +74,7 @@ __global__ __launch_bounds__(256) void raster_vertex_kernel(const RasterArgs a0)
   const RasterArgs a = raster_instance(a0);
   const int i = blockIdx.x * 256 + threadIdx.x;
   // this launch also clears the z-buffer and the two queue counters (they are first touched by the NEXT launch)
-  for (int p = i; p < a.rw * a.rh; p += gridDim.x * 256) a.zbuf[p] = ~0ull;
+  for (int p = i; p < (a.sx1 - a.sx0) * (a.sy1 - a.sy0); p += gridDim.x * 256) a.zbuf[p] = ~0ull;
   if (i == 0) { a.big[0] = 0; a.clipq[0] = 0; }
   if (i >= a.V) return;
   const float px = a.verts[3 * i], py = a.verts[3 * i + 1], pz = a.verts[3 * i + 2];
@@ -169,7 +176,7 @@ __device__ __forceinline__ void depth_write(const RasterArgs& a, const TriSetup&
   const float z = plane_eval(s.zA, s.zB, s.zC, quad_coord(x, s.dx), quad_coord(y, s.dy));
   if (!(z < 1.0f)) return;   // GL_LESS against the cleared 1.0 (and NaN)
   const unsigned long long key = ((unsigned long long)sortable(z) << 32) | (unsigned)t;
-  atomicMin(a.zbuf + (size_t)y * a.rw + x, key);
+  atomicMin(a.zbuf + (size_t)(y - a.sy0) * (a.sx1 - a.sx0) + (x - a.sx0), key);
 }
 
 // integer edge functions of an unclipped triangle, orientation made positive
@@ -196,10 +203,10 @@ __device__ __forceinline__ bool edges_setup(const RasterArgs& a, const int4 snap
     e.tie[k] = e.dy[k] < 0 || (e.dy[k] == 0 && e.dx[k] > 0);
   }
   const int sb = a.sub_bits;
-  e.x0 = max(ceil_shift(min(X[0], min(X[1], X[2])), sb), 0);
-  e.x1 = min(ceil_shift(max(X[0], max(X[1], X[2])), sb), a.rw);
-  e.y0 = max(ceil_shift(min(Y[0], min(Y[1], Y[2])), sb), 0);
-  e.y1 = min(ceil_shift(max(Y[0], max(Y[1], Y[2])), sb), a.rh);
+  e.x0 = max(ceil_shift(min(X[0], min(X[1], X[2])), sb), a.sx0);
+  e.x1 = min(ceil_shift(max(X[0], max(X[1], X[2])), sb), a.sx1);
+  e.y0 = max(ceil_shift(min(Y[0], min(Y[1], Y[2])), sb), a.sy0);
+  e.y1 = min(ceil_shift(max(Y[0], max(Y[1], Y[2])), sb), a.sy1);
   return e.x0 < e.x1 && e.y0 < e.y1;
 }
 
@@ -383,7 +390,7 @@ __global__ __launch_bounds__(256) void raster_queue_kernel(const RasterArgs a0) 
     if (n < 3) continue;
     int ylo = INT_MAX, yhi = INT_MIN;
     for (int i = 0; i < n; ++i) { ylo = min(ylo, PY[i]); yhi = max(yhi, PY[i]); }
-    const int ymin = max(ceil_shift(ylo, sb), 0), ymax = min(ceil_shift(yhi, sb), a.rh);
+    const int ymin = max(ceil_shift(ylo, sb), a.sy0), ymax = min(ceil_shift(yhi, sb), a.sy1);
     for (int y = ymin + lane; y < ymax; y += 64) { tab[0][y] = 0; tab[1][y] = 0; }
     __syncthreads();
     const int di = d ? 1 : 0;
@@ -393,7 +400,7 @@ __global__ __launch_bounds__(256) void raster_queue_kernel(const RasterArgs a0) 
       if (Ya != Yb) {
         const bool swap = Yb < Ya;
         const long long X1 = swap ? Xb : Xa, Y1 = swap ? Yb : Ya, X2 = swap ? Xa : Xb, Y2 = swap ? Ya : Yb;
-        const int y1 = max(ceil_shift((int)Y1, sb), 0), y2 = min(ceil_shift((int)Y2, sb), a.rh);
+        const int y1 = max(ceil_shift((int)Y1, sb), a.sy0), y2 = min(ceil_shift((int)Y2, sb), a.sy1);
         const long long DX = X2 - X1, DY = Y2 - Y1, den = DY << sb;
         for (int y = y1 + lane; y < y2; y += 64) {
           const long long num = X1 * DY + DX * (((long long)y << sb) - Y1);
@@ -407,7 +414,7 @@ __global__ __launch_bounds__(256) void raster_queue_kernel(const RasterArgs a0) 
     TriSetup s;
     tri_setup<false>(post, snap, sb, s);
     for (int y = ymin; y < ymax; ++y) {
-      const int xl = tab[0][y], xr = tab[1][y];
+      const int xl = max(tab[0][y], a.sx0), xr = min(tab[1][y], a.sx1);
       for (int x = xl + lane; x < xr; x += 64) depth_write(a, s, x, y, t);
     }
   }
@@ -465,12 +472,16 @@ __device__ __forceinline__ float interp(const TriSetup& s, const Interp& it, flo
 __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a0) {
   const RasterArgs a = raster_instance(a0);
   const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.rw * a.rh) return;
+  const int bw = a.sx1 - a.sx0, bh = a.sy1 - a.sy0;
+  if (p >= bw * bh) return;
   // GL window row j counts bottom-up, and glReadPixels returns rows in that order.  Mode 0: the reference reshapes the buffer
   // as-is (`bottom` is the LARGER Y = cy - fy y/z, i.e. the smaller OpenCV v, so array row j is already top-down in the OpenCV
   // image).  Mode 1: pyrender flips the rows on read-back.
-  const int j = p / a.rw, i = p - j * a.rw;
-  const size_t o = a.mode == 1 ? (size_t)(a.rh - 1 - j) * a.rw + i : (size_t)p;
+  // (jj, ii): position in the scissor rectangle = in the z-buffer and the output; (j, i): ABSOLUTE window coordinates, at which
+  // everything below is evaluated
+  const int jj = p / bw, ii = p - jj * bw;
+  const int j = a.sy0 + jj, i = a.sx0 + ii;
+  const size_t o = a.mode == 1 ? (size_t)(bh - 1 - jj) * bw + ii : (size_t)p;
   const unsigned long long key = a.zbuf[p];
   uint8_t* rgb = a.rgb + o * 3;
   if (key == ~0ull) {
@@ -562,13 +573,15 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a0
 hipError_t launch_raster(const RasterArgs& a, hipStream_t st, int instances) {
   // one thread per vertex; the z-buffer clear strides over the grid (at least 128 blocks, or one per 256 pixels if that is fewer)
   // instances > 1 (a.inst set): grid.y = instance, the same four launches for all poses
-  const int vb = (a.V + 255) / 256, zb = (a.rw * a.rh + 255) / 256;
+  // scissored: the z-buffer and the output hold a.spx pixels per instance (the largest rectangle of the call)
+  const int zpx = a.scissor ? a.spx : a.rw * a.rh;
+  const int vb = (a.V + 255) / 256, zb = (zpx + 255) / 256;
   const int clear_blocks = zb < 128 ? zb : 128;
   const unsigned ny = a.inst ? (unsigned)instances : 1u;
   hipLaunchKernelGGL(raster_vertex_kernel, dim3(vb > clear_blocks ? vb : clear_blocks, ny), dim3(256), 0, st, a);
   hipLaunchKernelGGL(raster_triangle_kernel, dim3((a.F + 255) / 256, ny), dim3(256), 0, st, a);
   hipLaunchKernelGGL(raster_queue_kernel, dim3(BIG_BLOCKS + CLIP_BLOCKS, ny), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(raster_resolve_kernel, dim3((a.rw * a.rh + 255) / 256, ny), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(raster_resolve_kernel, dim3(zb, ny), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -234,6 +234,10 @@ struct CropArgs {  // one launch handles up to MAX crops
   // nullptr: every crop normalises with mean / stdv above.  Otherwise a DEVICE table [n_first][16] (mean[8] | std[8] per object):
   // crop i normalises with row (i < n_first ? i : i - n_first) -- several models' crops in one launch (se3tn_on_track_objects)
   const double* norm = nullptr;
+  // non-null: crop i < n_first also stores its raw pixels (crop_bbox alone, what launch_crop_raw writes) as image i of raw_rgb
+  // [n_first,176,176,3] / raw_depth [n_first,176,176] -- image A of the full-frame route, in the launch that normalises it
+  uint8_t* raw_rgb = nullptr;
+  uint16_t* raw_depth = nullptr;
 };
 
 static_assert(sizeof(CropArgs) <= 4096, "CropArgs travels as kernel arguments: HIP's limit is 4 KB");
@@ -330,6 +334,7 @@ struct RasterInstance {
   const float *verts, *normals, *colors;
   const int* faces;
   int V, F;
+  int rect[4];   // RasterArgs::scissor != 0: this instance's rectangle sx0, sy0, sx1, sy1 (GL window coordinates; may be empty)
 };
 struct RasterArgs {
   const RasterInstance* inst;  // nullptr: one instance, uniforms below.  Otherwise instance b = blockIdx.y takes PV / light / dA / dB from
@@ -360,6 +365,12 @@ struct RasterArgs {
   float kd[3];           // base colour factor (mtl Kd)
   int inst_mesh = 0;     // batched launch: 1 = every instance brings its own mesh (RasterInstance verts .. F); V / F above are then
                          // the LARGEST counts (grid and scratch strides), and threads past their own instance's counts exit
+  // scissor != 0 (mode 1, se3tn_render_frame_rect): only the pixels [sx0, sx1) x [sy0, sy1) of the rw x rh window (GL window coordinates:
+  // row 0 at the BOTTOM) are cleared, covered and resolved; zbuf / rgb / depth hold that rectangle tightly packed, spx pixels per
+  // instance (>= the area of every rectangle of the launch).  0: the whole window (the kernels set the rectangle themselves)
+  int scissor = 0;
+  int sx0 = 0, sy0 = 0, sx1 = 0, sy1 = 0;
+  int spx = 0;
 };
 hipError_t launch_raster(const RasterArgs& a, hipStream_t st, int instances = 1);
 

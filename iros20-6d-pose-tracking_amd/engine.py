@@ -378,6 +378,18 @@ def compute_bbox(pose, K, object_width_mm):
     return np.array(out[:], dtype=np.int32).reshape(4, 2)
 
 
+def frame_rect(pose, K, object_width_mm, H, W):
+    """The rectangle (x0, y0, x1, y1) of an H x W frame the full-frame (pyrender) route renders for this pose: compute_bbox's crop
+    window clipped to the frame (se3tn_frame_rect); None when the window misses the frame."""
+    lib = _lib.load()
+    p = (C.c_double * 16)(*np.asarray(pose, np.float64).reshape(16))
+    k = (C.c_double * 9)(*np.asarray(K, np.float64).reshape(9))
+    out = (C.c_int32 * 4)()
+    check(lib.se3tn_frame_rect(p, k, float(object_width_mm), int(H), int(W), out), "se3tn_frame_rect")
+    r = tuple(int(x) for x in out)
+    return r if r[2] > r[0] and r[3] > r[1] else None
+
+
 def pose_update_host(A_in_cam, trans, rot, trans_normalizer, rot_normalizer):
     """datasets.py:159-175 processPredict (host float64)."""
     lib = _lib.load()

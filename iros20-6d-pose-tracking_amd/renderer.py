@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import utils as U
-from ._lib import check
+from ._lib import ROUTE_FRAME, check
 from .engine import _stream_ptr
 
 
@@ -54,6 +54,8 @@ class HipRenderer:
                       "se3tn_mesh_set_texture")
             else:
                 check(engine.lib.se3tn_mesh_set_texture(self._m, None, None, 0, 0, kd), "se3tn_mesh_set_texture")
+            # se3tn_on_track / _batch render image A of this mesh as predict.py:209-213 does (the frame's rectangle under the crop window)
+            check(engine.lib.se3tn_mesh_set_route(self._m, ROUTE_FRAME), "se3tn_mesh_set_route")
             self.H, self.W = int(frame_size[0]), int(frame_size[1])
             self.rgb = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=dev)
             self.depth = torch.empty((self.H, self.W), dtype=torch.int16, device=dev)
@@ -95,6 +97,24 @@ class HipRenderer:
         check(self.engine.lib.se3tn_render_frame(self.engine._h, self._m, p, k, self.W, self.H, C.c_void_p(self.rgb.data_ptr()),
                                                  C.c_void_p(self.depth.data_ptr()), _stream_ptr()), "se3tn_render_frame")
         return self.rgb, self.depth
+
+    def render_frame_rect(self, ob2cam, K, rect, device=False):
+        """mode 'pyrender': only the rectangle rect = (x0, y0, x1, y1) of the camera frame (columns [x0, x1), rows [y0, y1), row 0 =
+        top) -- every byte as render_frame()[y0:y1, x0:x1] has it.  numpy (rgb uint8 [y1-y0, x1-x0, 3], depth uint16 mm), or with
+        device=True the device tensors (uint8, uint16-as-int16); asynchronous then."""
+        assert self.full_frame
+        x0, y0, x1, y1 = [int(v) for v in rect]
+        dev = self.rgb.device
+        rgb = torch.empty((max(y1 - y0, 0), max(x1 - x0, 0), 3), dtype=torch.uint8, device=dev)
+        depth = torch.empty((max(y1 - y0, 0), max(x1 - x0, 0)), dtype=torch.int16, device=dev)
+        p = (C.c_double * 16)(*np.asarray(ob2cam, np.float64).reshape(16))
+        k = (C.c_double * 9)(*np.asarray(K, np.float64).reshape(9))
+        r = (C.c_int32 * 4)(x0, y0, x1, y1)
+        check(self.engine.lib.se3tn_render_frame_rect(self.engine._h, self._m, p, k, self.W, self.H, r, C.c_void_p(rgb.data_ptr()),
+                                                      C.c_void_p(depth.data_ptr()), _stream_ptr()), "se3tn_render_frame_rect")
+        if device:
+            return rgb, depth
+        return rgb.cpu().numpy(), depth.cpu().numpy().view(np.uint16)
 
     def render_frame(self, ob2cam, K):
         """numpy (rgb uint8 [H,W,3], depth uint16 [H,W] mm) == (color, (depth * 1000).astype(uint16)) of

@@ -99,7 +99,8 @@ class Tracker:
         self.frame_cnt = 0
         self._one_call_state = None
         self._batch_state = None
-        self.one_call = True     # on_track through se3tn_on_track when the built-in rasteriser renders image A (False: step by step)
+        self.one_call = True     # on_track through se3tn_on_track when the built-in rasteriser renders image A, window or full-frame
+                                 # route (False: step by step)
         self.errs = []
         dev = "cuda:%d" % device
         self._dev = dev
@@ -166,7 +167,7 @@ class Tracker:
                 return self.on_track(prev_pose, current_rgb, current_depth, gt_A_in_cam, gt_B_in_cam, debug, samples)
         prev_pose = np.asarray(prev_pose, np.float64)
         from .renderer import HipRenderer
-        if self.one_call and isinstance(self.renderer, HipRenderer) and not self.renderer.full_frame and int(samples) <= 1:
+        if self.one_call and isinstance(self.renderer, HipRenderer) and int(samples) <= 1:
             return self._on_track_one_call(prev_pose, current_rgb, current_depth)
         bb = U.compute_bbox(prev_pose, self.K, self.object_width, scale=(1000, 1000, 1000))
         dev = self._dev
@@ -222,16 +223,24 @@ class Tracker:
                 C=C, check=check, stream=_stream_ptr, fn=self.engine.lib.se3tn_on_track, P=np.empty((4, 4), np.float64),
                 K=np.ascontiguousarray(self.K, np.float64), pose=np.empty((4, 4), np.float64), tr=np.empty(3, np.float32),
                 ro=np.empty(3, np.float32), bb=np.empty((4, 2), np.int32))
+            if self.renderer.full_frame:
+                # pyrender route: the renderer's own buffers hold a whole frame; image A (the 176 x 176 crop of the render, what
+                # render_window returns) goes to buffers of the tracker
+                st["rgbA"] = torch.empty((176, 176, 3), dtype=torch.uint8, device=self._dev)
+                st["depthA"] = torch.empty((176, 176), dtype=torch.int16, device=self._dev)
             for k, t in (("P", C.c_double), ("K", C.c_double), ("pose", C.c_double), ("tr", C.c_float), ("ro", C.c_float), ("bb", C.c_int32)):
                 st["p_" + k] = st[k].ctypes.data_as(C.POINTER(t))
         C = st["C"]
         st["P"][...] = prev_pose
         r = self.renderer
+        rgbA, depthA = (st["rgbA"], st["depthA"]) if "rgbA" in st else (r.rgb, r.depth)
         st["check"](st["fn"](self.engine._h, r._m, st["p_P"], st["p_K"], C.c_double(float(self.object_width)), C.c_void_p(rgb.ctypes.data),
-                             C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]), C.c_void_p(r.rgb.data_ptr()),
-                             C.c_void_p(r.depth.data_ptr()), st["p_pose"], st["p_tr"], st["p_ro"], st["p_bb"], st["stream"]()),
+                             C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]), C.c_void_p(rgbA.data_ptr()),
+                             C.c_void_p(depthA.data_ptr()), st["p_pose"], st["p_tr"], st["p_ro"], st["p_bb"], st["stream"]()),
                     "se3tn_on_track")
         self.last_prediction = dict(trans=st["tr"].reshape(1, 3).copy(), rot=st["ro"].reshape(1, 3).copy(), bbox=st["bb"].copy())
+        if "rgbA" in st:
+            self.last_prediction.update(rgbA=rgbA, depthA=depthA)
         self.prev_rgb = current_rgb
         self.prev_depth = current_depth
         self.frame_cnt += 1
@@ -247,7 +256,7 @@ class Tracker:
         n = len(prev_poses)
         if n > self.engine.max_batch:
             raise ValueError("on_track_batch: %d pairs > max_samples=%d given to Tracker()" % (n, self.engine.max_batch))
-        if self.one_call and isinstance(self.renderer, HipRenderer) and not self.renderer.full_frame and n > 0:
+        if self.one_call and isinstance(self.renderer, HipRenderer) and n > 0:
             return self._on_track_batch_one_call(prev_poses, rgbs, depths)
         return self._on_track_batch_stepwise(prev_poses, rgbs, depths)
 
@@ -292,7 +301,7 @@ class Tracker:
         return out.reshape(n, 4, 4)
 
     def _on_track_batch_stepwise(self, prev_poses, rgbs, depths):
-        """on_track_batch step by step (injected renderers, the pyrender route, one_call = False): per pair a render and two uploads"""
+        """on_track_batch step by step (injected renderers, one_call = False): per pair a render and two uploads"""
         from .renderer import HipRenderer
         n = len(prev_poses)
         dev = self._dev
