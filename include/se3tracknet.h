@@ -310,7 +310,10 @@ int se3tn_on_track_batch(se3tn_ctx* ctx, se3tn_mesh* mesh, int n, const double* 
  * [H,W] millimetres), each with its own model:
  *   objects[i].model  the context whose bound weights, se3tn_set_normalization mean / std and se3tn_set_normalizers tn / rn object i
  *                     uses (read only; no weights are copied).  A model may appear several times and `ctx` may be one of them;
- *   objects[i].mesh   vertex-colour mesh of the VispyRenderer route (not textured);
+ *   objects[i].mesh   EITHER every object a vertex-colour mesh on SE3TN_ROUTE_WINDOW (the VispyRenderer route, not textured), OR every
+ *                     object a mesh on SE3TN_ROUTE_FRAME (the pyrender route) that se3tn_mesh_set_texture has given a material: a
+ *                     texture, or a Kd over its vertex colours.  Textured and un-textured meshes, textures of different sizes and
+ *                     meshes of different sizes share a call; the two routes do not (one rasteriser mode per launch);
  *   objects[i].object_width_mm, prev_poses [n,16] row-major.
  * `ctx` runs the call: its workspaces, staging, streams, offset rule and raster rule.  Image A of all n objects comes out of FOUR
  * rasteriser launches (grid.y = object, each instance with its own mesh), the frame's n crop windows go up in one copy, and the network
@@ -323,12 +326,20 @@ int se3tn_on_track_batch(se3tn_ctx* ctx, se3tn_mesh* mesh, int n, const double* 
  * pose_out [n,16], trans_out / rot_out [n,3] and bbox_vu [n,4,2] (may be NULL); rgbA_dev / depthA_dev optional device [n,176,176,3] /
  * [n,176,176].  1 <= n <= se3tn_max_batch(ctx).  SYNCHRONOUS on `stream`, refused inside a stream capture; the first call (a larger n,
  * mesh or frame) allocates.
- * SE3TN_E_ARG: n out of range, a NULL or textured mesh or one on SE3TN_ROUTE_FRAME, a pose with z <= 0 or not finite.  SE3TN_E_STATE: a model without weights or
+ * All objects on SE3TN_ROUTE_FRAME: per object exactly se3tn_on_track's arithmetic on that route -- compute_bbox, rectangle = crop
+ * window intersected with the frame, all n rectangles rendered in the same FOUR launches (each instance with its own mesh and material
+ * at its own pose; z-buffers and sub-images sized n x the largest rectangle of the call), a window that misses the frame = an empty
+ * rectangle and an all-zero image A; image A (the sub-image under the window shifted by the rectangle's origin) and the camera frame
+ * cropped with each model's own mean / std, then the network as above.  rgbA_dev / depthA_dev then receive the 176 x 176 crop_bbox of
+ * every render (what se3tn_on_track writes there on this route), from the launch that crops.
+ * SE3TN_E_ARG: n out of range, a NULL mesh, a textured mesh left on SE3TN_ROUTE_WINDOW, a mesh on SE3TN_ROUTE_FRAME that
+ * se3tn_mesh_set_texture was never called on, a call that mixes SE3TN_ROUTE_WINDOW and SE3TN_ROUTE_FRAME objects, H > 2048 on
+ * SE3TN_ROUTE_FRAME, a pose with z <= 0 or not finite.  SE3TN_E_STATE: a model without weights or
  * normalisation, on another device, with another packed size, offset rule or raster rule than ctx; ctx in SE3TN_PREC_F16X3, with the
  * small kernels off or with se3tn_keep_intermediates on.  The context stays usable after a refusal. */
 typedef struct se3tn_object {
   const se3tn_ctx* model;   /* weights (bound blob), mean / std, trans / rot normalisers of this object */
-  se3tn_mesh* mesh;         /* vertex-colour mesh (VispyRenderer route)                              */
+  se3tn_mesh* mesh;         /* all objects of a call on one route: vertex-colour meshes (SE3TN_ROUTE_WINDOW) or meshes with a material (SE3TN_ROUTE_FRAME) */
   double object_width_mm;
 } se3tn_object;
 int se3tn_on_track_objects(se3tn_ctx* ctx, int n, const se3tn_object* objects, const double* prev_poses, const double K[9],

@@ -115,7 +115,7 @@ struct se3tn_ctx {
   // se3tn_on_track_batch: instance table (pinned host + device), z-buffers, image A stack, staging, outputs -- grown at first use / larger n
   int tb_cap = 0;
   size_t tb_stage_bytes = 0;
-  RasterInstance *tb_inst_host = nullptr, *tb_inst_dev = nullptr;
+  RasterInstance *tb_inst_host = nullptr, *tb_inst_dev = nullptr;   // (room for a RasterMaterial per instance behind the n instances)
   unsigned long long* tb_zbuf = nullptr;
   uint8_t *tb_rgbA = nullptr, *tb_stage_host = nullptr, *tb_stage_dev = nullptr, *tb_out_host = nullptr, *tb_out_dev = nullptr;
   uint16_t* tb_depthA = nullptr;
@@ -178,6 +178,7 @@ struct se3tn_mesh {
   int tw = 0, th = 0, tlevels = 0;
   unsigned tex_off[16] = {};
   float kd[3] = {1.f, 1.f, 1.f};
+  bool has_material = false;        // se3tn_mesh_set_texture has been called (a texture, or a Kd over the vertex colours)
   int route = SE3TN_ROUTE_WINDOW;   // se3tn_mesh_set_route: the renderer se3tn_on_track / _batch use for image A
 };
 
@@ -1064,6 +1065,7 @@ int se3tn_mesh_set_texture(se3tn_mesh* m, const float* uv, const uint8_t* rgb, i
   if (m->uv) { (void)hipFree(m->uv); m->uv = nullptr; }
   if (m->tex) { (void)hipFree(m->tex); m->tex = nullptr; }
   m->tlevels = 0;
+  m->has_material = true;
   if (!rgb) return SE3TN_OK;
   // mip pyramid: 2x2 box filter per level (what glGenerateMipmap implementations do), levels back to back
   std::vector<uint8_t> pyr(rgb, rgb + (size_t)tw * th * 3);
@@ -1491,9 +1493,9 @@ static int reserve_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, size_t stage_
     c->tb_inst_host = nullptr; c->tb_out_host = nullptr; c->tb_inst_dev = nullptr; c->tb_zbuf = nullptr; c->tb_rgbA = nullptr;
     c->tb_depthA = nullptr; c->tb_out_dev = nullptr; c->tb_cap = 0;
     const int cap = n > c->max_batch ? n : c->max_batch;
-    HIPCHK(hipHostMalloc((void**)&c->tb_inst_host, sizeof(RasterInstance) * cap, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void**)&c->tb_inst_host, (sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap, hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void**)&c->tb_out_host, (size_t)cap * 160, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&c->tb_inst_dev, sizeof(RasterInstance) * cap));
+    HIPCHK(hipMalloc((void**)&c->tb_inst_dev, (sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap));
     HIPCHK(hipMalloc((void**)&c->tb_zbuf, sizeof(unsigned long long) * RES * RES * cap));
     HIPCHK(hipMalloc((void**)&c->tb_rgbA, (size_t)RES * RES * 3 * cap));
     HIPCHK(hipMalloc((void**)&c->tb_depthA, (size_t)RES * RES * 2 * cap));
@@ -1778,12 +1780,21 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
   if (stream_is_capturing((hipStream_t)stream)) return fail(SE3TN_E_STATE, "se3tn_on_track_objects: synchronous call, not capturable");
   const std::string who = "se3tn_on_track_objects: object ";
   int maxV = 0, maxF = 0;
+  // one rasteriser mode per launch, so one route per call: all objects on SE3TN_ROUTE_WINDOW (vertex-colour meshes) or all on
+  // SE3TN_ROUTE_FRAME (meshes with a material: a texture, or a Kd over the vertex colours)
+  bool frame_route = false;
   for (int i = 0; i < n; ++i) {
     const se3tn_object& o = objs[i];
     const std::string id = who + std::to_string(i);
     if (!o.mesh) return fail(SE3TN_E_ARG, id + ": null mesh");
-    if (o.mesh->tex || o.mesh->uv) return fail(SE3TN_E_ARG, id + ": textured mesh (the full-frame renderer's route: se3tn_on_track per object)");
-    if (o.mesh->route != SE3TN_ROUTE_WINDOW) return fail(SE3TN_E_ARG, id + ": mesh on SE3TN_ROUTE_FRAME (se3tn_on_track per object)");
+    const bool fr = o.mesh->route == SE3TN_ROUTE_FRAME;
+    if (!fr && (o.mesh->tex || o.mesh->uv))
+      return fail(SE3TN_E_ARG, id + ": textured mesh on SE3TN_ROUTE_WINDOW (the full-frame renderer's route: se3tn_mesh_set_route)");
+    if (fr && !o.mesh->has_material)
+      return fail(SE3TN_E_ARG, id + ": mesh on SE3TN_ROUTE_FRAME without a material (se3tn_mesh_set_texture: a texture, or a Kd over the vertex colours)");
+    if (i == 0) frame_route = fr;
+    else if (fr != frame_route)
+      return fail(SE3TN_E_ARG, id + ": the call mixes SE3TN_ROUTE_WINDOW and SE3TN_ROUTE_FRAME objects (one rasteriser mode per launch: one route per call)");
     if (!(o.object_width_mm > 0)) return fail(SE3TN_E_ARG, id + ": object width must be > 0");
     const se3tn_ctx* m = o.model;
     if (!m) return fail(SE3TN_E_ARG, id + ": null model");
@@ -1798,6 +1809,8 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     maxV = o.mesh->V > maxV ? o.mesh->V : maxV;
     maxF = o.mesh->F > maxF ? o.mesh->F : maxF;
   }
+  if (frame_route && H > 2048)
+    return fail(SE3TN_E_ARG, "se3tn_on_track_objects: frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
   hipStream_t st = (hipStream_t)stream;
   // pass 1 (host float64): the windows of every object (predict.py:231-235 / :201-206) and its staged sub-image of the frame
   std::vector<int32_t> win(8 * (size_t)n), vu(8 * (size_t)n);
@@ -1824,6 +1837,18 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
   }
   if (int rc = reserve_track_batch(c, nullptr, n, bytes)) return rc;
   if (int rc = reserve_objects_raster(c, n, maxV, maxF)) return rc;
+  // SE3TN_ROUTE_FRAME (predict.py:209-213): per object the rectangle of the full-frame render its crop window covers -- geo above, the
+  // same rectangle as the staged part of the camera frame.  Z-buffers and sub-images: n x the largest rectangle of the call
+  size_t maxpx = 0, fr_d_off = 0;
+  if (frame_route) {
+    for (int i = 0; i < n; ++i)
+      if (geo[4 * i + 2] > 0) maxpx = std::max(maxpx, (size_t)geo[4 * i + 2] * (size_t)geo[4 * i + 3]);
+    const size_t need = maxpx ? (size_t)n * maxpx : 1, cap = (size_t)n * H * W;
+    // windows change from frame to frame: grow with half as much again in hand (never past n whole frames)
+    if (need > c->fr_px)
+      if (int rc = reserve_frame_route(c, std::max(need, std::min(need + need / 2, cap)))) return rc;
+    fr_d_off = 64 + (((size_t)n * maxpx * 3 + 63) & ~(size_t)63);
+  }
   if (c->rearm_counters) {   // (as se3tn_infer: a launch sequence that failed half-way may have left the tail's counters non-zero)
     HIPCHK(hipMemsetAsync(c->tail_arrive, 0, sizeof(int) * c->max_batch, st));
     c->rearm_counters = false;
@@ -1836,20 +1861,42 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
   ra.rw = RES; ra.rh = RES; ra.mode = 0;
   ra.vpost = c->mo_vpost; ra.vsnap = c->mo_vsnap; ra.big = c->mo_big; ra.clipq = c->mo_clipq; ra.zbuf = c->tb_zbuf;
   ra.V = maxV; ra.F = maxF; ra.inst_mesh = 1;
+  // frame route: the materials travel behind the n instances, in the same copy
+  RasterMaterial* mat_host = (RasterMaterial*)(c->tb_inst_host + n);
+  if (frame_route) {
+    ra.rw = W; ra.rh = H; ra.mode = 1;   // (matrix, mesh, material and rectangle come from the tables)
+    ra.rgb = c->fr_sub + 64; ra.depth = (uint16_t*)(c->fr_sub + fr_d_off);
+    ra.zbuf = c->fr_zbuf;
+    ra.scissor = 1; ra.spx = (int)maxpx;
+    ra.inst_mesh = 2;   // every instance with its own material: the table behind the n instance records
+  }
   for (int i = 0; i < n; ++i) {
     RasterArgs one{};
-    if (!vispy_uniforms(one, prev_poses + 16 * (size_t)i, K, &win[8 * (size_t)i + 4]))
-      return fail(SE3TN_E_ARG, who + std::to_string(i) + ": singular pose");
     const se3tn_mesh* m = objs[i].mesh;
     RasterInstance& I = c->tb_inst_host[i];
+    if (frame_route) {
+      frame_uniforms(one, m, prev_poses + 16 * (size_t)i, K, W, H);
+      const int32_t r[4] = {geo[4 * i], geo[4 * i + 1], geo[4 * i] + geo[4 * i + 2], geo[4 * i + 1] + geo[4 * i + 3]};
+      if (geo[4 * i + 2] > 0) rect_to_scissor(r, H, I.rect);
+      else I.rect[0] = I.rect[1] = I.rect[2] = I.rect[3] = 0;   // the window misses the frame: an empty rectangle, nothing written
+      RasterMaterial& M = mat_host[i];
+      M.uv = one.uv; M.tex = one.tex; M.tw = one.tw; M.th = one.th; M.tlevels = one.tlevels;
+      std::memcpy(M.kd, one.kd, sizeof(M.kd));
+      std::memcpy(M.tex_off, one.tex_off, sizeof(M.tex_off));
+    } else if (!vispy_uniforms(one, prev_poses + 16 * (size_t)i, K, &win[8 * (size_t)i + 4])) {
+      return fail(SE3TN_E_ARG, who + std::to_string(i) + ": singular pose");
+    }
     std::memcpy(I.PV, one.PV, sizeof(I.PV));
     std::memcpy(I.light, one.light, sizeof(I.light));
     I._pad = 0.f; I.dA = one.dA; I.dB = one.dB;
     I.verts = m->verts; I.normals = m->normals; I.colors = m->colors; I.faces = m->faces; I.V = m->V; I.F = m->F;
   }
-  HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, sizeof(RasterInstance) * n, hipMemcpyHostToDevice, st));
-  ra.inst = c->tb_inst_dev;
-  HIPCHK(launch_raster(ra, st, n));
+  if (!frame_route || maxpx > 0) {   // (frame route with every window off the frame: nothing to render)
+    const size_t tab_bytes = sizeof(RasterInstance) * n + (frame_route ? sizeof(RasterMaterial) * n : 0);
+    HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, tab_bytes, hipMemcpyHostToDevice, st));
+    ra.inst = c->tb_inst_dev;
+    HIPCHK(launch_raster(ra, st, n));
+  }
   // the poses, every object's mean | std and the frame's n windows: staged through pinned memory while the rasteriser runs, ONE copy
   uint8_t* hp = c->tb_stage_host;
   std::memcpy(hp, prev_poses, (size_t)n * 128);
@@ -1887,10 +1934,22 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
       se3tn_crop& cb = a.c[kg + j];
       const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
       const int32_t* wB = &win[8 * (size_t)i];
+      if (frame_route) {   // image A = the rendered rectangle under the window shifted by its origin (a miss: the 1 x 1 zero image)
+        ca.rgb = sw < 0 ? c->fr_sub : c->fr_sub + 64 + (size_t)i * maxpx * 3;
+        ca.depth = sw < 0 ? (const uint16_t*)(c->fr_sub + 32) : (const uint16_t*)(c->fr_sub + fr_d_off) + (size_t)i * maxpx;
+        ca.H = sw < 0 ? 1 : sh; ca.W = sw < 0 ? 1 : sw;
+        ca.left = wB[0] - x0; ca.top = wB[1] - y0; ca.right = wB[2] - x0; ca.bottom = wB[3] - y0;
+      }
       cb.rgb = c->tb_stage_dev + off_rgb[i]; cb.depth = (const uint16_t*)(c->tb_stage_dev + off_d[i]);
       cb.H = sw < 0 ? 1 : sh; cb.W = sw < 0 ? 1 : sw;
       cb.left = wB[0] - x0; cb.top = wB[1] - y0; cb.right = wB[2] - x0; cb.bottom = wB[3] - y0;
       cb.z_offset_mm = z_mm; cb.stats = 1; cb._pad = 0;
+    }
+    // frame route: the crops of image A also leave their raw pixels (crop_bbox of the render = Tracker.render_window) in rgbA_dev /
+    // depthA_dev (the one not given goes to the internal buffer)
+    if (frame_route && (rgbA_dev || depthA_dev)) {
+      a.raw_rgb = rA + (size_t)g0 * RES * RES * 3;
+      a.raw_depth = dA + (size_t)g0 * RES * RES;
     }
     a.n = 2 * kg; a.n_first = kg;
     a.out = c->inA + (size_t)g0 * img_floats; a.out2 = c->inB + (size_t)g0 * img_floats; a.padded = 1; a.split = 0;

@@ -421,9 +421,10 @@ __global__ __launch_bounds__(256) void raster_queue_kernel(const RasterArgs a0) 
 }
 
 // texel (x, y) of mip level l (RGB uint8, levels stored back to back, level l is max(tw >> l, 1) x max(th >> l, 1)); REPEAT wrap
-__device__ __forceinline__ void sample_bilinear(const RasterArgs& a, int level, float u, float v, float* out) {
+// tex_off: the level's byte offset (a.tex_off[level], or the instance's own from its RasterMaterial)
+__device__ __forceinline__ void sample_bilinear(const RasterArgs& a, int level, unsigned tex_off, float u, float v, float* out) {
   const int w = max(a.tw >> level, 1), h = max(a.th >> level, 1);
-  const uint8_t* base = a.tex + a.tex_off[level];
+  const uint8_t* base = a.tex + tex_off;
   // image row 0 is the TOP of the picture, v = 0 its bottom (OBJ / GL convention)
   const float x = u * w - 0.5f, y = (1.0f - v) * h - 0.5f;
   const float xf = floorf(x), yf = floorf(y);
@@ -469,8 +470,19 @@ __device__ __forceinline__ float interp(const TriSetup& s, const Interp& it, flo
   return plane_eval(A, B, C, it.xx, it.yy) * it.rcp;
 }
 
+// InstMat (a0.inst_mesh == 2): every instance (blockIdx.y) of a mode-1 launch shades with its own material, record b of the table
+// behind the gridDim.y instance records -- several meshes, textured or not, with textures of different sizes and level counts, in
+// one launch.  false: the launch uniforms, the code the single-mesh calls have always run
+template <bool InstMat>
 __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a0) {
-  const RasterArgs a = raster_instance(a0);
+  RasterArgs a = raster_instance(a0);
+  const RasterMaterial* __restrict__ mat = nullptr;
+  if (InstMat) {   // (uniform over the workgroup: scalar loads)
+    mat = reinterpret_cast<const RasterMaterial*>(a0.inst + gridDim.y) + blockIdx.y;
+    a.uv = mat->uv; a.tex = mat->tex; a.tw = mat->tw; a.th = mat->th; a.tlevels = mat->tlevels;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.kd[k] = mat->kd[k];
+  }
   const int p = blockIdx.x * 256 + threadIdx.x;
   const int bw = a.sx1 - a.sx0, bh = a.sy1 - a.sy0;
   if (p >= bw * bh) return;
@@ -526,8 +538,8 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const RasterArgs a0
       const int l0i = (int)floorf(lod), l1i = min(l0i + 1, a.tlevels - 1);
       const float fl = lod - (float)l0i;
       float c0[3], c1[3];
-      sample_bilinear(a, l0i, u, v, c0);
-      sample_bilinear(a, l1i, u, v, c1);
+      sample_bilinear(a, l0i, InstMat ? mat->tex_off[l0i] : a.tex_off[l0i], u, v, c0);
+      sample_bilinear(a, l1i, InstMat ? mat->tex_off[l1i] : a.tex_off[l1i], u, v, c1);
 #pragma unroll
       for (int c = 0; c < 3; ++c) col[c] = (c0[c] + fl * (c1[c] - c0[c])) * (1.0f / 255.0f);
     } else {
@@ -574,6 +586,8 @@ hipError_t launch_raster(const RasterArgs& a, hipStream_t st, int instances) {
   // one thread per vertex; the z-buffer clear strides over the grid (at least 128 blocks, or one per 256 pixels if that is fewer)
   // instances > 1 (a.inst set): grid.y = instance, the same four launches for all poses
   // scissored: the z-buffer and the output hold a.spx pixels per instance (the largest rectangle of the call)
+  // per-instance materials (inst_mesh == 2): mode 1 with an instance table only
+  if (a.inst_mesh == 2 && (a.mode != 1 || a.inst == nullptr)) return hipErrorInvalidValue;
   const int zpx = a.scissor ? a.spx : a.rw * a.rh;
   const int vb = (a.V + 255) / 256, zb = (zpx + 255) / 256;
   const int clear_blocks = zb < 128 ? zb : 128;
@@ -581,7 +595,11 @@ hipError_t launch_raster(const RasterArgs& a, hipStream_t st, int instances) {
   hipLaunchKernelGGL(raster_vertex_kernel, dim3(vb > clear_blocks ? vb : clear_blocks, ny), dim3(256), 0, st, a);
   hipLaunchKernelGGL(raster_triangle_kernel, dim3((a.F + 255) / 256, ny), dim3(256), 0, st, a);
   hipLaunchKernelGGL(raster_queue_kernel, dim3(BIG_BLOCKS + CLIP_BLOCKS, ny), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(raster_resolve_kernel, dim3(zb, ny), dim3(256), 0, st, a);
+  if (a.inst_mesh == 2) {
+    hipLaunchKernelGGL(raster_resolve_kernel<true>, dim3(zb, ny), dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(raster_resolve_kernel<false>, dim3(zb, ny), dim3(256), 0, st, a);
+  }
   return hipGetLastError();
 }
 

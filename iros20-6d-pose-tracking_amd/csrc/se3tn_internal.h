@@ -336,6 +336,17 @@ struct RasterInstance {
   int V, F;
   int rect[4];   // RasterArgs::scissor != 0: this instance's rectangle sx0, sy0, sx1, sy1 (GL window coordinates; may be empty)
 };
+// per-instance material of a batched mode-1 launch with several meshes (RasterArgs::inst_mesh == 2, se3tn_on_track_objects on
+// SE3TN_ROUTE_FRAME): what RasterArgs uv .. kd hold for a single mesh.  The table of a launch of n instances is
+// [n x RasterInstance | n x RasterMaterial] in one allocation (one upload).  Only raster_resolve_kernel reads the materials.
+// tex == nullptr: the instance's vertex colours are the base colour (textured and un-textured instances share a launch)
+struct RasterMaterial {
+  const float* uv;
+  const uint8_t* tex;
+  int tw, th, tlevels;
+  float kd[3];
+  unsigned tex_off[16];
+};
 struct RasterArgs {
   const RasterInstance* inst;  // nullptr: one instance, uniforms below.  Otherwise instance b = blockIdx.y takes PV / light / dA / dB from
                                // inst[b] and its scratch / outputs at b x (V | 1 + F | rw rh) elements behind the pointers below
@@ -365,6 +376,8 @@ struct RasterArgs {
   float kd[3];           // base colour factor (mtl Kd)
   int inst_mesh = 0;     // batched launch: 1 = every instance brings its own mesh (RasterInstance verts .. F); V / F above are then
                          // the LARGEST counts (grid and scratch strides), and threads past their own instance's counts exit
+                         // 2 (mode 1 only) = and its own material: instance b shades with the RasterMaterial b that follows the
+                         // launch's RasterInstance records (uv .. kd above are then unused) -- the resolve kernel's InstMat instantiation
   // scissor != 0 (mode 1, se3tn_render_frame_rect): only the pixels [sx0, sx1) x [sy0, sy1) of the rw x rh window (GL window coordinates:
   // row 0 at the BOTTOM) are cleared, covered and resolved; zbuf / rgb / depth hold that rectangle tightly packed, spx pixels per
   // instance (>= the area of every rectangle of the launch).  0: the whole window (the kernels set the rectangle themselves)

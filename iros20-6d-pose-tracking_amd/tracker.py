@@ -344,7 +344,10 @@ class MultiTracker:
     rasteriser launches, the frame's crop windows in one upload, the network in chunks of <= 5 objects on the batch 1-5 kernel family
     with every object reading its own tracker's weights -- object i gets exactly the bits ``trackers[i].on_track`` gives it.
     The trackers are used as they are (their weights, normalisation and meshes stay where they live; nothing is copied); they must
-    render image A with the built-in vertex-colour rasteriser.  The MultiTracker owns one executing ``Engine`` of
+    render image A with the built-in rasteriser (``HipRenderer``), ALL on the window route (vertex-colour meshes) or ALL on the
+    full-frame route (``dataset_info['renderer'] == 'pyrenderer'``: textured .obj models, or un-textured ones with a Kd) -- one
+    rasteriser mode per launch.  On the full-frame route ``last_prediction["rgbA"/"depthA"]`` hold the raw 176 x 176 crops of the
+    renders, what ``Tracker.render_window`` returns there.  The MultiTracker owns one executing ``Engine`` of
     max_batch = len(trackers) (workspaces, staging)."""
 
     def __init__(self, trackers, device=0):
@@ -355,15 +358,20 @@ class MultiTracker:
         if not trackers:
             raise ValueError("MultiTracker: no trackers")
         for i, t in enumerate(trackers):
-            if not isinstance(t.renderer, HipRenderer) or t.renderer.full_frame:
-                raise ValueError("MultiTracker: tracker %d does not render image A with the built-in vertex-colour rasteriser (an "
-                                 "injected or full-frame renderer): track it with its own on_track" % i)
+            if not isinstance(t.renderer, HipRenderer):
+                raise ValueError("MultiTracker: tracker %d does not render image A with the built-in rasteriser (an injected "
+                                 "renderer): track it with its own on_track" % i)
+            if bool(t.renderer.full_frame) != bool(trackers[0].renderer.full_frame):
+                raise ValueError("MultiTracker: tracker %d renders image A on the %s route, tracker 0 on the %s route (one rasteriser "
+                                 "mode per call: all window-route or all full-frame trackers)"
+                                 % (i, *[("full-frame" if x.renderer.full_frame else "window") for x in (t, trackers[0])]))
             if int(t.engine.device) != int(device):
                 raise ValueError("MultiTracker: tracker %d lives on device %d, not %d" % (i, t.engine.device, device))
             if not np.array_equal(np.asarray(t.K, np.float64), np.asarray(trackers[0].K, np.float64)):
                 raise ValueError("MultiTracker: tracker %d has another camera matrix than tracker 0 (one camera frame per call)" % i)
         self.trackers = trackers
         self.n = len(trackers)
+        self.full_frame = bool(trackers[0].renderer.full_frame)
         self.engine = Engine(device, self.n)
         self.K = np.ascontiguousarray(trackers[0].K, np.float64)
         self._dev = "cuda:%d" % device
