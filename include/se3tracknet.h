@@ -358,6 +358,28 @@ int se3tn_on_track_objects(se3tn_ctx* ctx, int n, const se3tn_object* objects, c
 #define SE3TN_BLUR_GAUSSIAN 2
 int se3tn_fill_depth(se3tn_ctx* ctx, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate,
                      int blur, uint16_t* out_mm, float* out_m, void* stream);
+/* se3tn_fill_depth restricted to a rectangle of the frame: rect = {x0, y0, x1, y1} as se3tn_render_frame_rect takes it.
+ * out_mm_sub: device uint16 [y1-y0, x1-x0], every value the same pixel of se3tn_fill_depth's out_mm, bit for bit.
+ * With extrapolate == 0 at most four stream operations: the chain up to the median of the whole frame as ONE tiled launch (the
+ * bilateral table needs the range of the whole image), the table, blur + invert-back + uint16 of the rectangle only, one reset.
+ * Stream-ordered, capturable after se3tn_reserve; SE3TN_E_ARG for an empty rectangle or one not inside the frame, a bad blur. */
+int se3tn_fill_depth_rect(se3tn_ctx* ctx, const uint16_t* depth_mm_dev, int H, int W, double max_depth_m, int extrapolate, int blur,
+                          const int32_t rect[4], uint16_t* out_mm_sub, void* stream);
+
+#define SE3TN_COLOR_RGB 0
+#define SE3TN_COLOR_BGR 1   /* what CvBridge 'bgr8' delivers (predict_ros.py:45-46) */
+/* predict_ros.py:38-60 in ONE call: grab_depth's fill_depth + grab_color's channel order + Tracker.on_track.
+ * se3tn_on_track with another staging step: color (HOST uint8 [H,W,3], channel order color_order) travels as the crop window's rows /
+ * columns, swapped to RGB during that copy; depth_raw (HOST uint16 [H,W], the camera's millimetres with holes) goes up WHOLE on the
+ * copy stream beside the rasteriser launches, and se3tn_fill_depth_rect of the window's part of the frame writes image B's depth where
+ * the crop launch reads it -- the filled frame never visits the host.  depth_filled_dev (optional, device uint16 [H,W]): the whole
+ * filled frame too (= se3tn_fill_depth's out_mm).  Everything else, the refusals included, as se3tn_on_track; synchronous on `stream`,
+ * SE3TN_E_STATE inside a stream capture, SE3TN_E_ARG for a bad color_order / blur. */
+int se3tn_on_track_live(se3tn_ctx* ctx, se3tn_mesh* mesh, const double prev_pose[16], const double K[9], double object_width_mm,
+                        const uint8_t* color, int color_order, const uint16_t* depth_raw, int H, int W,
+                        double max_depth_m, int extrapolate, int blur, uint16_t* depth_filled_dev /* optional, device [H,W] */,
+                        uint8_t* rgbA_dev, uint16_t* depthA_dev, double pose_out[16], float trans_out[3], float rot_out[3],
+                        int32_t bbox_vu[8], void* stream);
 
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K

@@ -1307,20 +1307,47 @@ static bool bbox_window(const double pose[16], const double K[9], double width, 
   return true;
 }
 
-int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], const double K[9], double object_width_mm,
-                   const uint8_t* rgb, const uint16_t* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev,
-                   double pose_out[16], float trans_out[3], float rot_out[3], int32_t bbox_vu[8], void* stream) {
+static int fill_depth_rect_enqueue(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
+                                   const int32_t comp[4], uint16_t* out_full, const int32_t sub[4], uint16_t* out_sub, hipStream_t st);
+
+// the live camera's part of se3tn_on_track_live: `rgb` / `depth` of on_track_frame are then the camera's colour frame in color_order
+// and its RAW depth frame, filled on the device (predict_ros.py:38-46)
+struct LiveFrame {
+  int color_order;
+  double max_depth_m;
+  int extrapolate, blur;
+  uint16_t* depth_filled;   // device [H,W] or nullptr
+};
+
+// se3tn_on_track (live == nullptr) and se3tn_on_track_live: one body, two staging steps
+static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], const double K[9], double object_width_mm,
+                          const uint8_t* rgb, const uint16_t* depth, int H, int W, const LiveFrame* live, uint8_t* rgbA_dev,
+                          uint16_t* depthA_dev, double pose_out[16], float trans_out[3], float rot_out[3], int32_t bbox_vu[8], void* stream) {
+  const char* who = live ? "se3tn_on_track_live" : "se3tn_on_track";
   if (!c || c->device < 0 || !m || !prev_pose || !K || !rgb || !depth || H < 1 || W < 1 || !pose_out || !(object_width_mm > 0))
-    return fail(SE3TN_E_ARG, "se3tn_on_track: bad argument");
-  if (!c->have_norm) return fail(SE3TN_E_STATE, "se3tn_on_track: call se3tn_set_normalization first");
+    return fail(SE3TN_E_ARG, std::string(who) + ": bad argument");
+  if (live && ((unsigned)live->color_order > 1u || (unsigned)live->blur > 2u))
+    return fail(SE3TN_E_ARG, "se3tn_on_track_live: bad color_order or blur");
+  if (!c->have_norm) return fail(SE3TN_E_STATE, std::string(who) + ": call se3tn_set_normalization first");
   hipStream_t st = (hipStream_t)stream;
+  if (live && stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_on_track_live: the call is synchronous, it cannot be captured");
   static const bool trace = std::getenv("SE3TN_TRACK_TRACE") != nullptr;   // developer switch: host-side timeline of the call
-  static double acc[6] = {0, 0, 0, 0, 0, 0};
-  static int ncall = 0;
+  static double acc_both[2][7] = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0}};
+  static int ncall_both[2] = {0, 0};
+  double* acc = acc_both[live ? 1 : 0];
+  int& ncall = ncall_both[live ? 1 : 0];
   auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = trace ? now() : 0.0;
+  auto a64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  const size_t fpx = (size_t)H * W;
   // start-up allocations (first call / larger frame): pinned staging for a whole frame, its device mirror, outputs
-  const size_t need = 256 + (size_t)H * W * 5 + 64;
+  // (live: pose | window rgb | one zero pixel | RAW depth frame | the window's filled depth, written on the device)
+  const size_t need = live ? 256 + a64(fpx * 3) + 64 + a64(fpx * 2) + fpx * 2 + 64 : 256 + fpx * 5 + 64;
+  if (live && fpx > c->fd_pixels) {
+    DeviceGuard dg(c->device);
+    if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+    if (int rc = reserve_fill_depth(c, fpx)) return rc;
+  }
   if (need > c->trk_bytes) {
     DeviceGuard dg(c->device);                     //  staging buffers belong to the context's device, whatever the caller's current one
     if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
@@ -1352,8 +1379,8 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
   // empty or mirrored; predict.py never gets there): refuse instead of running the frame
   if (!(prev_pose[11] > 0) || !bbox_window(prev_pose, K, object_width_mm, 1000.0, winB, vu) ||
       !bbox_window(prev_pose, K, object_width_mm, -1000.0, winA, nullptr))
-    return fail(SE3TN_E_ARG, "se3tn_on_track: pose is not in front of the camera (z <= 0 or not finite)");
-  if (winB[2] <= winB[0] || winB[3] <= winB[1]) return fail(SE3TN_E_ARG, "se3tn_on_track: empty crop window (pose behind the camera?)");
+    return fail(SE3TN_E_ARG, std::string(who) + ": pose is not in front of the camera (z <= 0 or not finite)");
+  if (winB[2] <= winB[0] || winB[3] <= winB[1]) return fail(SE3TN_E_ARG, std::string(who) + ": empty crop window (pose behind the camera?)");
   // image A first: its four launches run on the device while the host stages the frame
   uint8_t* rA = rgbA_dev ? rgbA_dev : c->trk_rgbA;
   uint16_t* dA = depthA_dev ? depthA_dev : c->trk_depthA;
@@ -1364,7 +1391,7 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
   if (frame_route) {
     // predict.py:209-213: the full-frame render cropped with the SAME window as the camera frame -- only the rectangle of the frame
     // the window covers is rendered (every byte of it as se3tn_render_frame gives it)
-    if (H > 2048) return fail(SE3TN_E_ARG, "se3tn_on_track: frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
+    if (H > 2048) return fail(SE3TN_E_ARG, std::string(who) + ": frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
     if (int rc = reserve_frame_route(c, (size_t)H * W)) return rc;
     missA = !window_rect(winB, H, W, rectA);
     if (!missA) {
@@ -1394,21 +1421,53 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
   uint8_t* h_rgb = hp + 256;
   const bool miss = sw <= 0 || sh <= 0;   // the window misses the frame: a 1 x 1 zero sub-image it does not touch
   if (miss) { sw = sh = 1; x0 = winB[0] - 8; y0 = winB[1] - 8; }
-  const size_t d_off = 256 + (((size_t)sw * sh * 3 + 63) & ~(size_t)63);
-  if (miss) {
-    std::memset(h_rgb, 0, 3);
-    std::memset(hp + d_off, 0, 2);
-  } else {
-    for (int y = 0; y < sh; ++y) {
-      std::memcpy(h_rgb + (size_t)y * sw * 3, rgb + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
-      std::memcpy(hp + d_off + (size_t)y * sw * 2, depth + (size_t)(y0 + y) * W + x0, (size_t)sw * 2);
+  size_t d_off = 256 + (((size_t)sw * sh * 3 + 63) & ~(size_t)63);   // image B's depth on the device
+  size_t bytes, raw_off = 0;
+  const bool fill = live && (!miss || live->depth_filled);
+  if (live) {
+    // window rgb with the channel order made RGB on the way | one zero pixel (a window that misses the frame) | the WHOLE raw depth frame;
+    // the window's filled depth is written behind it by the rectangle pass below
+    const size_t z_off = d_off;
+    raw_off = z_off + 64;
+    if (miss) {
+      std::memset(h_rgb, 0, 3);
+    } else if (live->color_order == SE3TN_COLOR_BGR) {
+      for (int y = 0; y < sh; ++y) {
+        const uint8_t* src = rgb + ((size_t)(y0 + y) * W + x0) * 3;
+        uint8_t* dst = h_rgb + (size_t)y * sw * 3;
+        for (int x = 0; x < sw; ++x, src += 3, dst += 3) { dst[0] = src[2]; dst[1] = src[1]; dst[2] = src[0]; }
+      }
+    } else {
+      for (int y = 0; y < sh; ++y) std::memcpy(h_rgb + (size_t)y * sw * 3, rgb + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
     }
+    std::memset(hp + z_off, 0, 2);
+    if (fill) std::memcpy(hp + raw_off, depth, fpx * 2);
+    bytes = fill ? raw_off + fpx * 2 : raw_off;
+    d_off = miss ? z_off : a64(raw_off + fpx * 2);
+  } else {
+    if (miss) {
+      std::memset(h_rgb, 0, 3);
+      std::memset(hp + d_off, 0, 2);
+    } else {
+      for (int y = 0; y < sh; ++y) {
+        std::memcpy(h_rgb + (size_t)y * sw * 3, rgb + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
+        std::memcpy(hp + d_off + (size_t)y * sw * 2, depth + (size_t)(y0 + y) * W + x0, (size_t)sw * 2);
+      }
+    }
+    bytes = d_off + (size_t)sw * sh * 2;
   }
-  const size_t bytes = d_off + (size_t)sw * sh * 2;
   HIPCHK(hipMemcpyAsync(c->trk_dev, hp, bytes, hipMemcpyHostToDevice, c->trk_copy_stream));
   HIPCHK(hipEventRecord(c->trk_copy_event, c->trk_copy_stream));
   HIPCHK(hipStreamWaitEvent(st, c->trk_copy_event, 0));
   const double t2 = trace ? now() : 0.0;
+  if (fill) {   // predict_ros.py:38-41 for the pixels the crop reads (the whole frame when the caller wants it)
+    const int32_t whole[4] = {0, 0, W, H}, sub[4] = {x0, y0, x1, y1};
+    const int rc = fill_depth_rect_enqueue(c, (const uint16_t*)(c->trk_dev + raw_off), H, W, live->max_depth_m,
+                                           live->extrapolate, live->blur, live->depth_filled ? whole : sub, live->depth_filled, sub,
+                                           miss ? nullptr : (uint16_t*)(c->trk_dev + d_off), st);
+    if (rc) { (void)hipStreamSynchronize(c->trk_copy_stream); return rc; }
+  }
+  const double t2f = trace ? now() : 0.0;
   // image A and image B in ONE preprocess launch (data_augmentation.py:124-189 for both, with poseA's z)
   CropArgs a;
   std::memcpy(a.mean, c->mean, sizeof(a.mean));
@@ -1462,12 +1521,17 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
   if (!seen) HIPCHK(hipStreamSynchronize(st));
   if (trace) {
     const double t5 = now();
-    const double d[6] = {t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t5 - t0};
-    for (int i = 0; i < 6; ++i) acc[i] += d[i];
+    const double d[7] = {t1 - t0, t2 - t1, t3 - t2f, t4 - t3, t5 - t4, t5 - t0, t2f - t2};
+    for (int i = 0; i < 7; ++i) acc[i] += d[i];
     if (++ncall % 200 == 0) {
-      std::fprintf(stderr, "se3tn_on_track host timeline (mean of 200, us): bbox+render enqueue %.1f | stage+H2D enqueue %.1f | preprocess enqueue %.1f | "
-                   "infer enqueue %.1f | wait for the tail's word %.1f | total %.1f\n", acc[0] / 200, acc[1] / 200, acc[2] / 200, acc[3] / 200, acc[4] / 200, acc[5] / 200);
-      for (double& v : acc) v = 0;
+      if (live)
+        std::fprintf(stderr, "se3tn_on_track_live host timeline (mean of 200, us): bbox+render enqueue %.1f | stage+H2D enqueue %.1f | fill enqueue %.1f | "
+                     "preprocess enqueue %.1f | infer enqueue %.1f | wait for the tail's word %.1f | total %.1f\n", acc[0] / 200, acc[1] / 200,
+                     acc[6] / 200, acc[2] / 200, acc[3] / 200, acc[4] / 200, acc[5] / 200);
+      else
+        std::fprintf(stderr, "se3tn_on_track host timeline (mean of 200, us): bbox+render enqueue %.1f | stage+H2D enqueue %.1f | preprocess enqueue %.1f | "
+                     "infer enqueue %.1f | wait for the tail's word %.1f | total %.1f\n", acc[0] / 200, acc[1] / 200, acc[2] / 200, acc[3] / 200, acc[4] / 200, acc[5] / 200);
+      for (int i = 0; i < 7; ++i) acc[i] = 0;
     }
   }
   std::memcpy(pose_out, c->trk_out_host, 128);
@@ -1475,6 +1539,22 @@ int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], cons
   if (rot_out) std::memcpy(rot_out, c->trk_out_host + 144, 12);
   if (bbox_vu) std::memcpy(bbox_vu, vu, sizeof(vu));
   return SE3TN_OK;
+}
+
+int se3tn_on_track(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], const double K[9], double object_width_mm,
+                   const uint8_t* rgb, const uint16_t* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev,
+                   double pose_out[16], float trans_out[3], float rot_out[3], int32_t bbox_vu[8], void* stream) {
+  return on_track_frame(c, m, prev_pose, K, object_width_mm, rgb, depth, H, W, nullptr, rgbA_dev, depthA_dev, pose_out, trans_out, rot_out,
+                        bbox_vu, stream);
+}
+
+int se3tn_on_track_live(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], const double K[9], double object_width_mm,
+                        const uint8_t* color, int color_order, const uint16_t* depth_raw, int H, int W, double max_depth_m, int extrapolate,
+                        int blur, uint16_t* depth_filled_dev, uint8_t* rgbA_dev, uint16_t* depthA_dev, double pose_out[16],
+                        float trans_out[3], float rot_out[3], int32_t bbox_vu[8], void* stream) {
+  const LiveFrame live{color_order, max_depth_m, extrapolate, blur, depth_filled_dev};
+  return on_track_frame(c, m, prev_pose, K, object_width_mm, color, depth_raw, H, W, &live, rgbA_dev, depthA_dev, pose_out, trans_out,
+                        rot_out, bbox_vu, stream);
 }
 
 // ---- n tracks per call -------------------------------------------------------------------------------------------------------
@@ -2007,6 +2087,40 @@ int se3tn_fill_depth(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, doubl
   a.out_mm = out_mm; a.out_m = out_m;
   HIPCHK(launch_fill_depth(a, (hipStream_t)stream));
   return SE3TN_OK;
+}
+
+// comp: the pixels the last pass computes (written to out_full at their place in the frame); sub: the rectangle out_sub holds.
+// Both inside the frame and not empty; the scratch is reserved.
+static int fill_depth_rect_enqueue(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
+                                   const int32_t comp[4], uint16_t* out_full, const int32_t sub[4], uint16_t* out_sub, hipStream_t st) {
+  const size_t px = (size_t)H * W;
+  FillDepthRectArgs a{};
+  FillDepthArgs& f = a.f;
+  f.depth_mm = depth_mm; f.H = H; f.W = W; f.max_depth = max_depth_m; f.extrapolate = extrapolate; f.blur = blur;
+  f.sigma_color = 1.5; f.sigma_space = 2.0;   // Utils.py:505 cv2.bilateralFilter(depth, 5, 1.5, 2.0)
+  f.buf0 = c->fd_buf; f.buf1 = c->fd_buf + px; f.buf2 = c->fd_buf + 2 * px;
+  f.minmax = reinterpret_cast<unsigned*>(c->fd_buf + 3 * px);
+  f.lut = c->fd_buf + 3 * px + 2;
+  a.cx0 = comp[0]; a.cy0 = comp[1]; a.cx1 = comp[2]; a.cy1 = comp[3];
+  a.out_full = out_full; a.out_sub = out_sub;
+  a.sx0 = sub[0]; a.sy0 = sub[1]; a.sx1 = sub[2]; a.sy1 = sub[3];
+  HIPCHK(launch_fill_depth_rect(a, st));
+  return SE3TN_OK;
+}
+
+int se3tn_fill_depth_rect(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
+                          const int32_t rect[4], uint16_t* out_mm_sub, void* stream) {
+  if (!c || c->device < 0 || !depth_mm || H < 1 || W < 1 || !rect || !out_mm_sub || blur < 0 || blur > 2)
+    return fail(SE3TN_E_ARG, "se3tn_fill_depth_rect: bad argument");
+  if (rect[2] <= rect[0] || rect[3] <= rect[1]) return fail(SE3TN_E_ARG, "se3tn_fill_depth_rect: empty rectangle");
+  if (rect[0] < 0 || rect[1] < 0 || rect[2] > W || rect[3] > H) return fail(SE3TN_E_ARG, "se3tn_fill_depth_rect: rectangle outside the frame");
+  const size_t px = (size_t)H * W;
+  if (px > c->fd_pixels) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
+    if (stream_is_capturing((hipStream_t)stream))
+      return fail(SE3TN_E_STATE, "se3tn_fill_depth_rect: scratch too small for this frame inside a stream capture: call se3tn_reserve(ctx, H, W) first");
+    if (int rc = reserve_fill_depth(c, px)) return rc;
+  }
+  return fill_depth_rect_enqueue(c, depth_mm, H, W, max_depth_m, extrapolate, blur, rect, nullptr, rect, out_mm_sub, (hipStream_t)stream);
 }
 
 int se3tn_render_frame(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[16], const double K[9], int W, int H, uint8_t* rgb,

@@ -20,16 +20,9 @@
 #include <cmath>
 
 #include "se3tn_internal.h"
+#include "depth_fill_common.h"
 
 namespace se3tn {
-
-struct BilateralTaps { float w[12]; };
-
-__device__ __forceinline__ int reflect101(int p, int n) {
-  if (p < 0) p = -p;
-  if (p >= n) p = 2 * n - 2 - p;
-  return p < 0 ? 0 : (p >= n ? n - 1 : p);
-}
 
 // uint16 millimetres -> float32 inverted metres (Utils.py:459-471)
 __global__ __launch_bounds__(256) void fd_prepare_kernel(const uint16_t* __restrict__ mm, float* __restrict__ out, int total,
@@ -104,14 +97,6 @@ __global__ __launch_bounds__(256) void fd_median5_kernel(const float* __restrict
   out[i] = v[12];
 }
 
-// min / max of the image as order-preserving unsigned keys (any sign), mm[0] = min key, mm[1] = max key
-__device__ __forceinline__ unsigned f32_key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 __global__ __launch_bounds__(256) void fd_minmax_kernel(const float* __restrict__ in, int total, unsigned* __restrict__ mm) {
   unsigned lo = 0xffffffffu, hi = 0u;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
@@ -128,8 +113,6 @@ __global__ __launch_bounds__(256) void fd_minmax_kernel(const float* __restrict_
 
 // the two blurs keep multiply and add separate (as the scalar OpenCV loops and the numpy oracle do)
 #pragma clang fp contract(off)
-
-constexpr int BIL_BINS = 1 << 12;
 
 // expLUT of bilateralFilter_32f: lut[i] = exp((i / scale_index)^2 * gauss_color_coeff), zeros once it underflowed
 __global__ __launch_bounds__(256) void fd_bilateral_lut_kernel(const unsigned* __restrict__ mm, float* __restrict__ lut,
@@ -218,7 +201,8 @@ __global__ __launch_bounds__(256) void fd_finish_kernel(const float* __restrict_
   }
 }
 
-hipError_t launch_fill_depth(const FillDepthArgs& a, hipStream_t st) {
+// the chain up to the median, one launch per step: *median = the buffer that holds the median image, *spare = the other of buf0 / buf1
+void launch_fill_depth_to_median(const FillDepthArgs& a, hipStream_t st, float** median, float** spare) {
   const int total = a.H * a.W, grid = (total + 255) / 256;
   float *p = a.buf0, *q = a.buf1;
   auto swap = [&]() { float* t = p; p = q; q = t; };
@@ -233,6 +217,26 @@ hipError_t launch_fill_depth(const FillDepthArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((fd_morph_kernel<0, 0, 15, 1>), dim3(grid), dim3(256), 0, st, p, q, a.H, a.W); swap();  // holes := dilate 31x31
   }
   hipLaunchKernelGGL(fd_median5_kernel, dim3(grid), dim3(256), 0, st, p, q, a.H, a.W); swap();
+  *median = p; *spare = q;
+}
+
+void bilateral_space_taps(double sigma_space, float w[12]) {
+  const double gauss_space_coeff = -0.5 / (sigma_space * sigma_space);
+  int k = 0;
+  for (int dy = -2; dy <= 2; ++dy)
+    for (int dx = -2; dx <= 2; ++dx) {
+      const double r = std::sqrt((double)dy * dy + (double)dx * dx);
+      if (r > 2 || (dy == 0 && dx == 0)) continue;
+      w[k++] = (float)std::exp(r * r * gauss_space_coeff);
+    }
+}
+
+hipError_t launch_fill_depth(const FillDepthArgs& a, hipStream_t st) {
+  const int total = a.H * a.W, grid = (total + 255) / 256;
+  float *p, *q;
+  auto swap = [&]() { float* t = p; p = q; q = t; };
+  const float md = (float)a.max_depth;
+  launch_fill_depth_to_median(a, st, &p, &q);
   if (a.blur == 1) {         // bilateral (the reference's default)
     hipError_t e = hipMemsetAsync(a.minmax, 0xff, sizeof(unsigned), st);              // min key := 0xffffffff
     if (e == hipSuccess) e = hipMemsetAsync(a.minmax + 1, 0, sizeof(unsigned), st);   // max key := 0
@@ -241,16 +245,7 @@ hipError_t launch_fill_depth(const FillDepthArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(fd_bilateral_lut_kernel, dim3((BIL_BINS + 2 + 255) / 256), dim3(256), 0, st, a.minmax, a.lut,
                        -0.5 / (a.sigma_color * a.sigma_color));
     BilateralTaps taps;
-    {
-      const double gauss_space_coeff = -0.5 / (a.sigma_space * a.sigma_space);
-      int k = 0;
-      for (int dy = -2; dy <= 2; ++dy)
-        for (int dx = -2; dx <= 2; ++dx) {
-          const double r = std::sqrt((double)dy * dy + (double)dx * dx);
-          if (r > 2 || (dy == 0 && dx == 0)) continue;
-          taps.w[k++] = (float)std::exp(r * r * gauss_space_coeff);
-        }
-    }
+    bilateral_space_taps(a.sigma_space, taps.w);
     hipLaunchKernelGGL(fd_bilateral5_kernel, dim3(grid), dim3(256), 0, st, p, q, a.H, a.W, a.minmax, a.lut, taps);
     swap();
   } else if (a.blur == 2) {  // gaussian, valid pixels only

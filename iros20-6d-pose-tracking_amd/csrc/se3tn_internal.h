@@ -402,6 +402,19 @@ struct FillDepthArgs {
   float* out_m;              // [H,W] or nullptr
 };
 hipError_t launch_fill_depth(const FillDepthArgs& a, hipStream_t st);
+void launch_fill_depth_to_median(const FillDepthArgs& a, hipStream_t st, float** median, float** spare);
+void bilateral_space_taps(double sigma_space, float w[12]);   // cv2.bilateralFilter's 12 space weights of the radius-2 disc
+
+// the same on a rectangle of the frame (depth_fill_fused.hip): the chain up to the median in one tiled launch over the whole frame
+// (extrapolate != 0: the launches above), then blur + invert-back + uint16 on the pixels asked for only.  out_mm / out_m unused.
+struct FillDepthRectArgs {
+  FillDepthArgs f;
+  int cx0, cy0, cx1, cy1;    // pixels the last pass computes: [cy0, cy1) x [cx0, cx1), inside the frame, not empty
+  uint16_t* out_full;        // [H,W]: every computed pixel at its place in the frame, or nullptr
+  uint16_t* out_sub;         // [sy1 - sy0, sx1 - sx0] tightly packed: the computed pixels inside [sy0, sy1) x [sx0, sx1), or nullptr
+  int sx0, sy0, sx1, sy1;
+};
+hipError_t launch_fill_depth_rect(const FillDepthRectArgs& a, hipStream_t st);
 
 // host-side packer (weights.cpp)
 struct HostTensor {

@@ -266,6 +266,23 @@ class Engine:
             return (mm, out_m.cpu().numpy()) if return_metres else mm
         return (out, out_m) if return_metres else out
 
+    def fill_depth_rect(self, depth_mm, rect, max_depth=2.0, extrapolate=False, blur_type="bilateral"):
+        """fill_depth for the pixels of one rectangle (se3tn_fill_depth_rect): rect = (x0, y0, x1, y1) inside the frame ->
+        uint16 millimetres [y1-y0, x1-x0], every value the same pixel of fill_depth's result (same container kind as
+        depth_mm: numpy [H,W] or a cuda int16/uint16 tensor)."""
+        dev = "cuda:%d" % self.device
+        is_np = not torch.is_tensor(depth_mm)
+        d = torch.from_numpy(np.ascontiguousarray(depth_mm, dtype=np.uint16).view(np.int16)).to(dev) if is_np else depth_mm
+        assert d.is_cuda and d.element_size() == 2 and d.dim() == 2 and d.is_contiguous()
+        H, W = int(d.shape[0]), int(d.shape[1])
+        r = (C.c_int32 * 4)(*[int(v) for v in rect])
+        out = torch.empty((max(r[3] - r[1], 0), max(r[2] - r[0], 0)), dtype=torch.int16, device=dev)
+        blur = blur_type if isinstance(blur_type, int) else \
+            {"bilateral": _lib.BLUR_BILATERAL, "gaussian": _lib.BLUR_GAUSSIAN}.get(blur_type, _lib.BLUR_NONE)
+        check(self.lib.se3tn_fill_depth_rect(self._h, C.c_void_p(d.data_ptr()), H, W, float(max_depth), 1 if extrapolate else 0, blur, r,
+                                             C.c_void_p(out.data_ptr()), _stream_ptr()), "se3tn_fill_depth_rect")
+        return out.cpu().numpy().view(np.uint16) if is_np else out
+
     def infer(self, A, B, n, layout=NCHW, trans=None, rot=None, poseA=None, poseB=None):
         def p(x):
             if x is None:

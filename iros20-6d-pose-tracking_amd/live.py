@@ -7,6 +7,10 @@ reference's method names so that a rospy / ROS 2 / RealSense wrapper only has to
     grab_color(bgr)        BGR uint8 frame -> RGB (cv2.cvtColor(..., COLOR_BGR2RGB), :43-46)
     on_track()             Tracker.on_track on the latest pair, pose feedback (:48-60); returns what the node
                            publishes on tf: (translation [3], quaternion x,y,z,w, stamp) (:62-66)
+
+``LiveTracker(..., one_call=True)`` with the built-in rasteriser: the two grabs only keep the camera's frames and on_track is ONE
+library call (Tracker.on_track_live -> se3tn_on_track_live: fill_depth of the crop window's pixels, the BGR swap of the window and
+on_track); ``depth`` is then fetched from the device when somebody reads it.
 """
 import numpy as np
 
@@ -33,34 +37,75 @@ def quaternion_from_matrix(matrix):
 class LiveTracker:
     """predict_ros.py:19-66 `TrackerRos` minus the ROS plumbing."""
 
-    def __init__(self, tracker, pose_init, max_depth=2.0, extrapolate=False, blur_type="bilateral"):
+    def __init__(self, tracker, pose_init, max_depth=2.0, extrapolate=False, blur_type="bilateral", one_call=False):
         self.tracker = tracker
         self.color = None
-        self.depth = None
+        self._depth = None
         self.cur_time = None
         self.A_in_cam = np.asarray(pose_init, np.float64).copy()
         self._fill = dict(max_depth=max_depth, extrapolate=extrapolate, blur_type=blur_type)
+        from .renderer import HipRenderer
+        # one library call per frame needs the built-in rasteriser (False by default: not measured on the MI355X yet)
+        self.one_call = bool(one_call) and isinstance(tracker.renderer, HipRenderer)
+        self._raw = None           # one_call: the camera's depth frame as it came
+        self._filled_dev = None    # one_call: the filled frame of the last on_track, on the device
+        self._filled_valid = False
 
     def reset(self, pose_init):
         self.color = None
-        self.depth = None
+        self._depth = None
+        self._raw = None
+        self._filled_valid = False
         self.cur_time = None
         self.A_in_cam = np.asarray(pose_init, np.float64).copy()
 
+    @property
+    def depth(self):
+        """The hole-filled uint16 mm frame on_track reads.  one_call: fetched from the device on demand (of the last on_track; a
+        frame grabbed since is filled here, off the per-frame path)."""
+        if not self.one_call:
+            return self._depth
+        if self._raw is None:
+            return None
+        if self._filled_valid:
+            return self._filled_dev.cpu().numpy().view(np.uint16)
+        return self.tracker.engine.fill_depth(self._raw, **self._fill)
+
+    @depth.setter
+    def depth(self, value):
+        self._depth = value
+
     def grab_depth(self, depth_mm):
         """depth_mm: HxW array in millimetres (what CvBridge 'passthrough' hands over, cast to uint16)."""
-        self.depth = self.tracker.engine.fill_depth(np.asarray(depth_mm).astype(np.uint16), **self._fill)
+        if self.one_call:
+            self._raw = np.ascontiguousarray(depth_mm, dtype=np.uint16) if np.asarray(depth_mm).dtype == np.uint16 \
+                else np.asarray(depth_mm).astype(np.uint16)
+            self._filled_valid = False
+            return
+        self._depth = self.tracker.engine.fill_depth(np.asarray(depth_mm).astype(np.uint16), **self._fill)
 
     def grab_color(self, bgr, stamp=0.0):
-        """bgr: HxWx3 uint8 as CvBridge 'bgr8' delivers it; stored as RGB."""
+        """bgr: HxWx3 uint8 as CvBridge 'bgr8' delivers it; stored as RGB (one_call: kept as it came, swapped inside the call)."""
         self.cur_time = stamp
-        self.color = np.ascontiguousarray(np.asarray(bgr)[:, :, ::-1])
+        self.color = np.ascontiguousarray(bgr, dtype=np.uint8) if self.one_call else np.ascontiguousarray(np.asarray(bgr)[:, :, ::-1])
+
+    def _on_track_one_call(self):
+        import torch
+        if self._filled_dev is None or tuple(self._filled_dev.shape) != self._raw.shape:
+            self._filled_dev = torch.empty(self._raw.shape, dtype=torch.int16, device="cuda:%d" % self.tracker.engine.device)
+        self._filled_valid = False
+        pose = self.tracker.on_track_live(self.A_in_cam, self.color, self._raw, bgr=True, depth_filled=self._filled_dev, **self._fill)
+        self._filled_valid = True
+        return pose
 
     def on_track(self):
-        if self.color is None or self.depth is None or self.cur_time is None:
+        if self.color is None or (self._raw if self.one_call else self._depth) is None or self.cur_time is None:
             return None
-        ob_in_cam = self.tracker.on_track(self.A_in_cam, self.color.astype(np.uint8), self.depth,
-                                          gt_A_in_cam=np.eye(4), gt_B_in_cam=np.eye(4), debug=False, samples=1)
+        if self.one_call:
+            ob_in_cam = self._on_track_one_call()
+        else:
+            ob_in_cam = self.tracker.on_track(self.A_in_cam, self.color.astype(np.uint8), self._depth,
+                                              gt_A_in_cam=np.eye(4), gt_B_in_cam=np.eye(4), debug=False, samples=1)
         self.A_in_cam = ob_in_cam.copy()
         trans = ob_in_cam[:3, 3]
         q_wxyz = quaternion_from_matrix(ob_in_cam)

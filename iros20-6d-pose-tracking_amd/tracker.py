@@ -214,8 +214,21 @@ class Tracker:
             raise ValueError("rgb must be HxWx3 uint8")
         dep = current_depth if (type(current_depth) is np.ndarray and current_depth.dtype == np.uint16 and current_depth.flags.c_contiguous
                                 and current_depth.shape == rgb.shape[:2]) else _depth_u16(current_depth, rgb)
+        st = self._one_call_args()
+        C = st["C"]
+        st["P"][...] = prev_pose
+        r = self.renderer
+        rgbA, depthA = (st["rgbA"], st["depthA"]) if "rgbA" in st else (r.rgb, r.depth)
+        st["check"](st["fn"](self.engine._h, r._m, st["p_P"], st["p_K"], C.c_double(float(self.object_width)), C.c_void_p(rgb.ctypes.data),
+                             C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]), C.c_void_p(rgbA.data_ptr()),
+                             C.c_void_p(depthA.data_ptr()), st["p_pose"], st["p_tr"], st["p_ro"], st["p_bb"], st["stream"]()),
+                    "se3tn_on_track")
+        return self._one_call_result(st, rgbA, depthA, current_rgb, current_depth)
+
+    def _one_call_args(self):
+        """per-tracker constants of se3tn_on_track / se3tn_on_track_live: argument objects are built once, not per frame"""
         st = self._one_call_state
-        if st is None:   # per-tracker constants of the call: argument objects are built once, not per frame
+        if st is None:
             import ctypes as C
             from ._lib import check
             from .engine import _stream_ptr
@@ -230,14 +243,9 @@ class Tracker:
                 st["depthA"] = torch.empty((176, 176), dtype=torch.int16, device=self._dev)
             for k, t in (("P", C.c_double), ("K", C.c_double), ("pose", C.c_double), ("tr", C.c_float), ("ro", C.c_float), ("bb", C.c_int32)):
                 st["p_" + k] = st[k].ctypes.data_as(C.POINTER(t))
-        C = st["C"]
-        st["P"][...] = prev_pose
-        r = self.renderer
-        rgbA, depthA = (st["rgbA"], st["depthA"]) if "rgbA" in st else (r.rgb, r.depth)
-        st["check"](st["fn"](self.engine._h, r._m, st["p_P"], st["p_K"], C.c_double(float(self.object_width)), C.c_void_p(rgb.ctypes.data),
-                             C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]), C.c_void_p(rgbA.data_ptr()),
-                             C.c_void_p(depthA.data_ptr()), st["p_pose"], st["p_tr"], st["p_ro"], st["p_bb"], st["stream"]()),
-                    "se3tn_on_track")
+        return st
+
+    def _one_call_result(self, st, rgbA, depthA, current_rgb, current_depth):
         self.last_prediction = dict(trans=st["tr"].reshape(1, 3).copy(), rot=st["ro"].reshape(1, 3).copy(), bbox=st["bb"].copy())
         if "rgbA" in st:
             self.last_prediction.update(rgbA=rgbA, depthA=depthA)
@@ -245,6 +253,51 @@ class Tracker:
         self.prev_depth = current_depth
         self.frame_cnt += 1
         return st["pose"].copy()
+
+    def on_track_live(self, prev_pose, color, depth_raw, bgr=False, max_depth=2.0, extrapolate=False, blur_type="bilateral",
+                      depth_filled=None):
+        """predict_ros.py:38-60 for one camera frame: fill_depth of the RAW depth frame (HxW uint16 mm with holes), the colour
+        frame's channel order (bgr=True: what CvBridge 'bgr8' delivers) and on_track.  With the built-in rasteriser this is ONE
+        library call (se3tn_on_track_live): the raw depth frame goes up whole, only the crop window's part of it is blurred and
+        converted, and the filled frame never visits the host.  depth_filled (optional cuda int16/uint16 [H,W]) receives the whole
+        filled frame.  With an injected renderer (or one_call = False) it composes engine.fill_depth + on_track.  Returns the 4x4
+        float64 pose; prev_rgb / prev_depth keep the frames as given."""
+        if self._stream is not None and torch.cuda.current_stream() != self._stream:
+            with torch.cuda.stream(self._stream):
+                return self.on_track_live(prev_pose, color, depth_raw, bgr, max_depth, extrapolate, blur_type, depth_filled)
+        prev_pose = np.asarray(prev_pose, np.float64)
+        from . import _lib
+        from .renderer import HipRenderer
+        if not (self.one_call and isinstance(self.renderer, HipRenderer)):
+            filled = self.engine.fill_depth(np.asarray(depth_raw).astype(np.uint16), max_depth, extrapolate, blur_type)
+            if depth_filled is not None:
+                depth_filled.copy_(torch.from_numpy(filled.view(np.int16)).view(depth_filled.dtype))
+            rgb = np.ascontiguousarray(np.asarray(color)[:, :, ::-1]) if bgr else color
+            return self.on_track(prev_pose, rgb, filled)
+        col = color if (type(color) is np.ndarray and color.dtype == np.uint8 and color.flags.c_contiguous) \
+            else np.ascontiguousarray(color, dtype=np.uint8)
+        if col.ndim != 3 or col.shape[2] != 3:
+            raise ValueError("color must be HxWx3 uint8")
+        raw = depth_raw if (type(depth_raw) is np.ndarray and depth_raw.dtype == np.uint16 and depth_raw.flags.c_contiguous
+                            and depth_raw.shape == col.shape[:2]) else _depth_u16(depth_raw, col)
+        H, W = int(col.shape[0]), int(col.shape[1])
+        if depth_filled is not None:
+            assert depth_filled.is_cuda and depth_filled.element_size() == 2 and depth_filled.is_contiguous() \
+                and tuple(depth_filled.shape) == (H, W)
+        st = self._one_call_args()
+        C = st["C"]
+        st["P"][...] = prev_pose
+        r = self.renderer
+        rgbA, depthA = (st["rgbA"], st["depthA"]) if "rgbA" in st else (r.rgb, r.depth)
+        blur = blur_type if isinstance(blur_type, int) else \
+            {"bilateral": _lib.BLUR_BILATERAL, "gaussian": _lib.BLUR_GAUSSIAN}.get(blur_type, _lib.BLUR_NONE)
+        order = bgr if (isinstance(bgr, int) and not isinstance(bgr, bool)) else (_lib.COLOR_BGR if bgr else _lib.COLOR_RGB)
+        st["check"](self.engine.lib.se3tn_on_track_live(
+            self.engine._h, r._m, st["p_P"], st["p_K"], C.c_double(float(self.object_width)), C.c_void_p(col.ctypes.data), int(order),
+            C.c_void_p(raw.ctypes.data), H, W, C.c_double(float(max_depth)), 1 if extrapolate else 0, int(blur),
+            C.c_void_p(depth_filled.data_ptr()) if depth_filled is not None else None, C.c_void_p(rgbA.data_ptr()),
+            C.c_void_p(depthA.data_ptr()), st["p_pose"], st["p_tr"], st["p_ro"], st["p_bb"], st["stream"]()), "se3tn_on_track_live")
+        return self._one_call_result(st, rgbA, depthA, color, depth_raw)
 
     def on_track_batch(self, prev_poses, rgbs, depths):
         """Extension: n independent (pose, frame) pairs of the SAME object in one engine call -- several

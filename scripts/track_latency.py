@@ -73,7 +73,83 @@ def main(frames=300, faces_subdiv=None, f16x3=False, pyrender=False, one_call=No
                       "note": "batch 1, 480x640 frame uploaded per call (pageable H2D), %s, pose D2H sync per frame" % rdesc}))
 
 
+def _live_tracker():
+    from oracle import raster_oracle as R
+    mean, std = Fx.mean_std(0)
+    mesh = R.icosphere(6, 0.06, 0)                                   # 81,920 faces
+    trk = se3.Tracker(dict(Fx.DATASET_INFO, object_width=150.0), mean, std, {"state_dict": O.make_state_dict(0, head_gain=0.0005)})
+    trk.renderer = se3.HipRenderer(trk.engine, mesh)
+    return trk, len(mesh["faces"])
+
+
+def live(frames=300, passes=2, trace_dir=None):
+    """The live-camera front end (predict_ros.TrackerRos) per frame: grab_depth + grab_color + on_track of LiveTracker step by step
+    (fill_depth as 10-13 launches, the filled frame to the host and its window back up) against one_call=True (se3tn_on_track_live).
+    Built-in rasteriser, 480 x 640 synthetic frames with holes; the legs alternate in one session, one JSON line per leg and pass.
+    trace_dir: one frame of each leg in a child process of its own under `rocprofv3 --kernel-trace --stats` (no counters)."""
+    trk, faces = _live_tracker()
+    seq = [Fx.synthetic_frame(200 + i) for i in range(8)]
+    seq = [(np.ascontiguousarray(rgb[:, :, ::-1]), depth) for rgb, depth in seq]      # as CvBridge 'bgr8' delivers them
+    P0 = Fx.pose(3)
+    legs = [("step_by_step", se3.LiveTracker(trk, P0)), ("one_call", se3.LiveTracker(trk, P0, one_call=True))]
+    assert legs[1][1].one_call
+
+    def frame(lt, i):
+        bgr, depth = seq[i % len(seq)]
+        lt.grab_depth(depth)
+        lt.grab_color(bgr, stamp=float(i))
+        return lt.on_track()
+
+    for p in range(passes):
+        for name, lt in legs:
+            lt.reset(P0)
+            for i in range(20):
+                frame(lt, i)
+            lt.reset(P0)
+            torch.cuda.synchronize()
+            lat = []
+            for i in range(frames):
+                t0 = time.perf_counter()
+                frame(lt, i)
+                lat.append(time.perf_counter() - t0)
+            lat = np.array(lat) * 1e3
+            print(json.dumps({"leg": name, "pass": p, "frame_ms_median": round(float(np.median(lat)), 4),
+                              "frame_ms_p95": round(float(np.percentile(lat, 95)), 4), "hz_median": round(1000.0 / float(np.median(lat)), 1),
+                              "frames": frames, "note": "LiveTracker grab_depth + grab_color + on_track per frame, 480x640 frames with holes, "
+                              "HIP rasteriser, %d faces, pose fed back" % faces}), flush=True)
+    if trace_dir:
+        import shutil
+        import subprocess
+        prof = shutil.which("rocprofv3")
+        if prof is None:
+            print(json.dumps({"trace": "rocprofv3 not found: no kernel trace recorded"}))
+            return
+        for name, _ in legs:
+            out = os.path.join(trace_dir, name)
+            subprocess.run([prof, "--kernel-trace", "--stats", "-d", out, "--", sys.executable, os.path.abspath(__file__), "live-frame", name],
+                           check=True, timeout=300)
+            print(json.dumps({"trace": out, "leg": name}), flush=True)
+
+
+def live_frame(leg):
+    """what the traced child runs: two frames of one leg (the first pays the start-up allocations)"""
+    trk, _ = _live_tracker()
+    lt = se3.LiveTracker(trk, Fx.pose(3), one_call=leg == "one_call")
+    for i in range(2):
+        rgb, depth = Fx.synthetic_frame(200 + i)
+        lt.grab_depth(depth)
+        lt.grab_color(np.ascontiguousarray(rgb[:, :, ::-1]), stamp=float(i))
+        lt.on_track()
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["live"]:          # `track_latency.py live [--trace DIR]`: the live-camera front end, both legs
+        live(trace_dir=sys.argv[3] if sys.argv[2:3] == ["--trace"] and len(sys.argv) > 3 else None)
+        sys.exit(0)
+    if sys.argv[1:2] == ["live-frame"]:
+        live_frame(sys.argv[2])
+        sys.exit(0)
     if "pyrender" not in sys.argv[1:]:     # `track_latency.py pyrender`: the two pyrender legs only
         main()
         main(faces_subdiv=6)
