@@ -160,3 +160,206 @@ def textured_sphere(subdiv=2, radius=0.05, tex_hw=(64, 128)):
     tex = np.stack([(xx * 255 // (tw - 1)), (yy * 255 // (th - 1)), ((xx // 8 + yy // 8) % 2) * 200 + 30], -1).astype(np.uint8)
     tex[rng.random((th, tw)) < 0.05] = (255, 255, 255)
     return dict(vertices=v, faces=m["faces"], uv=uv, texture=tex, kd=np.array([0.9, 1.0, 0.8]), colors=m["colors"])
+
+
+# ---- triangle soups: the geometry a closed, convex, well-conditioned sphere never shows the rasteriser ----------------------------
+# (tests/test_raster_soups_oracle.py holds the oracle to itself and to the live GL library on them and proves each family reaches
+# the path it names; tests/test_gpu_raster_soups.py holds the HIP kernels to the oracle.)  Every triangle has its OWN three
+# vertices (faces = arange), so colours and normals differ per triangle and a wrong owner shows in rgb; normals point anywhere,
+# so max(ndl, 0) of the window shader takes both branches.  The soups are modelled around the object origin and seen under
+# soup_poses(family): a pure translation (the pose the lattice is back-projected for) and a rotated pose at the same place.
+SOUP_FAMILIES = ("small", "big", "near", "far", "lattice", "ties")
+SOUP_WIDTH = 150.0                       # object_width (mm): the 176 x 176 window spans +-75 mm at the object's depth
+SOUP_T = dict(small=(0.02, -0.01, 0.5), big=(0.02, -0.01, 0.5), near=(0.01, 0.005, 0.14), far=(-0.01, 0.02, 1.95),
+              lattice=(0.02, -0.01, 0.5), ties=(0.02, -0.01, 0.5))
+# |w| (= camera z) of every vertex stays above this under every pose of its family.  The rasteriser gives up on a window
+# coordinate at |Xf| >= 1e9 (csrc/raster.hip), oracle/ss_rules.project at 2^30: nothing pins either value to the live library, so
+# the soups stay far below both (tests/test_raster_soups_oracle.py asserts |X|, |Y| < 2^24).
+SOUP_MIN_W = 4e-3
+SOUP_POSE_SEED = dict(small=20, big=21, near=31, far=22, ties=25)       # of the rotated pose
+
+
+def gl_window(P, K, width):
+    """left, top, right, bottom of the render window (predict.py:201-207: compute_bbox in the y-flipped GL image)"""
+    x, y, z = P[0, 3] * 1000, P[1, 3] * -1000, P[2, 3] * 1000
+    u = np.round(np.array([x - width / 2, x + width / 2]) * K[0, 0] / z + K[0, 2]).astype(np.int32)
+    v = np.round(np.array([y - width / 2, y + width / 2]) * K[1, 1] / z + K[1, 2]).astype(np.int32)
+    return (int(u.min()), int(v.min()), int(u.max()), int(v.max()))
+
+
+def soup_poses(family):
+    P0 = np.eye(4)
+    P0[:3, 3] = SOUP_T[family]
+    if family == "lattice":                      # the grid alignment exists under the pose it was back-projected for only
+        return [P0]
+    return [P0, pose(SOUP_POSE_SEED[family], SOUP_T[family])]
+
+
+def _window_to_object(g, z, P, K, win, size=176):
+    """object coordinates (float64) of the points that the window render under the pure translation P shows at window position g
+    [..., 2] (pixels; pixel i's centre is i + 0.5; GL rows, bottom-up) and camera depth z [...]"""
+    left, top, right, bottom = win
+    u = left + g[..., 0] * (right - left) / float(size)
+    vf = top + g[..., 1] * (bottom - top) / float(size)
+    cam = np.stack([(u - K[0, 2]) * z / K[0, 0], (K[1, 2] - vf) * z / K[1, 1], z], -1)
+    return cam - P[:3, 3]
+
+
+def _soup_pack(tris, rng, faces=None):
+    tris = np.asarray(tris, np.float64).reshape(-1, 3, 3)
+    n = len(tris)
+    nrm = rng.normal(0, 1, (3 * n, 3))
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    return dict(vertices=tris.reshape(-1, 3).astype(np.float32), faces=(np.arange(3 * n).reshape(n, 3) if faces is None else faces).astype(np.int32),
+                colors=rng.integers(40, 256, (3 * n, 3)).astype(np.uint8), normals=nrm.astype(np.float32))
+
+
+def _random_tris(rng, n, spread, size):
+    """n triangles: centres uniform in +-spread (x, y, z), vertices uniform in +-size around them (size: scalar, [3] or [n,1,1])"""
+    c = rng.uniform(-1, 1, (n, 3)) * np.asarray(spread, np.float64)
+    return c[:, None, :] + rng.uniform(-1, 1, (n, 3, 3)) * size
+
+
+def _off_the_camera_plane(m, poses, rng):
+    """moves the (few) vertices whose camera z comes closer to 0 than SOUP_MIN_W under one of the poses"""
+    v = m["vertices"]
+    for _ in range(50):
+        bad = np.zeros(len(v), bool)
+        for P in poses:
+            bad |= np.abs(v.astype(np.float64) @ P[2, :3] + P[2, 3]) < 1.5 * SOUP_MIN_W
+        if not bad.any():
+            return m
+        v[bad] += rng.normal(0, 0.01, (int(bad.sum()), 3)).astype(np.float32)
+    raise AssertionError("soup vertices stay on the camera plane")
+
+
+def soup(family, seed=0):
+    """dict(vertices float32 [3n,3], faces int32 [n,3], colors uint8 [3n,3], normals float32 [3n,3]) of one family:
+      small    ~400 triangles with edges of 2-15 window pixels, random winding, heavily overlapping in depth; mixed in: faces that
+               repeat a vertex index, collinear vertices, triangles smaller than a pixel laid between the pixel centres, slivers over
+               100 pixels long and under 1/16 pixel wide
+      big      40 triangles with edges of 50-150 pixels (bounding boxes beyond the rasteriser's RASTER_BIG_PX), some across the window's edges
+      near     triangles across the near plane (0.1 m) and the camera plane: one, two and three vertices with w < 0
+      far      triangles across the far plane (2 m), and very large ones that the near, the far and two or more side planes cut at once
+      lattice  vertices back-projected (float64) from the half-pixel grid of the window at varying depth: after the float32 projection
+               they snap onto it exactly, so pixel centres lie ON edges and vertices; fans around one point, pairs on one edge
+      ties     exact copies of triangles (own vertices, other colours) later and earlier in draw order, copies with permuted vertex
+               order (the same plane through another anchor vertex), overlapping triangles in one plane z = const of the camera (equal
+               w on three vertices) and with equal w on two vertices"""
+    rng = np.random.default_rng(1000 + 17 * SOUP_FAMILIES.index(family) + seed)
+    poses = soup_poses(family)
+    P0, T = poses[0], np.asarray(SOUP_T[family])
+    win = gl_window(P0, K_YCB, SOUP_WIDTH)
+    if family == "small":
+        tris = [_random_tris(rng, 380, (0.05, 0.05, 0.05), rng.uniform(0.002, 0.0085, (380, 1, 1)))]
+        a, b = _random_tris(rng, 5, (0.05, 0.05, 0.03), 0.01)[:, :2].transpose(1, 0, 2)
+        tris.append(np.stack([a, b, a + rng.uniform(0.2, 0.8, (5, 1)) * (b - a)], 1))                 # collinear
+        g = rng.integers(20, 156, (6, 1, 2)) + rng.uniform(-0.2, 0.2, (6, 3, 2))                       # around pixel CORNERS: no centre inside
+        tris.append(_window_to_object(g, np.repeat(rng.uniform(0.42, 0.5, (6, 1)), 3, 1), P0, K_YCB, win))
+        a = _random_tris(rng, 4, (0.02, 0.02, 0.03), 0.0)[:, 0]
+        d = rng.normal(0, 1, (4, 3)) * (1, 1, 0.2)
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        b = a + 0.1 * d                                                                                # 117 pixels long ...
+        c = (a + b) / 2 + 2e-5 * np.stack([-d[:, 1], d[:, 0], 0 * d[:, 0]], 1)                         # ... 0.02 pixel wide
+        tris.append(np.stack([a, b, c], 1))
+        tris.append(_random_tris(rng, 5, (0.05, 0.05, 0.03), 0.006))                                   # faces (i, i, j) below
+        m = _soup_pack(np.concatenate(tris), rng)
+        m["faces"][-5:, 1] = m["faces"][-5:, 0]
+    elif family == "big":
+        m = _soup_pack(np.concatenate([_random_tris(rng, 28, (0.02, 0.02, 0.04), (0.045, 0.045, 0.03)),
+                                       _random_tris(rng, 12, (0.07, 0.07, 0.04), (0.05, 0.05, 0.03))]), rng)
+    elif family == "near":
+        tris = [_random_tris(rng, 90, (0.03, 0.03, 0.1), 0.05)]
+        for k in (1, 2, 3):                                                                            # k vertices behind the camera
+            t = rng.uniform(-1, 1, (8, 3, 3)) * (0.05, 0.05, 0)
+            zc = rng.uniform(0.12, 0.35, (8, 3))
+            zc[:, :k] = rng.uniform(-0.2, -0.01, (8, k))
+            t[..., 2] = zc - T[2]
+            tris.append(t[:, rng.permutation(3)])
+        m = _soup_pack(np.concatenate(tris), rng)
+    elif family == "far":
+        tris = [_random_tris(rng, 50, (0.05, 0.05, 0.1), (0.04, 0.04, 0.15)),
+                _random_tris(rng, 20, (0.05, 0.05, 0.004), (0.03, 0.03, 0.012)) + (0, 0, 2.0 - T[2])]     # steep and gentle
+        # from before the near plane to beyond the far one, in a plane that all but holds the camera centre, n . (x, y) = a z + b
+        # (x, y measured from the ray through the window's centre):
+        # the window shows it as a diagonal band between the line where the near plane cuts it and the line where the far plane does,
+        # its ends cut off by the window's sides -- near, far and two to four side planes on one triangle
+        t = np.zeros((4, 3, 3))
+        for i, (deg, a, b) in enumerate([(45, -0.008, 0.002), (135, 0.007, -0.0018), (45, 0.006, -0.0018), (135, -0.009, 0.0022)]):
+            n_ = np.array([np.cos(np.radians(deg)), np.sin(np.radians(deg))])
+            for k, (z, l) in enumerate([(0.05, rng.uniform(-0.002, 0.002)), (rng.uniform(2.3, 2.6), -0.6), (rng.uniform(2.3, 2.6), 0.6)]):
+                t[i, k] = np.r_[(a * z + b) * n_ + l * np.array([-n_[1], n_[0]]) + z * T[:2] / T[2], z]
+            if i % 2:
+                t[i] = t[i, ::-1]
+        tris.append(t - T)
+        m = _soup_pack(np.concatenate(tris), rng)
+    elif family == "lattice":
+        half = lambda lo, hi, shape: rng.integers(2 * lo, 2 * hi + 1, shape) / 2.0                      # the half-pixel grid
+        pts, zs = [], []
+        g = half(10, 166, (60, 3, 2))                                                                  # large
+        pts.append(g); zs.append(rng.uniform(0.35, 0.65, (60, 3)))
+        g = half(20, 156, (80, 1, 2)) + half(-8, 8, (80, 3, 2))                                        # small
+        pts.append(g); zs.append(rng.uniform(0.35, 0.65, (80, 3)))
+        for _ in range(5):                                                                             # fans around a pixel centre
+            hub, hz = rng.integers(30, 146, 2) + 0.5, rng.uniform(0.4, 0.6)
+            ang = np.sort(rng.uniform(0, 2 * np.pi, 6))
+            ring = hub + np.round(2 * rng.uniform(6, 20, (6, 1)) * np.stack([np.cos(ang), np.sin(ang)], 1)) / 2.0
+            rz = rng.uniform(0.4, 0.6, 6)
+            for i in range(6):
+                j = (i + 1) % 6
+                pts.append(np.stack([hub, ring[i], ring[j]])[None]); zs.append(np.array([[hz, rz[i], rz[j]]]))
+        for _ in range(15):                                                                            # (a, b, c) and (a, b, d): one edge, two windings
+            q, qz = half(20, 156, (1, 2)) + half(-15, 15, (4, 2)), rng.uniform(0.4, 0.6, 4)
+            pts.append(q[[0, 1, 2]][None]); zs.append(qz[[0, 1, 2]][None])
+            pts.append(q[[0, 1, 3]][None]); zs.append(qz[[0, 1, 3]][None])
+        g, z = np.concatenate(pts), np.concatenate(zs)
+        m = _soup_pack(_window_to_object(g, z, P0, K_YCB, win), rng)
+    elif family == "ties":
+        base = _random_tris(rng, 60, (0.05, 0.05, 0.04), 0.015)
+        flat = _random_tris(rng, 20, (0.03, 0.03, 0.0), (0.03, 0.03, 0.0))
+        flat[..., 2] = 0.47 - T[2]                                                                     # one plane of the camera: w equal on all three
+        two = _random_tris(rng, 15, (0.05, 0.05, 0.03), 0.02)
+        two[:, :2, 2] = 0.45 - T[2]                                                                    # ... on two
+        two = np.stack([two[i][rng.permutation(3)] for i in range(15)])
+        perms = [[1, 2, 0], [2, 0, 1], [0, 2, 1], [1, 0, 2], [2, 1, 0]]
+        permuted = np.stack([base[30 + i][perms[i % 5]] for i in range(15)])
+        m = _soup_pack(np.concatenate([base[15:30], base, flat, two, base[0:15], permuted]), rng)      # copies drawn earlier | ... | later
+    else:
+        raise ValueError(family)
+    return _off_the_camera_plane(m, poses, rng)
+
+
+SOUP_FRAME_HW = (120, 160)
+SOUP_FRAME_K = np.array([[266.7, 0, 78.2], [0, 266.9, 60.3], [0, 0, 1.0]])       # the small camera of tests/test_renderer.py
+
+
+def soup_frame(seed=0):
+    """The soup of the full-frame route's tests: 90 triangles spread over the edges of the SOUP_FRAME_HW frame and the near plane under
+    soup_frame_pose(), with a planar texture map (affine in the vertex position, reaching outside [0, 1]: REPEAT wraps) and
+    textured_sphere's texture.  colors as the window soups'; kd for both the textured and the vertex-colour mesh."""
+    rng = np.random.default_rng(2000 + seed)
+    m = _off_the_camera_plane(_soup_pack(_random_tris(rng, 90, (0.12, 0.1, 0.25), 0.06), rng), [soup_frame_pose()], rng)
+    v = m["vertices"].astype(np.float64)
+    m["uv"] = np.stack([0.5 + 3.0 * v[:, 0] + 1.0 * v[:, 1], 0.4 - 1.5 * v[:, 0] + 3.5 * v[:, 1] + 1.0 * v[:, 2]], 1)
+    m["texture"] = textured_sphere(0)["texture"]
+    m["kd"] = np.array([0.9, 1.0, 0.8])
+    return m
+
+
+def soup_frame_pose():
+    return pose(4, (0.01, -0.02, 0.28))
+
+
+def soup_composite_poses():
+    """two ordinary views and a close-up that puts much of the model before the near plane and some of it behind the camera"""
+    return [pose(32, (0.02, -0.01, 0.5)), pose(33, (-0.03, 0.02, 0.62)), pose(34, (0.01, 0.0, 0.16))]
+
+
+def soup_composite(seed=0):
+    """small + big + near in one model (394 triangles): the model of the batched-launch tests, seen under soup_composite_poses()"""
+    parts = [soup("small", seed), soup("big", seed), soup("near", seed)]
+    take = [250, 30, 114]
+    m = {k: np.concatenate([p[k][:3 * n] for p, n in zip(parts, take)]) for k in ("vertices", "colors", "normals")}
+    off = np.cumsum([0] + [3 * n for n in take[:-1]])
+    m["faces"] = np.concatenate([p["faces"][:n] + o for p, n, o in zip(parts, take, off)]).astype(np.int32)
+    return _off_the_camera_plane(m, soup_composite_poses(), np.random.default_rng(3000 + seed))
