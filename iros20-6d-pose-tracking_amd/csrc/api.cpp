@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "se3tn_internal.h"
+#include "tex_pyramid.h"
 #include "weights.h"
 
 using namespace se3tn;
@@ -1067,29 +1068,9 @@ int se3tn_mesh_set_texture(se3tn_mesh* m, const float* uv, const uint8_t* rgb, i
   m->tlevels = 0;
   m->has_material = true;
   if (!rgb) return SE3TN_OK;
-  // mip pyramid: 2x2 box filter per level (what glGenerateMipmap implementations do), levels back to back
-  std::vector<uint8_t> pyr(rgb, rgb + (size_t)tw * th * 3);
-  int w = tw, h = th, levels = 1;
-  size_t off = 0;
-  m->tex_off[0] = 0;
-  while ((w > 1 || h > 1) && levels < 16) {
-    const int nw = w > 1 ? w / 2 : 1, nh = h > 1 ? h / 2 : 1;
-    const size_t noff = off + (size_t)w * h * 3;
-    pyr.resize(noff + (size_t)nw * nh * 3);
-    const uint8_t* src = pyr.data() + off;
-    uint8_t* dst = pyr.data() + noff;
-    for (int y = 0; y < nh; ++y)
-      for (int x = 0; x < nw; ++x)
-        for (int ch = 0; ch < 3; ++ch) {
-          const int x0 = 2 * x < w ? 2 * x : w - 1, x1 = 2 * x + 1 < w ? 2 * x + 1 : w - 1;
-          const int y0 = 2 * y < h ? 2 * y : h - 1, y1 = 2 * y + 1 < h ? 2 * y + 1 : h - 1;
-          const int sum = src[((size_t)y0 * w + x0) * 3 + ch] + src[((size_t)y0 * w + x1) * 3 + ch] +
-                          src[((size_t)y1 * w + x0) * 3 + ch] + src[((size_t)y1 * w + x1) * 3 + ch];
-          dst[((size_t)y * nw + x) * 3 + ch] = (uint8_t)((sum + 2) >> 2);
-        }
-    m->tex_off[levels] = (unsigned)noff;
-    off = noff; w = nw; h = nh; ++levels;
-  }
+  // mip pyramid: 2x2 box filter per level, levels back to back (tex_pyramid.h)
+  std::vector<uint8_t> pyr;
+  const int levels = se3tn_build_mip_pyramid(rgb, tw, th, pyr, m->tex_off);
   // both buffers exist and are filled before either is published: the resolve kernel reads uv whenever tex is set
   uint8_t* d_tex = nullptr;
   float* d_uv = nullptr;

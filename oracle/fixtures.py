@@ -363,3 +363,168 @@ def soup_composite(seed=0):
     off = np.cumsum([0] + [3 * n for n in take[:-1]])
     m["faces"] = np.concatenate([p["faces"][:n] + o for p, n, o in zip(parts, take, off)]).astype(np.int32)
     return _off_the_camera_plane(m, soup_composite_poses(), np.random.default_rng(3000 + seed))
+
+
+# ---- textured cards: the hard cases of the full-frame renderer's texture filter ---------------------------------------------------
+# (oracle/texture_oracle.py states the filter in float64 with a per-pixel bound; tests/test_texture_filter_oracle.py holds the float32
+# oracle and planted faults to it on the CPU, tests/test_gpu_texture_filter.py the HIP kernel.)  A card is a fronto-parallel rectangle
+# of the SOUP_FRAME_HW frame, a 2 x 2 grid of quads (8 triangles, each with its own vertices), seen under a pure translation with a
+# texture map that is affine in the image position: w is constant, so the level of detail is the same at every pixel and known in
+# closed form from the map's Jacobian J (base-level texels per pixel; rows u, v; columns image x, y):
+# rho = max(|J[:, 0]|, |J[:, 1]|), lod = clamp(log2 rho).
+CARD_T = (0.01, -0.02, 0.4)
+# the 3 x 3 grid's columns and rows in continuous image coordinates (pixel i's centre: i + 0.5), on multiples of 1/16 pixel: the
+# rasteriser snaps vertices to that grid, so the map below holds at the pixel centres up to float32 rounding, not up to 1/32 pixel
+CARD_GRID_X, CARD_GRID_Y = (49.3125, 81.875, 110.6875), (38.625, 57.75, 81.1875)
+CARD_RECT = (CARD_GRID_X[0], CARD_GRID_Y[0], CARD_GRID_X[2], CARD_GRID_Y[2])         # left, top, right, bottom
+# the image point where u = v = 0.  Generic, so that the real colour does not sit ON a byte boundary (bilinear weights of exactly 1/2
+# on both axes make it a multiple of 1/4: every fourth pixel-channel would admit two bytes by construction); the two "edges" cards
+# put one axis on the centre of pixel 80 / 60 and leave the other generic
+CARD_ORIGIN = (80.37, 60.21)
+CARD_ORIGINS = {"edges_u": (80.5, 60.21), "edges_v": (80.37, 60.5)}
+FILTER_TEXTURES = ("noise", "noise40x24", "noise5x3", "row1x7", "col7x1", "one", "corners", "channels")
+FILTER_KDS = ((0.9, 1.0, 0.8), (0.0, 1.0, 2.5), None)      # the reference's material; zero and saturation; the default
+# name -> J, or a function of the texture's level count L (the top level and the clamp above it), or "uv": a map given in uv units
+CARDS = {
+    "mag4": np.eye(2) * 0.25,                           # magnification, 1/4 texel per pixel: lod clamped at 0 from below
+    "lod0": np.eye(2) * 1.0,                            # rho = 1: lod 0 without the clamp (up to rounding)
+    "lod0.5": np.eye(2) * 2.0 ** 0.5,
+    "lod1": np.eye(2) * 2.0,                            # fl = 0: a pure level
+    "lod2": np.eye(2) * 4.0,
+    "lod2.37": np.eye(2) * 2.0 ** 2.37,
+    "top": lambda L: np.eye(2) * 2.0 ** (L - 1),        # the top level, reached exactly
+    "beyond": lambda L: np.eye(2) * 2.0 ** (L + 2),     # 8 x beyond it: lod clamped from above
+    "aniso_x": np.diag([4.0, 0.5]),                     # rho is the larger axis, in both orders
+    "aniso_y": np.diag([0.5, 4.0]),
+    "sheared": np.array([[1.5, 2.0], [-2.5, 0.5]]),     # |J[:, 0]| = 2.92 > |J[:, 1]| = 2.06
+    "edges_u": np.eye(2) * 0.5,                         # pixel centres ON texel edges (x = k - 0.5) and centres (x = k), through u = 0
+    "edges_v": np.eye(2) * 0.5,                         # the same in v
+    "repeats": "uv",                                    # u and v from -3.25 to 2.5 across the card: negative, above 1, several repeats
+}
+
+
+def filter_texture(name):
+    """RGB uint8 [th,tw,3] of FILTER_TEXTURES"""
+    rng = np.random.default_rng(4000 + FILTER_TEXTURES.index(name))
+    noise = lambda th, tw: rng.integers(0, 256, (th, tw, 3), dtype=np.uint8)
+    if name == "noise":
+        return noise(64, 128)                           # the largest gradients: a one-texel or one-level slip moves bytes by tens
+    if name == "noise40x24":
+        return noise(40, 24)                            # 40 x 24 -> ... -> 5 x 3 -> 2 x 1: an odd size drops its last row / column
+    if name == "noise5x3":
+        return noise(5, 3)
+    if name == "row1x7":
+        return noise(1, 7)                              # one texel high while the width still halves
+    if name == "col7x1":
+        return noise(7, 1)
+    if name == "one":
+        return noise(1, 1)
+    if name == "corners":                               # black with one lit texel in each corner: a wrap that clamps shows at once
+        t = np.zeros((16, 16, 3), np.uint8)             # (white, red, green, blue: four EQUAL corners would look the same wrapped or clamped)
+        t[[0, 0, -1, -1], [0, -1, 0, -1]] = [(255, 255, 255), (255, 0, 0), (0, 255, 0), (0, 0, 255)]
+        return t
+    if name == "channels":                              # other noise in every channel, in disjoint ranges: a permutation shows
+        return np.stack([rng.integers(lo, lo + 80, (32, 32)) for lo in (0, 88, 176)], -1).astype(np.uint8)
+    raise ValueError(name)
+
+
+def _levels_of(th, tw):
+    return int(np.floor(np.log2(max(th, tw)))) + 1
+
+
+def card_jacobian(card, tex_hw):
+    """J (base texels per pixel) of card `card` on a th x tw texture, and the closed-form lod"""
+    th, tw = tex_hw
+    L = _levels_of(th, tw)
+    J = CARDS[card]
+    if callable(J):
+        J = J(L)
+    elif isinstance(J, str):
+        l, t, r, b = CARD_RECT
+        J = np.diag([(2.5 + 3.25) * tw / (r - l), (2.5 + 3.25) * th / (b - t)])
+    rho = max(np.hypot(*J[:, 0]), np.hypot(*J[:, 1]))
+    return J, float(min(max(np.log2(rho), 0.0), L - 1))
+
+
+def _card_texels(card, tex_hw, pts):
+    """texel coordinates (u tw, v th) of the image points pts [...,2] under the card's map"""
+    th, tw = tex_hw
+    J, _ = card_jacobian(card, tex_hw)
+    if isinstance(CARDS[card], str):
+        l, t, r, b = CARD_RECT
+        return np.stack([-3.25 * tw + J[0, 0] * (pts[..., 0] - l), -3.25 * th + J[1, 1] * (pts[..., 1] - t)], -1)
+    return (pts - np.asarray(CARD_ORIGINS.get(card, CARD_ORIGIN))) @ J.T
+
+
+def card_allows(card, tex_hw):
+    """the range rule: |u w_l|, |v h_l| < 512 at the sampled level l = floor(lod), where the rounding of x = u w_l - 0.5 (an ulp of
+    its magnitude, times the texel differences) still leaves most pixels a single admissible byte"""
+    l, t, r, b = CARD_RECT
+    tex = np.abs(_card_texels(card, tex_hw, np.array([[l, t], [r, t], [l, b], [r, b]])))
+    _, lod = card_jacobian(card, tex_hw)
+    return bool(tex.max() / 2.0 ** np.floor(lod) < 512)
+
+
+def card_pose():
+    P = np.eye(4)
+    P[:3, 3] = CARD_T
+    return P
+
+
+def _card_pack(pts_obj, uv):
+    """3 x 3 grid of points -> 8 triangles with their own vertices (both diagonals occur)"""
+    quads = [(0, 1, 4, 3), (1, 2, 5, 4), (3, 4, 7, 6), (4, 5, 8, 7)]
+    idx = []
+    for k, (a, b, c, d) in enumerate(quads):
+        idx += [a, b, c, a, c, d] if k % 2 == 0 else [a, b, d, b, c, d]
+    idx = np.array(idx)
+    n = len(idx)
+    return dict(vertices=pts_obj[idx].astype(np.float32), faces=np.arange(n).reshape(-1, 3).astype(np.int32), uv=uv[idx].astype(np.float64),
+                colors=np.full((n, 3), 200, np.uint8), normals=np.tile(np.array([0, 0, -1], np.float32), (n, 1)))
+
+
+def card(name, tex_hw):
+    """mesh dict (vertices, faces, uv, colors, normals) of card `name` for a th x tw texture, seen under card_pose() with SOUP_FRAME_K"""
+    th, tw = tex_hw
+    K, T = SOUP_FRAME_K, np.asarray(CARD_T)
+    gx, gy = np.meshgrid(CARD_GRID_X, CARD_GRID_Y)
+    pts = np.stack([gx.ravel(), gy.ravel()], 1)
+    obj = np.stack([(pts[:, 0] - K[0, 2]) * T[2] / K[0, 0] - T[0], (pts[:, 1] - K[1, 2]) * T[2] / K[1, 1] - T[1], np.zeros(9)], 1)
+    return _card_pack(obj, _card_texels(name, tex_hw, pts) / np.array([tw, th], np.float64))
+
+
+def filter_cases():
+    """(card, texture, kd index) of every card on every texture its map allows, under every Kd"""
+    return [(c, t, k) for c in CARDS for t in FILTER_TEXTURES if card_allows(c, filter_texture(t).shape[:2]) for k in range(len(FILTER_KDS))]
+
+
+def card_tilted():
+    """A card rotated about both image axes, z from about 0.2 to 0.5 m: the level of detail varies continuously over several
+    floor(lod) transitions.  Returns (mesh dict for the 64 x 128 noise texture, pose)."""
+    from scipy.spatial.transform import Rotation
+    P = np.eye(4)
+    P[:3, :3] = Rotation.from_euler("xy", [35, 50], degrees=True).as_matrix()
+    P[:3, 3] = (0.0, 0.005, 0.35)
+    gx, gy = np.meshgrid([-0.15, 0.01, 0.15], [-0.035, 0.004, 0.035])
+    obj = np.stack([gx.ravel(), gy.ravel(), np.zeros(9)], 1)
+    uv = np.stack([obj[:, 0] / 0.15 * 1.9 + 0.13, obj[:, 1] / 0.035 * 0.9 + 0.41], 1)
+    return _card_pack(obj, uv), P
+
+
+def soup_horizon():
+    """Three triangles in planes that pass within millimetres of the camera centre, from 0.15 m to beyond the far plane: each shows as
+    a wedge that ends at the plane's horizon (1 / w = 0) where the far plane cuts it.  The 1 / w plane falls by more than the far
+    plane's 0.5 / m within one pixel there, so covered pixels have a quad corner ACROSS w = 0 (extrapolated uv that mean nothing: the
+    level of detail must survive them), and the level of detail runs through every level of the 64 x 128 noise texture on the way.
+    (soup_frame() has no such pixel.)  Returns (mesh dict, pose)."""
+    P = np.eye(4)
+    P[:3, 3] = (0.0, 0.0, 0.5)
+    tris = []
+    for d, ang in ((0.005, 0.0), (-0.004, 0.5), (0.006, -0.9)):              # the plane n . (x, y) = d of the camera
+        n = np.array([np.sin(ang), np.cos(ang)])
+        along = np.array([n[1], -n[0]])
+        tris.append([np.r_[d * n + l * along, z] - P[:3, 3] for z, l in ((0.15, 0.0), (2.6, -0.5), (2.6, 0.5))])
+    m = _soup_pack(np.array(tris), np.random.default_rng(2100))
+    v = m["vertices"].astype(np.float64)
+    m["uv"] = np.stack([0.5 + 1.5 * v[:, 0] + 0.2 * v[:, 2], 0.3 + 1.2 * v[:, 1] + 0.3 * v[:, 2]], 1)
+    return m, P

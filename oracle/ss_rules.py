@@ -405,19 +405,24 @@ def depth_mm(zbuf, A, B, numpy_rule="numpy2"):
         return (distance * f32(1000)).astype(f32).astype(np.uint16)
 
 
-def render_frame(vertices, colors01, faces, ob2cam, K, W, H, uv=None, texture=None, kd=(1.0, 1.0, 1.0), near=NEAR, far=FAR):
-    """The second renderer's GL work (oracle/swiftshader_gl.py: render_frame_gl, this repo's statement of pyrender's scene) on this
-    model: coverage, depth and vertex colours by the rules above (exact); the texture FILTER is plain float32 arithmetic
-    (raster_oracle's bilinear / trilinear with the level of detail from the 2 x 2 quad's differences) -- the implementation
-    filters in 16-bit fixed point, so textured colours agree to a few / 255 only.  rgb uint8 [H,W,3], depth uint16 [H,W]."""
-    from . import raster_oracle as R
+def frame_pv(ob2cam, K, W, H, near=NEAR, far=FAR):
+    """projection . view of the second renderer's camera (IntrinsicsCamera at W x H, cvcam_in_glcam . ob_in_cvcam), float32"""
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     P = np.zeros((4, 4))
     P[0, 0] = 2.0 * fx / W; P[1, 1] = 2.0 * fy / H
     P[0, 2] = 1.0 - 2.0 * cx / W; P[1, 2] = 2.0 * cy / H - 1.0
     P[2, 2] = (far + near) / (near - far); P[2, 3] = 2 * far * near / (near - far); P[3, 2] = -1.0
     V = np.diag([1.0, -1.0, -1.0, 1.0]).dot(np.asarray(ob2cam, np.float64))
-    PV = (P @ V).astype(np.float32)
+    return (P @ V).astype(np.float32)
+
+
+def render_frame(vertices, colors01, faces, ob2cam, K, W, H, uv=None, texture=None, kd=(1.0, 1.0, 1.0), near=NEAR, far=FAR):
+    """The second renderer's GL work (oracle/swiftshader_gl.py: render_frame_gl, this repo's statement of pyrender's scene) on this
+    model: coverage, depth and vertex colours by the rules above (exact); the texture FILTER is plain float32 arithmetic
+    (raster_oracle's bilinear / trilinear with the level of detail from the 2 x 2 quad's differences) -- the implementation
+    filters in 16-bit fixed point, so textured colours agree to a few / 255 only.  rgb uint8 [H,W,3], depth uint16 [H,W]."""
+    from . import raster_oracle as R
+    PV = frame_pv(ob2cam, K, W, H, near, far)
     v32 = np.asarray(vertices, np.float32)
     pv = project(clip_positions(v32, PV), W, H)
     zbuf, owner, setups = rasterize(pv, faces, W, H)

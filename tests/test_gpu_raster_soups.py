@@ -169,6 +169,9 @@ def test_full_frame_route_textured(se3, eng, frame_oracle):
           % (d.max(), np.median(d), (d > 6).mean()))
     assert np.median(d) <= 1 and (d > 6).mean() < 0.02
     assert len(np.unique(rgb[want_d > 0].reshape(-1, 3), axis=0)) > 500                   # (a texture is really sampled)
+    # ... and per pixel: every byte inside the range the float64 statement of the filter admits (oracle/texture_oracle.py)
+    from oracle import texture_oracle as T
+    T.check(rgb, T.Expect(m["vertices"], m["faces"], m["uv"], m["texture"], m["kd"], P, K, W, H), "full frame, textured")
 
 
 RECTS = [("inside", (40, 30, 121, 95)), ("across the right and bottom edges' triangles", (97, 61, 160, 120)),

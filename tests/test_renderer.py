@@ -168,6 +168,14 @@ def test_hip_full_frame_renderer_vs_pyrender_oracle(se3, tmp_path):
         u = K[0, 0] * P[0, 3] / P[2, 3] + K[0, 2]; v = K[1, 1] * P[1, 3] / P[2, 3] + K[1, 2]
         assert abs(xs.mean() + 0.5 - u) < 1.0 and abs(ys.mean() + 0.5 - v) < 1.0
         assert 450 - 51 <= depth[depth > 0].min() <= 450 - 45
+        if textured:
+            # the same model built from the dict (the fixture's own vertex numbering): per pixel, every byte inside the range the
+            # float64 statement of the filter admits (oracle/texture_oracle.py)
+            from oracle import texture_oracle as T
+            ren = se3.HipRenderer(eng, dict(mesh, colors=R.icosphere(2, 0.05, 3)["colors"]), mode="pyrender", frame_size=(H, W))
+            rgb2, depth2 = ren.render_frame(P, K)
+            assert np.array_equal(depth2, odepth) and (rgb2[depth2 == 0] == 0).all()
+            T.check(rgb2, T.Expect(mesh["vertices"], mesh["faces"], mesh["uv"], mesh["texture"], mesh["kd"], P, K, W, H), "textured sphere")
 
 
 @pytest.mark.gpu
