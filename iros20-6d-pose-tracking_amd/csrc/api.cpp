@@ -13,6 +13,7 @@
 
 #include "se3tn_internal.h"
 #include "tex_pyramid.h"
+#include "track_plan.h"
 #include "weights.h"
 
 using namespace se3tn;
@@ -113,15 +114,17 @@ struct se3tn_ctx {
   // se3tn_on_track: pinned host staging [pose 128 B | frame window rgb | depth], its device mirror, device outputs and their pinned copy
   uint8_t* trk_host = nullptr; uint8_t* trk_dev = nullptr; size_t trk_bytes = 0;
   uint8_t* trk_out_dev = nullptr; uint8_t* trk_out_host = nullptr;   // ONE mapped pinned block: device address | host address
-  // se3tn_on_track_batch: instance table (pinned host + device), z-buffers, image A stack, staging, outputs -- grown at first use / larger n
+  // se3tn_on_track_batch / _objects: instance table (pinned host + device, fill_instance), z-buffers, image A stack, staging (the
+  // TrackWindows of track_plan.h, upload_staged), outputs (read_back_tracks) -- grown at first use / larger n (reserve_track_batch)
   int tb_cap = 0;
   size_t tb_stage_bytes = 0;
   RasterInstance *tb_inst_host = nullptr, *tb_inst_dev = nullptr;   // (room for a RasterMaterial per instance behind the n instances)
   unsigned long long* tb_zbuf = nullptr;
   uint8_t *tb_rgbA = nullptr, *tb_stage_host = nullptr, *tb_stage_dev = nullptr, *tb_out_host = nullptr, *tb_out_dev = nullptr;
   uint16_t* tb_depthA = nullptr;
-  // SE3TN_ROUTE_FRAME meshes (se3tn_on_track, se3tn_on_track_batch): the rendered rectangles [64 zero bytes | rgb of every pair | depth of
-  // every pair] and, for the batch, their z-buffers -- fr_px pixels in all (pairs x the largest rectangle of the call), grown at need.
+  // SE3TN_ROUTE_FRAME meshes (se3tn_on_track, se3tn_on_track_batch, _objects): the rendered rectangles [64 zero bytes | rgb of every pair |
+  // depth of every pair] and, for n pairs, their z-buffers -- fr_px pixels in all (pairs x the largest rectangle of the call), grown at need
+  // (reserve_frame_rects).
   // The 64 bytes in front are zeroed at allocation and never written: the 1 x 1 image A of a window that misses the frame
   uint8_t* fr_sub = nullptr;
   unsigned long long* fr_zbuf = nullptr;
@@ -1211,14 +1214,6 @@ static void frame_uniforms(RasterArgs& a, const se3tn_mesh* m, const double ob_i
 static void rect_to_scissor(const int32_t rect[4], int H, int s[4]) {
   s[0] = rect[0]; s[1] = H - rect[3]; s[2] = rect[2]; s[3] = H - rect[1];
 }
-// crop window (left, top, right, bottom) intersected with the frame; false: they do not meet (rect = {0, 0, 0, 0})
-static bool window_rect(const int32_t win[4], int H, int W, int32_t rect[4]) {
-  const int32_t x0 = win[0] > 0 ? win[0] : 0, x1 = win[2] < W ? win[2] : W;
-  const int32_t y0 = win[1] > 0 ? win[1] : 0, y1 = win[3] < H ? win[3] : H;
-  if (x1 <= x0 || y1 <= y0) { rect[0] = rect[1] = rect[2] = rect[3] = 0; return false; }
-  rect[0] = x0; rect[1] = y0; rect[2] = x1; rect[3] = y1;
-  return true;
-}
 // sub-images and z-buffers of the SE3TN_ROUTE_FRAME calls for `px` pixels in all (never inside a capture: the callers are synchronous)
 static int reserve_frame_route(se3tn_ctx* c, size_t px) {
   if (px <= c->fr_px) return SE3TN_OK;
@@ -1265,29 +1260,6 @@ int se3tn_render_frame_rect(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[
   return SE3TN_OK;
 }
 
-// np.round: round half to even
-static double round_half_even(double x) { return std::nearbyint(x); }
-
-// Utils.py:302-316 compute_bbox with scale (1000, sy, 1000) -> (left, top, right, bottom) = min / max of the (u, v) corners
-// Returns false when a corner is not a finite value inside the int32 range (z == 0, NaN, a pose at the camera centre): the
-// float -> int cast would be undefined behaviour.
-static bool bbox_window(const double pose[16], const double K[9], double width, double sy, int32_t win[4], int32_t vu[8]) {
-  const double x = pose[3] * 1000, y = pose[7] * sy, z = pose[11] * 1000, off = width / 2;
-  const double px[4] = {x - off, x - off, x + off, x + off};
-  const double py[4] = {y - off, y + off, y - off, y + off};
-  int32_t umin = INT32_MAX, umax = INT32_MIN, vmin = INT32_MAX, vmax = INT32_MIN;
-  for (int i = 0; i < 4; ++i) {
-    const double uf = round_half_even(px[i] * K[0] / z + K[2]), vf = round_half_even(py[i] * K[4] / z + K[5]);
-    if (!(std::fabs(uf) < 1.0e9) || !(std::fabs(vf) < 1.0e9)) return false;   // (also false for NaN)
-    const int32_t u = (int32_t)uf, v = (int32_t)vf;
-    if (vu) { vu[2 * i] = v; vu[2 * i + 1] = u; }
-    umin = u < umin ? u : umin; umax = u > umax ? u : umax;
-    vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
-  }
-  win[0] = umin; win[1] = vmin; win[2] = umax; win[3] = vmax;
-  return true;
-}
-
 static int fill_depth_rect_enqueue(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
                                    const int32_t comp[4], uint16_t* out_full, const int32_t sub[4], uint16_t* out_sub, hipStream_t st);
 
@@ -1299,6 +1271,16 @@ struct LiveFrame {
   int extrapolate, blur;
   uint16_t* depth_filled;   // device [H,W] or nullptr
 };
+
+// From the upload of a staged (pinned) buffer on, that buffer is travelling: the next call would overwrite it under the copy, so every
+// error return synchronises the copy stream first.  One of these per body, armed at the upload; done() once the launch stream (which
+// waits for the copy) has been waited for
+struct StagedUpload {
+  hipStream_t copy;
+  ~StagedUpload() { if (copy) (void)hipStreamSynchronize(copy); }
+  void done() { copy = nullptr; }
+};
+static int upload_staged(se3tn_ctx* c, uint8_t* dev, const uint8_t* host, size_t bytes, hipStream_t st);
 
 // se3tn_on_track (live == nullptr) and se3tn_on_track_live: one body, two staging steps
 static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], const double K[9], double object_width_mm,
@@ -1353,129 +1335,92 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
     HIPCHK(hipStreamCreateWithFlags(&c->trk_copy_stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&c->trk_copy_event, hipEventDisableTiming));
   }
-  // predict.py:231-235: bbox of the previous pose (host float64, round half to even) -> crop window of image B;
-  // :201-206: the same with the y axis flipped -> the renderer's window
-  int32_t winB[4], winA[4], vu[8];
-  // an object at or behind the camera plane has no crop window (the reference's compute_bbox divides by z and its crop comes out
-  // empty or mirrored; predict.py never gets there): refuse instead of running the frame
-  if (!(prev_pose[11] > 0) || !bbox_window(prev_pose, K, object_width_mm, 1000.0, winB, vu) ||
-      !bbox_window(prev_pose, K, object_width_mm, -1000.0, winA, nullptr))
-    return fail(SE3TN_E_ARG, std::string(who) + ": pose is not in front of the camera (z <= 0 or not finite)");
-  if (winB[2] <= winB[0] || winB[3] <= winB[1]) return fail(SE3TN_E_ARG, std::string(who) + ": empty crop window (pose behind the camera?)");
+  // the windows of the pair and the part of the frame that travels (track_plan.h; host float64, round half to even), behind the pose
+  TrackWindow w;
+  size_t planned = 256;
+  const PlanStatus ps = plan_window(prev_pose, K, object_width_mm, H, W, planned, w);
+  if (ps == PlanStatus::NOT_IN_FRONT) return fail(SE3TN_E_ARG, std::string(who) + ": pose is not in front of the camera (z <= 0 or not finite)");
+  if (ps == PlanStatus::EMPTY_WINDOW) return fail(SE3TN_E_ARG, std::string(who) + ": empty crop window (pose behind the camera?)");
   // image A first: its four launches run on the device while the host stages the frame
   uint8_t* rA = rgbA_dev ? rgbA_dev : c->trk_rgbA;
   uint16_t* dA = depthA_dev ? depthA_dev : c->trk_depthA;
   const bool frame_route = m->route == SE3TN_ROUTE_FRAME;
-  int32_t rectA[4] = {0, 0, 0, 0};
-  bool missA = false;
   size_t subA_d_off = 0;   // frame route: offset of the sub-image's depth in c->fr_sub
   if (frame_route) {
     // predict.py:209-213: the full-frame render cropped with the SAME window as the camera frame -- only the rectangle of the frame
     // the window covers is rendered (every byte of it as se3tn_render_frame gives it)
     if (H > 2048) return fail(SE3TN_E_ARG, std::string(who) + ": frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
     if (int rc = reserve_frame_route(c, (size_t)H * W)) return rc;
-    missA = !window_rect(winB, H, W, rectA);
-    if (!missA) {
-      const size_t px = (size_t)(rectA[2] - rectA[0]) * (size_t)(rectA[3] - rectA[1]);
-      subA_d_off = 64 + ((px * 3 + 63) & ~(size_t)63);
+    if (!w.miss) {
+      const size_t px = (size_t)w.sw * w.sh;
+      subA_d_off = 64 + a64(px * 3);
       RasterArgs ra{};
       raster_common(ra, c, m, c->fr_sub + 64, (uint16_t*)(c->fr_sub + subA_d_off));
       ra.zbuf = c->fr_zbuf;
       frame_uniforms(ra, m, prev_pose, K, W, H);
+      const int32_t rectA[4] = {w.x0, w.y0, w.x0 + w.sw, w.y0 + w.sh};
       int s[4];
       rect_to_scissor(rectA, H, s);
       ra.scissor = 1; ra.sx0 = s[0]; ra.sy0 = s[1]; ra.sx1 = s[2]; ra.sy1 = s[3]; ra.spx = (int)px;
       HIPCHK(launch_raster(ra, st));
     }
-  } else if (int rc = se3tn_render(c, m, prev_pose, K, winA, rA, dA, stream)) {
+  } else if (int rc = se3tn_render(c, m, prev_pose, K, w.winA, rA, dA, stream)) {
     return rc;
   }
   const double t1 = trace ? now() : 0.0;
   // only the part of the frame the window covers travels: rows / columns [y0, y1) x [x0, x1) into pinned memory, ONE copy
-  // with the pose in front, on a copy stream of its own (beside the rasteriser, not behind it).  crop_bbox's canvas is zero
-  // outside the frame (Utils.py:327-342): outside this sub-image too.
-  int x0 = winB[0] > 0 ? winB[0] : 0, x1 = winB[2] < W ? winB[2] : W;
-  int y0 = winB[1] > 0 ? winB[1] : 0, y1 = winB[3] < H ? winB[3] : H;
-  int sw = x1 - x0, sh = y1 - y0;
+  // with the pose in front, on a copy stream of its own (beside the rasteriser, not behind it)
   uint8_t* hp = c->trk_host;
   std::memcpy(hp, prev_pose, 128);
-  uint8_t* h_rgb = hp + 256;
-  const bool miss = sw <= 0 || sh <= 0;   // the window misses the frame: a 1 x 1 zero sub-image it does not touch
-  if (miss) { sw = sh = 1; x0 = winB[0] - 8; y0 = winB[1] - 8; }
-  size_t d_off = 256 + (((size_t)sw * sh * 3 + 63) & ~(size_t)63);   // image B's depth on the device
   size_t bytes, raw_off = 0;
-  const bool fill = live && (!miss || live->depth_filled);
+  const bool fill = live && (!w.miss || live->depth_filled);
   if (live) {
     // window rgb with the channel order made RGB on the way | one zero pixel (a window that misses the frame) | the WHOLE raw depth frame;
     // the window's filled depth is written behind it by the rectangle pass below
-    const size_t z_off = d_off;
+    const size_t z_off = w.off_d;
     raw_off = z_off + 64;
-    if (miss) {
-      std::memset(h_rgb, 0, 3);
-    } else if (live->color_order == SE3TN_COLOR_BGR) {
-      for (int y = 0; y < sh; ++y) {
-        const uint8_t* src = rgb + ((size_t)(y0 + y) * W + x0) * 3;
-        uint8_t* dst = h_rgb + (size_t)y * sw * 3;
-        for (int x = 0; x < sw; ++x, src += 3, dst += 3) { dst[0] = src[2]; dst[1] = src[1]; dst[2] = src[0]; }
+    if (!w.miss && live->color_order == SE3TN_COLOR_BGR) {
+      for (int y = 0; y < w.sh; ++y) {
+        const uint8_t* src = rgb + ((size_t)(w.y0 + y) * W + w.x0) * 3;
+        uint8_t* dst = hp + w.off_rgb + (size_t)y * w.sw * 3;
+        for (int x = 0; x < w.sw; ++x, src += 3, dst += 3) { dst[0] = src[2]; dst[1] = src[1]; dst[2] = src[0]; }
       }
     } else {
-      for (int y = 0; y < sh; ++y) std::memcpy(h_rgb + (size_t)y * sw * 3, rgb + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
+      stage_window(w, rgb, nullptr, W, hp);
     }
     std::memset(hp + z_off, 0, 2);
     if (fill) std::memcpy(hp + raw_off, depth, fpx * 2);
     bytes = fill ? raw_off + fpx * 2 : raw_off;
-    d_off = miss ? z_off : a64(raw_off + fpx * 2);
+    w.off_d = w.miss ? z_off : a64(raw_off + fpx * 2);   // image B's depth on the device
   } else {
-    if (miss) {
-      std::memset(h_rgb, 0, 3);
-      std::memset(hp + d_off, 0, 2);
-    } else {
-      for (int y = 0; y < sh; ++y) {
-        std::memcpy(h_rgb + (size_t)y * sw * 3, rgb + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
-        std::memcpy(hp + d_off + (size_t)y * sw * 2, depth + (size_t)(y0 + y) * W + x0, (size_t)sw * 2);
-      }
-    }
-    bytes = d_off + (size_t)sw * sh * 2;
+    stage_window(w, rgb, depth, W, hp);
+    bytes = w.off_d + (size_t)w.sw * w.sh * 2;
   }
-  HIPCHK(hipMemcpyAsync(c->trk_dev, hp, bytes, hipMemcpyHostToDevice, c->trk_copy_stream));
-  HIPCHK(hipEventRecord(c->trk_copy_event, c->trk_copy_stream));
-  HIPCHK(hipStreamWaitEvent(st, c->trk_copy_event, 0));
+  StagedUpload up{c->trk_copy_stream};
+  if (int rc = upload_staged(c, c->trk_dev, hp, bytes, st)) return rc;
   const double t2 = trace ? now() : 0.0;
   if (fill) {   // predict_ros.py:38-41 for the pixels the crop reads (the whole frame when the caller wants it)
-    const int32_t whole[4] = {0, 0, W, H}, sub[4] = {x0, y0, x1, y1};
+    const int32_t whole[4] = {0, 0, W, H}, sub[4] = {w.x0, w.y0, w.x0 + w.sw, w.y0 + w.sh};
     const int rc = fill_depth_rect_enqueue(c, (const uint16_t*)(c->trk_dev + raw_off), H, W, live->max_depth_m,
                                            live->extrapolate, live->blur, live->depth_filled ? whole : sub, live->depth_filled, sub,
-                                           miss ? nullptr : (uint16_t*)(c->trk_dev + d_off), st);
-    if (rc) { (void)hipStreamSynchronize(c->trk_copy_stream); return rc; }
+                                           w.miss ? nullptr : (uint16_t*)(c->trk_dev + w.off_d), st);
+    if (rc) return rc;
   }
   const double t2f = trace ? now() : 0.0;
   // image A and image B in ONE preprocess launch (data_augmentation.py:124-189 for both, with poseA's z)
   CropArgs a;
   std::memcpy(a.mean, c->mean, sizeof(a.mean));
   std::memcpy(a.stdv, c->stdv, sizeof(a.stdv));
-  const double z_mm = prev_pose[11] * 1000;
-  se3tn_crop& ca = a.c[0];
-  ca.rgb = rA; ca.depth = dA; ca.H = RES; ca.W = RES; ca.left = 0; ca.top = 0; ca.right = RES; ca.bottom = RES;
-  ca.z_offset_mm = z_mm; ca.stats = 0; ca._pad = 0;
-  if (frame_route) {
-    // image A = the rendered rectangle with the window shifted by its origin (a window that misses the frame: the 1 x 1 zero image in
-    // front of the buffer, which the shifted window does not touch); the same launch writes its raw crop = Tracker.render_window
-    const int ox = missA ? winB[0] - 8 : rectA[0], oy = missA ? winB[1] - 8 : rectA[1];
-    ca.rgb = missA ? c->fr_sub : c->fr_sub + 64;
-    ca.depth = missA ? (const uint16_t*)(c->fr_sub + 32) : (const uint16_t*)(c->fr_sub + subA_d_off);
-    ca.H = missA ? 1 : rectA[3] - rectA[1]; ca.W = missA ? 1 : rectA[2] - rectA[0];
-    ca.left = winB[0] - ox; ca.top = winB[1] - oy; ca.right = winB[2] - ox; ca.bottom = winB[3] - oy;
-    if (rgbA_dev || depthA_dev) { a.raw_rgb = rA; a.raw_depth = dA; }   // (the one not given goes to the internal buffer)
-  }
-  se3tn_crop& cb = a.c[1];
-  cb.rgb = c->trk_dev + 256; cb.depth = (const uint16_t*)(c->trk_dev + d_off); cb.H = sh; cb.W = sw;
-  cb.left = winB[0] - x0; cb.top = winB[1] - y0; cb.right = winB[2] - x0; cb.bottom = winB[3] - y0;
-  cb.z_offset_mm = z_mm; cb.stats = 1; cb._pad = 0;
+  // frame route: image A = the rendered rectangle (a window that misses the frame: the 1 x 1 zero image in front of the buffer); the same
+  // launch writes its raw crop = Tracker.render_window (the one not given goes to the internal buffer)
+  const ImageA imgA = frame_route ? ImageA{c->fr_sub + 64, (const uint16_t*)(c->fr_sub + subA_d_off), c->fr_sub} : ImageA{rA, dA, nullptr};
+  crop_pair(w, prev_pose[11] * 1000, imgA, c->trk_dev, a.c[0], a.c[1]);
+  if (frame_route && (rgbA_dev || depthA_dev)) { a.raw_rgb = rA; a.raw_depth = dA; }
   a.n = 2; a.n_first = 1; a.out = c->inA; a.out2 = c->inB; a.padded = 1;
   a.split = c->prec == SE3TN_PREC_F16X3 ? 1 : 0;
   a.overflow = c->overflow; a.offset_rule = c->offset_rule;
   c->in_split[0] = c->in_split[1] = a.split;
-  if (const hipError_t e = launch_preprocess(a, st)) { (void)hipStreamSynchronize(c->trk_copy_stream); return hipfail(e, "launch_preprocess"); }
+  if (const hipError_t e = launch_preprocess(a, st)) return hipfail(e, "launch_preprocess");
   const double t3 = trace ? now() : 0.0;
   float* trans_d = (float*)(c->trk_out_dev + 128);
   float* rot_d = (float*)(c->trk_out_dev + 144);
@@ -1486,10 +1431,7 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   c->tail_flag = poll ? flag_d : nullptr;
   const int rc_inf = se3tn_infer(c, c->inA, c->inB, 1, SE3TN_NHWC, trans_d, rot_d, (const double*)c->trk_dev, (double*)c->trk_out_dev, stream);
   c->tail_flag = nullptr;
-  if (rc_inf) {   // the staged frame is still travelling: the next call would overwrite the pinned buffer under the copy
-    (void)hipStreamSynchronize(c->trk_copy_stream);
-    return rc_inf;
-  }
+  if (rc_inf) return rc_inf;
   const double t4 = trace ? now() : 0.0;
   bool seen = false;
   if (poll) {   // 5 ms of polling covers every healthy frame; anything slower (or a fault) falls through to the stream wait
@@ -1500,6 +1442,7 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
     }
   }
   if (!seen) HIPCHK(hipStreamSynchronize(st));
+  up.done();
   if (trace) {
     const double t5 = now();
     const double d[7] = {t1 - t0, t2 - t1, t3 - t2f, t4 - t3, t5 - t4, t5 - t0, t2f - t2};
@@ -1518,7 +1461,7 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   std::memcpy(pose_out, c->trk_out_host, 128);
   if (trans_out) std::memcpy(trans_out, c->trk_out_host + 128, 12);
   if (rot_out) std::memcpy(rot_out, c->trk_out_host + 144, 12);
-  if (bbox_vu) std::memcpy(bbox_vu, vu, sizeof(vu));
+  if (bbox_vu) std::memcpy(bbox_vu, w.vu, sizeof(w.vu));
   return SE3TN_OK;
 }
 
@@ -1589,6 +1532,70 @@ static int reserve_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, size_t stage_
   return SE3TN_OK;
 }
 
+// SE3TN_ROUTE_FRAME (predict.py:209-213): per pair the rectangle of the full-frame render its crop window covers -- the same rectangle as
+// the staged part of the camera frame.  Z-buffers and sub-images are sized by the largest rectangle of the call (maxpx; 0: every window
+// misses the frame); fr_d_off: where the depth sub-images start in c->fr_sub
+static int reserve_frame_rects(se3tn_ctx* c, int n, const TrackWindow* windows, int H, int W, size_t* maxpx, size_t* fr_d_off) {
+  size_t mx = 0;
+  for (int i = 0; i < n; ++i)
+    if (!windows[i].miss) mx = std::max(mx, (size_t)windows[i].sw * (size_t)windows[i].sh);
+  const size_t need = mx ? (size_t)n * mx : 1, cap = (size_t)n * H * W;
+  // windows change from frame to frame: grow with half as much again in hand (never past n whole frames)
+  if (need > c->fr_px)
+    if (int rc = reserve_frame_route(c, std::max(need, std::min(need + need / 2, cap)))) return rc;
+  *maxpx = mx;
+  *fr_d_off = 64 + (((size_t)n * mx * 3 + 63) & ~(size_t)63);
+  return SE3TN_OK;
+}
+
+// image A of pair i of n: its 176 x 176 render in the stack rA / dA, or (frame route) its rectangle in c->fr_sub
+static ImageA image_a(const se3tn_ctx* c, bool frame_route, int i, const uint8_t* rA, const uint16_t* dA, size_t maxpx, size_t fr_d_off) {
+  if (frame_route) return ImageA{c->fr_sub + 64 + (size_t)i * maxpx * 3, (const uint16_t*)(c->fr_sub + fr_d_off) + (size_t)i * maxpx, c->fr_sub};
+  return ImageA{rA + (size_t)i * RES * RES * 3, dA + (size_t)i * RES * RES, nullptr};
+}
+
+// One record of the rasteriser's instance table: the uniforms of `pose` and, on the frame route, the pair's rectangle as a scissor
+// (mesh pointers and material: se3tn_on_track_objects adds them).  false: singular pose (window route)
+static bool fill_instance(RasterInstance& I, bool frame_route, const se3tn_mesh* m, const double pose[16], const double K[9], int W, int H,
+                          const TrackWindow& t) {
+  RasterArgs one{};
+  if (frame_route) {
+    frame_uniforms(one, m, pose, K, W, H);
+    const int32_t r[4] = {t.x0, t.y0, t.x0 + t.sw, t.y0 + t.sh};
+    if (!t.miss) rect_to_scissor(r, H, I.rect);
+    // the window misses the frame: an empty rectangle.  The instance still runs its vertex / triangle / queue workgroups (one grid
+    // for all instances) and writes nothing: a few microseconds wasted on a case a tracker does not stay in
+    else I.rect[0] = I.rect[1] = I.rect[2] = I.rect[3] = 0;
+  } else if (!vispy_uniforms(one, pose, K, t.winA)) {
+    return false;
+  }
+  std::memcpy(I.PV, one.PV, sizeof(I.PV));
+  std::memcpy(I.light, one.light, sizeof(I.light));
+  I._pad = 0.f; I.dA = one.dA; I.dB = one.dB;
+  return true;
+}
+
+// the staged (pinned) buffer goes up in ONE copy on the copy stream (beside the rasteriser, not behind it); `st` waits for it
+static int upload_staged(se3tn_ctx* c, uint8_t* dev, const uint8_t* host, size_t bytes, hipStream_t st) {
+  HIPCHK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->trk_copy_stream));
+  HIPCHK(hipEventRecord(c->trk_copy_event, c->trk_copy_stream));
+  HIPCHK(hipStreamWaitEvent(st, c->trk_copy_event, 0));
+  return SE3TN_OK;
+}
+
+// [n poses | n trans | n rot] of c->tb_out_dev back to the caller (waits for `st`), and the bboxes of the windows
+static int read_back_tracks(se3tn_ctx* c, int n, hipStream_t st, double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu,
+                            const TrackWindow* windows) {
+  HIPCHK(hipMemcpyAsync(c->tb_out_host, c->tb_out_dev, (size_t)n * 152, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(pose_out, c->tb_out_host, (size_t)n * 128);
+  if (trans_out) std::memcpy(trans_out, c->tb_out_host + (size_t)n * 128, (size_t)n * 12);
+  if (rot_out) std::memcpy(rot_out, c->tb_out_host + (size_t)n * 140, (size_t)n * 12);
+  if (bbox_vu)
+    for (int i = 0; i < n; ++i) std::memcpy(bbox_vu + 8 * (size_t)i, windows[i].vu, sizeof(windows[i].vu));
+  return SE3TN_OK;
+}
+
 int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_poses, const double K[9], double object_width_mm,
                          const uint8_t* const* rgb, const uint16_t* const* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev,
                          double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu, void* stream) {
@@ -1604,44 +1611,23 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = trace ? now() : 0.0;
   // pass 1 (host float64): the windows of every pair (predict.py:231-235 / :201-206) and the size of the staged sub-images
-  std::vector<int32_t> win(8 * (size_t)n), vu(8 * (size_t)n);
-  std::vector<size_t> off_rgb(n), off_d(n);
-  std::vector<int> geo(4 * (size_t)n);        // x0, y0, sw, sh of the staged sub-image
+  std::vector<TrackWindow> windows(n);
   size_t bytes = (((size_t)n * 128) + 255) & ~(size_t)255;   // the poses in front
   for (int i = 0; i < n; ++i) {
-    const double* P = prev_poses + 16 * (size_t)i;
-    int32_t* wB = &win[8 * (size_t)i];
-    int32_t* wA = wB + 4;
     if (!rgb[i] || !depth[i]) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: null frame pointer");
-    if (!(P[11] > 0) || !bbox_window(P, K, object_width_mm, 1000.0, wB, &vu[8 * (size_t)i]) || !bbox_window(P, K, object_width_mm, -1000.0, wA, nullptr))
-      return fail(SE3TN_E_ARG, "se3tn_on_track_batch: a pose is not in front of the camera (z <= 0 or not finite)");
-    if (wB[2] <= wB[0] || wB[3] <= wB[1]) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: empty crop window");
-    int x0 = wB[0] > 0 ? wB[0] : 0, x1 = wB[2] < W ? wB[2] : W;
-    int y0 = wB[1] > 0 ? wB[1] : 0, y1 = wB[3] < H ? wB[3] : H;
-    int sw = x1 - x0, sh = y1 - y0;
-    if (sw <= 0 || sh <= 0) { sw = sh = -1; x0 = wB[0] - 8; y0 = wB[1] - 8; }   // the window misses the frame: a 1 x 1 zero sub-image
-    geo[4 * i] = x0; geo[4 * i + 1] = y0; geo[4 * i + 2] = sw; geo[4 * i + 3] = sh;
-    const size_t px = sw > 0 ? (size_t)sw * sh : 1;
-    off_rgb[i] = bytes; bytes += (px * 3 + 63) & ~(size_t)63;
-    off_d[i] = bytes;   bytes += (px * 2 + 63) & ~(size_t)63;
+    const PlanStatus ps = plan_window(prev_poses + 16 * (size_t)i, K, object_width_mm, H, W, bytes, windows[i]);
+    if (ps == PlanStatus::NOT_IN_FRONT) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: a pose is not in front of the camera (z <= 0 or not finite)");
+    if (ps == PlanStatus::EMPTY_WINDOW) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: empty crop window");
   }
   if (int rc = reserve_track_batch(c, m, n, bytes)) return rc;
   // image A of all n poses: the instance table goes up on the launch stream, then FOUR launches (grid.y = pose)
   uint8_t* rA = rgbA_dev ? rgbA_dev : c->tb_rgbA;
   uint16_t* dA = depthA_dev ? depthA_dev : c->tb_depthA;
-  // SE3TN_ROUTE_FRAME (predict.py:209-213): per pair the rectangle of the full-frame render its crop window covers -- geo above, the
-  // same rectangle as the staged part of the camera frame.  Z-buffers and sub-images are sized by the largest rectangle of the call
   const bool frame_route = m->route == SE3TN_ROUTE_FRAME;
   size_t maxpx = 0, fr_d_off = 0;
   if (frame_route) {
     if (H > 2048) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
-    for (int i = 0; i < n; ++i)
-      if (geo[4 * i + 2] > 0) maxpx = std::max(maxpx, (size_t)geo[4 * i + 2] * (size_t)geo[4 * i + 3]);
-    const size_t need = maxpx ? (size_t)n * maxpx : 1, cap = (size_t)n * H * W;
-    // windows change from frame to frame: grow with half as much again in hand (never past n whole frames)
-    if (need > c->fr_px)
-      if (int rc = reserve_frame_route(c, std::max(need, std::min(need + need / 2, cap)))) return rc;
-    fr_d_off = 64 + (((size_t)n * maxpx * 3 + 63) & ~(size_t)63);
+    if (int rc = reserve_frame_rects(c, n, windows.data(), H, W, &maxpx, &fr_d_off)) return rc;
   }
   RasterArgs ra{};
   raster_common(ra, c, m, rA, dA);
@@ -1652,23 +1638,9 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
     ra.scissor = 1; ra.spx = (int)maxpx;
   }
   ra.vpost = m->b_vpost; ra.vsnap = m->b_vsnap; ra.big = m->b_big; ra.clipq = m->b_clipq; ra.zbuf = frame_route ? c->fr_zbuf : c->tb_zbuf;
-  for (int i = 0; i < n; ++i) {
-    RasterArgs one{};
-    RasterInstance& I = c->tb_inst_host[i];
-    if (frame_route) {
-      frame_uniforms(one, m, prev_poses + 16 * (size_t)i, K, W, H);
-      const int32_t r[4] = {geo[4 * i], geo[4 * i + 1], geo[4 * i] + geo[4 * i + 2], geo[4 * i + 1] + geo[4 * i + 3]};
-      if (geo[4 * i + 2] > 0) rect_to_scissor(r, H, I.rect);
-      // the window misses the frame: an empty rectangle.  The instance still runs its vertex / triangle / queue workgroups (one grid
-      // for all instances) and writes nothing: a few microseconds wasted on a case a tracker does not stay in
-      else I.rect[0] = I.rect[1] = I.rect[2] = I.rect[3] = 0;
-    } else if (!vispy_uniforms(one, prev_poses + 16 * (size_t)i, K, &win[8 * (size_t)i + 4])) {
+  for (int i = 0; i < n; ++i)
+    if (!fill_instance(c->tb_inst_host[i], frame_route, m, prev_poses + 16 * (size_t)i, K, W, H, windows[i]))
       return fail(SE3TN_E_ARG, "se3tn_on_track_batch: singular pose");
-    }
-    std::memcpy(I.PV, one.PV, sizeof(I.PV));
-    std::memcpy(I.light, one.light, sizeof(I.light));
-    I._pad = 0.f; I.dA = one.dA; I.dB = one.dB;
-  }
   if (!frame_route || maxpx > 0) {
     HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, sizeof(RasterInstance) * n, hipMemcpyHostToDevice, st));
     ra.inst = c->tb_inst_dev;
@@ -1679,14 +1651,7 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   uint8_t* hp = c->tb_stage_host;
   std::memcpy(hp, prev_poses, (size_t)n * 128);
   auto stage_pairs = [&](int i0, int i1) {
-    for (int i = i0; i < i1; ++i) {
-      const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
-      if (sw < 0) { std::memset(hp + off_rgb[i], 0, 3); std::memset(hp + off_d[i], 0, 2); continue; }
-      for (int y = 0; y < sh; ++y) {
-        std::memcpy(hp + off_rgb[i] + (size_t)y * sw * 3, rgb[i] + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
-        std::memcpy(hp + off_d[i] + (size_t)y * sw * 2, depth[i] + (size_t)(y0 + y) * W + x0, (size_t)sw * 2);
-      }
-    }
+    for (int i = i0; i < i1; ++i) stage_window(windows[i], rgb[i], depth[i], W, hp);
   };
   // above ~8 MB the row-wise gather is worth helper threads (measured, profiles/r06_tracker_batch_staging.txt: 13.5 MB at 64 tracks 0.34-0.43 ms
   // on one core, 0.25 ms on four; 4.5 MB at 21 tracks 0.10 ms on one core, 0.15 ms on four -- the thread start costs more than it
@@ -1706,30 +1671,13 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
     stage_pairs(0, n);
   }
   const double t2 = trace ? now() : 0.0;
-  HIPCHK(hipMemcpyAsync(c->tb_stage_dev, hp, bytes, hipMemcpyHostToDevice, c->trk_copy_stream));
-  HIPCHK(hipEventRecord(c->trk_copy_event, c->trk_copy_stream));
-  HIPCHK(hipStreamWaitEvent(st, c->trk_copy_event, 0));
+  StagedUpload up{c->trk_copy_stream};
+  if (int rc = upload_staged(c, c->tb_stage_dev, hp, bytes, st)) return rc;
   // both crops of every pair (data_augmentation.py:124-189 with poseA's z), 64 descriptors per launch
   std::vector<se3tn_crop> crops(2 * (size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const double z_mm = prev_poses[16 * (size_t)i + 11] * 1000;
-    se3tn_crop& ca = crops[i];
-    ca.rgb = rA + (size_t)i * RES * RES * 3; ca.depth = dA + (size_t)i * RES * RES; ca.H = RES; ca.W = RES;
-    ca.left = 0; ca.top = 0; ca.right = RES; ca.bottom = RES; ca.z_offset_mm = z_mm; ca.stats = 0; ca._pad = 0;
-    se3tn_crop& cb = crops[(size_t)n + i];
-    const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
-    const int32_t* wB = &win[8 * (size_t)i];
-    if (frame_route) {   // image A = the rendered rectangle under the window shifted by its origin (a miss: the 1 x 1 zero image)
-      ca.rgb = sw < 0 ? c->fr_sub : c->fr_sub + 64 + (size_t)i * maxpx * 3;
-      ca.depth = sw < 0 ? (const uint16_t*)(c->fr_sub + 32) : (const uint16_t*)(c->fr_sub + fr_d_off) + (size_t)i * maxpx;
-      ca.H = sw < 0 ? 1 : sh; ca.W = sw < 0 ? 1 : sw;
-      ca.left = wB[0] - x0; ca.top = wB[1] - y0; ca.right = wB[2] - x0; ca.bottom = wB[3] - y0;
-    }
-    cb.rgb = c->tb_stage_dev + off_rgb[i]; cb.depth = (const uint16_t*)(c->tb_stage_dev + off_d[i]);
-    cb.H = sw < 0 ? 1 : sh; cb.W = sw < 0 ? 1 : sw;
-    cb.left = wB[0] - x0; cb.top = wB[1] - y0; cb.right = wB[2] - x0; cb.bottom = wB[3] - y0;
-    cb.z_offset_mm = z_mm; cb.stats = 1; cb._pad = 0;
-  }
+  for (int i = 0; i < n; ++i)
+    crop_pair(windows[i], prev_poses[16 * (size_t)i + 11] * 1000, image_a(c, frame_route, i, rA, dA, maxpx, fr_d_off), c->tb_stage_dev, crops[i],
+              crops[(size_t)n + i]);
   // frame route: the crops of image A also leave their raw pixels (crop_bbox of the render = Tracker.render_window) in rgbA_dev / depthA_dev
   const bool rawA = frame_route && (rgbA_dev || depthA_dev);
   int rc = preprocess_impl(c, crops.data(), n, c->inA, rawA ? rA : nullptr, rawA ? dA : nullptr, stream);
@@ -1738,10 +1686,10 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   float* rot_d = trans_d + 3 * (size_t)n;
   if (rc == SE3TN_OK)
     rc = se3tn_infer(c, c->inA, c->inB, n, SE3TN_NHWC, trans_d, rot_d, (const double*)c->tb_stage_dev, (double*)c->tb_out_dev, stream);
-  if (rc != SE3TN_OK) { (void)hipStreamSynchronize(c->trk_copy_stream); return rc; }
+  if (rc != SE3TN_OK) return rc;
   const double t3 = trace ? now() : 0.0;
-  HIPCHK(hipMemcpyAsync(c->tb_out_host, c->tb_out_dev, (size_t)n * 152, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if ((rc = read_back_tracks(c, n, st, pose_out, trans_out, rot_out, bbox_vu, windows.data()))) return rc;
+  up.done();
   if (trace) {
     const double t4 = now();
     const double d[5] = {t1 - t0, t2 - t1, t3 - t2, t4 - t3, t4 - t0};
@@ -1753,10 +1701,6 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
       for (double& v : tb_acc) v = 0;
     }
   }
-  std::memcpy(pose_out, c->tb_out_host, (size_t)n * 128);
-  if (trans_out) std::memcpy(trans_out, c->tb_out_host + (size_t)n * 128, (size_t)n * 12);
-  if (rot_out) std::memcpy(rot_out, c->tb_out_host + (size_t)n * 140, (size_t)n * 12);
-  if (bbox_vu) std::memcpy(bbox_vu, vu.data(), sizeof(int32_t) * 8 * (size_t)n);
   return SE3TN_OK;
 }
 
@@ -1874,42 +1818,19 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     return fail(SE3TN_E_ARG, "se3tn_on_track_objects: frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
   hipStream_t st = (hipStream_t)stream;
   // pass 1 (host float64): the windows of every object (predict.py:231-235 / :201-206) and its staged sub-image of the frame
-  std::vector<int32_t> win(8 * (size_t)n), vu(8 * (size_t)n);
-  std::vector<size_t> off_rgb(n), off_d(n);
-  std::vector<int> geo(4 * (size_t)n);
+  std::vector<TrackWindow> windows(n);
   const size_t norm_off = (((size_t)n * 128) + 255) & ~(size_t)255;              // the poses in front, then mean | std per object
   size_t bytes = norm_off + ((((size_t)n * 128) + 255) & ~(size_t)255);
   for (int i = 0; i < n; ++i) {
-    const double* P = prev_poses + 16 * (size_t)i;
-    int32_t* wB = &win[8 * (size_t)i];
-    int32_t* wA = wB + 4;
-    const double wd = objs[i].object_width_mm;
-    if (!(P[11] > 0) || !bbox_window(P, K, wd, 1000.0, wB, &vu[8 * (size_t)i]) || !bbox_window(P, K, wd, -1000.0, wA, nullptr))
-      return fail(SE3TN_E_ARG, who + std::to_string(i) + ": pose is not in front of the camera (z <= 0 or not finite)");
-    if (wB[2] <= wB[0] || wB[3] <= wB[1]) return fail(SE3TN_E_ARG, who + std::to_string(i) + ": empty crop window");
-    int x0 = wB[0] > 0 ? wB[0] : 0, x1 = wB[2] < W ? wB[2] : W;
-    int y0 = wB[1] > 0 ? wB[1] : 0, y1 = wB[3] < H ? wB[3] : H;
-    int sw = x1 - x0, sh = y1 - y0;
-    if (sw <= 0 || sh <= 0) { sw = sh = -1; x0 = wB[0] - 8; y0 = wB[1] - 8; }   // the window misses the frame: a 1 x 1 zero sub-image
-    geo[4 * i] = x0; geo[4 * i + 1] = y0; geo[4 * i + 2] = sw; geo[4 * i + 3] = sh;
-    const size_t px = sw > 0 ? (size_t)sw * sh : 1;
-    off_rgb[i] = bytes; bytes += (px * 3 + 63) & ~(size_t)63;
-    off_d[i] = bytes;   bytes += (px * 2 + 63) & ~(size_t)63;
+    const PlanStatus ps = plan_window(prev_poses + 16 * (size_t)i, K, objs[i].object_width_mm, H, W, bytes, windows[i]);
+    if (ps == PlanStatus::NOT_IN_FRONT) return fail(SE3TN_E_ARG, who + std::to_string(i) + ": pose is not in front of the camera (z <= 0 or not finite)");
+    if (ps == PlanStatus::EMPTY_WINDOW) return fail(SE3TN_E_ARG, who + std::to_string(i) + ": empty crop window");
   }
   if (int rc = reserve_track_batch(c, nullptr, n, bytes)) return rc;
   if (int rc = reserve_objects_raster(c, n, maxV, maxF)) return rc;
-  // SE3TN_ROUTE_FRAME (predict.py:209-213): per object the rectangle of the full-frame render its crop window covers -- geo above, the
-  // same rectangle as the staged part of the camera frame.  Z-buffers and sub-images: n x the largest rectangle of the call
   size_t maxpx = 0, fr_d_off = 0;
-  if (frame_route) {
-    for (int i = 0; i < n; ++i)
-      if (geo[4 * i + 2] > 0) maxpx = std::max(maxpx, (size_t)geo[4 * i + 2] * (size_t)geo[4 * i + 3]);
-    const size_t need = maxpx ? (size_t)n * maxpx : 1, cap = (size_t)n * H * W;
-    // windows change from frame to frame: grow with half as much again in hand (never past n whole frames)
-    if (need > c->fr_px)
-      if (int rc = reserve_frame_route(c, std::max(need, std::min(need + need / 2, cap)))) return rc;
-    fr_d_off = 64 + (((size_t)n * maxpx * 3 + 63) & ~(size_t)63);
-  }
+  if (frame_route)
+    if (int rc = reserve_frame_rects(c, n, windows.data(), H, W, &maxpx, &fr_d_off)) return rc;
   if (c->rearm_counters) {   // (as se3tn_infer: a launch sequence that failed half-way may have left the tail's counters non-zero)
     HIPCHK(hipMemsetAsync(c->tail_arrive, 0, sizeof(int) * c->max_batch, st));
     c->rearm_counters = false;
@@ -1932,25 +1853,17 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     ra.inst_mesh = 2;   // every instance with its own material: the table behind the n instance records
   }
   for (int i = 0; i < n; ++i) {
-    RasterArgs one{};
     const se3tn_mesh* m = objs[i].mesh;
     RasterInstance& I = c->tb_inst_host[i];
-    if (frame_route) {
-      frame_uniforms(one, m, prev_poses + 16 * (size_t)i, K, W, H);
-      const int32_t r[4] = {geo[4 * i], geo[4 * i + 1], geo[4 * i] + geo[4 * i + 2], geo[4 * i + 1] + geo[4 * i + 3]};
-      if (geo[4 * i + 2] > 0) rect_to_scissor(r, H, I.rect);
-      else I.rect[0] = I.rect[1] = I.rect[2] = I.rect[3] = 0;   // the window misses the frame: an empty rectangle, nothing written
-      RasterMaterial& M = mat_host[i];
-      M.uv = one.uv; M.tex = one.tex; M.tw = one.tw; M.th = one.th; M.tlevels = one.tlevels;
-      std::memcpy(M.kd, one.kd, sizeof(M.kd));
-      std::memcpy(M.tex_off, one.tex_off, sizeof(M.tex_off));
-    } else if (!vispy_uniforms(one, prev_poses + 16 * (size_t)i, K, &win[8 * (size_t)i + 4])) {
+    if (!fill_instance(I, frame_route, m, prev_poses + 16 * (size_t)i, K, W, H, windows[i]))
       return fail(SE3TN_E_ARG, who + std::to_string(i) + ": singular pose");
-    }
-    std::memcpy(I.PV, one.PV, sizeof(I.PV));
-    std::memcpy(I.light, one.light, sizeof(I.light));
-    I._pad = 0.f; I.dA = one.dA; I.dB = one.dB;
     I.verts = m->verts; I.normals = m->normals; I.colors = m->colors; I.faces = m->faces; I.V = m->V; I.F = m->F;
+    if (frame_route) {
+      RasterMaterial& M = mat_host[i];
+      M.uv = m->uv; M.tex = m->tex; M.tw = m->tw; M.th = m->th; M.tlevels = m->tlevels;
+      std::memcpy(M.kd, m->kd, sizeof(M.kd));
+      std::memcpy(M.tex_off, m->tex_off, sizeof(M.tex_off));
+    }
   }
   if (!frame_route || maxpx > 0) {   // (frame route with every window off the frame: nothing to render)
     const size_t tab_bytes = sizeof(RasterInstance) * n + (frame_route ? sizeof(RasterMaterial) * n : 0);
@@ -1966,17 +1879,9 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     std::memcpy(norm_h + 16 * (size_t)i, objs[i].model->mean, 8 * sizeof(double));
     std::memcpy(norm_h + 16 * (size_t)i + 8, objs[i].model->stdv, 8 * sizeof(double));
   }
-  for (int i = 0; i < n; ++i) {
-    const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
-    if (sw < 0) { std::memset(hp + off_rgb[i], 0, 3); std::memset(hp + off_d[i], 0, 2); continue; }
-    for (int y = 0; y < sh; ++y) {
-      std::memcpy(hp + off_rgb[i] + (size_t)y * sw * 3, rgb + ((size_t)(y0 + y) * W + x0) * 3, (size_t)sw * 3);
-      std::memcpy(hp + off_d[i] + (size_t)y * sw * 2, depth + (size_t)(y0 + y) * W + x0, (size_t)sw * 2);
-    }
-  }
-  HIPCHK(hipMemcpyAsync(c->tb_stage_dev, hp, bytes, hipMemcpyHostToDevice, c->trk_copy_stream));
-  HIPCHK(hipEventRecord(c->trk_copy_event, c->trk_copy_stream));
-  HIPCHK(hipStreamWaitEvent(st, c->trk_copy_event, 0));
+  for (int i = 0; i < n; ++i) stage_window(windows[i], rgb, depth, W, hp);
+  StagedUpload up{c->trk_copy_stream};
+  if (int rc = upload_staged(c, c->tb_stage_dev, hp, bytes, st)) return rc;
   // both crops of every object, each normalised with its own model's mean / std (the device table staged above); up to 32 objects
   // (64 descriptors) per launch: images A into inA, images B into inB
   const size_t img_floats = (size_t)IN_P * IN_P * 4;
@@ -1988,23 +1893,8 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     std::memcpy(a.stdv, c->stdv, sizeof(a.stdv));
     for (int j = 0; j < kg; ++j) {
       const int i = g0 + j;
-      const double z_mm = prev_poses[16 * (size_t)i + 11] * 1000;
-      se3tn_crop& ca = a.c[j];
-      ca.rgb = rA + (size_t)i * RES * RES * 3; ca.depth = dA + (size_t)i * RES * RES; ca.H = RES; ca.W = RES;
-      ca.left = 0; ca.top = 0; ca.right = RES; ca.bottom = RES; ca.z_offset_mm = z_mm; ca.stats = 0; ca._pad = 0;
-      se3tn_crop& cb = a.c[kg + j];
-      const int x0 = geo[4 * i], y0 = geo[4 * i + 1], sw = geo[4 * i + 2], sh = geo[4 * i + 3];
-      const int32_t* wB = &win[8 * (size_t)i];
-      if (frame_route) {   // image A = the rendered rectangle under the window shifted by its origin (a miss: the 1 x 1 zero image)
-        ca.rgb = sw < 0 ? c->fr_sub : c->fr_sub + 64 + (size_t)i * maxpx * 3;
-        ca.depth = sw < 0 ? (const uint16_t*)(c->fr_sub + 32) : (const uint16_t*)(c->fr_sub + fr_d_off) + (size_t)i * maxpx;
-        ca.H = sw < 0 ? 1 : sh; ca.W = sw < 0 ? 1 : sw;
-        ca.left = wB[0] - x0; ca.top = wB[1] - y0; ca.right = wB[2] - x0; ca.bottom = wB[3] - y0;
-      }
-      cb.rgb = c->tb_stage_dev + off_rgb[i]; cb.depth = (const uint16_t*)(c->tb_stage_dev + off_d[i]);
-      cb.H = sw < 0 ? 1 : sh; cb.W = sw < 0 ? 1 : sw;
-      cb.left = wB[0] - x0; cb.top = wB[1] - y0; cb.right = wB[2] - x0; cb.bottom = wB[3] - y0;
-      cb.z_offset_mm = z_mm; cb.stats = 1; cb._pad = 0;
+      crop_pair(windows[i], prev_poses[16 * (size_t)i + 11] * 1000, image_a(c, frame_route, i, rA, dA, maxpx, fr_d_off), c->tb_stage_dev,
+                a.c[j], a.c[kg + j]);
     }
     // frame route: the crops of image A also leave their raw pixels (crop_bbox of the render = Tracker.render_window) in rgbA_dev /
     // depthA_dev (the one not given goes to the internal buffer)
@@ -2035,17 +1925,9 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     rc = infer_small_objects(c, W0, ip, c->inA + (size_t)i0 * img_floats, c->inB + (size_t)i0 * img_floats, k, trans_d + 3 * (size_t)i0,
                              rot_d + 3 * (size_t)i0, (const double*)c->tb_stage_dev + 16 * (size_t)i0, (double*)c->tb_out_dev + 16 * (size_t)i0, st);
   }
-  if (rc != SE3TN_OK) {
-    c->rearm_counters = true;
-    (void)hipStreamSynchronize(c->trk_copy_stream);   // the staged frame may still be travelling
-    return rc;
-  }
-  HIPCHK(hipMemcpyAsync(c->tb_out_host, c->tb_out_dev, (size_t)n * 152, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(pose_out, c->tb_out_host, (size_t)n * 128);
-  if (trans_out) std::memcpy(trans_out, c->tb_out_host + (size_t)n * 128, (size_t)n * 12);
-  if (rot_out) std::memcpy(rot_out, c->tb_out_host + (size_t)n * 140, (size_t)n * 12);
-  if (bbox_vu) std::memcpy(bbox_vu, vu.data(), sizeof(int32_t) * 8 * (size_t)n);
+  if (rc != SE3TN_OK) { c->rearm_counters = true; return rc; }
+  if ((rc = read_back_tracks(c, n, st, pose_out, trans_out, rot_out, bbox_vu, windows.data()))) return rc;
+  up.done();
   return SE3TN_OK;
 }
 

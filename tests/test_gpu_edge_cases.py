@@ -263,6 +263,37 @@ def test_on_track_batch_one_call_equals_the_stepwise_path(se3, n):
         assert np.abs(one - got[:len(one)]).max() < 1e-6
 
 
+def test_on_track_batch_threaded_staging_equals_the_stepwise_path(se3):
+    """The helper-thread staging of se3tn_on_track_batch (more than 8 MiB of staged windows): the same comparison as
+    test_on_track_batch_one_call_equals_the_stepwise_path.  A 400 mm object at z = 0.3 m has a window of ~1422 pixels, larger than the
+    480 x 640 frame wherever it is centred here, so every pair stages its whole frame (921,600 + 614,400 bytes): 6 pairs are the fewest
+    that cross the threshold, and the default four threads take uneven ranges of them (1, 2, 1, 2)."""
+    n, frame_bytes = 6, 480 * 640 * 5
+    assert n * frame_bytes > (8 << 20) > (n - 1) * frame_bytes + 4096
+    sd = O.make_state_dict(0, head_gain=0.01)
+    mean, std = Fx.mean_std(0)
+    trk = se3.Tracker(dict(Fx.DATASET_INFO, object_width=400.0), mean, std, {"state_dict": sd}, max_samples=n)
+    trk.renderer = se3.HipRenderer(trk.engine, Fx.icosphere(3, 0.05, 2))
+    frames = [Fx.synthetic_frame(80 + i) for i in range(n)]
+    poses = [Fx.pose(3 + i, (0.01 * i - 0.02, 0.015 - 0.007 * i, 0.3)) for i in range(n)]
+    rgbs, deps = [f[0] for f in frames], [f[1] for f in frames]
+    assert trk.one_call
+    got = trk.on_track_batch(poses, rgbs, deps)
+    lp = trk.last_prediction
+    g = dict(trans=lp["trans"].copy(), rot=lp["rot"].copy(), bbox=lp["bbox"].copy(),
+             rgbA=[t.cpu().numpy() for t in lp["rgbA"]], depthA=[t.cpu().numpy() for t in lp["depthA"]])
+    bb = g["bbox"].reshape(n, 4, 2)   # (v, u) corners: every window covers the whole frame
+    assert (bb[:, :, 0].min(1) <= 0).all() and (bb[:, :, 0].max(1) >= 480).all() and (bb[:, :, 1].min(1) <= 0).all() and (bb[:, :, 1].max(1) >= 640).all()
+    trk.one_call = False
+    want = trk.on_track_batch(poses, rgbs, deps)
+    lw = trk.last_prediction
+    assert got.shape == (n, 4, 4) and np.array_equal(got, want)
+    assert np.array_equal(g["trans"], lw["trans"]) and np.array_equal(g["rot"], lw["rot"]) and np.array_equal(g["bbox"], lw["bbox"])
+    for i in range(n):
+        assert np.array_equal(g["rgbA"][i], lw["rgbA"][i].cpu().numpy()) and np.array_equal(g["depthA"][i], lw["depthA"][i].cpu().numpy()), i
+        assert (g["depthA"][i] != 0).sum() > 500
+
+
 def test_on_track_refuses_poses_that_have_no_crop_window(se3):
     """se3tn_on_track / se3tn_on_track_batch reject a pose at or behind the camera plane, a non-finite pose and a
     non-finite projection BEFORE the float -> int32 cast of compute_bbox's corners (undefined behaviour in C++), with an error code

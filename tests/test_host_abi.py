@@ -269,3 +269,21 @@ def test_winograd_tile_codes_offset_rule_and_the_ctypes_mirror(se3):
     eng.set_offset_rule(L.OFFSET_RULE_NUMPY1)
     assert eng.get_offset_rule() == "numpy1"
     assert lib.se3tn_set_offset_rule(eng._h, 2) == -1 and lib.se3tn_get_offset_rule(None) == -1
+
+
+def test_track_plan_host_arithmetic_under_sanitizers(tmp_path):
+    """csrc/track_plan.h (the windows, staging offsets, row gather and crop descriptors all three on_track bodies share) in a
+    stand-alone host program built with AddressSanitizer + UBSan: the staging buffer is malloc'ed with exactly the planned bytes, so an
+    overrun of the gather is a report; every window pixel read through the descriptors equals the frame with zero outside."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "track_plan_check")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "iros20-6d-pose-tracking_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c_abi", "track_plan_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    assert "track_plan_check: ok" in out.stdout
