@@ -366,6 +366,19 @@ int se3tn_fill_depth(se3tn_ctx* ctx, const uint16_t* depth_mm, int H, int W, dou
 int se3tn_fill_depth_rect(se3tn_ctx* ctx, const uint16_t* depth_mm_dev, int H, int W, double max_depth_m, int extrapolate, int blur,
                           const int32_t rect[4], uint16_t* out_mm_sub, void* stream);
 
+/* se3tn_fill_depth_rect for n rectangles of ONE frame: rects HOST int32 [n,4] {x0, y0, x1, y1}, out_offsets HOST size_t [n] in uint16
+ * elements from out_mm_base (device): rectangle i goes tightly packed, [y1-y0, x1-x0], to out_mm_base + out_offsets[i], every value the
+ * same pixel of se3tn_fill_depth's out_mm, bit for bit -- whatever other rectangles the call holds, whether they overlap or repeat, and
+ * in whatever order (the outputs must not overlap each other).  The chain up to the median, the range and the bilateral table run ONCE
+ * for the frame; the last pass serves up to 64 rectangles per launch (the table travels as kernel arguments, read from the host
+ * arrays during the call: stream-ordered, capturable after se3tn_reserve; SE3TN_E_STATE when the scratch would have to grow inside a
+ * capture).  A rectangle with x1 <= x0 or y1 <= y0 is SKIPPED (what se3tn_frame_rect reports for a window that misses the frame); if
+ * every rectangle is empty nothing is enqueued.  SE3TN_E_ARG: a rectangle that is not empty and not inside the frame, n < 1, a NULL
+ * pointer, a bad blur. */
+int se3tn_fill_depth_rects(se3tn_ctx* ctx, const uint16_t* depth_mm_dev, int H, int W, double max_depth_m, int extrapolate, int blur,
+                           int n, const int32_t* rects /* host [n,4] */, const size_t* out_offsets /* host [n], uint16 elements */,
+                           uint16_t* out_mm_base /* device */, void* stream);
+
 #define SE3TN_COLOR_RGB 0
 #define SE3TN_COLOR_BGR 1   /* what CvBridge 'bgr8' delivers (predict_ros.py:45-46) */
 /* predict_ros.py:38-60 in ONE call: grab_depth's fill_depth + grab_color's channel order + Tracker.on_track.
@@ -380,6 +393,24 @@ int se3tn_on_track_live(se3tn_ctx* ctx, se3tn_mesh* mesh, const double prev_pose
                         double max_depth_m, int extrapolate, int blur, uint16_t* depth_filled_dev /* optional, device [H,W] */,
                         uint8_t* rgbA_dev, uint16_t* depthA_dev, double pose_out[16], float trans_out[3], float rot_out[3],
                         int32_t bbox_vu[8], void* stream);
+
+/* predict_ros.py:38-60 for n objects of ONE camera frame in ONE call: se3tn_on_track_objects with se3tn_on_track_live's staging.
+ * color (HOST uint8 [H,W,3], channel order color_order) travels as every object's crop window, made RGB during that copy; depth_raw
+ * (HOST uint16 [H,W], the camera's millimetres with holes) goes up WHOLE, ONCE, in the same copy.  The chain of se3tn_fill_depth up to
+ * the median runs once for the frame whatever n, and se3tn_fill_depth_rects of the n windows' parts of the frame writes every object's
+ * image-B depth where the crop launch reads it; an object whose window misses the frame has no rectangle and reads one zero pixel.
+ * If every window misses and depth_filled_dev is NULL, the raw frame is not uploaded and no fill is enqueued.  depth_filled_dev
+ * (optional, device uint16 [H,W]): the whole filled frame too (= se3tn_fill_depth's out_mm).
+ * Object i gets exactly the bits se3tn_on_track_live on its own model context gives it (under the conditions se3tn_on_track_objects
+ * states) -- equivalently the bits of se3tn_on_track_objects on se3tn_fill_depth's output with the colours already swapped --
+ * whatever n, the order or the company.  Objects, routes (all SE3TN_ROUTE_WINDOW or all SE3TN_ROUTE_FRAME), outputs and every refusal
+ * as se3tn_on_track_objects; SE3TN_E_ARG for a bad color_order / blur as se3tn_on_track_live.  SYNCHRONOUS on `stream`, SE3TN_E_STATE
+ * inside a stream capture.  The context stays usable after a refusal. */
+int se3tn_on_track_objects_live(se3tn_ctx* ctx, int n, const se3tn_object* objects, const double* prev_poses, const double K[9],
+                                const uint8_t* color, int color_order, const uint16_t* depth_raw, int H, int W,
+                                double max_depth_m, int extrapolate, int blur, uint16_t* depth_filled_dev /* optional, device [H,W] */,
+                                uint8_t* rgbA_dev, uint16_t* depthA_dev, double* pose_out, float* trans_out, float* rot_out,
+                                int32_t* bbox_vu, void* stream);
 
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K

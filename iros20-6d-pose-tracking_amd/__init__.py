@@ -12,9 +12,9 @@ from .tracker import Tracker, MultiTracker
 from .utils import compute_bbox, crop_window
 from . import metrics, sequence
 from .renderer import HipRenderer
-from .live import LiveTracker, quaternion_from_matrix
+from .live import LiveTracker, LiveMultiTracker, quaternion_from_matrix
 
 _lib.load()
 
 __all__ = ["Engine", "PipelinedEngine", "Se3TrackNet", "Tracker", "MultiTracker", "compute_bbox", "crop_window", "pack_crops", "pose_update_host", "frame_rect", "NCHW", "NHWC",
-           "metrics", "sequence", "HipRenderer", "LiveTracker", "quaternion_from_matrix"]
+           "metrics", "sequence", "HipRenderer", "LiveTracker", "LiveMultiTracker", "quaternion_from_matrix"]

@@ -18,7 +18,7 @@ WINOGRAD_TILE_6_4, WINOGRAD_HEADS_TILE6_MAX_ROT = 64, 0.2     # F(6x6) 256-chann
 TRUNK_WINOGRAD_DEFAULT_MIN_BATCH, TRUNK_WINOGRAD_DEFAULT_MIN_FILL = 8, 55   # as include/se3tracknet.h (tests/test_host_abi.py)
 OFFSET_RULE_NUMPY1, OFFSET_RULE_NUMPY2 = 0, 1   # as include/se3tracknet.h: rounding of OffsetDepth's float64-scalar subtraction
 BLUR_NONE, BLUR_BILATERAL, BLUR_GAUSSIAN = 0, 1, 2
-COLOR_RGB, COLOR_BGR = 0, 1        # se3tn_on_track_live's color_order
+COLOR_RGB, COLOR_BGR = 0, 1        # se3tn_on_track_live's / se3tn_on_track_objects_live's color_order
 ROUTE_WINDOW, ROUTE_FRAME = 0, 1   # as include/se3tracknet.h: the renderer se3tn_on_track uses for a mesh's image A
 RES = 176
 
@@ -109,6 +109,11 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p]),
     "se3tn_fill_depth_rect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                         C.c_void_p, C.c_void_p]),
+    "se3tn_fill_depth_rects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]),
+    "se3tn_on_track_objects_live": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Object), C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_on_track_live": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p]),

@@ -1262,9 +1262,11 @@ int se3tn_render_frame_rect(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[
 
 static int fill_depth_rect_enqueue(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
                                    const int32_t comp[4], uint16_t* out_full, const int32_t sub[4], uint16_t* out_sub, hipStream_t st);
+static int fill_depth_rects_enqueue(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
+                                    int n, const int32_t* rects, const size_t* offs, uint16_t* out_base, uint16_t* out_full, hipStream_t st);
 
-// the live camera's part of se3tn_on_track_live: `rgb` / `depth` of on_track_frame are then the camera's colour frame in color_order
-// and its RAW depth frame, filled on the device (predict_ros.py:38-46)
+// the live camera's part of se3tn_on_track_live and se3tn_on_track_objects_live: `rgb` / `depth` of on_track_frame / on_track_objects_frame
+// are then the camera's colour frame in color_order and its RAW depth frame, filled on the device (predict_ros.py:38-46)
 struct LiveFrame {
   int color_order;
   double max_depth_m;
@@ -1379,15 +1381,7 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
     // the window's filled depth is written behind it by the rectangle pass below
     const size_t z_off = w.off_d;
     raw_off = z_off + 64;
-    if (!w.miss && live->color_order == SE3TN_COLOR_BGR) {
-      for (int y = 0; y < w.sh; ++y) {
-        const uint8_t* src = rgb + ((size_t)(w.y0 + y) * W + w.x0) * 3;
-        uint8_t* dst = hp + w.off_rgb + (size_t)y * w.sw * 3;
-        for (int x = 0; x < w.sw; ++x, src += 3, dst += 3) { dst[0] = src[2]; dst[1] = src[1]; dst[2] = src[0]; }
-      }
-    } else {
-      stage_window(w, rgb, nullptr, W, hp);
-    }
+    stage_window(w, rgb, nullptr, W, hp, live->color_order == SE3TN_COLOR_BGR);
     std::memset(hp + z_off, 0, 2);
     if (fill) std::memcpy(hp + raw_off, depth, fpx * 2);
     bytes = fill ? raw_off + fpx * 2 : raw_off;
@@ -1772,18 +1766,21 @@ static int infer_small_objects(se3tn_ctx* c, const float* W, const ImgParams& ip
   return SE3TN_OK;
 }
 
-int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const double* prev_poses, const double K[9], const uint8_t* rgb,
-                           const uint16_t* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev, double* pose_out, float* trans_out,
-                           float* rot_out, int32_t* bbox_vu, void* stream) {
+// se3tn_on_track_objects (live == nullptr) and se3tn_on_track_objects_live: one body, two staging steps
+static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs, const double* prev_poses, const double K[9], const uint8_t* rgb,
+                                  const uint16_t* depth, int H, int W, const LiveFrame* live, uint8_t* rgbA_dev, uint16_t* depthA_dev,
+                                  double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu, void* stream) {
+  const std::string fn = live ? "se3tn_on_track_objects_live" : "se3tn_on_track_objects";
   if (!c || c->device < 0 || !objs || !prev_poses || !K || !rgb || !depth || H < 1 || W < 1 || !pose_out)
-    return fail(SE3TN_E_ARG, "se3tn_on_track_objects: bad argument");
-  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_on_track_objects: n outside [1, max_batch]");
+    return fail(SE3TN_E_ARG, fn + ": bad argument");
+  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, fn + ": n outside [1, max_batch]");
+  if (live && ((unsigned)live->color_order > 1u || (unsigned)live->blur > 2u)) return fail(SE3TN_E_ARG, fn + ": bad color_order or blur");
   if (c->prec != SE3TN_PREC_F32)
-    return fail(SE3TN_E_STATE, "se3tn_on_track_objects: ctx is in SE3TN_PREC_F16X3 (the batch 1-5 kernel family is float32)");
-  if (!c->small_kernels) return fail(SE3TN_E_STATE, "se3tn_on_track_objects: ctx has the batch 1-5 kernels switched off (se3tn_set_small_kernels)");
-  if (c->keep_intermediates) return fail(SE3TN_E_STATE, "se3tn_on_track_objects: ctx keeps intermediates (se3tn_keep_intermediates)");
-  if (stream_is_capturing((hipStream_t)stream)) return fail(SE3TN_E_STATE, "se3tn_on_track_objects: synchronous call, not capturable");
-  const std::string who = "se3tn_on_track_objects: object ";
+    return fail(SE3TN_E_STATE, fn + ": ctx is in SE3TN_PREC_F16X3 (the batch 1-5 kernel family is float32)");
+  if (!c->small_kernels) return fail(SE3TN_E_STATE, fn + ": ctx has the batch 1-5 kernels switched off (se3tn_set_small_kernels)");
+  if (c->keep_intermediates) return fail(SE3TN_E_STATE, fn + ": ctx keeps intermediates (se3tn_keep_intermediates)");
+  if (stream_is_capturing((hipStream_t)stream)) return fail(SE3TN_E_STATE, fn + ": synchronous call, not capturable");
+  const std::string who = fn + ": object ";
   int maxV = 0, maxF = 0;
   // one rasteriser mode per launch, so one route per call: all objects on SE3TN_ROUTE_WINDOW (vertex-colour meshes) or all on
   // SE3TN_ROUTE_FRAME (meshes with a material: a texture, or a Kd over the vertex colours)
@@ -1815,16 +1812,30 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     maxF = o.mesh->F > maxF ? o.mesh->F : maxF;
   }
   if (frame_route && H > 2048)
-    return fail(SE3TN_E_ARG, "se3tn_on_track_objects: frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
+    return fail(SE3TN_E_ARG, fn + ": frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
   hipStream_t st = (hipStream_t)stream;
   // pass 1 (host float64): the windows of every object (predict.py:231-235 / :201-206) and its staged sub-image of the frame
   std::vector<TrackWindow> windows(n);
   const size_t norm_off = (((size_t)n * 128) + 255) & ~(size_t)255;              // the poses in front, then mean | std per object
-  size_t bytes = norm_off + ((((size_t)n * 128) + 255) & ~(size_t)255);
+  const size_t win_off = norm_off + ((((size_t)n * 128) + 255) & ~(size_t)255);
+  size_t bytes = win_off;
   for (int i = 0; i < n; ++i) {
     const PlanStatus ps = plan_window(prev_poses + 16 * (size_t)i, K, objs[i].object_width_mm, H, W, bytes, windows[i]);
     if (ps == PlanStatus::NOT_IN_FRONT) return fail(SE3TN_E_ARG, who + std::to_string(i) + ": pose is not in front of the camera (z <= 0 or not finite)");
     if (ps == PlanStatus::EMPTY_WINDOW) return fail(SE3TN_E_ARG, who + std::to_string(i) + ": empty crop window");
+  }
+  // live: colour windows | zero pixel | the whole RAW depth frame, once | (device only) every object's filled depth window (track_plan.h)
+  LiveLayout lay{};
+  bool fill = false;
+  if (live) {
+    lay = plan_live(n, windows.data(), H, W, win_off);
+    fill = lay.fills > 0 || live->depth_filled;
+    bytes = lay.total;
+    if ((size_t)H * W > c->fd_pixels) {
+      DeviceGuard dg(c->device);
+      if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+      if (int rc = reserve_fill_depth(c, (size_t)H * W)) return rc;
+    }
   }
   if (int rc = reserve_track_batch(c, nullptr, n, bytes)) return rc;
   if (int rc = reserve_objects_raster(c, n, maxV, maxF)) return rc;
@@ -1879,9 +1890,28 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
     std::memcpy(norm_h + 16 * (size_t)i, objs[i].model->mean, 8 * sizeof(double));
     std::memcpy(norm_h + 16 * (size_t)i + 8, objs[i].model->stdv, 8 * sizeof(double));
   }
-  for (int i = 0; i < n; ++i) stage_window(windows[i], rgb, depth, W, hp);
+  if (live) {
+    for (int i = 0; i < n; ++i) stage_window(windows[i], rgb, nullptr, W, hp, live->color_order == SE3TN_COLOR_BGR);
+    std::memset(hp + lay.zero_off, 0, 2);
+    if (fill) std::memcpy(hp + lay.raw_off, depth, (size_t)H * W * 2);
+  } else {
+    for (int i = 0; i < n; ++i) stage_window(windows[i], rgb, depth, W, hp);
+  }
   StagedUpload up{c->trk_copy_stream};
-  if (int rc = upload_staged(c, c->tb_stage_dev, hp, bytes, st)) return rc;
+  if (int rc = upload_staged(c, c->tb_stage_dev, hp, !live ? bytes : fill ? lay.upload_bytes : lay.raw_off, st)) return rc;
+  if (fill) {   // predict_ros.py:38-41 ONCE for the frame, then the pixels each object's crop reads (and the whole frame when the caller wants it)
+    std::vector<int32_t> rects(4 * (size_t)n, 0);   // (a miss keeps the empty rectangle: skipped)
+    std::vector<size_t> offs(n, 0);
+    for (int i = 0; i < n; ++i) {
+      const TrackWindow& t = windows[i];
+      if (t.miss) continue;
+      rects[4 * (size_t)i] = t.x0; rects[4 * (size_t)i + 1] = t.y0; rects[4 * (size_t)i + 2] = t.x0 + t.sw; rects[4 * (size_t)i + 3] = t.y0 + t.sh;
+      offs[i] = t.off_d / 2;
+    }
+    if (int rc = fill_depth_rects_enqueue(c, (const uint16_t*)(c->tb_stage_dev + lay.raw_off), H, W, live->max_depth_m, live->extrapolate,
+                                          live->blur, n, rects.data(), offs.data(), (uint16_t*)c->tb_stage_dev, live->depth_filled, st))
+      return rc;
+  }
   // both crops of every object, each normalised with its own model's mean / std (the device table staged above); up to 32 objects
   // (64 descriptors) per launch: images A into inA, images B into inB
   const size_t img_floats = (size_t)IN_P * IN_P * 4;
@@ -1931,6 +1961,34 @@ int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const 
   return SE3TN_OK;
 }
 
+int se3tn_on_track_objects(se3tn_ctx* c, int n, const se3tn_object* objs, const double* prev_poses, const double K[9], const uint8_t* rgb,
+                           const uint16_t* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev, double* pose_out, float* trans_out,
+                           float* rot_out, int32_t* bbox_vu, void* stream) {
+  return on_track_objects_frame(c, n, objs, prev_poses, K, rgb, depth, H, W, nullptr, rgbA_dev, depthA_dev, pose_out, trans_out, rot_out,
+                                bbox_vu, stream);
+}
+
+int se3tn_on_track_objects_live(se3tn_ctx* c, int n, const se3tn_object* objs, const double* prev_poses, const double K[9],
+                                const uint8_t* color, int color_order, const uint16_t* depth_raw, int H, int W, double max_depth_m,
+                                int extrapolate, int blur, uint16_t* depth_filled_dev, uint8_t* rgbA_dev, uint16_t* depthA_dev,
+                                double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu, void* stream) {
+  const LiveFrame live{color_order, max_depth_m, extrapolate, blur, depth_filled_dev};
+  return on_track_objects_frame(c, n, objs, prev_poses, K, color, depth_raw, H, W, &live, rgbA_dev, depthA_dev, pose_out, trans_out, rot_out,
+                                bbox_vu, stream);
+}
+
+// the scratch of the depth fill as its launches take it (Utils.py:505 cv2.bilateralFilter(depth, 5, 1.5, 2.0))
+static FillDepthArgs fill_depth_args(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur) {
+  const size_t px = (size_t)H * W;
+  FillDepthArgs f{};
+  f.depth_mm = depth_mm; f.H = H; f.W = W; f.max_depth = max_depth_m; f.extrapolate = extrapolate; f.blur = blur;
+  f.sigma_color = 1.5; f.sigma_space = 2.0;
+  f.buf0 = c->fd_buf; f.buf1 = c->fd_buf + px; f.buf2 = c->fd_buf + 2 * px;
+  f.minmax = reinterpret_cast<unsigned*>(c->fd_buf + 3 * px);
+  f.lut = c->fd_buf + 3 * px + 2;
+  return f;
+}
+
 int se3tn_fill_depth(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
                      uint16_t* out_mm, float* out_m, void* stream) {
   if (!c || c->device < 0 || !depth_mm || H < 1 || W < 1 || (!out_mm && !out_m) || blur < 0 || blur > 2)
@@ -1941,12 +1999,7 @@ int se3tn_fill_depth(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, doubl
       return fail(SE3TN_E_STATE, "se3tn_fill_depth: scratch too small for this frame inside a stream capture: call se3tn_reserve(ctx, H, W) first");
     if (int rc = reserve_fill_depth(c, px)) return rc;
   }
-  FillDepthArgs a{};
-  a.depth_mm = depth_mm; a.H = H; a.W = W; a.max_depth = max_depth_m; a.extrapolate = extrapolate; a.blur = blur;
-  a.sigma_color = 1.5; a.sigma_space = 2.0;   // Utils.py:505 cv2.bilateralFilter(depth, 5, 1.5, 2.0)
-  a.buf0 = c->fd_buf; a.buf1 = c->fd_buf + px; a.buf2 = c->fd_buf + 2 * px;
-  a.minmax = reinterpret_cast<unsigned*>(c->fd_buf + 3 * px);
-  a.lut = c->fd_buf + 3 * px + 2;
+  FillDepthArgs a = fill_depth_args(c, depth_mm, H, W, max_depth_m, extrapolate, blur);
   a.out_mm = out_mm; a.out_m = out_m;
   HIPCHK(launch_fill_depth(a, (hipStream_t)stream));
   return SE3TN_OK;
@@ -1956,14 +2009,8 @@ int se3tn_fill_depth(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, doubl
 // Both inside the frame and not empty; the scratch is reserved.
 static int fill_depth_rect_enqueue(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
                                    const int32_t comp[4], uint16_t* out_full, const int32_t sub[4], uint16_t* out_sub, hipStream_t st) {
-  const size_t px = (size_t)H * W;
   FillDepthRectArgs a{};
-  FillDepthArgs& f = a.f;
-  f.depth_mm = depth_mm; f.H = H; f.W = W; f.max_depth = max_depth_m; f.extrapolate = extrapolate; f.blur = blur;
-  f.sigma_color = 1.5; f.sigma_space = 2.0;   // Utils.py:505 cv2.bilateralFilter(depth, 5, 1.5, 2.0)
-  f.buf0 = c->fd_buf; f.buf1 = c->fd_buf + px; f.buf2 = c->fd_buf + 2 * px;
-  f.minmax = reinterpret_cast<unsigned*>(c->fd_buf + 3 * px);
-  f.lut = c->fd_buf + 3 * px + 2;
+  a.f = fill_depth_args(c, depth_mm, H, W, max_depth_m, extrapolate, blur);
   a.cx0 = comp[0]; a.cy0 = comp[1]; a.cx1 = comp[2]; a.cy1 = comp[3];
   a.out_full = out_full; a.out_sub = out_sub;
   a.sx0 = sub[0]; a.sy0 = sub[1]; a.sx1 = sub[2]; a.sy1 = sub[3];
@@ -1984,6 +2031,39 @@ int se3tn_fill_depth_rect(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, 
     if (int rc = reserve_fill_depth(c, px)) return rc;
   }
   return fill_depth_rect_enqueue(c, depth_mm, H, W, max_depth_m, extrapolate, blur, rect, nullptr, rect, out_mm_sub, (hipStream_t)stream);
+}
+
+// rects: every one inside the frame or empty; the scratch is reserved
+static int fill_depth_rects_enqueue(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur,
+                                    int n, const int32_t* rects, const size_t* offs, uint16_t* out_base, uint16_t* out_full, hipStream_t st) {
+  FillDepthRectsArgs a{};
+  a.f = fill_depth_args(c, depth_mm, H, W, max_depth_m, extrapolate, blur);
+  a.n = n; a.rects = rects; a.offs = offs; a.out_base = out_base; a.out_full = out_full;
+  HIPCHK(launch_fill_depth_rects(a, st));
+  return SE3TN_OK;
+}
+
+int se3tn_fill_depth_rects(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, double max_depth_m, int extrapolate, int blur, int n,
+                           const int32_t* rects, const size_t* out_offsets, uint16_t* out_mm_base, void* stream) {
+  if (!c || c->device < 0 || !depth_mm || H < 1 || W < 1 || n < 1 || !rects || !out_offsets || !out_mm_base || blur < 0 || blur > 2)
+    return fail(SE3TN_E_ARG, "se3tn_fill_depth_rects: bad argument");
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const int32_t* r = rects + 4 * (size_t)i;
+    if (r[2] <= r[0] || r[3] <= r[1]) continue;   // what se3tn_frame_rect reports for a window that misses the frame: skipped
+    if (r[0] < 0 || r[1] < 0 || r[2] > W || r[3] > H)
+      return fail(SE3TN_E_ARG, "se3tn_fill_depth_rects: rectangle " + std::to_string(i) + " is not inside the frame");
+    any = true;
+  }
+  if (!any) return SE3TN_OK;
+  const size_t px = (size_t)H * W;
+  if (px > c->fd_pixels) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
+    if (stream_is_capturing((hipStream_t)stream))
+      return fail(SE3TN_E_STATE, "se3tn_fill_depth_rects: scratch too small for this frame inside a stream capture: call se3tn_reserve(ctx, H, W) first");
+    if (int rc = reserve_fill_depth(c, px)) return rc;
+  }
+  return fill_depth_rects_enqueue(c, depth_mm, H, W, max_depth_m, extrapolate, blur, n, rects, out_offsets, out_mm_base, nullptr,
+                                  (hipStream_t)stream);
 }
 
 int se3tn_render_frame(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[16], const double K[9], int W, int H, uint8_t* rgb,

@@ -12,8 +12,10 @@
 //   2. fd_rect_lut_kernel: the 4098-entry table of the bilateral filter (bilateral only).
 //   3. fd_rect_kernel: bilateral / gaussian / no blur, invert back and the uint16 conversion for the pixels of the rectangle only, each
 //      with the operations, their order and fp contract(off) of fd_bilateral5_kernel / fd_gauss5_kernel + fd_select_valid_kernel /
-//      fd_finish_kernel.
+//      fd_finish_kernel.  fd_rects_kernel (se3tn_fill_depth_rects, se3tn_on_track_objects_live): the same pass for a table of up to 64
+//      rectangles per launch, behind steps 1 and 2 run ONCE for the frame.
 // The two min / max words are kept so that ONE memset resets both: word 0 = min of the keys, word 1 = min of the COMPLEMENTED keys.
+#include <algorithm>
 #include <cmath>
 
 #include "se3tn_internal.h"
@@ -145,15 +147,11 @@ __global__ __launch_bounds__(256) void fd_rect_lut_kernel(const unsigned* __rest
   lut[i] = (float)exp(val * val * gauss_color_coeff);
 }
 
-// BLUR as SE3TN_BLUR_*: 0 none, 1 bilateral, 2 gaussian on the valid pixels.  One thread per pixel of [cy0, cy0 + ch) x [cx0, cx0 + cw)
+// BLUR as SE3TN_BLUR_*: 0 none, 1 bilateral, 2 gaussian on the valid pixels.  The last pass for frame pixel (y, x): blur, invert back and
+// the uint16 conversion -- the one body of fd_rect_kernel and fd_rects_kernel
 template <int BLUR>
-__global__ __launch_bounds__(256) void fd_rect_kernel(const float* __restrict__ in, int H, int W, int cx0, int cy0, int cw, int ch,
-                                                       const unsigned* __restrict__ mm, const float* __restrict__ lut,
-                                                       const BilateralTaps taps, float max_depth, uint16_t* __restrict__ out_full,
-                                                       uint16_t* __restrict__ out_sub, int sx0, int sy0, int sx1, int sy1) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= cw * ch) return;
-  const int y = cy0 + i / cw, x = cx0 + i % cw;
+__device__ __forceinline__ uint16_t fd_rect_pixel(const float* __restrict__ in, int H, int W, int y, int x, const unsigned* __restrict__ mm,
+                                                  const float* __restrict__ lut, const BilateralTaps& taps, float max_depth) {
   const float val0 = in[(size_t)y * W + x];
   float d = val0;
   if (BLUR == 1) {   // fd_bilateral5_kernel
@@ -195,37 +193,108 @@ __global__ __launch_bounds__(256) void fd_rect_kernel(const float* __restrict__ 
   if (d > 0.1f) d = max_depth - d;
   const float mmv = d * 1000.f;
   const int iv = (mmv >= -2147483648.f && mmv < 2147483648.f) ? (int)mmv : (int)0x80000000u;
-  const uint16_t o = (uint16_t)(unsigned)iv;
+  return (uint16_t)(unsigned)iv;
+}
+
+// One thread per pixel of [cy0, cy0 + ch) x [cx0, cx0 + cw)
+template <int BLUR>
+__global__ __launch_bounds__(256) void fd_rect_kernel(const float* __restrict__ in, int H, int W, int cx0, int cy0, int cw, int ch,
+                                                       const unsigned* __restrict__ mm, const float* __restrict__ lut,
+                                                       const BilateralTaps taps, float max_depth, uint16_t* __restrict__ out_full,
+                                                       uint16_t* __restrict__ out_sub, int sx0, int sy0, int sx1, int sy1) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cw * ch) return;
+  const int y = cy0 + i / cw, x = cx0 + i % cw;
+  const uint16_t o = fd_rect_pixel<BLUR>(in, H, W, y, x, mm, lut, taps, max_depth);
   if (out_full) out_full[(size_t)y * W + x] = o;
   if (out_sub && x >= sx0 && x < sx1 && y >= sy0 && y < sy1) out_sub[(size_t)(y - sy0) * (sx1 - sx0) + (x - sx0)] = o;
 }
 
-hipError_t launch_fill_depth_rect(const FillDepthRectArgs& a, hipStream_t st) {
-  const FillDepthArgs& f = a.f;
+// The same for a table of rectangles of ONE frame: grid.y = rectangle, grid.x sized by the largest of the launch (threads past their
+// rectangle's area exit).  Rectangle r goes tightly packed to out_base + off[r]; rectangle `full` (if any) to out_full instead.
+// Rectangles may overlap or repeat: every pixel value depends on the frame only, and every rectangle has its own output.
+template <int BLUR>
+__global__ __launch_bounds__(256) void fd_rects_kernel(const float* __restrict__ in, int H, int W, const FillRectTable tab,
+                                                        const unsigned* __restrict__ mm, const float* __restrict__ lut,
+                                                        const BilateralTaps taps, float max_depth, uint16_t* __restrict__ out_base,
+                                                        uint16_t* __restrict__ out_full) {
+  const int r = blockIdx.y;   // (uniform: the table is read with scalar loads)
+  const int cw = tab.w[r], ch = tab.h[r];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cw * ch) return;
+  const int ly = i / cw, lx = i % cw;
+  const uint16_t o = fd_rect_pixel<BLUR>(in, H, W, tab.y0[r] + ly, tab.x0[r] + lx, mm, lut, taps, max_depth);
+  uint16_t* out = r == tab.full ? out_full : out_base + tab.off[r];
+  out[(size_t)ly * cw + lx] = o;
+}
+
+// The part in front of the last pass, ONCE per frame: the chain up to the median of the whole frame, the range of that image and the
+// table of the bilateral filter
+static hipError_t fill_chain_to_median(const FillDepthArgs& f, hipStream_t st, float** median, BilateralTaps& taps) {
   const int total = f.H * f.W;
-  const float md = (float)f.max_depth;
   if (f.blur == 1)   // min word := 0xffffffff, complemented max word := 0xffffffff
     if (const hipError_t e = hipMemsetAsync(f.minmax, 0xff, 2 * sizeof(unsigned), st)) return e;
   float* med = f.buf0;
   if (!f.extrapolate) {
     hipLaunchKernelGGL(fd_fused_chain_kernel, dim3((f.W + FT_W - 1) / FT_W, (f.H + FT_H - 1) / FT_H), dim3(256), 0, st, f.depth_mm, med,
-                       f.H, f.W, md, f.blur == 1 ? f.minmax : nullptr);
+                       f.H, f.W, (float)f.max_depth, f.blur == 1 ? f.minmax : nullptr);
   } else {   // a per-column pass over the whole frame and a 31 x 31 dilate: the one-launch-per-step chain
     float* spare;
     launch_fill_depth_to_median(f, st, &med, &spare);
     if (f.blur == 1) hipLaunchKernelGGL(fd_rect_minmax_kernel, dim3(64), dim3(256), 0, st, med, total, f.minmax);
   }
-  BilateralTaps taps{};
   if (f.blur == 1) {
     hipLaunchKernelGGL(fd_rect_lut_kernel, dim3((BIL_BINS + 2 + 255) / 256), dim3(256), 0, st, f.minmax, f.lut,
                        -0.5 / (f.sigma_color * f.sigma_color));
     bilateral_space_taps(f.sigma_space, taps.w);
   }
+  *median = med;
+  return hipSuccess;
+}
+
+hipError_t launch_fill_depth_rect(const FillDepthRectArgs& a, hipStream_t st) {
+  const FillDepthArgs& f = a.f;
+  float* med;
+  BilateralTaps taps{};
+  if (const hipError_t e = fill_chain_to_median(f, st, &med, taps)) return e;
   const int cw = a.cx1 - a.cx0, ch = a.cy1 - a.cy0;
   const dim3 grid((unsigned)(((size_t)cw * ch + 255) / 256));
   auto k = f.blur == 1 ? fd_rect_kernel<1> : f.blur == 2 ? fd_rect_kernel<2> : fd_rect_kernel<0>;
   hipLaunchKernelGGL(k, grid, dim3(256), 0, st, (const float*)med, f.H, f.W, a.cx0, a.cy0, cw, ch, (const unsigned*)f.minmax,
-                     (const float*)f.lut, taps, md, a.out_full, a.out_sub, a.sx0, a.sy0, a.sx1, a.sy1);
+                     (const float*)f.lut, taps, (float)f.max_depth, a.out_full, a.out_sub, a.sx0, a.sy0, a.sx1, a.sy1);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_depth_rects(const FillDepthRectsArgs& a, hipStream_t st) {
+  const FillDepthArgs& f = a.f;
+  int live = a.out_full ? 1 : 0;
+  for (int i = 0; i < a.n; ++i) live += a.rects[4 * i + 2] > a.rects[4 * i] && a.rects[4 * i + 3] > a.rects[4 * i + 1];
+  if (!live) return hipSuccess;   // every rectangle empty: nothing is enqueued
+  float* med;
+  BilateralTaps taps{};
+  if (const hipError_t e = fill_chain_to_median(f, st, &med, taps)) return e;
+  auto k = f.blur == 1 ? fd_rects_kernel<1> : f.blur == 2 ? fd_rects_kernel<2> : fd_rects_kernel<0>;
+  FillRectTable tab;
+  auto flush = [&] {
+    size_t mx = 0;
+    for (int j = 0; j < tab.n; ++j) mx = std::max(mx, (size_t)tab.w[j] * tab.h[j]);
+    hipLaunchKernelGGL(k, dim3((unsigned)((mx + 255) / 256), tab.n), dim3(256), 0, st, (const float*)med, f.H, f.W, tab,
+                       (const unsigned*)f.minmax, (const float*)f.lut, taps, (float)f.max_depth, a.out_base, a.out_full);
+    tab = FillRectTable{};
+  };
+  tab = FillRectTable{};
+  for (int i = 0; i < a.n; ++i) {
+    const int32_t* r = a.rects + 4 * (size_t)i;
+    if (r[2] <= r[0] || r[3] <= r[1]) continue;
+    const int j = tab.n++;
+    tab.x0[j] = r[0]; tab.y0[j] = r[1]; tab.w[j] = r[2] - r[0]; tab.h[j] = r[3] - r[1]; tab.off[j] = (long long)a.offs[i];
+    if (tab.n == FillRectTable::MAX) flush();
+  }
+  if (a.out_full) {   // the whole frame as one more rectangle
+    const int j = tab.n++;
+    tab.x0[j] = 0; tab.y0[j] = 0; tab.w[j] = f.W; tab.h[j] = f.H; tab.off[j] = 0; tab.full = j;
+  }
+  if (tab.n) flush();
   return hipGetLastError();
 }
 

@@ -416,6 +416,25 @@ struct FillDepthRectArgs {
 };
 hipError_t launch_fill_depth_rect(const FillDepthRectArgs& a, hipStream_t st);
 
+// n rectangles of ONE frame behind one run of the chain.  The rectangles travel as kernel arguments, MAX per launch (as CropArgs)
+struct FillRectTable {
+  static constexpr int MAX = 64;   // 64 x 24 B + constants = 1.5 KB of kernel arguments
+  int n = 0;
+  int full = -1;                   // this entry writes out_full (the whole frame), not out_base + off
+  int x0[MAX], y0[MAX], w[MAX], h[MAX];
+  long long off[MAX];              // uint16 elements from out_base
+};
+static_assert(sizeof(FillRectTable) <= 2048, "FillRectTable travels as kernel arguments beside the taps and pointers: HIP's limit is 4 KB");
+struct FillDepthRectsArgs {
+  FillDepthArgs f;
+  int n;
+  const int32_t* rects;      // host [n,4] {x0, y0, x1, y1}: inside the frame, or empty (x1 <= x0 or y1 <= y0: skipped)
+  const size_t* offs;        // host [n]: where rectangle i goes, tightly packed, in uint16 elements from out_base
+  uint16_t* out_base;
+  uint16_t* out_full;        // [H,W]: the whole frame as well, or nullptr
+};
+hipError_t launch_fill_depth_rects(const FillDepthRectsArgs& a, hipStream_t st);
+
 // host-side packer (weights.cpp)
 struct HostTensor {
   const float* data;

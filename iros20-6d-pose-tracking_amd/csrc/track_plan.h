@@ -75,15 +75,52 @@ inline PlanStatus plan_window(const double pose[16], const double K[9], double w
 }
 
 // The sub-image of frame `rgb` / `depth` ([H,W,3] / [H,W], W columns) into the (pinned) staging buffer: a row-wise gather, or the
-// zero pixel of a miss.  depth == nullptr: the rgb part only (se3tn_on_track_live fills its depth on the device)
-inline void stage_window(const TrackWindow& t, const uint8_t* rgb, const uint16_t* depth, int W, uint8_t* host) {
+// zero pixel of a miss.  depth == nullptr: the rgb part only (the live-camera calls fill their depth on the device).  swap_rb: the
+// frame is BGR, the staged pixels are RGB (predict_ros.py:45-46)
+inline void stage_window(const TrackWindow& t, const uint8_t* rgb, const uint16_t* depth, int W, uint8_t* host, bool swap_rb = false) {
   uint8_t* h_rgb = host + t.off_rgb;
   uint8_t* h_d = host + t.off_d;
   if (t.miss) { std::memset(h_rgb, 0, 3); if (depth) std::memset(h_d, 0, 2); return; }
   for (int y = 0; y < t.sh; ++y) {
-    std::memcpy(h_rgb + (size_t)y * t.sw * 3, rgb + ((size_t)(t.y0 + y) * W + t.x0) * 3, (size_t)t.sw * 3);
+    const uint8_t* src = rgb + ((size_t)(t.y0 + y) * W + t.x0) * 3;
+    uint8_t* dst = h_rgb + (size_t)y * t.sw * 3;
+    if (swap_rb)
+      for (int x = 0; x < t.sw; ++x, src += 3, dst += 3) { dst[0] = src[2]; dst[1] = src[1]; dst[2] = src[0]; }
+    else
+      std::memcpy(dst, src, (size_t)t.sw * 3);
     if (depth) std::memcpy(h_d + (size_t)y * t.sw * 2, depth + (size_t)(t.y0 + y) * W + t.x0, (size_t)t.sw * 2);
   }
+}
+
+// The staging buffer of a live-camera call for n objects of one frame (se3tn_on_track_objects_live), from `begin` (the end of the
+// poses and the mean / std table) on:
+//   every object's colour window | one zero pixel | the WHOLE raw depth frame, once | every object's FILLED depth window
+// The first three travel (up to upload_bytes; up to raw_off when no fill runs); the depth windows exist on the device only, written
+// by the n-rectangle pass.  An object whose window misses the frame reads the zero pixel for its depth.  Every region starts on a
+// 64-byte boundary.  Re-places off_rgb / off_d of windows that plan_window has planned; crop_pair takes them unchanged.
+struct LiveLayout {
+  size_t zero_off;       // the zero pixel (64 bytes reserved)
+  size_t raw_off;        // the raw depth frame, H * W uint16
+  size_t upload_bytes;   // end of the raw frame = end of the upload
+  size_t total;          // end of the last depth window = the size the buffers need
+  int fills;             // objects whose window meets the frame (= rectangles of the fill)
+};
+inline LiveLayout plan_live(int n, TrackWindow* t, int H, int W, size_t begin) {
+  auto a64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  LiveLayout L{};
+  size_t bytes = a64(begin);
+  for (int i = 0; i < n; ++i) { t[i].off_rgb = bytes; bytes += a64((size_t)t[i].sw * t[i].sh * 3); }
+  L.zero_off = bytes; bytes += 64;
+  L.raw_off = bytes;
+  L.upload_bytes = L.raw_off + (size_t)H * W * 2;
+  bytes = a64(L.upload_bytes);
+  for (int i = 0; i < n; ++i) {
+    if (t[i].miss) { t[i].off_d = L.zero_off; continue; }
+    t[i].off_d = bytes; bytes += a64((size_t)t[i].sw * t[i].sh * 2);
+    ++L.fills;
+  }
+  L.total = bytes;
+  return L;
 }
 
 // Where a pair's image A lies on the device

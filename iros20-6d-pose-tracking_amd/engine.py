@@ -283,6 +283,38 @@ class Engine:
                                              C.c_void_p(out.data_ptr()), _stream_ptr()), "se3tn_fill_depth_rect")
         return out.cpu().numpy().view(np.uint16) if is_np else out
 
+    def fill_depth_rects(self, depth_mm, rects, max_depth=2.0, extrapolate=False, blur_type="bilateral"):
+        """fill_depth for the pixels of n rectangles of ONE frame in one call (se3tn_fill_depth_rects: the chain up to the median
+        once, the last pass for all rectangles in one launch per 64): rects = n x (x0, y0, x1, y1), each inside the frame or empty
+        (x1 <= x0 or y1 <= y0: skipped, an array of shape (0, 0) comes back) -> a list of n uint16 millimetre arrays
+        [y1-y0, x1-x0], every value the same pixel of fill_depth's result whatever the other rectangles (same container kind as
+        depth_mm: numpy [H,W] or a cuda int16/uint16 tensor)."""
+        dev = "cuda:%d" % self.device
+        is_np = not torch.is_tensor(depth_mm)
+        d = torch.from_numpy(np.ascontiguousarray(depth_mm, dtype=np.uint16).view(np.int16)).to(dev) if is_np else depth_mm
+        assert d.is_cuda and d.element_size() == 2 and d.dim() == 2 and d.is_contiguous()
+        H, W = int(d.shape[0]), int(d.shape[1])
+        r = np.ascontiguousarray(np.asarray(rects, np.int64).reshape(-1, 4).astype(np.int32))
+        n = int(r.shape[0])
+        hw = [(max(int(q[3]) - int(q[1]), 0), max(int(q[2]) - int(q[0]), 0)) for q in r]
+        hw = [(h, w) if h and w else (0, 0) for h, w in hw]
+        offs = np.zeros(max(n, 1), np.uintp)
+        total = 0
+        for i, (h, w) in enumerate(hw):
+            offs[i] = total
+            total += h * w
+        out = torch.empty((max(total, 1),), dtype=torch.int16, device=dev)
+        blur = blur_type if isinstance(blur_type, int) else \
+            {"bilateral": _lib.BLUR_BILATERAL, "gaussian": _lib.BLUR_GAUSSIAN}.get(blur_type, _lib.BLUR_NONE)
+        check(self.lib.se3tn_fill_depth_rects(self._h, C.c_void_p(d.data_ptr()), H, W, float(max_depth), 1 if extrapolate else 0, blur, n,
+                                              r.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                              C.c_void_p(out.data_ptr()), _stream_ptr()), "se3tn_fill_depth_rects")
+        parts = [out[int(offs[i]):int(offs[i]) + h * w].view(h, w) for i, (h, w) in enumerate(hw)]
+        if is_np:
+            flat = out.cpu().numpy().view(np.uint16)
+            return [flat[int(offs[i]):int(offs[i]) + h * w].reshape(h, w).copy() for i, (h, w) in enumerate(hw)]
+        return parts
+
     def infer(self, A, B, n, layout=NCHW, trans=None, rot=None, poseA=None, poseB=None):
         def p(x):
             if x is None:

@@ -11,6 +11,10 @@ reference's method names so that a rospy / ROS 2 / RealSense wrapper only has to
 ``LiveTracker(..., one_call=True)`` with the built-in rasteriser: the two grabs only keep the camera's frames and on_track is ONE
 library call (Tracker.on_track_live -> se3tn_on_track_live: fill_depth of the crop window's pixels, the BGR swap of the window and
 on_track); ``depth`` is then fetched from the device when somebody reads it.
+
+``LiveMultiTracker`` is the same surface over a ``MultiTracker``: several objects of one camera, one (trans, quaternion, stamp) per
+object and frame; ``one_call=True`` makes on_track ONE library call for all of them (MultiTracker.on_track_live ->
+se3tn_on_track_objects_live).
 """
 import numpy as np
 
@@ -111,3 +115,88 @@ class LiveTracker:
         q_wxyz = quaternion_from_matrix(ob_in_cam)
         q_xyzw = [q_wxyz[1], q_wxyz[2], q_wxyz[3], q_wxyz[0]]
         return trans, q_xyzw, self.cur_time
+
+
+class LiveMultiTracker:
+    """`TrackerRos` for several objects seen by one camera: a ``MultiTracker`` instead of a ``Tracker``, n poses instead of one.
+    The surface of ``LiveTracker``; on_track() returns a list of n (translation [3], quaternion x,y,z,w, stamp) and feeds the n
+    poses back.  one_call=False composes engine.fill_depth + the channel swap + MultiTracker.on_track; one_call=True is ONE library
+    call per frame (opt-in, as LiveTracker's; measured in profiles/EXPERIMENTS.md item 73)."""
+
+    def __init__(self, multi_tracker, poses_init, max_depth=2.0, extrapolate=False, blur_type="bilateral", one_call=False):
+        self.tracker = multi_tracker
+        self.color = None
+        self._depth = None
+        self.cur_time = None
+        self.A_in_cam = self._poses(poses_init)
+        self._fill = dict(max_depth=max_depth, extrapolate=extrapolate, blur_type=blur_type)
+        self.one_call = bool(one_call)
+        self._raw = None           # one_call: the camera's depth frame as it came
+        self._filled_dev = None    # one_call: the filled frame of the last on_track, on the device
+        self._filled_valid = False
+
+    def _poses(self, poses):
+        p = np.asarray(poses, np.float64).reshape(-1, 4, 4).copy()
+        if p.shape[0] != self.tracker.n:
+            raise ValueError("LiveMultiTracker: %d poses for %d objects" % (p.shape[0], self.tracker.n))
+        return p
+
+    def reset(self, poses_init):
+        self.color = None
+        self._depth = None
+        self._raw = None
+        self._filled_valid = False
+        self.cur_time = None
+        self.A_in_cam = self._poses(poses_init)
+
+    @property
+    def depth(self):
+        """The hole-filled uint16 mm frame on_track reads.  one_call: fetched from the device on demand (of the last on_track; a
+        frame grabbed since is filled here, off the per-frame path)."""
+        if not self.one_call:
+            return self._depth
+        if self._raw is None:
+            return None
+        if self._filled_valid:
+            return self._filled_dev.cpu().numpy().view(np.uint16)
+        return self.tracker.engine.fill_depth(self._raw, **self._fill)
+
+    @depth.setter
+    def depth(self, value):
+        self._depth = value
+
+    def grab_depth(self, depth_mm):
+        """depth_mm: HxW array in millimetres (what CvBridge 'passthrough' hands over, cast to uint16)."""
+        if self.one_call:
+            self._raw = np.ascontiguousarray(np.asarray(depth_mm).astype(np.uint16, copy=False))
+            self._filled_valid = False
+            return
+        self._depth = self.tracker.engine.fill_depth(np.asarray(depth_mm).astype(np.uint16), **self._fill)
+
+    def grab_color(self, bgr, stamp=0.0):
+        """bgr: HxWx3 uint8 as CvBridge 'bgr8' delivers it; stored as RGB (one_call: kept as it came, swapped inside the call)."""
+        self.cur_time = stamp
+        self.color = np.ascontiguousarray(bgr, dtype=np.uint8) if self.one_call else np.ascontiguousarray(np.asarray(bgr)[:, :, ::-1])
+
+    def _on_track_one_call(self):
+        import torch
+        if self._filled_dev is None or tuple(self._filled_dev.shape) != self._raw.shape:
+            self._filled_dev = torch.empty(self._raw.shape, dtype=torch.int16, device="cuda:%d" % self.tracker.engine.device)
+        self._filled_valid = False
+        poses = self.tracker.on_track_live(self.A_in_cam, self.color, self._raw, bgr=True, depth_filled=self._filled_dev, **self._fill)
+        self._filled_valid = True
+        return poses
+
+    def on_track(self):
+        if self.color is None or (self._raw if self.one_call else self._depth) is None or self.cur_time is None:
+            return None
+        if self.one_call:
+            obs_in_cam = self._on_track_one_call()
+        else:
+            obs_in_cam = self.tracker.on_track(self.A_in_cam, self.color.astype(np.uint8), self._depth)
+        self.A_in_cam = obs_in_cam.copy()
+        out = []
+        for ob_in_cam in obs_in_cam:
+            q_wxyz = quaternion_from_matrix(ob_in_cam)
+            out.append((ob_in_cam[:3, 3], [q_wxyz[1], q_wxyz[2], q_wxyz[3], q_wxyz[0]], self.cur_time))
+        return out

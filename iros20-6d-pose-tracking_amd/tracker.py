@@ -440,6 +440,24 @@ class MultiTracker:
         Returns [n,4,4] float64.  rgbA_out / depthA_out: optional device tensors uint8 [n,176,176,3] / 16-bit [n,176,176] that receive
         the images A (default: the MultiTracker's own, kept in last_prediction); bbox_out: optional host int32 [n,4,2] array that
         receives compute_bbox's corners."""
+        return self._on_track(prev_poses, rgb, depth, None, rgbA_out, depthA_out, bbox_out)
+
+    def on_track_live(self, prev_poses, color, depth_raw, bgr=False, max_depth=2.0, extrapolate=False, blur_type="bilateral",
+                      depth_filled=None, rgbA_out=None, depthA_out=None, bbox_out=None):
+        """predict_ros.py:38-60 for all n objects of one camera frame in ONE library call (se3tn_on_track_objects_live): color HxWx3
+        uint8 in the camera's channel order (bgr=True: what CvBridge 'bgr8' delivers), depth_raw HxW uint16 millimetres WITH holes.
+        The raw frame goes up once, fill_depth's chain runs once for the frame, only the crop windows' pixels are blurred and
+        converted, and the filled frame never visits the host.  depth_filled (optional cuda int16/uint16 [H,W]) receives the whole
+        filled frame.  Object i gets the bits ``trackers[i].on_track_live`` gives it = the bits of
+        ``on_track(prev_poses, rgb, engine.fill_depth(depth_raw))``.  Return value, last_prediction and the other arguments as on_track."""
+        from . import _lib
+        blur = blur_type if isinstance(blur_type, int) else \
+            {"bilateral": _lib.BLUR_BILATERAL, "gaussian": _lib.BLUR_GAUSSIAN}.get(blur_type, _lib.BLUR_NONE)
+        order = bgr if (isinstance(bgr, int) and not isinstance(bgr, bool)) else (_lib.COLOR_BGR if bgr else _lib.COLOR_RGB)
+        live = (int(order), float(max_depth), 1 if extrapolate else 0, int(blur), depth_filled)
+        return self._on_track(prev_poses, color, depth_raw, live, rgbA_out, depthA_out, bbox_out)
+
+    def _on_track(self, prev_poses, rgb, depth, live, rgbA_out, depthA_out, bbox_out):
         C = self._C
         from ._lib import check
         from .engine import _stream_ptr
@@ -470,11 +488,22 @@ class MultiTracker:
         self.engine.set_raster_rule(t0.get_raster_rule())
         out = np.empty((n, 16), np.float64)
         tr, ro = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
-        check(self.engine.lib.se3tn_on_track_objects(
-            self.engine._h, n, self._objs, C.c_void_p(poses.ctypes.data), self.K.ctypes.data_as(C.POINTER(C.c_double)),
-            C.c_void_p(rgb.ctypes.data), C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]), C.c_void_p(rA.data_ptr()),
-            C.c_void_p(dA.data_ptr()), C.c_void_p(out.ctypes.data), C.c_void_p(tr.ctypes.data), C.c_void_p(ro.ctypes.data),
-            C.c_void_p(bb.ctypes.data), _stream_ptr()), "se3tn_on_track_objects")
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        outs = (C.c_void_p(rA.data_ptr()), C.c_void_p(dA.data_ptr()), C.c_void_p(out.ctypes.data), C.c_void_p(tr.ctypes.data),
+                C.c_void_p(ro.ctypes.data), C.c_void_p(bb.ctypes.data), _stream_ptr())
+        if live is None:
+            check(self.engine.lib.se3tn_on_track_objects(
+                self.engine._h, n, self._objs, C.c_void_p(poses.ctypes.data), self.K.ctypes.data_as(C.POINTER(C.c_double)),
+                C.c_void_p(rgb.ctypes.data), C.c_void_p(dep.ctypes.data), H, W, *outs), "se3tn_on_track_objects")
+        else:
+            order, max_depth, extrapolate, blur, filled = live
+            if filled is not None and not (filled.is_cuda and filled.element_size() == 2 and filled.is_contiguous()
+                                           and tuple(filled.shape) == (H, W)):
+                raise ValueError("depth_filled must be a contiguous 16-bit device tensor [H,W]")
+            check(self.engine.lib.se3tn_on_track_objects_live(
+                self.engine._h, n, self._objs, C.c_void_p(poses.ctypes.data), self.K.ctypes.data_as(C.POINTER(C.c_double)),
+                C.c_void_p(rgb.ctypes.data), order, C.c_void_p(dep.ctypes.data), H, W, C.c_double(max_depth), extrapolate, blur,
+                C.c_void_p(filled.data_ptr()) if filled is not None else None, *outs), "se3tn_on_track_objects_live")
         self.last_prediction = dict(trans=tr, rot=ro, bbox=bb, rgbA=list(rA), depthA=list(dA))
         self.frame_cnt += 1
         return out.reshape(n, 4, 4)

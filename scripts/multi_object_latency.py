@@ -10,7 +10,14 @@ Prints one JSON line per K.
 one textured model per class: textured spheres of 81,920 / 20,480 / 5,120 faces with textures of 64 x 128 / 128 x 256 / 256 x 256
 texels (object i takes mesh i % 3), each with its own weights, on one 480 x 640 frame.  The poses are HELD (as `track_latency.py
 pyrender` holds them, and for the same reason: with synthetic weights a fed-back pose leaves the frame, and an empty render costs
-nothing), so every frame renders the rectangles it starts with.  --passes N repeats the whole K list N times (run-to-run spread)."""
+nothing), so every frame renders the rectangles it starts with.  --passes N repeats the whole K list N times (run-to-run spread).
+
+`multi_object_latency.py live`: the live-camera front end for K = 1, 3, 5, 7 objects of one 480 x 640 frame with holes: per frame
+grab_depth + grab_color + on_track of LiveMultiTracker, ONE library call (one_call=True: se3tn_on_track_objects_live) beside the
+composition (one_call=False: engine.fill_depth through the host, the channel swap, MultiTracker.on_track), interleaved frame by frame
+in the same process.  Both compute the same bits (tests/test_gpu_multi_object_live.py); the loop checks it on the first frames.
+`--trace DIR` then counts the kernel launches of ONE frame at K = 3 per leg: one and two frames of the leg, each in a child process of
+its own under `rocprofv3 --kernel-trace` (no counters), and the difference of the two dispatch counts."""
 import argparse
 import json
 import os
@@ -32,10 +39,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--ks", default="1,2,3,4,5,8")
+    ap.add_argument("--ks", default=None, help="default 1,2,3,4,5,8 (live: 1,3,5,7)")
     ap.add_argument("--passes", type=int, default=1)
-    ap.add_argument("route", nargs="?", default="vispy", choices=("vispy", "pyrender"))
+    ap.add_argument("--trace", default=None, help="live: directory for the kernel traces of one frame per leg")
+    ap.add_argument("--trace-child", default=None, help=argparse.SUPPRESS)   # LEG:FRAMES, what the traced child runs
+    ap.add_argument("route", nargs="?", default="vispy", choices=("vispy", "pyrender", "live"))
     args = ap.parse_args()
+    if args.ks is None:
+        args.ks = "1,3,5,7" if args.route == "live" else "1,2,3,4,5,8"
     pyrender = args.route == "pyrender"
     models = []
     for regime in ("ycbineoat_30deg", "ycb_video_5deg"):
@@ -47,7 +58,7 @@ def main():
         for subdiv, tex_hw in ((6, (64, 128)), (5, (128, 256)), (4, (256, 256))):
             ms = Fx.textured_sphere(subdiv, 0.06, tex_hw)
             textured.append(dict(vertices=ms["vertices"], faces=ms["faces"], colors=ms["colors"], uv=ms["uv"], texture=ms["texture"], kd=ms["kd"]))
-    ks = [int(k) for k in args.ks.split(",")]
+    ks = [3] if args.trace_child else [int(k) for k in args.ks.split(",")]
     trackers = []
     for i in range(max(ks)):
         sd, mean, std, tn, rn = models[i % 2]
@@ -58,6 +69,8 @@ def main():
         t.renderer = se3.HipRenderer(t.engine, textured[i % 3], mode="pyrender", frame_size=(480, 640)) if pyrender else se3.HipRenderer(t.engine, mesh)
         trackers.append(t)
     rgb, depth = Fx.structured_frame(401)
+    if args.route == "live":
+        return live_leg(args, ks, trackers)
     start = [Fx.pose(60 + i, (0.08 * np.cos(1.1 * i), 0.05 * np.sin(1.7 * i), 0.75 + 0.02 * i)) for i in range(max(ks))]
     for K in ks * args.passes:
         trks = trackers[:K]
@@ -95,6 +108,80 @@ def main():
                                   % ("textured spheres of %s faces on the full-frame route, poses held" % "/".join(str(len(m["faces"])) for m in textured)
                                      if pyrender else "ellipsoid mesh (%d faces)" % len(mesh["faces"]))}),
               flush=True)
+
+
+def live_trace(trace_dir):
+    import glob
+    import shutil
+    import subprocess
+    prof = shutil.which("rocprofv3")
+    if prof is None:
+        print(json.dumps({"trace": "rocprofv3 not found: no kernel trace recorded"}))
+        return
+    for leg in ("composition", "one_call"):
+        counts = []
+        for frames in (1, 2):
+            out = os.path.join(trace_dir, "%s_%d" % (leg, frames))
+            subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__), "live",
+                            "--trace-child", "%s:%d" % (leg, frames)], check=True, timeout=300)
+            rows = 0
+            for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True):
+                with open(f) as fh:
+                    rows += max(sum(1 for _ in fh) - 1, 0)
+            counts.append(rows)
+        print(json.dumps({"leg": leg, "objects": 3, "kernel_launches_per_frame": counts[1] - counts[0],
+                          "dispatches_one_frame_run": counts[0], "dispatches_two_frame_run": counts[1], "trace": trace_dir}), flush=True)
+
+
+def live_leg(args, ks, trackers):
+    if args.trace_child:      # the traced child: FRAMES frames of one leg at K = 3
+        leg, frames = args.trace_child.split(":")
+        bgr, raw = Fx.synthetic_frame(230)
+        P0 = np.stack([Fx.pose(60 + i, (0.08 * np.cos(1.1 * i), 0.05 * np.sin(1.7 * i), 0.75 + 0.02 * i)) for i in range(3)])
+        lt = se3.LiveMultiTracker(se3.MultiTracker(trackers[:3]), P0, one_call=leg == "one_call")
+        for f in range(int(frames)):
+            lt.grab_depth(raw)
+            lt.grab_color(bgr, stamp=float(f))
+            lt.on_track()
+            lt.A_in_cam = P0.copy()
+        torch.cuda.synchronize()
+        return
+    bgr, raw = Fx.synthetic_frame(230)          # 480 x 640, 10 % holes / near / far pixels
+    start = [Fx.pose(60 + i, (0.08 * np.cos(1.1 * i), 0.05 * np.sin(1.7 * i), 0.75 + 0.02 * i)) for i in range(max(ks))]
+    for K in ks * args.passes:
+        P0 = np.stack(start[:K])
+        legs = [se3.LiveMultiTracker(se3.MultiTracker(trackers[:K]), P0, one_call=oc) for oc in (False, True)]
+        times = ([], [])
+        for f in range(args.warmup + args.frames):
+            outs = []
+            for lt, acc in zip(legs, times):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                lt.grab_depth(raw)
+                lt.grab_color(bgr, stamp=float(f))
+                outs.append(lt.on_track())
+                t1 = time.perf_counter()
+                if f >= args.warmup:
+                    acc.append(t1 - t0)
+            if f < 3:
+                assert np.array_equal(legs[0].A_in_cam, legs[1].A_in_cam), "the one call differs from the composition"
+                assert np.array_equal(legs[0].depth, legs[1].depth), "the filled frames differ"
+            if f % 50 == 49:    # back to the start poses now and then: the frame does not move, the tracks would drift off it
+                for lt in legs:
+                    lt.A_in_cam = P0.copy()
+        for lt in legs:
+            lt.tracker.close()
+        ms = [float(np.median(t)) * 1e3 for t in times]
+        print(json.dumps({"objects": K, "composition_ms": round(ms[0], 4), "one_call_ms": round(ms[1], 4), "speedup": round(ms[0] / ms[1], 3),
+                          "composition_p95_ms": round(float(np.percentile(times[0], 95)) * 1e3, 4),
+                          "one_call_p95_ms": round(float(np.percentile(times[1], 95)) * 1e3, 4), "frames": args.frames, "warmup": args.warmup,
+                          "route": "live",
+                          "note": "LiveMultiTracker grab_depth + grab_color + on_track per frame, one 480x640 frame with holes, K objects "
+                                  "alternating the 30- / 5-degree trained stand-ins, bilateral; one_call=False (engine.fill_depth + channel swap + "
+                                  "se3tn_on_track_objects) vs one_call=True (se3tn_on_track_objects_live), interleaved; median ms per frame"}),
+              flush=True)
+    if args.trace:
+        live_trace(args.trace)
 
 
 if __name__ == "__main__":
