@@ -226,6 +226,43 @@ class _Runner:
         return self.eng.logits(n).cpu().numpy(), self.pB[:n].cpu().numpy().reshape(n, 4, 4)
 
 
+def _cfg_op(cfg, op):
+    """one switch call in the test's own record of the configuration (what `expected` reads)"""
+    if op[0] == "wino":
+        cfg["wmin"] = op[1]
+        cfg["tile"] = op[2] or cfg["tile"]
+    elif op[0] == "trunk":
+        cfg["tmin"], cfg["tfill"] = op[1], op[2]
+    elif op[0] == "small":
+        cfg["small"] = bool(op[1])
+    elif op[0] == "keep":
+        cfg["keep"] = bool(op[1])
+    elif op[0] == "norm":
+        cfg["tn"], cfg["rn"] = op[1], op[2]
+    elif op[0] == "f16":                    # ("f16",) selects f16x3, ("f16", 0) goes back to float32
+        cfg["f16"] = bool(op[1]) if len(op) > 1 else True
+    else:
+        raise ValueError(op)
+
+
+def _eng_op(se3, eng, op):
+    """the same switch call on the context"""
+    if op[0] == "wino":
+        eng.set_winograd(op[1], op[2])
+    elif op[0] == "trunk":
+        eng.set_trunk_winograd(op[1], op[2])
+    elif op[0] == "small":
+        eng.set_small_kernels(bool(op[1]))
+    elif op[0] == "keep":
+        eng.keep_intermediates(bool(op[1]))
+    elif op[0] == "norm":
+        eng.set_normalizers(op[1], op[2])
+    elif op[0] == "f16":
+        eng.set_precision(se3._lib.PREC_F16X3 if (len(op) == 1 or op[1]) else se3._lib.PREC_F32)
+    else:
+        raise ValueError(op)
+
+
 def _engine(se3, ref, env, ops, n_max):
     saved = {k: os.environ.get(k) for k in env}
     os.environ.update(env)                  # read by se3tn_create
@@ -245,25 +282,8 @@ def _engine(se3, ref, env, ops, n_max):
                fuse=env.get("SE3TN_WINOGRAD_FUSE", "1") != "0", tail_parts=env.get("SE3TN_TAIL_PARTS", "1") != "0",
                ovr=[v if v in (4, 6) else 0 for v in ovr])
     for op in ops:
-        if op[0] == "wino":
-            eng.set_winograd(op[1], op[2])
-            cfg["wmin"] = op[1]
-            cfg["tile"] = op[2] or cfg["tile"]
-        elif op[0] == "trunk":
-            eng.set_trunk_winograd(op[1], op[2])
-            cfg["tmin"], cfg["tfill"] = op[1], op[2]
-        elif op[0] == "small":
-            eng.set_small_kernels(bool(op[1]))
-            cfg["small"] = bool(op[1])
-        elif op[0] == "keep":
-            eng.keep_intermediates(bool(op[1]))
-            cfg["keep"] = bool(op[1])
-        elif op[0] == "norm":
-            eng.set_normalizers(op[1], op[2])
-            cfg["tn"], cfg["rn"] = op[1], op[2]
-        elif op[0] == "f16":
-            eng.set_precision(se3._lib.PREC_F16X3)
-            cfg["f16"] = True
+        _eng_op(se3, eng, op)
+        _cfg_op(cfg, op)
     return eng, cfg
 
 
@@ -288,11 +308,18 @@ def _check(se3, eng, run, ref, cfg, n, cid):
         names = [nm for nm, _ in eng.profile_launches(0)]
     finally:
         eng.profile_enable(0)
+    got_w = _check_call(se3, eng, ref, cfg, n, chk, lg, pose, names, cid, WORST)
+    return lg, pose, got_w
+
+
+def _check_call(se3, eng, ref, cfg, n, chk, lg, pose, names, cid, worst):
+    """one profiled call on pool pairs `chk`, after the fact: logits and poses against float64, the route from its launch names, the
+    stages se3tn_debug_buffer hands out; -> {stage: readable}"""
     want_r, written = expected(cfg, n)
     cls = tol_class(cfg, want_r)
     err = np.abs(lg.astype(np.float64) - ref["lg64"][chk])
     e = float(err.max())
-    WORST[cls] = max(WORST.get(cls, 0.0), e)
+    worst[cls] = max(worst.get(cls, 0.0), e)
     assert e <= CLASS_TOL[cls], "%s n=%d: max |d logit| vs float64 %.3e > %.0e (%s), pair %d" % (
         cid, n, e, CLASS_TOL[cls], cls, chk[int(err.max(1).argmax())])
     for j, i in enumerate(chk):
@@ -315,7 +342,7 @@ def _check(se3, eng, run, ref, cfg, n, cid):
             want = _stage_ref(ref, chk[j])[s]
             _close("%s n=%d %s pair %d" % (cid, n, s, chk[j]), got, want, ACT_RTOL, 1e-5 if s in ("stem", "pool") else 0,
                    sc_trunk if s in ("stem", "pool", "t64", "q64") else sc_all)
-    return lg, pose, got_w
+    return got_w
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
