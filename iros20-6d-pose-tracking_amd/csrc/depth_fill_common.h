@@ -7,6 +7,10 @@ namespace se3tn {
 
 struct BilateralTaps { float w[12]; };
 
+// cv::borderInterpolate(p, n, BORDER_REFLECT_101) for the taps of a 5-wide kernel (-2 <= p <= n + 1): one fold at each end, which is
+// the rule for every n >= 3; n = 1 ends in the clamp (every tap is pixel 0).  On n = 2 the rule folds p = 3 a second time, to 1,
+// where the clamp gives 0: no difference to the blurs, which get an image that is constant along every axis of 3 pixels or fewer
+// (every window of the 5 x 5 dilation in front of them holds the whole axis; tests/test_fill_depth_hard_frames_oracle.py).
 __device__ __forceinline__ int reflect101(int p, int n) {
   if (p < 0) p = -p;
   if (p >= n) p = 2 * n - 2 - p;

@@ -15,8 +15,10 @@ published behaviour (all float32 images):
   cv2.GaussianBlur(5, 0)   sigma <= 0 and ksize 5: the fixed kernel [1 4 6 4 1]/16, separable, BORDER_REFLECT_101
 
 PARITY UNPINNED for these OpenCV conventions (no reference test or golden pins fill_depth either).  What IS pinned
-(tests/test_fill_depth.py): the morphology and the median against scipy.ndimage's independent implementations,
-bit for bit, and the HIP kernels against this file (bit-exact up to the median, float32-roundoff after the blur).
+(tests/test_fill_depth.py, tests/test_fill_depth_hard_frames_oracle.py): the morphology and the median against scipy.ndimage's
+independent implementations, bit for bit, the two blurs against float64 evaluations of the same rules per pixel, and the HIP kernels
+against this file (bit-exact up to the median, float32-roundoff after the blur), on smooth frames and on frames built to reach
+every branch (thresholds, ranges of the bilateral table, column kinds, frames smaller than the kernels, plateaus).
 """
 import math
 
@@ -117,20 +119,27 @@ def gaussian5(img):
 
 def fill_depth(depth, max_depth=2.0, extrapolate=False, blur_type="bilateral", stages=None):
     """Utils.py:455-514, statement by statement.  depth in metres (any float dtype) -> float32 metres.
-    `stages`: optional dict that receives the intermediate images (tests)."""
+    `stages`: optional dict that receives copies of the intermediate images (tests): "prepared" (inverted), "holes_filled" (after the
+    7 x 7 fill), "extrapolated", "filled" (what the median gets), "median", "blurred" (what the last comparison gets)."""
     depth = depth.astype(np.float32)
     valid = depth > 0.1
     depth[valid] = np.float32(max_depth) - depth[valid]
+    if stages is not None:
+        stages["prepared"] = depth.copy()
     depth = dilate(depth, DIAMOND5)
     depth = erode(dilate(depth, np.ones((5, 5), np.uint8)), np.ones((5, 5), np.uint8))    # MORPH_CLOSE
     empty = depth < 0.1
     dil = dilate(depth, np.ones((7, 7), np.uint8))
     depth[empty] = dil[empty]
+    if stages is not None:
+        stages["holes_filled"] = depth.copy()
     if extrapolate:
         top = np.argmax(depth > 0.1, axis=0)
         vals = depth[top, range(depth.shape[1])]
         for c in range(depth.shape[1]):
             depth[0:top[c], c] = vals[c]
+        if stages is not None:
+            stages["extrapolated"] = depth.copy()
         empty = depth < 0.1
         dil = dilate(depth, np.ones((31, 31), np.uint8))
         depth[empty] = dil[empty]
@@ -145,6 +154,8 @@ def fill_depth(depth, max_depth=2.0, extrapolate=False, blur_type="bilateral", s
         valid = depth > 0.1
         blurred = gaussian5(depth)
         depth[valid] = blurred[valid]
+    if stages is not None:
+        stages["blurred"] = depth.copy()
     valid = depth > 0.1
     depth[valid] = np.float32(max_depth) - depth[valid]
     return depth

@@ -120,6 +120,117 @@ def depth_frame_with_far_wall(seed):
     return mm
 
 
+# ---- depth frames built to reach the branches of the fill chain that smooth mid-range surfaces never reach --------------------
+# (tests/test_fill_depth_hard_frames_oracle.py proves on the CPU that each family reaches the branch it names;
+#  tests/test_gpu_fill_depth_hard_frames.py holds the HIP kernels to the oracle on them)
+def _speckle(mm, rng, frac):
+    """isolated zero pixels, none within 3 of another (the 7 x 7 fill closes each of them)"""
+    H, W = mm.shape
+    for _ in range(max(1, int(frac * H * W))):
+        y, x = int(rng.integers(0, H)), int(rng.integers(0, W))
+        if (mm[max(y - 3, 0):y + 4, max(x - 3, 0):x + 4] > 0).all():
+            mm[y, x] = 0
+    return mm
+
+
+def depth_frame_thresholds(max_depth=2.0, seed=0, H=24):
+    """The two `> 0.1` comparisons of fill_depth, before and after the inversion max_depth - d: vertical bands 12 pixels wide of
+    holes | 99 | 100 | 101 mm | a mid-range surface | far - 101 | far - 100 | far - 99 (far = max_depth in mm) | 98..102 and
+    far - 102..far - 98 per pixel | a surface beyond max_depth (negative once inverted) | the mid-range surface again."""
+    rng = np.random.default_rng(seed)
+    far = int(round(max_depth * 1000))
+    mid = far // 2
+    B = 12
+    surf = lambda: mid + rng.integers(-40, 41, (H, B))
+    bands = [np.zeros((H, B)), np.full((H, B), 99), np.full((H, B), 100), np.full((H, B), 101), surf(),
+             np.full((H, B), far - 101), np.full((H, B), far - 100), np.full((H, B), far - 99),
+             rng.integers(98, 103, (H, B)), far - rng.integers(98, 103, (H, B)), far + rng.integers(300, 900, (H, B)), surf()]
+    return np.concatenate(bands, 1).astype(np.uint16)
+
+
+def depth_frame_constant(seed=0, H=20, W=30, level=700):
+    """one flat surface with isolated holes: constant after the median, the bilateral filter's copy-through branch"""
+    return _speckle(np.full((H, W), level, np.uint16), np.random.default_rng(seed), 0.03)
+
+
+def depth_frame_near_constant(seed=0, H=20, W=30, level=700):
+    """two flat halves one millimetre apart: the smallest range above FLT_EPSILON that a uint16 frame can have after the median.
+    Every tap across the step indexes the LAST bins of the bilateral table (idx = BIL_BINS)."""
+    mm = np.full((H, W), level, np.uint16)
+    mm[:, W // 2:] = level + 1
+    return _speckle(mm, np.random.default_rng(seed), 0.03)
+
+
+def depth_frame_huge_range(seed=0, H=40, W=56):
+    """a block of 65535 (inverted: about -63.5 m, larger than every structuring element, so its core stays) inside a near surface
+    with holes and, against the block, a patch at 101 mm (the largest inverted value there is): the bilateral table's scale_index is about 63 bins per metre, the table underflows to zeros
+    and the taps across the block's rim index its last bins"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    d = 600 + 150 * np.sin(xx / 9.0) + 100 * np.cos(yy / 7.0) + rng.integers(-8, 9, (H, W))
+    d[rng.random((H, W)) < 0.08] = 0
+    d[10:30, 18:40] = 65535
+    d[12:22, 40:48] = 101                          # touches the block: the image's max next to its min
+    d[32:, :6] = 0
+    return d.astype(np.uint16)
+
+
+def depth_frame_columns(seed=0, H=20, W=257):
+    """fd_extrapolate_kernel's columns, in seven segments of W // 7 columns (the last takes the rest, so that at W = 257 the second
+    workgroup's only column has a top of its own):
+      0 a surface that reaches row 0 | 1 NO valid pixel: 100 mm (exactly 0.1, neither valid nor empty) over zeros |
+      2 a surface in the lower half only | 3 NO valid pixel: zeros over a band beyond max_depth |
+      4 the only valid pixels in the LAST row | 5, 6 a surface that starts at row 6 + x % 12, with holes"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    surf = 700 + 120 * np.sin(xx / 13.0) + 60 * np.cos(yy / 5.0) + rng.integers(-8, 9, (H, W))
+    seg = np.minimum(xx // max(W // 7, 1), 6)
+    d = np.zeros((H, W))
+    d[seg == 0] = surf[seg == 0]
+    d[(seg == 1) & (yy < H // 3)] = 100
+    m = (seg == 2) & (yy >= H // 2); d[m] = surf[m]
+    d[(seg == 3) & (yy >= H // 2) & (yy < H // 2 + 3)] = 2600
+    m = (seg == 4) & (yy == H - 1); d[m] = surf[m]
+    m = (seg >= 5) & (yy >= 6 + xx % 12) & (rng.random((H, W)) > 0.1); d[m] = surf[m]
+    if H > 31:                                     # a hole that only the 31 x 31 fill behind the extrapolation closes
+        d[H // 2:H // 2 + 16, W // 6:W // 6 + 16] = 0
+    return d.astype(np.uint16)
+
+
+def depth_frame_geometry(H, W, seed=0):
+    """any size from 1 x 1 up: a stepped surface with noise, holes, an empty first pixel (frames of four pixels and more) and a
+    valid last one.  A strip (one or two pixels across, six or more long) starts with five holes, then 700 and 640 mm: the 7-wide
+    fill closes the holes with 700, 640, 640, the median keeps a step two pixels from the end of the strip, and the taps the blurs
+    reflect there read another value than the end pixel (a strip of five or fewer is flat by the time it is blurred)."""
+    rng = np.random.default_rng(seed + 1000 * H + W)
+    yy, xx = np.mgrid[0:H, 0:W]
+    d = 600 + 20 * ((xx * 7 + yy * 13) % 11) + rng.integers(-8, 9, (H, W))
+    d[rng.random((H, W)) < 0.15] = 0
+    if min(H, W) <= 2 and max(H, W) >= 7:
+        head = np.array([0, 0, 0, 0, 0, 700, 640])
+        if W >= H:
+            d[:, :7] = head[None, :]
+        else:
+            d[:7, :] = head[:, None]
+    if H * W >= 4:
+        d[0, 0] = 0
+    d[H - 1, W - 1] = 640
+    return d.astype(np.uint16)
+
+
+def depth_frame_plateaus(seed=0, H=40, W=60):
+    """terraces of three flat levels with curved edges, a hole too large to be filled and small ones: after the fill the 25 taps of
+    the median hold two or three distinct values, and along the edges the 13th smallest sits on a step"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    ph = rng.random(4) * 6.28
+    f = np.sin(xx / 6.0 + ph[0]) + np.sin(yy / 5.0 + ph[1]) + np.sin((xx + yy) / 7.0 + ph[2]) + np.sin((xx - yy) / 9.0 + ph[3])
+    d = np.where(f < -0.7, 600, np.where(f < 0.7, 800, 1000)).astype(np.float64)
+    d[(yy - H // 2) ** 2 + (xx - W // 3) ** 2 < 81] = 0
+    d[rng.random((H, W)) < 0.1] = 0
+    return d.astype(np.uint16)
+
+
 def icosphere(subdiv=2, radius=0.05, seed=0):
     """Test mesh: subdivided icosahedron, outward (CCW) faces, random vertex colours, analytic normals."""
     t = (1 + 5 ** 0.5) / 2
