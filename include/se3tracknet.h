@@ -8,7 +8,7 @@
  * Conventions
  *   - plain C types only; device pointers are caller-owned (e.g. torch tensors' data_ptr());
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream);
- *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth) is stream-ordered and
+ *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth, fit_stats) is stream-ordered and
  *     asynchronous: no hipMalloc, no hipDeviceSynchronize, no host<->device copy of results => hipGraph-capturable.
  *     All device memory is allocated by the init-time calls: se3tn_create (activations, 176x176 z-buffer),
  *     se3tn_upload_weights / se3tn_bind_weights / se3tn_set_winograd (Winograd planes), se3tn_set_precision (f16x3 split
@@ -411,6 +411,54 @@ int se3tn_on_track_objects_live(se3tn_ctx* ctx, int n, const se3tn_object* objec
                                 double max_depth_m, int extrapolate, int blur, uint16_t* depth_filled_dev /* optional, device [H,W] */,
                                 uint8_t* rgbA_dev, uint16_t* depthA_dev, double* pose_out, float* trans_out, float* rot_out,
                                 int32_t* bbox_vu, void* stream);
+
+/* ---- how well a pose estimate fits the observed depth ------------------------------------------------------ */
+/* The reference renders the model again at its estimate after every frame (predict.py:284, render_window(final_estimate)) and
+ * pastes that render beside the observed crop for a person to look at (:285-290).  Headless, the same comparison is a record of
+ * integers.  For a pair, m(p) / o(p) = model / observed depth in millimetres at pixel p of the 176 x 176 crop, both sampled
+ * through a se3tn_crop descriptor with exactly se3tn_preprocess's / se3tn_crop_raw's index rule (resizeNN in float64, zero outside
+ * the image); valid(d) = 100 < d < 2000, the network's own validity rule (data_augmentation.py:160-164, maskA = depthA > 100 of
+ * predict.py:247).  seen_px == inlier_px + front_px + behind_px always. */
+typedef struct se3tn_fit {       /* all uint32, 32 bytes */
+  uint32_t model_px;    /* #{valid(m)}                                              */
+  uint32_t seen_px;     /* #{valid(m) && valid(o)}                                  */
+  uint32_t inlier_px;   /* #{seen && |o - m| <= tol_mm}                             */
+  uint32_t front_px;    /* #{seen && o <  m - tol_mm}   something in front          */
+  uint32_t behind_px;   /* #{seen && o >  m + tol_mm}   the sensor sees through it  */
+  uint32_t sum_abs_mm;  /* sum of |o - m| over the inliers (<= 30,976 * 65,535 < 2^32) */
+  uint32_t tol_mm;      /* echoed                                                   */
+  uint32_t _reserved;   /* 0                                                        */
+} se3tn_fit;
+/* `model` / `observed`: HOST arrays of n descriptors, as se3tn_preprocess takes them (copied into kernel arguments, no sync); only
+ * depth, H, W, left .. bottom are read (rgb may be NULL).  out_dev: n records in device memory, or in mapped pinned host memory (every
+ * word is stored there once, not accumulated there).  A launch takes SE3TN_FIT_MAX_PAIRS pairs; larger n are chunked.  Stream-ordered,
+ * capturable, allocates nothing (the per-pair counters belong to se3tn_create, and are zero again when a launch ends).  As every
+ * compute call of a context: one stream.  SE3TN_E_ARG: n outside [1, se3tn_max_batch], tol_mm outside [1, 65535], a NULL pointer,
+ * an empty window or image. */
+#define SE3TN_FIT_MAX_PAIRS 32
+int se3tn_fit_stats(se3tn_ctx* ctx, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm, se3tn_fit* out_dev,
+                    void* stream);
+/* The same check inside the one-call tracking bodies.  tol_mm = 0 (default): off -- not one launch, allocation or synchronisation more
+ * than before.  1 .. 65535: every se3tn_on_track / _live / _batch / _objects / _objects_live call that `ctx` executes gains one stage
+ * after its pose read-back: the mesh of every pair / object rendered at its ESTIMATE in the window of its PREVIOUS pose (the window
+ * route: se3tn_render's arithmetic at the y-flipped window of prev_pose; SE3TN_ROUTE_FRAME: the rectangle image A used, at the
+ * estimate) -- pixel-aligned with image B by the construction that aligns image A with it -- and se3tn_fit_stats of that render
+ * against image B's depth (the staged window of the frame; on the live calls the filled depth the rectangle pass wrote; a window that
+ * misses the frame reads its zero pixel: seen_px = 0).  The n renders take the rasteriser's four launches, the records one more, and
+ * the call waits for the stream a second time; pose, trans, rot, bbox and image A are the bits they are with the check off.  The
+ * first call with the check on allocates the render stack and the (pinned) records.  With the check on a call inside a stream capture
+ * is refused with SE3TN_E_STATE. */
+int se3tn_set_fit_check(se3tn_ctx* ctx, int tol_mm);   /* 0 = off (default) */
+int se3tn_get_fit_check(const se3tn_ctx* ctx);         /* -1 for a NULL ctx */
+/* The n records of the LAST tracking call `ctx` executed, into host memory.  SE3TN_E_STATE: that call ran with the check off, failed, or
+ * held another number of pairs / objects than n. */
+int se3tn_last_fit(se3tn_ctx* ctx, int n, se3tn_fit* out_host);
+/* The estimate renders of that call (device, the context's own, valid until its next tracking call): rgb uint8 [n,176,176,3], depth
+ * uint16 [n,176,176] -- `pred_color`, `pred_depth` of predict.py:284, with one difference: the reference renders them in the window of
+ * the ESTIMATE (render_window(final_estimate) computes a new bbox), these lie in the window of the PREVIOUS pose, the one image B was
+ * cropped with, so that the two compare pixel by pixel.  On SE3TN_ROUTE_FRAME they are the raw 176 x 176 crop_bbox of the rendered
+ * rectangle.  Either pointer may be NULL.  SE3TN_E_STATE as se3tn_last_fit. */
+int se3tn_last_fit_images(se3tn_ctx* ctx, const uint8_t** rgb_dev, const uint16_t** depth_dev);
 
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K

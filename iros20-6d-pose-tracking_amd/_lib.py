@@ -20,6 +20,7 @@ OFFSET_RULE_NUMPY1, OFFSET_RULE_NUMPY2 = 0, 1   # as include/se3tracknet.h: roun
 BLUR_NONE, BLUR_BILATERAL, BLUR_GAUSSIAN = 0, 1, 2
 COLOR_RGB, COLOR_BGR = 0, 1        # se3tn_on_track_live's / se3tn_on_track_objects_live's color_order
 ROUTE_WINDOW, ROUTE_FRAME = 0, 1   # as include/se3tracknet.h: the renderer se3tn_on_track uses for a mesh's image A
+FIT_MAX_PAIRS = 32                 # as include/se3tracknet.h: pairs per launch of se3tn_fit_stats (larger n are chunked)
 RES = 176
 
 
@@ -39,11 +40,20 @@ class Object(C.Structure):
     _fields_ = [("model", C.c_void_p), ("mesh", C.c_void_p), ("object_width_mm", C.c_double)]
 
 
+class Fit(C.Structure):
+    """se3tn_fit (include/se3tracknet.h): the fit record of one (model, observed) pair."""
+    _fields_ = [(k, C.c_uint32) for k in ("model_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm", "tol_mm",
+                                          "_reserved")]
+
+
 # the same record as a numpy dtype, for building many descriptors without a Python loop
 import numpy as _np
 CROP_DTYPE = _np.dtype([("rgb", "<u8"), ("depth", "<u8"), ("H", "<i4"), ("W", "<i4"), ("left", "<i4"), ("top", "<i4"),
                         ("right", "<i4"), ("bottom", "<i4"), ("z_offset_mm", "<f8"), ("stats", "<i4"), ("_pad", "<i4")])
 assert CROP_DTYPE.itemsize == C.sizeof(Crop)
+FIT_FIELDS = ("model_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm", "tol_mm")   # the seven that carry data
+FIT_DTYPE = _np.dtype([(k, "<u4") for k in FIT_FIELDS + ("_reserved",)])
+assert FIT_DTYPE.itemsize == C.sizeof(Fit) == 32
 
 
 _SIGS = {
@@ -117,6 +127,11 @@ _SIGS = {
     "se3tn_on_track_live": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p]),
+    "se3tn_fit_stats": (C.c_int, [C.c_void_p, C.POINTER(Crop), C.POINTER(Crop), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "se3tn_set_fit_check": (C.c_int, [C.c_void_p, C.c_int]),
+    "se3tn_get_fit_check": (C.c_int, [C.c_void_p]),
+    "se3tn_last_fit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "se3tn_last_fit_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "se3tn_compute_bbox": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(C.c_int32)]),
     "se3tn_pose_update_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float),

@@ -134,6 +134,14 @@ struct se3tn_ctx {
   float4* mo_vpost = nullptr;
   int4* mo_vsnap = nullptr;
   int *mo_big = nullptr, *mo_clipq = nullptr;
+  // se3tn_fit_stats: per-pair counters [max_batch][FitArgs::WORDS] (se3tn_create; zero between launches).  se3tn_set_fit_check: the
+  // tolerance (0 = off), the estimate renders [fit_cap,176,176,3] / [fit_cap,176,176] and the records in MAPPED pinned memory (host
+  // address | device address) -- allocated by the first tracking call with the check on; fit_last_n: pairs of the last tracking call
+  // this context executed whose records are valid (0: none)
+  unsigned* fit_counters = nullptr;
+  int fit_tol = 0, fit_last_n = 0, fit_cap = 0;
+  uint8_t* fit_rgb = nullptr; uint16_t* fit_depth = nullptr;
+  se3tn_fit *fit_host = nullptr, *fit_host_dev = nullptr;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive / splitk_sem before the next one
   int* tail_arrive = nullptr;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
   int* tail_flag = nullptr; int tail_seq = 0;   // set around se3tn_on_track's infer: the tail kernel stores tail_seq to this (mapped) word
@@ -407,6 +415,8 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
     if (e == hipSuccess) e = hipMemset(c->splitk_sem, 0, sizeof(int) * 2 * SE3TN_SPLITK_MAX_TILES);
     if (e == hipSuccess) e = hipMalloc((void**)&c->tail_arrive, sizeof(int) * c->max_batch);
     if (e == hipSuccess) e = hipMemset(c->tail_arrive, 0, sizeof(int) * c->max_batch);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->fit_counters, sizeof(unsigned) * FitArgs::WORDS * c->max_batch);
+    if (e == hipSuccess) e = hipMemset(c->fit_counters, 0, sizeof(unsigned) * FitArgs::WORDS * c->max_batch);
     if (const char* sf = std::getenv("SE3TN_SPLITK_FUSED")) c->splitk_fused = std::atoi(sf) != 0;
     if (const char* sk = std::getenv("SE3TN_SMALL_KERNELS")) c->small_kernels = std::atoi(sk) != 0;
     if (const char* tp = std::getenv("SE3TN_TAIL_PARTS")) { c->tail_parts = std::atoi(tp) != 0; c->tail_parts_ch = std::atoi(tp) == 2 ? 32 : 16; }
@@ -451,6 +461,9 @@ void se3tn_destroy(se3tn_ctx* c) {
     for (void* b : {(void*)c->mo_vpost, (void*)c->mo_vsnap, (void*)c->mo_big, (void*)c->mo_clipq})
       if (b) (void)hipFree(b);
     if (c->fd_buf) (void)hipFree(c->fd_buf);
+    for (void* b : {(void*)c->fit_counters, (void*)c->fit_rgb, (void*)c->fit_depth})
+      if (b) (void)hipFree(b);
+    if (c->fit_host) (void)hipHostFree(c->fit_host);
     if (c->fr_sub) (void)hipFree(c->fr_sub);
     if (c->fr_zbuf) (void)hipFree(c->fr_zbuf);
     for (int s = 0; s < c->slots; ++s)
@@ -1283,6 +1296,8 @@ struct StagedUpload {
   void done() { copy = nullptr; }
 };
 static int upload_staged(se3tn_ctx* c, uint8_t* dev, const uint8_t* host, size_t bytes, hipStream_t st);
+static int fit_check_stage(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* est, const double K[9], int H, int W,
+                           const se3tn::TrackWindow* windows, bool frame_route, const uint8_t* b_base, hipStream_t st, const std::string& who);
 
 // se3tn_on_track (live == nullptr) and se3tn_on_track_live: one body, two staging steps
 static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16], const double K[9], double object_width_mm,
@@ -1296,6 +1311,8 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   if (!c->have_norm) return fail(SE3TN_E_STATE, std::string(who) + ": call se3tn_set_normalization first");
   hipStream_t st = (hipStream_t)stream;
   if (live && stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_on_track_live: the call is synchronous, it cannot be captured");
+  c->fit_last_n = 0;
+  if (c->fit_tol && stream_is_capturing(st)) return fail(SE3TN_E_STATE, std::string(who) + ": the fit check waits for the stream, it cannot be captured");
   static const bool trace = std::getenv("SE3TN_TRACK_TRACE") != nullptr;   // developer switch: host-side timeline of the call
   static double acc_both[2][7] = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0}};
   static int ncall_both[2] = {0, 0};
@@ -1456,6 +1473,10 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   if (trans_out) std::memcpy(trans_out, c->trk_out_host + 128, 12);
   if (rot_out) std::memcpy(rot_out, c->trk_out_host + 144, 12);
   if (bbox_vu) std::memcpy(bbox_vu, w.vu, sizeof(w.vu));
+  if (c->fit_tol) {
+    const se3tn_mesh* mm = m;
+    return fit_check_stage(c, 1, &mm, pose_out, K, H, W, &w, frame_route, c->trk_dev, st, who);
+  }
   return SE3TN_OK;
 }
 
@@ -1590,6 +1611,140 @@ static int read_back_tracks(se3tn_ctx* c, int n, hipStream_t st, double* pose_ou
   return SE3TN_OK;
 }
 
+// ---- the fit record ---------------------------------------------------------------------------------------------------------------
+int se3tn_fit_stats(se3tn_ctx* c, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm, se3tn_fit* out_dev, void* stream) {
+  if (!c || c->device < 0 || !model || !observed || !out_dev) return fail(SE3TN_E_ARG, "se3tn_fit_stats: bad argument");
+  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_fit_stats: n outside [1, max_batch]");
+  if (tol_mm < 1 || tol_mm > 65535) return fail(SE3TN_E_ARG, "se3tn_fit_stats: tol_mm outside [1, 65535]");
+  for (int i = 0; i < n; ++i)
+    for (const se3tn_crop* k : {model + i, observed + i})
+      if (!k->depth || k->H < 1 || k->W < 1 || k->right <= k->left || k->bottom <= k->top)
+        return fail(SE3TN_E_ARG, "se3tn_fit_stats: descriptor " + std::to_string(i) + ": NULL depth, empty image or empty window");
+  for (int g0 = 0; g0 < n; g0 += FitArgs::MAX) {   // the descriptors travel as kernel arguments, FitArgs::MAX pairs per launch
+    const int k = n - g0 < FitArgs::MAX ? n - g0 : FitArgs::MAX;
+    FitArgs a;
+    std::memcpy(a.m, model + g0, sizeof(se3tn_crop) * k);
+    std::memcpy(a.o, observed + g0, sizeof(se3tn_crop) * k);
+    a.counters = c->fit_counters + (size_t)FitArgs::WORDS * g0;
+    a.out = out_dev + g0;
+    a.tol = tol_mm;
+    HIPCHK(launch_fit_stats(a, k, (hipStream_t)stream));
+  }
+  return SE3TN_OK;
+}
+
+int se3tn_set_fit_check(se3tn_ctx* c, int tol_mm) {
+  if (!c || tol_mm < 0 || tol_mm > 65535) return fail(SE3TN_E_ARG, "se3tn_set_fit_check: tol_mm must be 0 (off) or 1 .. 65535");
+  c->fit_tol = tol_mm;
+  return SE3TN_OK;
+}
+int se3tn_get_fit_check(const se3tn_ctx* c) { return c ? c->fit_tol : -1; }
+
+int se3tn_last_fit(se3tn_ctx* c, int n, se3tn_fit* out_host) {
+  if (!c || !out_host || n < 1) return fail(SE3TN_E_ARG, "se3tn_last_fit: bad argument");
+  if (c->fit_last_n == 0) return fail(SE3TN_E_STATE, "se3tn_last_fit: the last tracking call of this context left no records (se3tn_set_fit_check off, or the call failed)");
+  if (c->fit_last_n != n) return fail(SE3TN_E_STATE, "se3tn_last_fit: the last tracking call held " + std::to_string(c->fit_last_n) + " pairs, not " + std::to_string(n));
+  std::memcpy(out_host, c->fit_host, sizeof(se3tn_fit) * (size_t)n);
+  return SE3TN_OK;
+}
+
+int se3tn_last_fit_images(se3tn_ctx* c, const uint8_t** rgb_dev, const uint16_t** depth_dev) {
+  if (!c) return fail(SE3TN_E_ARG, "se3tn_last_fit_images: null ctx");
+  if (c->fit_last_n == 0) return fail(SE3TN_E_STATE, "se3tn_last_fit_images: the last tracking call of this context left no estimate renders (se3tn_set_fit_check off, or the call failed)");
+  if (rgb_dev) *rgb_dev = c->fit_rgb;
+  if (depth_dev) *depth_dev = c->fit_depth;
+  return SE3TN_OK;
+}
+
+static int reserve_objects_raster(se3tn_ctx* c, int n, int V, int F);
+
+// se3tn_set_fit_check's stage of the three bodies, after their pose read-back (so `st` is idle and the instance table, the rasteriser
+// scratch and, on the frame route, the rectangles' sub-images and z-buffers of image A are free again): every pair's mesh rendered at
+// its ESTIMATE est[i] in the window of its PREVIOUS pose -- the window route at windows[i].winA into the context's render stack, the
+// frame route into the rectangle image A was rendered into -- n instances in the rasteriser's four launches, each with its own mesh
+// (and material); then the fit kernel: the model descriptor is what crop_pair builds for image A, now showing that render, the observed
+// one is image B's (the staged window at b_base; live: the filled depth the rectangle pass wrote; a miss: its zero pixel).  On the frame
+// route the fit launch also leaves the raw 176 x 176 crop of every render in the stack.  The records land in mapped pinned memory;
+// the call waits for `st` once more
+static int fit_check_stage(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* est, const double K[9], int H, int W,
+                           const TrackWindow* windows, bool frame_route, const uint8_t* b_base, hipStream_t st, const std::string& who) {
+  int maxV = 0, maxF = 0;
+  for (int i = 0; i < n; ++i) {
+    maxV = meshes[i]->V > maxV ? meshes[i]->V : maxV;
+    maxF = meshes[i]->F > maxF ? meshes[i]->F : maxF;
+  }
+  if (n > c->fit_cap) {   // first call with the check on (or a larger n than max_batch: never)
+    DeviceGuard dg(c->device);
+    if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+    HIPCHK(hipDeviceSynchronize());
+    for (void* b : {(void*)c->fit_rgb, (void*)c->fit_depth})
+      if (b) HIPCHK(hipFree(b));
+    if (c->fit_host) HIPCHK(hipHostFree(c->fit_host));
+    c->fit_rgb = nullptr; c->fit_depth = nullptr; c->fit_host = nullptr; c->fit_host_dev = nullptr; c->fit_cap = 0;
+    const int cap = n > c->max_batch ? n : c->max_batch;
+    HIPCHK(hipMalloc((void**)&c->fit_rgb, (size_t)RES * RES * 3 * cap));
+    HIPCHK(hipMalloc((void**)&c->fit_depth, (size_t)RES * RES * 2 * cap));
+    HIPCHK(hipHostMalloc((void**)&c->fit_host, sizeof(se3tn_fit) * cap, hipHostMallocMapped));
+    std::memset(c->fit_host, 0, sizeof(se3tn_fit) * cap);
+    HIPCHK(hipHostGetDevicePointer((void**)&c->fit_host_dev, c->fit_host, 0));
+    c->fit_cap = cap;
+  }
+  if (int rc = reserve_track_batch(c, nullptr, n, 0)) return rc;
+  if (int rc = reserve_objects_raster(c, n, maxV, maxF)) return rc;
+  size_t maxpx = 0, fr_d_off = 0;
+  if (frame_route)
+    if (int rc = reserve_frame_rects(c, n, windows, H, W, &maxpx, &fr_d_off)) return rc;
+  RasterArgs ra{};
+  raster_common(ra, c, const_cast<se3tn_mesh*>(meshes[0]), c->fit_rgb, c->fit_depth);
+  ra.rw = RES; ra.rh = RES; ra.mode = 0;
+  ra.vpost = c->mo_vpost; ra.vsnap = c->mo_vsnap; ra.big = c->mo_big; ra.clipq = c->mo_clipq; ra.zbuf = c->tb_zbuf;
+  ra.V = maxV; ra.F = maxF; ra.inst_mesh = 1;
+  RasterMaterial* mat_host = (RasterMaterial*)(c->tb_inst_host + n);
+  if (frame_route) {
+    ra.rw = W; ra.rh = H; ra.mode = 1;
+    ra.rgb = c->fr_sub + 64; ra.depth = (uint16_t*)(c->fr_sub + fr_d_off);
+    ra.zbuf = c->fr_zbuf;
+    ra.scissor = 1; ra.spx = (int)maxpx;
+    ra.inst_mesh = 2;
+  }
+  for (int i = 0; i < n; ++i) {
+    const se3tn_mesh* m = meshes[i];
+    RasterInstance& I = c->tb_inst_host[i];
+    if (!fill_instance(I, frame_route, m, est + 16 * (size_t)i, K, W, H, windows[i]))
+      return fail(SE3TN_E_ARG, who + ": fit check: singular pose estimate");
+    I.verts = m->verts; I.normals = m->normals; I.colors = m->colors; I.faces = m->faces; I.V = m->V; I.F = m->F;
+    if (frame_route) {
+      RasterMaterial& M = mat_host[i];
+      M.uv = m->uv; M.tex = m->tex; M.tw = m->tw; M.th = m->th; M.tlevels = m->tlevels;
+      std::memcpy(M.kd, m->kd, sizeof(M.kd));
+      std::memcpy(M.tex_off, m->tex_off, sizeof(M.tex_off));
+    }
+  }
+  if (!frame_route || maxpx > 0) {   // (frame route with every window off the frame: nothing to render)
+    const size_t tab_bytes = sizeof(RasterInstance) * n + (frame_route ? sizeof(RasterMaterial) * n : 0);
+    HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, tab_bytes, hipMemcpyHostToDevice, st));
+    ra.inst = c->tb_inst_dev;
+    HIPCHK(launch_raster(ra, st, n));
+  }
+  for (int g0 = 0; g0 < n; g0 += FitArgs::MAX) {
+    const int k = n - g0 < FitArgs::MAX ? n - g0 : FitArgs::MAX;
+    FitArgs a;
+    for (int j = 0; j < k; ++j)
+      crop_pair(windows[g0 + j], 0.0, image_a(c, frame_route, g0 + j, c->fit_rgb, c->fit_depth, maxpx, fr_d_off), b_base, a.m[j], a.o[j]);
+    a.counters = c->fit_counters + (size_t)FitArgs::WORDS * g0;
+    a.out = c->fit_host_dev + g0;
+    a.tol = c->fit_tol;
+    if (frame_route) {
+      a.raw_rgb = c->fit_rgb + (size_t)g0 * RES * RES * 3;
+      a.raw_depth = c->fit_depth + (size_t)g0 * RES * RES;
+    }
+    HIPCHK(launch_fit_stats(a, k, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  c->fit_last_n = n;
+  return SE3TN_OK;
+}
+
 int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_poses, const double K[9], double object_width_mm,
                          const uint8_t* const* rgb, const uint16_t* const* depth, int H, int W, uint8_t* rgbA_dev, uint16_t* depthA_dev,
                          double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu, void* stream) {
@@ -1598,6 +1753,7 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_on_track_batch: n outside [1, max_batch]");
   if (!c->have_norm) return fail(SE3TN_E_STATE, "se3tn_on_track_batch: call se3tn_set_normalization first");
   if (stream_is_capturing((hipStream_t)stream)) return fail(SE3TN_E_STATE, "se3tn_on_track_batch: synchronous call, not capturable");
+  c->fit_last_n = 0;
   hipStream_t st = (hipStream_t)stream;
   static const bool trace = std::getenv("SE3TN_TRACK_TRACE") != nullptr;   // developer switch: host-side timeline of the call
   static double tb_acc[6] = {0, 0, 0, 0, 0, 0};
@@ -1695,6 +1851,10 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
       for (double& v : tb_acc) v = 0;
     }
   }
+  if (c->fit_tol) {
+    const std::vector<const se3tn_mesh*> meshes(n, m);
+    return fit_check_stage(c, n, meshes.data(), pose_out, K, H, W, windows.data(), frame_route, c->tb_stage_dev, st, "se3tn_on_track_batch");
+  }
   return SE3TN_OK;
 }
 
@@ -1780,6 +1940,7 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
   if (!c->small_kernels) return fail(SE3TN_E_STATE, fn + ": ctx has the batch 1-5 kernels switched off (se3tn_set_small_kernels)");
   if (c->keep_intermediates) return fail(SE3TN_E_STATE, fn + ": ctx keeps intermediates (se3tn_keep_intermediates)");
   if (stream_is_capturing((hipStream_t)stream)) return fail(SE3TN_E_STATE, fn + ": synchronous call, not capturable");
+  c->fit_last_n = 0;
   const std::string who = fn + ": object ";
   int maxV = 0, maxF = 0;
   // one rasteriser mode per launch, so one route per call: all objects on SE3TN_ROUTE_WINDOW (vertex-colour meshes) or all on
@@ -1958,6 +2119,11 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
   if (rc != SE3TN_OK) { c->rearm_counters = true; return rc; }
   if ((rc = read_back_tracks(c, n, st, pose_out, trans_out, rot_out, bbox_vu, windows.data()))) return rc;
   up.done();
+  if (c->fit_tol) {
+    std::vector<const se3tn_mesh*> meshes(n);
+    for (int i = 0; i < n; ++i) meshes[i] = objs[i].mesh;
+    return fit_check_stage(c, n, meshes.data(), pose_out, K, H, W, windows.data(), frame_route, c->tb_stage_dev, st, fn);
+  }
   return SE3TN_OK;
 }
 

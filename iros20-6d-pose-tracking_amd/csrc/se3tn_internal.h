@@ -242,6 +242,22 @@ struct CropArgs {  // one launch handles up to MAX crops
 
 static_assert(sizeof(CropArgs) <= 4096, "CropArgs travels as kernel arguments: HIP's limit is 4 KB");
 
+// fit record of up to MAX (model, observed) pairs per launch (fit_stats.hip); the descriptors travel as kernel arguments
+struct FitArgs {
+  static constexpr int MAX = SE3TN_FIT_MAX_PAIRS;   // 2 x 32 x 56 B + constants = 3.6 KB of kernel arguments (limit 4 KB, asserted below)
+  static constexpr int WORDS = 8;                    // counter words per pair: the six sums | the arrival counter | unused
+  se3tn_crop m[MAX], o[MAX];  // model / observed image of pair i: depth, H, W, left .. bottom are read (rgb: with raw_rgb only)
+  unsigned* counters;         // [n][WORDS], zero between launches (the last workgroup of a pair to arrive re-arms them)
+  se3tn_fit* out;             // [n] records: device memory, or mapped pinned host memory (each word stored once)
+  int tol;
+  // non-null: pair i also stores the raw crop of its MODEL image (crop_bbox alone, what launch_crop_raw writes) as image i of
+  // raw_rgb [n,176,176,3] / raw_depth [n,176,176] -- the estimate render of the full-frame route, in the launch that scores it
+  uint8_t* raw_rgb = nullptr;
+  uint16_t* raw_depth = nullptr;
+};
+static_assert(sizeof(FitArgs) <= 4096, "FitArgs travels as kernel arguments: HIP's limit is 4 KB");
+hipError_t launch_fit_stats(const FitArgs& a, int n, hipStream_t st);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per DEVICE: a launcher remembers which device
 // ordinals it has already raised the limit on (several contexts on different GPUs in one process).
 struct PerDeviceOnce {

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CROP_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import CROP_DTYPE, FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -42,6 +42,7 @@ class Engine:
         self._h = h
         self._blob = None  # keeps a bound (caller-owned) weight blob alive
         self.has_weights = False
+        self._fit_tol = None   # what set_fit_check last set (the per-frame paths read this, not the library)
         if self.device >= 0:
             torch.cuda.set_device(self.device)
 
@@ -228,9 +229,9 @@ class Engine:
         ptr = out.data_ptr() if torch.is_tensor(out) else int(out)
         check(self.lib.se3tn_preprocess(self._h, arr, n, C.c_void_p(ptr), _stream_ptr()), "se3tn_preprocess")
 
-    def crop_raw(self, rgb, depth, window):
+    def crop_raw(self, rgb, depth, window, device=False):
         """crop_bbox (Utils.py:320-359) alone: numpy rgb u8 [H,W,3] + depth u16 [H,W], window (left, top, right,
-        bottom) -> numpy (rgb u8 [176,176,3], depth u16 [176,176])."""
+        bottom) -> numpy (rgb u8 [176,176,3], depth u16 [176,176]); device=True: the device tensors (uint8, uint16-as-int16)."""
         dev = "cuda:%d" % self.device
         rgb_d = rgb if torch.is_tensor(rgb) else torch.from_numpy(np.ascontiguousarray(rgb, dtype=np.uint8)).to(dev)
         dep_d = depth if torch.is_tensor(depth) else torch.from_numpy(np.ascontiguousarray(depth, dtype=np.uint16).view(np.int16)).to(dev)
@@ -244,7 +245,64 @@ class Engine:
         out_d = torch.empty((RES, RES), dtype=torch.int16, device=dev)
         check(self.lib.se3tn_crop_raw(self._h, C.byref(c), C.c_void_p(out_rgb.data_ptr()), C.c_void_p(out_d.data_ptr()),
                                       _stream_ptr()), "se3tn_crop_raw")
+        if device:
+            return out_rgb, out_d
         return out_rgb.cpu().numpy(), out_d.cpu().numpy().view(np.uint16)
+
+    # ---- how well an estimate fits the observed depth -------------------------------------------
+    def fit_stats(self, model, observed, tol_mm):
+        """se3tn_fit_stats: model / observed = n descriptors each, dict(depth=cuda 16-bit [H,W], window=(left, top, right, bottom))
+        (the crop window in that image, as preprocess takes it) or 176 x 176 device depth images (window = the whole image).
+        Returns the n records as a structured array (_lib.FIT_DTYPE: model_px, seen_px, inlier_px, front_px, behind_px, sum_abs_mm,
+        tol_mm); synchronises on the current stream."""
+        n = len(model)
+        if len(observed) != n:
+            raise ValueError("fit_stats: %d model and %d observed descriptors" % (n, len(observed)))
+        arrs = []
+        for group in (model, observed):
+            arr = (Crop * max(n, 1))()
+            for i, c in enumerate(group):
+                if torch.is_tensor(c):
+                    c = dict(depth=c, window=(0, 0, int(c.shape[1]), int(c.shape[0])))
+                depth = c["depth"]
+                assert depth.is_cuda and depth.element_size() == 2 and depth.is_contiguous() and depth.dim() == 2
+                arr[i].rgb = None; arr[i].depth = depth.data_ptr()
+                arr[i].H, arr[i].W = int(depth.shape[0]), int(depth.shape[1])
+                arr[i].left, arr[i].top, arr[i].right, arr[i].bottom = [int(v) for v in c["window"]]
+            arrs.append(arr)
+        out = torch.empty((max(n, 1), 32), dtype=torch.uint8, device="cuda:%d" % self.device)
+        check(self.lib.se3tn_fit_stats(self._h, arrs[0], arrs[1], n, int(tol_mm), C.c_void_p(out.data_ptr()), _stream_ptr()),
+              "se3tn_fit_stats")
+        return out.cpu().numpy().reshape(-1).view(FIT_DTYPE)[:n].copy()
+
+    def set_fit_check(self, tol_mm):
+        """se3tn_set_fit_check: every one-call tracking call this engine executes also scores its estimates against the observed
+        depth with this tolerance in millimetres (None / 0: off, the default)."""
+        check(self.lib.se3tn_set_fit_check(self._h, int(tol_mm or 0)), "se3tn_set_fit_check")
+        self._fit_tol = int(tol_mm) if tol_mm else None
+
+    def get_fit_check(self):
+        """The tolerance in force, or None when the check is off."""
+        return self._fit_tol
+
+    def last_fit(self, n):
+        """The n records of the last tracking call this engine executed (structured array, _lib.FIT_DTYPE)."""
+        out = np.zeros(int(n), FIT_DTYPE)
+        check(self.lib.se3tn_last_fit(self._h, int(n), C.c_void_p(out.ctypes.data)), "se3tn_last_fit")
+        return out
+
+    def last_fit_images(self, n, rgb_out=None, depth_out=None):
+        """Copies of the estimate renders of that call: device tensors uint8 [n,176,176,3], uint16-as-int16 [n,176,176]
+        (stream-ordered copies into rgb_out / depth_out when given)."""
+        rgb_p, dep_p = C.c_void_p(), C.c_void_p()
+        check(self.lib.se3tn_last_fit_images(self._h, C.byref(rgb_p), C.byref(dep_p)), "se3tn_last_fit_images")
+        dev = "cuda:%d" % self.device
+        n = int(n)
+        rgb = rgb_out if rgb_out is not None else torch.empty((n, RES, RES, 3), dtype=torch.uint8, device=dev)
+        dep = depth_out if depth_out is not None else torch.empty((n, RES, RES), dtype=torch.int16, device=dev)
+        check(self.lib.se3tn_memcpy_d2d(C.c_void_p(rgb.data_ptr()), rgb_p, n * RES * RES * 3, _stream_ptr()), "se3tn_memcpy_d2d")
+        check(self.lib.se3tn_memcpy_d2d(C.c_void_p(dep.data_ptr()), dep_p, n * RES * RES * 2, _stream_ptr()), "se3tn_memcpy_d2d")
+        return rgb, dep
 
     def fill_depth(self, depth_mm, max_depth=2.0, extrapolate=False, blur_type="bilateral", return_metres=False):
         """Utils.py:455-514 fill_depth as predict_ros.py:38-41 applies it: uint16 millimetre frame (numpy [H,W] or a

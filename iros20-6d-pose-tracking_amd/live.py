@@ -55,6 +55,20 @@ class LiveTracker:
         self._filled_dev = None    # one_call: the filled frame of the last on_track, on the device
         self._filled_valid = False
 
+    @property
+    def fit_check(self):
+        """The tracker's fit_check (None | tol_mm): with it set every on_track also scores the estimate against the observed depth;
+        last_fit_ratio and tracker.last_prediction["fit" / "pred_rgb" / "pred_depth"] carry the result."""
+        return self.tracker.fit_check
+
+    @fit_check.setter
+    def fit_check(self, tol_mm):
+        self.tracker.fit_check = tol_mm
+
+    @property
+    def last_fit_ratio(self):
+        return self.tracker.last_fit_ratio
+
     def reset(self, pose_init):
         self.color = None
         self._depth = None
@@ -140,6 +154,20 @@ class LiveMultiTracker:
         if p.shape[0] != self.tracker.n:
             raise ValueError("LiveMultiTracker: %d poses for %d objects" % (p.shape[0], self.tracker.n))
         return p
+
+    @property
+    def fit_check(self):
+        """The tracker's fit_check (None | tol_mm): with it set every on_track also scores the estimate against the observed depth;
+        last_fit_ratio and tracker.last_prediction["fit" / "pred_rgb" / "pred_depth"] carry the result."""
+        return self.tracker.fit_check
+
+    @fit_check.setter
+    def fit_check(self, tol_mm):
+        self.tracker.fit_check = tol_mm
+
+    @property
+    def last_fit_ratio(self):
+        return self.tracker.last_fit_ratio
 
     def reset(self, poses_init):
         self.color = None

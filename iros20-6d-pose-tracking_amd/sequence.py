@@ -102,13 +102,18 @@ def poserbpf_pose(ycb_dir, class_id, seq_id):
 
 
 def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, reinit=None, max_frames=None, init="gt",
-                         reinit_frames=None, ycb_dir=None, seq_id=None):
+                         reinit_frames=None, ycb_dir=None, seq_id=None, reinit_below=None):
     """tracker: se3tracknet_amd.Tracker.
     init: 'gt' (what predict.py:447 hard-codes) | 'posecnn' (:480-496: start at the keyframe nearest to start_frame) | 'poserbpf'.
     reinit_frames: the reference's --reinit_frames, a comma-separated string or list of 'SSSS/FFFFFF': before tracking the image
     with index i (0-based; its YCB frame id is i + 1), if 'SSSS/%06d' % (i + 1) is listed, the pose fed in is the PoseCNN estimate
     nearest to frame NUMBER i - 1 (predict.py:538-541, use_posecnn_res).  Needs ycb_dir (the dataset root) and seq_id (default:
-    the directory name).  reinit: alternatively {frame_index: 4x4 pose}."""
+    the directory name).  reinit: alternatively {frame_index: 4x4 pose}.
+    reinit_below (extension): a fit ratio.  With ``tracker.fit_check`` set, before tracking index i the pose fed in is the PoseCNN
+    estimate nearest to frame number i - 1 -- the reference's rule for a listed frame -- whenever the previous call's
+    ``tracker.last_fit_ratio`` (inlier_px / model_px of its estimate against the observed depth) was below it: the list
+    --reinit_frames takes from somebody who watched the canvas, decided by the fit.  The indices come back as res["reinit_at"].
+    None (default): nothing changes."""
     rgb_files = sorted(glob.glob(os.path.join(seq_dir, "color", "*")))
     depth_files = sorted(glob.glob(os.path.join(seq_dir, "depth_filled", "*")))
     gt_files = sorted(glob.glob(os.path.join(seq_dir, "pose_gt", str(class_id), "*")))
@@ -117,9 +122,10 @@ def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, rei
     if isinstance(reinit_frames, str):
         reinit_frames = reinit_frames.split(",")
     reinit_frames = list(reinit_frames or [])
-    if seq_id is None and (reinit_frames or init != "gt"):
+    fit_driven = reinit_below is not None and bool(getattr(tracker, "fit_check", None))
+    if seq_id is None and (reinit_frames or init != "gt" or fit_driven):
         seq_id = int(os.path.basename(os.path.normpath(seq_dir)))
-    if (reinit_frames or init != "gt") and ycb_dir is None:
+    if (reinit_frames or init != "gt" or fit_driven) and ycb_dir is None:
         raise ValueError("PoseCNN / PoseRBPF initialisation needs ycb_dir (image_sets/, YCB_Video_toolbox/)")
     if init == "gt":
         prev_pose = gt_poses[start_frame].copy()          # predict.py:478-479
@@ -147,6 +153,7 @@ def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, rei
     pred_poses = [prev_pose]
     os.makedirs(out_dir, exist_ok=True)
     t_track = 0.0
+    prev_ratio, reinit_at = None, []
     for i in range(start_frame + 1, end):
         rgb = read_rgb(rgb_files[i])
         depth = read_depth_mm(depth_files[i])
@@ -155,9 +162,14 @@ def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, rei
             A_in_cam = np.asarray(reinit[i], np.float64).copy()
         if reinit_frames and "%04d/%06d" % (seq_id, i + 1) in reinit_frames:          # predict.py:538-541
             A_in_cam = use_posecnn_res(ycb_dir, class_id, "%04d/%06d" % (seq_id, i - 1))
+        if fit_driven and prev_ratio is not None and prev_ratio < reinit_below:
+            A_in_cam = use_posecnn_res(ycb_dir, class_id, "%04d/%06d" % (seq_id, i - 1))
+            reinit_at.append(i)
         t0 = time.perf_counter()
         cur_pose = tracker.on_track(A_in_cam, rgb, depth, gt_A_in_cam=gt_poses[i - 1], gt_B_in_cam=gt_poses[i])
         t_track += time.perf_counter() - t0
+        if fit_driven:
+            prev_ratio = tracker.last_fit_ratio
         prev_pose = cur_pose.copy()
         pred_poses.append(cur_pose)
     pred_poses = np.array(pred_poses)
@@ -170,6 +182,8 @@ def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, rei
             adi_errs.append(metrics.adi(pred_poses[k], gt_poses[start_frame + k], tracker.object_cloud))
     res = {"poses": pred_poses, "frames": len(pred_poses) - 1,
            "hz": (len(pred_poses) - 1) / t_track if t_track > 0 else float("nan")}
+    if reinit_below is not None:
+        res["reinit_at"] = reinit_at
     if adi_errs:
         res.update(add_errs=np.array(add_errs), adi_errs=np.array(adi_errs))
         res["add_auc"] = metrics.auc(add_errs)    # 0.0 when no frame is below 0.1 m (the reference's VOCap raises)

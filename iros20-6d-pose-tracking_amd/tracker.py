@@ -112,12 +112,63 @@ class Tracker:
         self._trans = self._out[ms * 128:ms * 140].view(torch.float32).view(ms, 3)
         self._rot = self._out[ms * 140:ms * 152].view(torch.float32).view(ms, 3)
         self.last_prediction = None
+        self.last_fit_ratio = None   # fit_check set: inlier_px / model_px of the last call (float; on_track_batch: [n] array)
+        self._fit_imgs = None
         # optional hipGraph replay of the ~20 dependent launches of a frame on a dedicated stream (the
         # null stream cannot be captured).  Off by default: measured 0.213 ms/frame with vs 0.194 without
         # (profiles/EXPERIMENTS.md item 54: the kernels are 5-15 us each and the eager launches already run ahead of the device)
         self._stream = torch.cuda.Stream(device=dev) if use_graphs else None
         if use_graphs:
             self.engine.enable_graphs(True)
+
+    @property
+    def fit_check(self):
+        """None (default) | tol_mm: every on_track / on_track_live / on_track_batch also scores its estimate against the observed
+        depth (se3tn_set_fit_check): the model rendered at the estimate in the window of the previous pose, compared with the depth
+        image B was cropped from.  last_prediction then carries ``fit`` (the records: structured array with model_px, seen_px,
+        inlier_px, front_px, behind_px, sum_abs_mm, tol_mm), ``pred_rgb`` / ``pred_depth`` (device tensors [n,176,176,3] /
+        [n,176,176]: `pred_color`, `pred_depth` of predict.py:284, in the previous pose's window) and last_fit_ratio is
+        inlier_px / model_px."""
+        return self.engine.get_fit_check()
+
+    @fit_check.setter
+    def fit_check(self, tol_mm):
+        self.engine.set_fit_check(tol_mm)
+        if not tol_mm:
+            self.last_fit_ratio = None
+
+    def _fit_from_call(self, n, single):
+        """fit_check set: the records and estimate renders the library call just left (se3tn_last_fit / _images) into last_prediction"""
+        if not self.engine.get_fit_check():
+            self.last_fit_ratio = None
+            return
+        fit = self.engine.last_fit(n)
+        if self._fit_imgs is None or self._fit_imgs[0].shape[0] < n:
+            self._fit_imgs = (torch.empty((n, 176, 176, 3), dtype=torch.uint8, device=self._dev),
+                              torch.empty((n, 176, 176), dtype=torch.int16, device=self._dev))
+        self.engine.last_fit_images(n, self._fit_imgs[0], self._fit_imgs[1])
+        self.last_prediction.update(fit=fit, pred_rgb=self._fit_imgs[0][:n], pred_depth=self._fit_imgs[1][:n])
+        r = U.fit_ratio(fit)
+        self.last_fit_ratio = float(r[0]) if single else r
+
+    def _fit_stepwise(self, prev_poses, ests, frame_depths, bboxes, single):
+        """fit_check set on the step-by-step path: per pair a render at the ESTIMATE in the window of the PREVIOUS pose
+        (render_window(est, window_of=prev)) against the uploaded frame under image B's window, through Engine.fit_stats -- the
+        records the one-call path gets from the library's own stage."""
+        tol = self.engine.get_fit_check()
+        if not tol:
+            self.last_fit_ratio = None
+            return
+        model, observed, rgbs = [], [], []
+        for prev, est, dep_d, bb in zip(prev_poses, ests, frame_depths, bboxes):
+            rgbP, depP = self.render_window(est, window_of=prev)
+            rgbs.append(torch.from_numpy(np.ascontiguousarray(rgbP)).to(self._dev))
+            model.append(torch.from_numpy(np.ascontiguousarray(depP).astype(np.uint16).view(np.int16)).to(self._dev))
+            observed.append(dict(depth=dep_d, window=U.crop_window(bb)))
+        fit = self.engine.fit_stats(model, observed, tol)
+        self.last_prediction.update(fit=fit, pred_rgb=torch.stack(rgbs), pred_depth=torch.stack(model))
+        r = U.fit_ratio(fit)
+        self.last_fit_ratio = float(r[0]) if single else r
 
     def _read_back(self, n):
         """(poseB [n,4,4] float64, trans [n,3], rot [n,3] float32) of the last engine call: one device-to-host copy."""
@@ -128,8 +179,10 @@ class Tracker:
         rot = host[ms * 140:ms * 152].view(np.float32).reshape(ms, 3)[:n].copy()
         return poseB, trans, rot
 
-    def render_window(self, ob2cam):
-        """predict.py:193-215.  Three renderer protocols, in the reference's order:
+    def render_window(self, ob2cam, window_of=None):
+        """predict.py:193-215.  window_of (extension): the pose whose bbox gives the window (default: ob2cam itself, as the
+        reference) -- the fit check renders the estimate in the previous pose's window.  Three renderer protocols, in the
+        reference's order:
           * VispyRenderer-like objects (``update_cam_mat`` + ``render_image``): driven exactly as
             predict.py:201-208 does -- y-flipped bbox (scale (1000,-1000,1000)), ``update_cam_mat(K, left,
             right, bottom, top)``, ``render_image(ob2cam_gl)``;
@@ -142,11 +195,12 @@ class Tracker:
             raise RuntimeError("Tracker.render_window: no renderer injected (rendering is outside the HIP hot path)")
         from .renderer import HipRenderer
         ob2cam = np.asarray(ob2cam, np.float64)
+        wpose = ob2cam if window_of is None else np.asarray(window_of, np.float64)
         if isinstance(self.renderer, HipRenderer) and self.renderer.full_frame:     # predict.py:209-213
             rgb_d, dep_d = self.renderer.render_frame_device(ob2cam, self.K)
-            bbox = U.compute_bbox(ob2cam, self.K, self.object_width, scale=(1000, 1000, 1000))
+            bbox = U.compute_bbox(wpose, self.K, self.object_width, scale=(1000, 1000, 1000))
             return self.engine.crop_raw(rgb_d, dep_d, U.crop_window(bbox))
-        win = HipRenderer.gl_window(ob2cam, self.K, self.object_width)      # left, top, right, bottom (GL image)
+        win = HipRenderer.gl_window(wpose, self.K, self.object_width)      # left, top, right, bottom (GL image)
         if hasattr(self.renderer, "update_cam_mat") and hasattr(self.renderer, "render_image"):
             glcam_in_cvcam = np.diag([1.0, -1.0, -1.0, 1.0])
             self.renderer.update_cam_mat(self.K, win[0], win[2], win[3], win[1])
@@ -154,7 +208,7 @@ class Tracker:
         if _is_full_frame_renderer(self.renderer):
             rgb, depth = self.renderer.render([ob2cam])
             depth = (np.asarray(depth) * 1000).astype(np.uint16)
-            bbox = U.compute_bbox(ob2cam, self.K, self.object_width, scale=(1000, 1000, 1000))
+            bbox = U.compute_bbox(wpose, self.K, self.object_width, scale=(1000, 1000, 1000))
             return self.engine.crop_raw(rgb, depth, U.crop_window(bbox))
         return self.renderer.render(ob2cam, self.K, win)
 
@@ -199,6 +253,7 @@ class Tracker:
                           self._trans, self._rot, self._poseA, self._poseB)
         poseB, trans_h, rot_h = self._read_back(n)               # one D2H + sync, as predict.py:275-276
         self.last_prediction = dict(trans=trans_h, rot=rot_h, bbox=bb)
+        self._fit_stepwise([prev_pose], [poseB[0]], [dep_d], [bb], True)
         self.prev_rgb = current_rgb
         self.prev_depth = current_depth
         self.frame_cnt += 1
@@ -249,6 +304,7 @@ class Tracker:
         self.last_prediction = dict(trans=st["tr"].reshape(1, 3).copy(), rot=st["ro"].reshape(1, 3).copy(), bbox=st["bb"].copy())
         if "rgbA" in st:
             self.last_prediction.update(rgbA=rgbA, depthA=depthA)
+        self._fit_from_call(1, True)
         self.prev_rgb = current_rgb
         self.prev_depth = current_depth
         self.frame_cnt += 1
@@ -350,6 +406,7 @@ class Tracker:
             C.c_void_p(out.ctypes.data), C.c_void_p(tr.ctypes.data), C.c_void_p(ro.ctypes.data), C.c_void_p(bb.ctypes.data), _stream_ptr()),
             "se3tn_on_track_batch")
         self.last_prediction = dict(trans=tr, rot=ro, bbox=bb, rgbA=list(st["rgbA"][:n]), depthA=list(st["depthA"][:n]))
+        self._fit_from_call(n, False)
         self.frame_cnt += 1
         return out.reshape(n, 4, 4)
 
@@ -386,6 +443,7 @@ class Tracker:
         out, trans_h, rot_h = self._read_back(n)
         # what on_track keeps in last_prediction / renderer.rgb, per pair (callers that log or check the step)
         self.last_prediction = dict(trans=trans_h, rot=rot_h, bbox=np.stack(bboxes), rgbA=keep[0::4], depthA=keep[1::4])
+        self._fit_stepwise(poses, out, keep[3::4], bboxes, False)
         self.frame_cnt += 1
         return out
 
@@ -433,7 +491,22 @@ class MultiTracker:
         self._depthA = torch.empty((self.n, 176, 176), dtype=torch.int16, device=self._dev)
         self._C = C
         self.last_prediction = None
+        self.last_fit_ratio = None   # fit_check set: inlier_px / model_px per object of the last call ([n] array)
+        self._pred_rgb = self._pred_depth = None
         self.frame_cnt = 0
+
+    @property
+    def fit_check(self):
+        """None (default) | tol_mm, as Tracker.fit_check: every call also scores each object's estimate against the observed depth
+        (the executing engine's se3tn_set_fit_check); last_prediction gains ``fit`` ([n] records), ``pred_rgb`` / ``pred_depth``
+        ([n,176,176,3] / [n,176,176] device tensors) and last_fit_ratio is inlier_px / model_px per object."""
+        return self.engine.get_fit_check()
+
+    @fit_check.setter
+    def fit_check(self, tol_mm):
+        self.engine.set_fit_check(tol_mm)
+        if not tol_mm:
+            self.last_fit_ratio = None
 
     def on_track(self, prev_poses, rgb, depth, rgbA_out=None, depthA_out=None, bbox_out=None):
         """prev_poses: n 4x4 poses (object i = trackers[i]); rgb HxWx3 uint8, depth HxW millimetres: ONE camera frame.
@@ -505,6 +578,15 @@ class MultiTracker:
                 C.c_void_p(rgb.ctypes.data), order, C.c_void_p(dep.ctypes.data), H, W, C.c_double(max_depth), extrapolate, blur,
                 C.c_void_p(filled.data_ptr()) if filled is not None else None, *outs), "se3tn_on_track_objects_live")
         self.last_prediction = dict(trans=tr, rot=ro, bbox=bb, rgbA=list(rA), depthA=list(dA))
+        self.last_fit_ratio = None
+        if self.engine.get_fit_check():
+            if self._pred_rgb is None:
+                self._pred_rgb = torch.empty((n, 176, 176, 3), dtype=torch.uint8, device=self._dev)
+                self._pred_depth = torch.empty((n, 176, 176), dtype=torch.int16, device=self._dev)
+            fit = self.engine.last_fit(n)
+            self.engine.last_fit_images(n, self._pred_rgb, self._pred_depth)
+            self.last_prediction.update(fit=fit, pred_rgb=self._pred_rgb, pred_depth=self._pred_depth)
+            self.last_fit_ratio = U.fit_ratio(fit)
         self.frame_cnt += 1
         return out.reshape(n, 4, 4)
 

@@ -402,3 +402,30 @@ def quaternion_matrix(quaternion):
                      [q[1, 2] + q[3, 0], 1.0 - q[1, 1] - q[3, 3], q[2, 3] - q[1, 0], 0.0],
                      [q[1, 3] - q[2, 0], q[2, 3] + q[1, 0], 1.0 - q[1, 1] - q[2, 2], 0.0],
                      [0.0, 0.0, 0.0, 1.0]])
+
+
+def fit_stats(model_depth_u16, observed_depth_u16, tol_mm):
+    """The fit record of se3tn_fit_stats (include/se3tracknet.h) in NumPy, for callers without a device image: model / observed
+    depth crops in millimetres, [..., 176, 176] (any shape whose last two axes are the image) -> a structured array of shape [...]
+    with the fields of se3tn_fit.  valid(d) = 100 < d < 2000; seen_px == inlier_px + front_px + behind_px."""
+    from ._lib import FIT_DTYPE
+    m = np.asarray(model_depth_u16).astype(np.int64)
+    o = np.asarray(observed_depth_u16).astype(np.int64)
+    d, tol = o - m, int(tol_mm)
+    model = (m > 100) & (m < 2000)
+    seen = model & (o > 100) & (o < 2000)
+    inlier = seen & (np.abs(d) <= tol)
+    rec = np.zeros(m.shape[:-2], FIT_DTYPE)
+    for key, mask in (("model_px", model), ("seen_px", seen), ("inlier_px", inlier), ("front_px", seen & (d < -tol)),
+                      ("behind_px", seen & (d > tol))):
+        rec[key] = mask.sum(axis=(-2, -1))
+    rec["sum_abs_mm"] = (np.abs(d) * inlier).sum(axis=(-2, -1))
+    rec["tol_mm"] = tol
+    return rec
+
+
+def fit_ratio(rec):
+    """inlier_px / model_px of fit records (0.0 where model_px == 0): float for one record, float64 array otherwise."""
+    rec = np.asarray(rec)
+    r = np.where(rec["model_px"] > 0, rec["inlier_px"] / np.maximum(rec["model_px"], 1), 0.0)
+    return float(r) if r.ndim == 0 else r

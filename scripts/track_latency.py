@@ -24,7 +24,7 @@ class StubRenderer:
         return self.rgb, self.depth
 
 
-def main(frames=300, faces_subdiv=None, f16x3=False, pyrender=False, one_call=None):
+def main(frames=300, faces_subdiv=None, f16x3=False, pyrender=False, one_call=None, fit_check=None):
     mean, std = Fx.mean_std(0)
     sd = {"state_dict": O.make_state_dict(0, head_gain=0.0005)}
     if faces_subdiv is None:
@@ -49,6 +49,9 @@ def main(frames=300, faces_subdiv=None, f16x3=False, pyrender=False, one_call=No
     if f16x3:
         trk.engine.set_precision(se3._lib.PREC_F16X3)
         rdesc += ", SE3TN_PREC_F16X3"
+    if fit_check:   # every call also renders the estimate and scores it against the observed depth (se3tn_set_fit_check)
+        trk.fit_check = int(fit_check)
+        rdesc += ", fit_check = %d mm" % trk.fit_check
     rgb, depth = Fx.synthetic_frame(3)
     P = Fx.pose(3)
     for _ in range(20):
@@ -149,6 +152,12 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:2] == ["live-frame"]:
         live_frame(sys.argv[2])
+        sys.exit(0)
+    if sys.argv[1:2] == ["fit"]:           # `track_latency.py fit [TOL_MM]`: window route and pyrender route, fit check off, then on
+        tol = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+        for check in (None, tol):
+            main(faces_subdiv=6, fit_check=check)
+            main(faces_subdiv=6, pyrender=True, fit_check=check)
         sys.exit(0)
     if "pyrender" not in sys.argv[1:]:     # `track_latency.py pyrender`: the two pyrender legs only
         main()
