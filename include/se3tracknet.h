@@ -52,7 +52,13 @@ const char* se3tn_last_error(void);
 
 /* ---- life cycle ------------------------------------------------------------------------- */
 /* Replaces `Se3TrackNet(image_size).cuda().eval()` (predict.py:155-158): selects `device`,
- * checks it is gfx950, allocates the activation workspace for up to `max_batch` pairs. */
+ * checks it is gfx950, allocates the activation workspace for up to `max_batch` pairs.
+ * 1 <= max_batch <= SE3TN_MAX_BATCH_LIMIT, else SE3TN_E_ARG before anything is allocated.  The limit is where a 32-bit BYTE offset
+ * from the base of a whole activation tensor would pass 2^31: the stride-2 gather kernel's DMA offsets into the 46 x 46 x 128 trunk
+ * map (1,083,392 bytes per pair; conv3x3_gather_s2_kernel) are formed in `int`; every other per-batch index of the network kernels is
+ * either 64-bit or reaches 2^31 later ("Routes and transitions").  Derived by reading the kernels, not by running there:
+ * the tests run up to 256 pairs. */
+#define SE3TN_MAX_BATCH_LIMIT 1982
 int se3tn_create(int device, int max_batch, se3tn_ctx** out);
 void se3tn_destroy(se3tn_ctx* ctx);
 int se3tn_max_batch(const se3tn_ctx* ctx);

@@ -21,6 +21,7 @@ BLUR_NONE, BLUR_BILATERAL, BLUR_GAUSSIAN = 0, 1, 2
 COLOR_RGB, COLOR_BGR = 0, 1        # se3tn_on_track_live's / se3tn_on_track_objects_live's color_order
 ROUTE_WINDOW, ROUTE_FRAME = 0, 1   # as include/se3tracknet.h: the renderer se3tn_on_track uses for a mesh's image A
 FIT_MAX_PAIRS = 32                 # as include/se3tracknet.h: pairs per launch of se3tn_fit_stats (larger n are chunked)
+MAX_BATCH_LIMIT = 1982             # as include/se3tracknet.h: the largest max_batch se3tn_create accepts
 RES = 176
 
 

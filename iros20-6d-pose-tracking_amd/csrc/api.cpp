@@ -364,6 +364,9 @@ const char* se3tn_last_error(void) { return g_err.c_str(); }
 
 int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
   if (!out || max_batch < 1) return fail(SE3TN_E_ARG, "se3tn_create: bad argument");
+  if (max_batch > SE3TN_MAX_BATCH_LIMIT)   // (the kernels' 32-bit byte offsets from a tensor's base: include/se3tracknet.h)
+    return fail(SE3TN_E_ARG, "se3tn_create: max_batch " + std::to_string(max_batch) + " exceeds SE3TN_MAX_BATCH_LIMIT (" +
+                                 std::to_string(SE3TN_MAX_BATCH_LIMIT) + "): run larger sets as several calls");
   se3tn_ctx* c = new se3tn_ctx();
   c->device = device;
   c->max_batch = max_batch;

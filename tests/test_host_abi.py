@@ -287,3 +287,21 @@ def test_track_plan_host_arithmetic_under_sanitizers(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
     assert "track_plan_check: ok" in out.stdout
+
+
+def test_create_refuses_a_max_batch_above_the_limit(se3):
+    """se3tn_create: SE3TN_E_ARG with a message above SE3TN_MAX_BATCH_LIMIT (the bound of the kernels' 32-bit byte offsets, derived by
+    reading them; nothing is run at or near it), before a context exists; a normal create works afterwards.  The constant is the
+    header's, mirrored in _lib, and is where the stride-2 gather's `int` offsets into the 46 x 46 x 128 map would pass 2^31."""
+    L = se3._lib
+    hdr = open(os.path.join(ROOT, "include", "se3tracknet.h")).read()
+    assert int(re.search(r"#define SE3TN_MAX_BATCH_LIMIT (\d+)", hdr).group(1)) == L.MAX_BATCH_LIMIT
+    per_pair = 46 * 46 * 128 * 4
+    assert L.MAX_BATCH_LIMIT * per_pair <= 2 ** 31 < (L.MAX_BATCH_LIMIT + 1) * per_pair
+    with pytest.raises(L.Se3tnError, match="SE3TN_MAX_BATCH_LIMIT"):
+        se3.Engine(-1, L.MAX_BATCH_LIMIT + 1)
+    h = C.c_void_p()
+    assert L.load().se3tn_create(-1, L.MAX_BATCH_LIMIT + 1, C.byref(h)) != 0 and not h.value
+    eng = se3.Engine(-1, 4)
+    assert eng.lib.se3tn_max_batch(eng._h) == 4
+    eng.close()
