@@ -1016,10 +1016,12 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
       HIPCHK(launch_tail_parts(c->part, route.slices, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head, 1024, W + L.fc_w, W + L.fc_b,
                                c->logits, trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart, c->tail_arrive, c->tail_flag, c->tail_seq,
                                c->tail_parts_ch));
+      c->tail_flag = nullptr;   // consumed: this tail stores the word (se3tn_on_track polls only then)
       HIPCHK((hipError_t)prof_mark(c, st, "tail slices+avgpool+fc+tanh+pose", false));
     } else {
       written |= STAGE_HEAD;
       HIPCHK(launch_tail(head_out, W + L.fc_w, W + L.fc_b, c->logits, trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart, c->tail_arrive, c->tail_flag, c->tail_seq));
+      c->tail_flag = nullptr;   // consumed
       HIPCHK((hipError_t)prof_mark(c, st, "tail avgpool+fc+tanh+pose", false));
     }
   }
@@ -1444,11 +1446,14 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   const int seq = ++c->tail_seq == 0 ? ++c->tail_seq : c->tail_seq;
   c->tail_flag = poll ? flag_d : nullptr;
   const int rc_inf = se3tn_infer(c, c->inA, c->inB, 1, SE3TN_NHWC, trans_d, rot_d, (const double*)c->trk_dev, (double*)c->trk_out_dev, stream);
+  // only launch_tail / launch_tail_parts take the word (and clear tail_flag when they do): the fused heads' tail (TailArgs) never stores
+  // it, and polling for it would spin for the whole 5 ms before the stream wait
+  const bool stored = poll && c->tail_flag == nullptr;
   c->tail_flag = nullptr;
   if (rc_inf) return rc_inf;
   const double t4 = trace ? now() : 0.0;
   bool seen = false;
-  if (poll) {   // 5 ms of polling covers every healthy frame; anything slower (or a fault) falls through to the stream wait
+  if (stored) {   // 5 ms of polling covers every healthy frame; anything slower (or a fault) falls through to the stream wait
     const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(5);
     for (;;) {
       for (int it = 0; it < 256 && !seen; ++it) seen = __atomic_load_n((const int*)flag_h, __ATOMIC_ACQUIRE) == seq;

@@ -273,7 +273,7 @@ class Tracker:
         C = st["C"]
         st["P"][...] = prev_pose
         r = self.renderer
-        rgbA, depthA = (st["rgbA"], st["depthA"]) if "rgbA" in st else (r.rgb, r.depth)
+        rgbA, depthA = (st["rgbA"], st["depthA"]) if st["full_frame"] else (r.rgb, r.depth)
         st["check"](st["fn"](self.engine._h, r._m, st["p_P"], st["p_K"], C.c_double(float(self.object_width)), C.c_void_p(rgb.ctypes.data),
                              C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]), C.c_void_p(rgbA.data_ptr()),
                              C.c_void_p(depthA.data_ptr()), st["p_pose"], st["p_tr"], st["p_ro"], st["p_bb"], st["stream"]()),
@@ -281,7 +281,9 @@ class Tracker:
         return self._one_call_result(st, rgbA, depthA, current_rgb, current_depth)
 
     def _one_call_args(self):
-        """per-tracker constants of se3tn_on_track / se3tn_on_track_live: argument objects are built once, not per frame"""
+        """argument objects of se3tn_on_track / se3tn_on_track_live: built once, not per frame.  ``K`` and ``renderer`` are public
+        attributes the step-by-step path reads on every call, so the camera matrix is copied into the argument buffer and the
+        renderer's route is looked up per call (no allocation unless a full-frame renderer is met for the first time)."""
         st = self._one_call_state
         if st is None:
             import ctypes as C
@@ -289,20 +291,22 @@ class Tracker:
             from .engine import _stream_ptr
             st = self._one_call_state = dict(
                 C=C, check=check, stream=_stream_ptr, fn=self.engine.lib.se3tn_on_track, P=np.empty((4, 4), np.float64),
-                K=np.ascontiguousarray(self.K, np.float64), pose=np.empty((4, 4), np.float64), tr=np.empty(3, np.float32),
+                K=np.empty((3, 3), np.float64), pose=np.empty((4, 4), np.float64), tr=np.empty(3, np.float32),
                 ro=np.empty(3, np.float32), bb=np.empty((4, 2), np.int32))
-            if self.renderer.full_frame:
-                # pyrender route: the renderer's own buffers hold a whole frame; image A (the 176 x 176 crop of the render, what
-                # render_window returns) goes to buffers of the tracker
-                st["rgbA"] = torch.empty((176, 176, 3), dtype=torch.uint8, device=self._dev)
-                st["depthA"] = torch.empty((176, 176), dtype=torch.int16, device=self._dev)
             for k, t in (("P", C.c_double), ("K", C.c_double), ("pose", C.c_double), ("tr", C.c_float), ("ro", C.c_float), ("bb", C.c_int32)):
                 st["p_" + k] = st[k].ctypes.data_as(C.POINTER(t))
+        st["K"][...] = self.K
+        st["full_frame"] = bool(self.renderer.full_frame)
+        if st["full_frame"] and "rgbA" not in st:
+            # pyrender route: the renderer's own buffers hold a whole frame; image A (the 176 x 176 crop of the render, what
+            # render_window returns) goes to buffers of the tracker
+            st["rgbA"] = torch.empty((176, 176, 3), dtype=torch.uint8, device=self._dev)
+            st["depthA"] = torch.empty((176, 176), dtype=torch.int16, device=self._dev)
         return st
 
     def _one_call_result(self, st, rgbA, depthA, current_rgb, current_depth):
         self.last_prediction = dict(trans=st["tr"].reshape(1, 3).copy(), rot=st["ro"].reshape(1, 3).copy(), bbox=st["bb"].copy())
-        if "rgbA" in st:
+        if st["full_frame"]:
             self.last_prediction.update(rgbA=rgbA, depthA=depthA)
         self._fit_from_call(1, True)
         self.prev_rgb = current_rgb
@@ -344,7 +348,7 @@ class Tracker:
         C = st["C"]
         st["P"][...] = prev_pose
         r = self.renderer
-        rgbA, depthA = (st["rgbA"], st["depthA"]) if "rgbA" in st else (r.rgb, r.depth)
+        rgbA, depthA = (st["rgbA"], st["depthA"]) if st["full_frame"] else (r.rgb, r.depth)
         blur = blur_type if isinstance(blur_type, int) else \
             {"bilateral": _lib.BLUR_BILATERAL, "gaussian": _lib.BLUR_GAUSSIAN}.get(blur_type, _lib.BLUR_NONE)
         order = bgr if (isinstance(bgr, int) and not isinstance(bgr, bool)) else (_lib.COLOR_BGR if bgr else _lib.COLOR_RGB)
@@ -394,8 +398,8 @@ class Tracker:
             dev = self._dev
             st = self._batch_state = dict(
                 n=n, rgbA=torch.empty((n, 176, 176, 3), dtype=torch.uint8, device=dev),
-                depthA=torch.empty((n, 176, 176), dtype=torch.int16, device=dev),
-                K=np.ascontiguousarray(self.K, np.float64))
+                depthA=torch.empty((n, 176, 176), dtype=torch.int16, device=dev), K=np.empty((3, 3), np.float64))
+        st["K"][...] = self.K      # (a public attribute: the camera of THIS call, as the step-by-step path reads it)
         out = np.empty((n, 16), np.float64)
         tr, ro, bb = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty((n, 4, 2), np.int32)
         prgb = (C.c_void_p * n)(*[f.ctypes.data for f in frames_rgb])
@@ -459,7 +463,9 @@ class MultiTracker:
     full-frame route (``dataset_info['renderer'] == 'pyrenderer'``: textured .obj models, or un-textured ones with a Kd) -- one
     rasteriser mode per launch.  On the full-frame route ``last_prediction["rgbA"/"depthA"]`` hold the raw 176 x 176 crops of the
     renders, what ``Tracker.render_window`` returns there.  The MultiTracker owns one executing ``Engine`` of
-    max_batch = len(trackers) (workspaces, staging)."""
+    max_batch = len(trackers) (workspaces, staging).  The trackers' K, object widths and context / mesh handles are snapshotted
+    HERE: unlike ``Tracker``, which reads its ``K`` and ``renderer`` on every call, a later assignment to a tracker's attributes does
+    not reach a MultiTracker built before it."""
 
     def __init__(self, trackers, device=0):
         from .renderer import HipRenderer

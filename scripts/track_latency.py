@@ -24,7 +24,7 @@ class StubRenderer:
         return self.rgb, self.depth
 
 
-def main(frames=300, faces_subdiv=None, f16x3=False, pyrender=False, one_call=None, fit_check=None):
+def main(frames=300, faces_subdiv=None, f16x3=False, pyrender=False, one_call=None, fit_check=None, winograd=None):
     mean, std = Fx.mean_std(0)
     sd = {"state_dict": O.make_state_dict(0, head_gain=0.0005)}
     if faces_subdiv is None:
@@ -49,6 +49,9 @@ def main(frames=300, faces_subdiv=None, f16x3=False, pyrender=False, one_call=No
     if f16x3:
         trk.engine.set_precision(se3._lib.PREC_F16X3)
         rdesc += ", SE3TN_PREC_F16X3"
+    if winograd:    # (min_batch, tile): se3tn_set_winograd -- (1, 4) / (1, 6) run one pair through the fused head block and its own tail
+        trk.engine.set_winograd(*winograd)
+        rdesc += ", set_winograd%s" % (tuple(winograd),)
     if fit_check:   # every call also renders the estimate and scores it against the observed depth (se3tn_set_fit_check)
         trk.fit_check = int(fit_check)
         rdesc += ", fit_check = %d mm" % trk.fit_check
@@ -158,6 +161,9 @@ if __name__ == "__main__":
         for check in (None, tol):
             main(faces_subdiv=6, fit_check=check)
             main(faces_subdiv=6, pyrender=True, fit_check=check)
+        sys.exit(0)
+    if sys.argv[1:2] == ["wino"]:          # `track_latency.py wino [TILE]`: window route, 200 frames under se3tn_set_winograd(1, TILE)
+        main(frames=200, faces_subdiv=6, winograd=(1, int(sys.argv[2]) if len(sys.argv) > 2 else 4))
         sys.exit(0)
     if "pyrender" not in sys.argv[1:]:     # `track_latency.py pyrender`: the two pyrender legs only
         main()
