@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "hip_buffers.h"
 #include "se3tn_internal.h"
 #include "tex_pyramid.h"
 #include "track_plan.h"
@@ -58,101 +59,98 @@ struct se3tn_ctx {
   int device = -1, max_batch = 0;
   TensorMap tensors;
   std::vector<float> packed;
-  float* blob_owned = nullptr;
+  DeviceBuf<float> blob_owned;
   const float* blob = nullptr;
   BlobLayout L;
   // activations (NHWC float32)
-  float *inA = nullptr, *inB = nullptr;         // [mb,182,182,4] (3-pixel zero border)
-  float* stem = nullptr;                        // [mb,88,88,128]
+  DeviceBuf<float> inA, inB;                    // [mb,182,182,4] (3-pixel zero border)
+  DeviceBuf<float> stem;                        // [mb,88,88,128]
   // zero-bordered conv activations (se3tn_internal.h: ConvArgs)
-  float *pool = nullptr, *t64 = nullptr, *q64 = nullptr;  // [mb,46,46,128]
-  float *ab = nullptr, *ab_t = nullptr;         // [mb,24,24,256]
-  float *head = nullptr, *head_t = nullptr;     // [mb,13,13,1024]
-  float* head_f = nullptr;                      // f16x3 mode: float32 output of the last head conv (the
+  DeviceBuf<float> pool, t64, q64;              // [mb,46,46,128]
+  DeviceBuf<float> ab, ab_t;                    // [mb,24,24,256]
+  DeviceBuf<float> head, head_t;                // [mb,13,13,1024]
+  DeviceBuf<float> head_f;                      // f16x3 mode: float32 output of the last head conv (the
                                                 // in-place residual update cannot change format)
   unsigned written = 0;                         // STAGE_* the last infer wrote (the others hold older data: se3tn_debug_buffer refuses them)
-  float* logits = nullptr;                      // [mb,6]
-  float* fcpart = nullptr;                      // [mb,2,<=32,3] partial FC dot products (fused Winograd tail: 8 slices per head; tail_kernel 8; tail_parts_kernel 32)
+  DeviceBuf<float> logits;                      // [mb,6]
+  DeviceBuf<float> fcpart;                      // [mb,2,<=32,3] partial FC dot products (fused Winograd tail: 8 slices per head; tail_kernel 8; tail_parts_kernel 32)
   bool keep_intermediates = false;              // se3tn_keep_intermediates: fused blocks also store ab_t / head_t / head
   int auto_tile_override[2] = {0, 0};           // SE3TN_WINOGRAD_AUTO_TILE_AB2 / _HEADS = 4 | 6: what AUTO picks per block (rounding studies)
   int trunk_kernel = 1;                         // SE3TN_TRUNK_KERNEL = 2: the register-V trunk experiment (only in -DSE3TN_TRUNK_REGV=1 builds)
   int gemmp = -1;                               // SE3TN_WINO_GEMMP = 0 | 1: never | always the persistent 128 x 256 Winograd GEMM (default: by tile count)
   bool wino_fuse = true;                        // whole residual blocks as one fused launch sequence (SE3TN_WINOGRAD_FUSE=0: conv by conv)
-  float* part = nullptr;                        // split-K partial sums (small-batch latency path)
-  int* splitk_sem = nullptr;                    // [2 x SE3TN_SPLITK_MAX_TILES] arrival / seen counters of the fused split-K reduction (zero between launches)
+  DeviceBuf<float> part;                        // split-K partial sums (small-batch latency path)
+  DeviceBuf<int> splitk_sem;                    // [2 x SE3TN_SPLITK_MAX_TILES] arrival / seen counters of the fused split-K reduction (zero between launches)
   int tail_parts_ch = 16;                       // SE3TN_TAIL_PARTS=2: 32 workgroups x 32 channels per pair instead of 64 x 16 (developer A/B)
   bool tail_parts = true;                       // SE3TN_TAIL_PARTS=0 (developer switch): batch 1-5 keeps conv_reduce + tail_kernel after the last head conv
   bool small_kernels = true;                    // SE3TN_SMALL_KERNELS=0 (developer switch): batch 1-5 through the split-K kernels only
   bool splitk_fused = false;                    // SE3TN_SPLITK_FUSED=1 (developer switch): the reduction inside the split-K launch -- bitwise the same results,
                                                 // but SLOWER on this chip (363 vs 268 us per batch-1 forward: EXPERIMENTS item 41), so off
-  size_t part_bytes = 0;
   // Winograd F(m x m,3x3) path (wino_mfma.hip) of convAB2.* and trans|rot conv2.* at n >= wino_min_batch
   int wino_min_batch = SE3TN_WINOGRAD_DEFAULT_MIN_BATCH;  // 0 = never
   int wino_tile = SE3TN_WINOGRAD_DEFAULT_TILE;            // m = 2 | 4 | 6 | SE3TN_WINOGRAD_TILE_AUTO
   int wino_tile_derived = 0;                              // the m wino_u was derived for
-  float* wino_u[4] = {nullptr, nullptr, nullptr, nullptr};  // U = G g G^T of LAB2_1, LAB2_2, LH2_1, LH2_2 (tile 2 | 4: wino_tile_derived)
-  float* wino_u6[4] = {nullptr, nullptr, nullptr, nullptr}; // the F(6x6) planes of the same four convs (tile 6 | AUTO only)
+  DeviceBuf<float> wino_u[4];                   // U = G g G^T of LAB2_1, LAB2_2, LH2_1, LH2_2 (tile 2 | 4: wino_tile_derived)
+  DeviceBuf<float> wino_u6[4];                  // the F(6x6) planes of the same four convs (tile 6 | AUTO only)
   const float* wino6_blob = nullptr;                        // the blob wino_u6 was derived from
-  float *wino_v = nullptr, *wino_m = nullptr;   // [g][16][T][C] input tiles / per-frequency products
+  DeviceBuf<float> wino_v, wino_m;              // [g][16][T][C] input tiles / per-frequency products
   const float* wino_blob = nullptr;             // the blob wino_u was derived from
   // fused F(2x2) path of the 64-channel trunk (wino64_fused.hip) at n >= wino64_min_batch (0 = never)
   int wino64_min_batch = SE3TN_TRUNK_WINOGRAD_DEFAULT_MIN_BATCH;
   int wino64_min_fill = SE3TN_TRUNK_WINOGRAD_DEFAULT_MIN_FILL;
   int num_cus = 256;   // compute units of the device (the fused trunk kernel runs one workgroup per CU: it pays in full rounds only)
-  float* wino64_u[4] = {nullptr, nullptr, nullptr, nullptr};   // F(2x2) planes of L64_1..L64_4 ([group][chunk 2][16][64][32])
+  DeviceBuf<float> wino64_u[4];   // F(2x2) planes of L64_1..L64_4 ([group][chunk 2][16][64][32])
   const float* wino64_blob = nullptr;
   SplitLayout SL;                               // f16x3 mode: split panels in split_w (derived from the blob, not part of it)
-  float* split_w = nullptr;
+  DeviceBuf<float> split_w;
   const float* split_blob = nullptr;            // the blob split_w was derived from
-  float* wino_us[4] = {nullptr, nullptr, nullptr, nullptr};   // f16x3 Winograd blocks: U as split rows ...
-  float* wino_usc[4] = {nullptr, nullptr, nullptr, nullptr};  // ... and their per-(group, frequency, cout) 2^-k
+  DeviceBuf<float> wino_us[4];                  // f16x3 Winograd blocks: U as split rows ...
+  DeviceBuf<float> wino_usc[4];                 // ... and their per-(group, frequency, cout) 2^-k
   const float* wino_us_blob = nullptr;          // the blob / tile the split planes were derived for
   int wino_us_tile = 0;
   int prec = SE3TN_PREC_F32;                    // se3tn_set_precision
   int offset_rule = SE3TN_OFFSET_RULE_NUMPY1;   // se3tn_set_offset_rule
   int raster_sub_bits = 4;                      // se3tn_set_raster_rule: sub-pixel bits of the rasteriser's window coordinates
   // se3tn_on_track: pinned host staging [pose 128 B | frame window rgb | depth], its device mirror, device outputs and their pinned copy
-  uint8_t* trk_host = nullptr; uint8_t* trk_dev = nullptr; size_t trk_bytes = 0;
-  uint8_t* trk_out_dev = nullptr; uint8_t* trk_out_host = nullptr;   // ONE mapped pinned block: device address | host address
+  PinnedBuf<uint8_t> trk_host; DeviceBuf<uint8_t> trk_dev; size_t trk_bytes = 0;
+  PinnedBuf<uint8_t> trk_out;   // ONE mapped pinned block: host address get() | device address dev()
   // se3tn_on_track_batch / _objects: instance table (pinned host + device, fill_instance), z-buffers, image A stack, staging (the
   // TrackWindows of track_plan.h, upload_staged), outputs (read_back_tracks) -- grown at first use / larger n (reserve_track_batch)
   int tb_cap = 0;
   size_t tb_stage_bytes = 0;
-  RasterInstance *tb_inst_host = nullptr, *tb_inst_dev = nullptr;   // (room for a RasterMaterial per instance behind the n instances)
-  unsigned long long* tb_zbuf = nullptr;
-  uint8_t *tb_rgbA = nullptr, *tb_stage_host = nullptr, *tb_stage_dev = nullptr, *tb_out_host = nullptr, *tb_out_dev = nullptr;
-  uint16_t* tb_depthA = nullptr;
+  PinnedBuf<uint8_t> tb_inst_host; DeviceBuf<uint8_t> tb_inst_dev;   // [cap RasterInstance | cap RasterMaterial]
+  DeviceBuf<unsigned long long> tb_zbuf;
+  DeviceBuf<uint8_t> tb_rgbA, tb_stage_dev, tb_out_dev;
+  PinnedBuf<uint8_t> tb_stage_host, tb_out_host;
+  DeviceBuf<uint16_t> tb_depthA;
   // SE3TN_ROUTE_FRAME meshes (se3tn_on_track, se3tn_on_track_batch, _objects): the rendered rectangles [64 zero bytes | rgb of every pair |
   // depth of every pair] and, for n pairs, their z-buffers -- fr_px pixels in all (pairs x the largest rectangle of the call), grown at need
   // (reserve_frame_rects).
   // The 64 bytes in front are zeroed at allocation and never written: the 1 x 1 image A of a window that misses the frame
-  uint8_t* fr_sub = nullptr;
-  unsigned long long* fr_zbuf = nullptr;
+  DeviceBuf<uint8_t> fr_sub;
+  DeviceBuf<unsigned long long> fr_zbuf;
   size_t fr_px = 0;
   // se3tn_on_track_objects: rasteriser scratch of up to mo_cap instances of up to mo_V vertices / mo_F triangles (several meshes per launch)
   int mo_cap = 0, mo_V = 0, mo_F = 0;
-  float4* mo_vpost = nullptr;
-  int4* mo_vsnap = nullptr;
-  int *mo_big = nullptr, *mo_clipq = nullptr;
+  RasterScratch mo;
   // se3tn_fit_stats: per-pair counters [max_batch][FitArgs::WORDS] (se3tn_create; zero between launches).  se3tn_set_fit_check: the
   // tolerance (0 = off), the estimate renders [fit_cap,176,176,3] / [fit_cap,176,176] and the records in MAPPED pinned memory (host
   // address | device address) -- allocated by the first tracking call with the check on; fit_last_n: pairs of the last tracking call
   // this context executed whose records are valid (0: none)
-  unsigned* fit_counters = nullptr;
+  DeviceBuf<unsigned> fit_counters;
   int fit_tol = 0, fit_last_n = 0, fit_cap = 0;
-  uint8_t* fit_rgb = nullptr; uint16_t* fit_depth = nullptr;
-  se3tn_fit *fit_host = nullptr, *fit_host_dev = nullptr;
+  DeviceBuf<uint8_t> fit_rgb; DeviceBuf<uint16_t> fit_depth;
+  PinnedBuf<se3tn_fit> fit_host;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive / splitk_sem before the next one
-  int* tail_arrive = nullptr;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
+  DeviceBuf<int> tail_arrive;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
   int* tail_flag = nullptr; int tail_seq = 0;   // set around se3tn_on_track's infer: the tail kernel stores tail_seq to this (mapped) word
   hipStream_t trk_copy_stream = nullptr; hipEvent_t trk_copy_event = nullptr;
-  uint8_t* trk_rgbA = nullptr; uint16_t* trk_depthA = nullptr;
+  DeviceBuf<uint8_t> trk_rgbA; DeviceBuf<uint16_t> trk_depthA;
   int in_split[2] = {0, 0};                     // pixel format currently held by inA / inB
   bool last_fast = false;                       // the last infer ran the f16x3 kernels (ab is split rows)
-  int* overflow = nullptr;                      // device flag: a split-row store left the f16 range
-  unsigned long long* zbuf = nullptr;           // rasteriser z-buffer keys [zbuf_px] (176*176, grown by se3tn_render_frame)
-  size_t zbuf_px = 0;
-  float* fd_buf = nullptr;                      // se3tn_fill_depth scratch: 3 images + minmax[2] + lut[4098]
+  DeviceBuf<int> overflow;                      // device flag: a split-row store left the f16 range
+  DeviceBuf<unsigned long long> zbuf;           // rasteriser z-buffer keys, one per pixel (176*176, grown by se3tn_render_frame)
+  DeviceBuf<float> fd_buf;                      // se3tn_fill_depth scratch for frames of up to fd_pixels: 3 images + minmax[2] + lut[4098]
   size_t fd_pixels = 0;
   bool use_graphs = false;                      // se3tn_enable_graphs
   std::vector<GraphEntry> graphs;
@@ -169,24 +167,28 @@ struct se3tn_ctx {
   int slot_launches[MAX_SLOTS];
   const char* names[MAX_LAUNCHES];
   bool is_conv[MAX_LAUNCHES];
+  // (the buffers free themselves; frees go to the owning device whatever device is current)
+  ~se3tn_ctx() {
+    for (auto& g : graphs)
+      if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    if (trk_copy_event) (void)hipEventDestroy(trk_copy_event);
+    if (trk_copy_stream) (void)hipStreamDestroy(trk_copy_stream);
+    for (int s = 0; s < slots; ++s)
+      for (auto& e : evs[s]) (void)hipEventDestroy(e);
+  }
 };
 
 struct se3tn_mesh {
-  float *verts = nullptr, *normals = nullptr, *colors = nullptr;
-  int* faces = nullptr;
-  float4* vpost = nullptr;  // [V] clip positions, [V] snapped window coordinates (raster_vertex_kernel)
-  int4* vsnap = nullptr;
-  int* big = nullptr;     // [1 + F] queue of large triangles (raster_queue_kernel)
-  int* clipq = nullptr;   // [1 + F] queue of triangles that cross the frustum (raster_queue_kernel)
+  DeviceBuf<float> verts, normals, colors;
+  DeviceBuf<int> faces;
   int V = 0, F = 0;
-  // batched rasteriser scratch (se3tn_on_track_batch): batch_cap instances of vpost / vsnap / big / clipq
+  RasterScratch scratch;   // of one instance (se3tn_render*, se3tn_on_track)
+  // batched rasteriser scratch (se3tn_on_track_batch): batch_cap instances
   int batch_cap = 0;
-  float4* b_vpost = nullptr;
-  int4* b_vsnap = nullptr;
-  int *b_big = nullptr, *b_clipq = nullptr;
+  RasterScratch batch;
   // pyrender-style material (se3tn_mesh_set_texture): uv per vertex, RGB mip pyramid, Kd
-  float* uv = nullptr;
-  uint8_t* tex = nullptr;
+  DeviceBuf<float> uv;
+  DeviceBuf<uint8_t> tex;
   int tw = 0, th = 0, tlevels = 0;
   unsigned tex_off[16] = {};
   float kd[3] = {1.f, 1.f, 1.f};
@@ -207,6 +209,19 @@ struct DeviceGuard {
   }
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+// The gate EVERY growth of a lazily sized buffer passes once its capacity test has failed.  Order: guard (the growth runs on the
+// context's device; `g` is the caller's so that it outlives the allocations), drain (alloc() frees the old block, and another stream
+// of this context may still be reading it: the whole DEVICE is waited for), then alloc() buffer by buffer, the capacity published
+// LAST -- a capacity kept in a field of its own is zeroed before the first alloc(), so a half-failed growth reads as empty and the
+// next call grows again
+static int begin_growth(DeviceGuard& g) {
+  if (g.err != hipSuccess) return hipfail(g.err, "hipSetDevice");
+  HIPCHK(hipDeviceSynchronize());
+  return SE3TN_OK;
+}
+static void raster_scratch(RasterArgs& a, const RasterScratch& s) {
+  a.vpost = s.vpost.get(); a.vsnap = s.vsnap.get(); a.big = s.big.get(); a.clipq = s.clipq.get();
+}
 
 // ---- Winograd workspaces ----------------------------------------------------------------------------
 static const ConvId kWinoConvs[4] = {LAB2_1, LAB2_2, LH2_1, LH2_2};
@@ -245,10 +260,10 @@ static int wino64_prepare(se3tn_ctx* c, hipStream_t st) {
   for (int i = 0; i < 4; ++i) {
     const Conv3& s = conv_specs()[kWino64Convs[i]];
     const size_t per_g = (size_t)16 * s.cin * s.cout;
-    if (!c->wino64_u[i]) HIPCHK(hipMalloc((void**)&c->wino64_u[i], s.groups * per_g * sizeof(float)));
+    if (!c->wino64_u[i]) HIPCHK(c->wino64_u[i].alloc(s.groups * per_g));
     for (int g = 0; g < s.groups; ++g)
       HIPCHK(launch_wino_weights(c->blob + c->L.conv_w[kWino64Convs[i]] + (size_t)g * conv3_words(s.cin, s.cout),
-                                 c->wino64_u[i] + g * per_g, s.cin, s.cout, 2, st));
+                                 c->wino64_u[i].get() + g * per_g, s.cin, s.cout, 2, st));
   }
   HIPCHK(hipStreamSynchronize(st));  // init-time
   c->wino64_blob = c->blob;
@@ -261,11 +276,11 @@ static int wino_prepare(se3tn_ctx* c, hipStream_t st) {
   if (int rc = wino64_prepare(c, st)) return rc;
   if (c->wino_min_batch <= 0 || c->max_batch < c->wino_min_batch) return SE3TN_OK;
   if (!c->wino_v) {
-    HIPCHK(hipMalloc((void**)&c->wino_v, wino_ws_floats(c->max_batch) * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&c->wino_m, wino_ws_floats(c->max_batch) * sizeof(float)));
+    HIPCHK(c->wino_v.alloc(wino_ws_floats(c->max_batch)));
+    HIPCHK(c->wino_m.alloc(wino_ws_floats(c->max_batch)));
     for (int i = 0; i < 4; ++i) {
       const Conv3& s = conv_specs()[kWinoConvs[i]];
-      HIPCHK(hipMalloc((void**)&c->wino_u[i], (size_t)s.groups * 36 * s.cin * s.cout * sizeof(float)));
+      HIPCHK(c->wino_u[i].alloc((size_t)s.groups * 36 * s.cin * s.cout));
     }
   }
   const int tile = c->wino_tile == 2 ? 2 : 4;   // the planes in wino_u (tile 6 | AUTO keep the F(4x4) set there as well)
@@ -273,10 +288,10 @@ static int wino_prepare(se3tn_ctx* c, hipStream_t st) {
       c->wino6_blob != c->blob) {
     for (int i = 0; i < 4; ++i) {
       const Conv3& s = conv_specs()[kWinoConvs[i]];
-      if (!c->wino_u6[i]) HIPCHK(hipMalloc((void**)&c->wino_u6[i], (size_t)s.groups * 64 * s.cin * s.cout * sizeof(float)));
+      if (!c->wino_u6[i]) HIPCHK(c->wino_u6[i].alloc((size_t)s.groups * 64 * s.cin * s.cout));
       for (int g = 0; g < s.groups; ++g)
         HIPCHK(launch_wino_weights(c->blob + c->L.conv_w[kWinoConvs[i]] + (size_t)g * conv3_words(s.cin, s.cout),
-                                   c->wino_u6[i] + (size_t)g * 64 * s.cin * s.cout, s.cin, s.cout, 6, st));
+                                   c->wino_u6[i].get() + (size_t)g * 64 * s.cin * s.cout, s.cin, s.cout, 6, st));
     }
     HIPCHK(hipStreamSynchronize(st));  // init-time
     c->wino6_blob = c->blob;
@@ -288,7 +303,7 @@ static int wino_prepare(se3tn_ctx* c, hipStream_t st) {
       const Conv3& s = conv_specs()[kWinoConvs[i]];
       for (int g = 0; g < s.groups; ++g)
         HIPCHK(launch_wino_weights(c->blob + c->L.conv_w[kWinoConvs[i]] + (size_t)g * conv3_words(s.cin, s.cout),
-                                   c->wino_u[i] + (size_t)g * nf * s.cin * s.cout, s.cin, s.cout, tile, st));
+                                   c->wino_u[i].get() + (size_t)g * nf * s.cin * s.cout, s.cin, s.cout, tile, st));
     }
     HIPCHK(hipStreamSynchronize(st));  // init-time
     c->wino_blob = c->blob;
@@ -305,23 +320,23 @@ static int split_prepare(se3tn_ctx* c, hipStream_t st) {
   DeviceGuard dg(c->device);
   HIPCHK(dg.err);
   if (c->split_blob != c->blob) {
-    if (!c->split_w) HIPCHK(hipMalloc((void**)&c->split_w, c->SL.total * sizeof(float)));
-    HIPCHK(launch_split_weights(c->blob, c->L, c->split_w, c->SL, st));
+    if (!c->split_w) HIPCHK(c->split_w.alloc(c->SL.total));
+    HIPCHK(launch_split_weights(c->blob, c->L, c->split_w.get(), c->SL, st));
     HIPCHK(hipStreamSynchronize(st));  // init-time
     c->split_blob = c->blob;
   }
   // the fused F(4x4) blocks in f16x3 mode: split rows of U = G g G^T (derived by wino_prepare, which runs first)
-  if (c->wino_u[0] && c->wino_blob == c->blob && c->wino_tile_derived == 4 &&
+  if (c->wino_u[0].get() && c->wino_blob == c->blob && c->wino_tile_derived == 4 &&
       (c->wino_us_blob != c->blob || c->wino_us_tile != 4)) {
     for (int i = 0; i < 4; ++i) {
       const Conv3& s = conv_specs()[kWinoConvs[i]];
       const size_t per_g = (size_t)36 * s.cin * s.cout;
       if (!c->wino_us[i]) {
-        HIPCHK(hipMalloc((void**)&c->wino_us[i], s.groups * per_g * sizeof(float)));
-        HIPCHK(hipMalloc((void**)&c->wino_usc[i], (size_t)s.groups * 36 * s.cout * sizeof(float)));
+        HIPCHK(c->wino_us[i].alloc(s.groups * per_g));
+        HIPCHK(c->wino_usc[i].alloc((size_t)s.groups * 36 * s.cout));
       }
       for (int g = 0; g < s.groups; ++g)
-        HIPCHK(launch_split_wino_u(c->wino_u[i] + g * per_g, c->wino_us[i] + g * per_g, c->wino_usc[i] + (size_t)g * 36 * s.cout, s.cin,
+        HIPCHK(launch_split_wino_u(c->wino_u[i].get() + g * per_g, c->wino_us[i].get() + g * per_g, c->wino_usc[i].get() + (size_t)g * 36 * s.cout, s.cin,
                                    s.cout, 36, st));
     }
     HIPCHK(hipStreamSynchronize(st));
@@ -332,29 +347,35 @@ static int split_prepare(se3tn_ctx* c, hipStream_t st) {
 }
 
 // scratch of se3tn_fill_depth (3 float images + min/max + table) and the rasteriser's z-buffer: grown here, at start-up
-// (se3tn_reserve) or on the first call with a larger frame.  Growing frees the old buffer, so the whole DEVICE is drained
-// first: another stream of this context may still be reading it.
+// (se3tn_reserve) or on the first call with a larger frame (begin_growth)
 static int reserve_fill_depth(se3tn_ctx* c, size_t px) {
   if (px <= c->fd_pixels) return SE3TN_OK;
-  HIPCHK(hipDeviceSynchronize());
-  if (c->fd_buf) HIPCHK(hipFree(c->fd_buf));
-  c->fd_buf = nullptr; c->fd_pixels = 0;
-  HIPCHK(hipMalloc((void**)&c->fd_buf, (3 * px + 2 + 4098 + 2) * sizeof(float)));
+  DeviceGuard dg(c->device);
+  if (int rc = begin_growth(dg)) return rc;
+  c->fd_pixels = 0;
+  HIPCHK(c->fd_buf.alloc(3 * px + 2 + 4098 + 2));
   c->fd_pixels = px;
   return SE3TN_OK;
 }
 static int reserve_zbuf(se3tn_ctx* c, size_t px) {
-  if (px <= c->zbuf_px) return SE3TN_OK;
-  HIPCHK(hipDeviceSynchronize());
-  if (c->zbuf) HIPCHK(hipFree(c->zbuf));
-  c->zbuf = nullptr; c->zbuf_px = 0;
-  HIPCHK(hipMalloc((void**)&c->zbuf, sizeof(unsigned long long) * px));
-  c->zbuf_px = px;
+  if (px <= c->zbuf.count()) return SE3TN_OK;
+  DeviceGuard dg(c->device);
+  if (int rc = begin_growth(dg)) return rc;
+  HIPCHK(c->zbuf.alloc(px));
   return SE3TN_OK;
 }
 static bool stream_is_capturing(hipStream_t st) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+// A stream-ordered entry point whose scratch is too small (not reserved: se3tn_reserve) grows it now -- impossible inside a stream
+// capture.  fill: the depth fill's scratch for a frame of px pixels, else the rasteriser's z-buffer for px pixels of a `what`
+static int grow_now_or_refuse(se3tn_ctx* c, const char* fn, bool fill, const char* what, size_t px, void* stream) {
+  if (px <= (fill ? c->fd_pixels : c->zbuf.count())) return SE3TN_OK;
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(SE3TN_E_STATE, std::string(fn) + (fill ? ": scratch" : ": z-buffer") + " too small for this " + what +
+                                   " inside a stream capture: call se3tn_reserve(ctx, H, W) first");
+  return fill ? reserve_fill_depth(c, px) : reserve_zbuf(c, px);
 }
 
 extern "C" {
@@ -395,7 +416,7 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
     if (e != hipSuccess) { delete c; return hipfail(e, "hipSetDevice"); }
     const size_t mb = (size_t)max_batch;
     auto padded = [&](int s, int ch) { return (mb * (s + 2) * (s + 2) + PAD_SLACK_PX) * ch; };
-    struct { float** p; size_t words; bool zero; } bufs[] = {
+    struct { DeviceBuf<float>* p; size_t words; bool zero; } bufs[] = {
         {&c->inA, (mb * IN_P + IN_SLACK_ROWS) * IN_P * 4, true},
         {&c->inB, (mb * IN_P + IN_SLACK_ROWS) * IN_P * 4, true},
         {&c->stem, mb * S1 * S1 * 128, false}, {&c->pool, padded(S2, 128), true},
@@ -405,75 +426,31 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
         {&c->head_f, padded(S4, 1024), true},
         {&c->logits, mb * 6, true},           {&c->fcpart, mb * 192, true}};
     for (auto& b : bufs) {
-      e = hipMalloc((void**)b.p, b.words * sizeof(float));
-      if (e != hipSuccess) { se3tn_destroy(c); return hipfail(e, "hipMalloc(workspace)"); }
       // the one-pixel borders are written here once and never again (kernels store interiors only)
-      if (b.zero) e = hipMemset(*b.p, 0, b.words * sizeof(float));
-      if (e != hipSuccess) { se3tn_destroy(c); return hipfail(e, "hipMemset(workspace)"); }
+      e = b.p->alloc(b.words, b.zero);
+      if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(workspace)"); }
     }
     // split-K workspace: 16 slices of the widest layer (1024 couts x 121 px) up to batch 16
-    c->part_bytes = (size_t)16 * 1024 * 121 * 16 * sizeof(float);
-    e = hipMalloc((void**)&c->part, c->part_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->splitk_sem, sizeof(int) * 2 * SE3TN_SPLITK_MAX_TILES);
-    if (e == hipSuccess) e = hipMemset(c->splitk_sem, 0, sizeof(int) * 2 * SE3TN_SPLITK_MAX_TILES);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->tail_arrive, sizeof(int) * c->max_batch);
-    if (e == hipSuccess) e = hipMemset(c->tail_arrive, 0, sizeof(int) * c->max_batch);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->fit_counters, sizeof(unsigned) * FitArgs::WORDS * c->max_batch);
-    if (e == hipSuccess) e = hipMemset(c->fit_counters, 0, sizeof(unsigned) * FitArgs::WORDS * c->max_batch);
+    e = c->part.alloc((size_t)16 * 1024 * 121 * 16);
+    if (e == hipSuccess) e = c->splitk_sem.alloc(2 * SE3TN_SPLITK_MAX_TILES, true);
+    if (e == hipSuccess) e = c->tail_arrive.alloc(c->max_batch, true);
+    if (e == hipSuccess) e = c->fit_counters.alloc((size_t)FitArgs::WORDS * c->max_batch, true);
     if (const char* sf = std::getenv("SE3TN_SPLITK_FUSED")) c->splitk_fused = std::atoi(sf) != 0;
     if (const char* sk = std::getenv("SE3TN_SMALL_KERNELS")) c->small_kernels = std::atoi(sk) != 0;
     if (const char* tp = std::getenv("SE3TN_TAIL_PARTS")) { c->tail_parts = std::atoi(tp) != 0; c->tail_parts_ch = std::atoi(tp) == 2 ? 32 : 16; }
-    if (e != hipSuccess) { se3tn_destroy(c); return hipfail(e, "hipMalloc(split-K workspace)"); }
-    e = hipMalloc((void**)&c->zbuf, sizeof(unsigned long long) * RES * RES);
-    if (e != hipSuccess) { se3tn_destroy(c); return hipfail(e, "hipMalloc(zbuf)"); }
-    c->zbuf_px = (size_t)RES * RES;
-    e = hipMalloc((void**)&c->overflow, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(c->overflow, 0, sizeof(int));
-    if (e != hipSuccess) { se3tn_destroy(c); return hipfail(e, "hipMalloc(overflow flag)"); }
+    if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(split-K workspace)"); }
+    e = c->zbuf.alloc((size_t)RES * RES);
+    if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(zbuf)"); }
+    e = c->overflow.alloc(1, true);
+    if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(overflow flag)"); }
     e = hipDeviceSynchronize();
-    if (e != hipSuccess) { se3tn_destroy(c); return hipfail(e, "hipDeviceSynchronize"); }
+    if (e != hipSuccess) { delete c; return hipfail(e, "hipDeviceSynchronize"); }
   }
   *out = c;
   return SE3TN_OK;
 }
 
-void se3tn_destroy(se3tn_ctx* c) {
-  if (!c) return;
-  if (c->device >= 0) {
-    float* bufs[] = {c->inA, c->inB, c->stem, c->pool, c->t64, c->q64, c->ab, c->ab_t, c->head,
-                     c->head_t, c->head_f, c->logits, c->fcpart, c->part, (float*)c->splitk_sem, (float*)c->tail_arrive, c->blob_owned, c->split_w, c->wino_v, c->wino_m,
-                     c->wino_u[0], c->wino_u[1], c->wino_u[2], c->wino_u[3], c->wino_u6[0], c->wino_u6[1], c->wino_u6[2], c->wino_u6[3],
-                     c->wino_us[0], c->wino_us[1], c->wino_us[2], c->wino_us[3], c->wino_usc[0], c->wino_usc[1], c->wino_usc[2],
-                     c->wino_usc[3], c->wino64_u[0], c->wino64_u[1], c->wino64_u[2], c->wino64_u[3]};
-    for (float* b : bufs)
-      if (b) (void)hipFree(b);
-    for (auto& g : c->graphs)
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (c->overflow) (void)hipFree(c->overflow);
-    if (c->trk_host) (void)hipHostFree(c->trk_host);
-    if (c->trk_out_host) (void)hipHostFree(c->trk_out_host);
-    if (c->trk_copy_event) (void)hipEventDestroy(c->trk_copy_event);
-    if (c->trk_copy_stream) (void)hipStreamDestroy(c->trk_copy_stream);
-    for (void* b : {(void*)c->trk_dev, (void*)c->trk_rgbA, (void*)c->trk_depthA})
-      if (b) (void)hipFree(b);
-    if (c->zbuf) (void)hipFree(c->zbuf);
-    for (void* b : {(void*)c->tb_inst_host, (void*)c->tb_out_host, (void*)c->tb_stage_host})
-      if (b) (void)hipHostFree(b);
-    for (void* b : {(void*)c->tb_inst_dev, (void*)c->tb_zbuf, (void*)c->tb_rgbA, (void*)c->tb_depthA, (void*)c->tb_out_dev, (void*)c->tb_stage_dev})
-      if (b) (void)hipFree(b);
-    for (void* b : {(void*)c->mo_vpost, (void*)c->mo_vsnap, (void*)c->mo_big, (void*)c->mo_clipq})
-      if (b) (void)hipFree(b);
-    if (c->fd_buf) (void)hipFree(c->fd_buf);
-    for (void* b : {(void*)c->fit_counters, (void*)c->fit_rgb, (void*)c->fit_depth})
-      if (b) (void)hipFree(b);
-    if (c->fit_host) (void)hipHostFree(c->fit_host);
-    if (c->fr_sub) (void)hipFree(c->fr_sub);
-    if (c->fr_zbuf) (void)hipFree(c->fr_zbuf);
-    for (int s = 0; s < c->slots; ++s)
-      for (auto& e : c->evs[s]) (void)hipEventDestroy(e);
-  }
-  delete c;
-}
+void se3tn_destroy(se3tn_ctx* c) { delete c; }
 
 int se3tn_max_batch(const se3tn_ctx* c) { return c ? c->max_batch : 0; }
 
@@ -511,11 +488,11 @@ int se3tn_upload_weights(se3tn_ctx* c, void* stream) {
   if (c->packed.empty()) return fail(SE3TN_E_STATE, "se3tn_upload_weights: call se3tn_pack_weights first");
   DeviceGuard dg(c->device);   // init-time entry point: runs on the context's device, leaves the caller's current device alone
   HIPCHK(dg.err);
-  if (!c->blob_owned) HIPCHK(hipMalloc((void**)&c->blob_owned, c->L.total * sizeof(float)));
-  HIPCHK(hipMemcpyAsync(c->blob_owned, c->packed.data(), c->L.total * sizeof(float), hipMemcpyHostToDevice,
+  if (!c->blob_owned) HIPCHK(c->blob_owned.alloc(c->L.total));
+  HIPCHK(hipMemcpyAsync(c->blob_owned.get(), c->packed.data(), c->L.total * sizeof(float), hipMemcpyHostToDevice,
                         (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // init-time only: the host vector may go away
-  c->blob = c->blob_owned;
+  c->blob = c->blob_owned.get();
   c->wino_blob = nullptr;  // same address, new contents: every derived plane set follows the weights
   c->wino6_blob = nullptr;
   c->wino64_blob = nullptr;
@@ -617,7 +594,7 @@ int se3tn_reserve(se3tn_ctx* c, int H, int W) {
 }
 
 size_t se3tn_split_weights_bytes(const se3tn_ctx* c) { return c ? c->SL.total * sizeof(float) : 0; }
-const void* se3tn_split_weights_device(const se3tn_ctx* c) { return (c && c->split_blob) ? c->split_w : nullptr; }
+const void* se3tn_split_weights_device(const se3tn_ctx* c) { return (c && c->split_blob) ? c->split_w.get() : nullptr; }
 int se3tn_split_weights_host(const void* packed_blob_host, size_t blob_bytes, void* out_split, size_t out_bytes) {
   const BlobLayout L = blob_layout();
   const SplitLayout S = split_layout();
@@ -635,8 +612,8 @@ int se3tn_keep_intermediates(se3tn_ctx* c, int on) {
 
 int se3tn_overflow(se3tn_ctx* c, int* flag) {
   if (!c || c->device < 0 || !flag) return fail(SE3TN_E_ARG, "se3tn_overflow: bad argument");
-  HIPCHK(hipMemcpy(flag, c->overflow, sizeof(int), hipMemcpyDeviceToHost));
-  if (*flag) HIPCHK(hipMemset(c->overflow, 0, sizeof(int)));
+  HIPCHK(hipMemcpy(flag, c->overflow.get(), sizeof(int), hipMemcpyDeviceToHost));
+  if (*flag) HIPCHK(hipMemset(c->overflow.get(), 0, sizeof(int)));
   return SE3TN_OK;
 }
 
@@ -654,7 +631,7 @@ int se3tn_set_normalizers(se3tn_ctx* c, double tn, double rn) {
   return SE3TN_OK;
 }
 
-float* se3tn_input_buffer(se3tn_ctx* c, int which) { return !c ? nullptr : (which == 0 ? c->inA : c->inB); }
+float* se3tn_input_buffer(se3tn_ctx* c, int which) { return !c ? nullptr : (which == 0 ? c->inA.get() : c->inB.get()); }
 
 // se3tn_preprocess; raw_rgb / raw_depth non-null: crop i also leaves its raw pixels (crop_bbox alone) as image i of [n,176,176,3] /
 // [n,176,176] (image A of the full-frame route: se3tn_on_track_batch)
@@ -662,7 +639,7 @@ static int preprocess_impl(se3tn_ctx* c, const se3tn_crop* crops, int n, float* 
   if (!c || c->device < 0 || !crops || !out || n < 0) return fail(SE3TN_E_ARG, "se3tn_preprocess: bad argument");
   if (!c->have_norm) return fail(SE3TN_E_STATE, "se3tn_preprocess: call se3tn_set_normalization first");
   // the context's own input buffers hold max_batch images: more crops would run past them
-  if ((out == c->inA || out == c->inB) && n > c->max_batch)
+  if ((out == c->inA.get() || out == c->inB.get()) && n > c->max_batch)
     return fail(SE3TN_E_ARG, "se3tn_preprocess: n > max_batch for the context's input buffer");
   for (int i = 0; i < n; ++i) {
     const se3tn_crop& k = crops[i];
@@ -676,12 +653,12 @@ static int preprocess_impl(se3tn_ctx* c, const se3tn_crop* crops, int n, float* 
     a.n = (n - i0 < CropArgs::MAX) ? n - i0 : CropArgs::MAX;
     std::memcpy(a.c, crops + i0, sizeof(se3tn_crop) * a.n);
     // the context's own input buffers are zero-bordered [n,182,182,4]; anything else is plain NHWC
-    a.padded = (out == c->inA || out == c->inB) ? 1 : 0;
+    a.padded = (out == c->inA.get() || out == c->inB.get()) ? 1 : 0;
     // the context's input buffers hold split pixels in f16x3 mode (consumed by the f16 stem)
     a.split = (a.padded && c->prec == SE3TN_PREC_F16X3) ? 1 : 0;
-    a.overflow = c->overflow;
+    a.overflow = c->overflow.get();
     a.offset_rule = c->offset_rule;
-    if (a.padded) c->in_split[out == c->inA ? 0 : 1] = a.split;
+    if (a.padded) c->in_split[out == c->inA.get() ? 0 : 1] = a.split;
     a.out = out + (size_t)i0 * (a.padded ? IN_P * IN_P : RES * RES) * 4;
     a.out2 = nullptr; a.n_first = a.n;
     a.raw_rgb = raw_rgb ? raw_rgb + (size_t)i0 * RES * RES * 3 : nullptr;
@@ -759,8 +736,8 @@ int se3tn_infer(se3tn_ctx* c, const float* A, const float* B, int n, int layout,
   if (c && c->rearm_counters && c->device >= 0 && !stream_is_capturing((hipStream_t)stream)) {
     // a launch sequence that failed half-way can leave the tail's arrival counters / the split-K semaphores non-zero, and every
     // later frame would then find no "last" workgroup: clear them, stream-ordered, before the next frame
-    if (c->tail_arrive) HIPCHK(hipMemsetAsync(c->tail_arrive, 0, sizeof(int) * c->max_batch, (hipStream_t)stream));
-    if (c->splitk_sem) HIPCHK(hipMemsetAsync(c->splitk_sem, 0, sizeof(int) * 2 * SE3TN_SPLITK_MAX_TILES, (hipStream_t)stream));
+    if (c->tail_arrive) HIPCHK(hipMemsetAsync(c->tail_arrive.get(), 0, sizeof(int) * c->max_batch, (hipStream_t)stream));
+    if (c->splitk_sem) HIPCHK(hipMemsetAsync(c->splitk_sem.get(), 0, sizeof(int) * 2 * SE3TN_SPLITK_MAX_TILES, (hipStream_t)stream));
     c->rearm_counters = false;
   }
   const int rc = infer_graph_or_launch(c, A, B, n, layout, trans, rot, poseA, poseB, stream);
@@ -785,7 +762,7 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
     if (!(g.key == key)) continue;
     if (g.exec) {
       const int want_split = c->prec == SE3TN_PREC_F16X3 ? 1 : 0;
-      if ((A == c->inA && c->in_split[0] != want_split) || (B == c->inB && c->in_split[1] != want_split))
+      if ((A == c->inA.get() && c->in_split[0] != want_split) || (B == c->inB.get() && c->in_split[1] != want_split))
         return fail(SE3TN_E_STATE, "se3tn_infer: the input buffers were filled under a different precision mode");
       HIPCHK(hipGraphLaunch(g.exec, st));
       c->last_fast = g.fast;
@@ -836,25 +813,25 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   }
 
   const int want_split = c->prec == SE3TN_PREC_F16X3 ? 1 : 0;
-  if (A != c->inA || B != c->inB) {  // external tensors: copy into the zero-bordered input buffers
-    if (A != c->inA) {
-      HIPCHK(launch_to_padded_input(A, c->inA, n, layout == SE3TN_NCHW, want_split, c->overflow, st));
+  if (A != c->inA.get() || B != c->inB.get()) {  // external tensors: copy into the zero-bordered input buffers
+    if (A != c->inA.get()) {
+      HIPCHK(launch_to_padded_input(A, c->inA.get(), n, layout == SE3TN_NCHW, want_split, c->overflow.get(), st));
       c->in_split[0] = want_split;
     }
-    if (B != c->inB) {
-      HIPCHK(launch_to_padded_input(B, c->inB, n, layout == SE3TN_NCHW, want_split, c->overflow, st));
+    if (B != c->inB.get()) {
+      HIPCHK(launch_to_padded_input(B, c->inB.get(), n, layout == SE3TN_NCHW, want_split, c->overflow.get(), st));
       c->in_split[1] = want_split;
     }
     HIPCHK((hipError_t)prof_mark(c, st, "to_padded_input", false));
-    A = c->inA;
-    B = c->inB;
+    A = c->inA.get();
+    B = c->inB.get();
   }
   if (c->in_split[0] != want_split || c->in_split[1] != want_split)
     return fail(SE3TN_E_STATE, "se3tn_infer: the input buffers were filled under a different precision mode "
                                "(call se3tn_set_precision before se3tn_preprocess)");
   if (want_split && c->split_blob != c->blob)
     return fail(SE3TN_E_STATE, "se3tn_infer: f16x3 split panels not derived (se3tn_set_precision after the weights are bound)");
-  const float* WS = c->split_w;
+  const float* WS = c->split_w.get();
   const SplitLayout& SL = c->SL;
   const bool fast = c->prec == SE3TN_PREC_F16X3;  // both the big-tile and the split-K kernels
   c->last_fast = fast;
@@ -865,16 +842,16 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   const bool small_stem = c->small_kernels && !want_split && !c->keep_intermediates && n <= SE3TN_STEM_SMALL_MAX_N;
   if (!small_stem) written |= STAGE_STEM;
   if (small_stem) {
-    HIPCHK(launch_stem_pool_small(A, B, W + L.stem_w, W + L.stem_b, c->pool, n, st));
+    HIPCHK(launch_stem_pool_small(A, B, W + L.stem_w, W + L.stem_b, c->pool.get(), n, st));
     HIPCHK((hipError_t)prof_mark(c, st, "stem7x7 + maxpool [small tiles]", false));
   } else {
     if (want_split)
-      HIPCHK(launch_stem(A, B, WS + SL.stem_ws, W + L.stem_b, WS + SL.stem_sc, c->stem, n, st));
+      HIPCHK(launch_stem(A, B, WS + SL.stem_ws, W + L.stem_b, WS + SL.stem_sc, c->stem.get(), n, st));
     else
-      HIPCHK(launch_stem(A, B, W + L.stem_w, W + L.stem_b, nullptr, c->stem, n, st));
+      HIPCHK(launch_stem(A, B, W + L.stem_w, W + L.stem_b, nullptr, c->stem.get(), n, st));
     HIPCHK((hipError_t)prof_mark(c, st, "stem7x7_mfma", false));
 #if !defined(SE3TN_ABLATE_POOL)   // (timing-only variant build: what the step costs WITHOUT the pool pass -- EXPERIMENTS item 43)
-    HIPCHK(launch_maxpool(c->stem, c->pool, n, fast ? 1 : 0, st));
+    HIPCHK(launch_maxpool(c->stem.get(), c->pool.get(), n, fast ? 1 : 0, st));
 #endif
     HIPCHK((hipError_t)prof_mark(c, st, "maxpool3x3s2", false));
   }
@@ -886,13 +863,13 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     const Conv3& s = conv_specs()[id];
     const int ws = wino_slot(id);
     const int wtile = tile_for(c, n, ws >= 2 ? 1 : 0);
-    const bool u_ready = wtile == 6 ? (c->wino_u6[0] && c->wino6_blob == c->blob) : (c->wino_tile_derived == wtile);
+    const bool u_ready = wtile == 6 ? (c->wino_u6[0].get() && c->wino6_blob == c->blob) : (c->wino_tile_derived == wtile);
     route = ConvRoute{};
-    if (ws >= 0 && !fast && c->wino_min_batch > 0 && n >= c->wino_min_batch && c->wino_v && u_ready) {
+    if (ws >= 0 && !fast && c->wino_min_batch > 0 && n >= c->wino_min_batch && c->wino_v.get() && u_ready) {
       route.algo = ConvRoute::WINO;
       WinoArgs w{};
-      w.in = in; w.U = wtile == 6 ? c->wino_u6[ws] : c->wino_u[ws]; w.bias = W + L.conv_b[id]; w.res = res; w.out = out;
-      w.V = c->wino_v; w.Mw = c->wino_m;
+      w.in = in; w.U = wtile == 6 ? c->wino_u6[ws].get() : c->wino_u[ws].get(); w.bias = W + L.conv_b[id]; w.res = res; w.out = out;
+      w.V = c->wino_v.get(); w.Mw = c->wino_m.get();
       w.in_ld = in_ld; w.res_ld = res_ld; w.out_ld = out_ld;
       w.m = wtile; w.nf = (w.m + 2) * (w.m + 2);
       w.H = hin; w.W = hin; w.th = (hin + w.m - 1) / w.m; w.tw = w.th;
@@ -908,7 +885,7 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     if (id <= L64_4 && !fast && wino64_pays(c, n, s.groups) && c->wino64_blob == c->blob && stride == 1 && hin == S2 && epi != 2) {
       const int slot64 = (int)id - (int)L64_1;
       route.algo = ConvRoute::WINO64;
-      hipError_t e = launch_wino64(in, in_ld, in_gs, c->wino64_u[slot64], (long long)16 * s.cin * s.cout, W + L.conv_b[id], s.cout, res,
+      hipError_t e = launch_wino64(in, in_ld, in_gs, c->wino64_u[slot64].get(), (long long)16 * s.cin * s.cout, W + L.conv_b[id], s.cout, res,
                                    res_ld, res_gs, out, out_ld, out_gs, n, s.groups, epi, c->trunk_kernel, st);
       if (e != hipSuccess) return hipfail(e, name);
       static const char* const fused_names[4] = {"conv64 A2.conv1|B2.conv1 [fused F(2x2)]", "conv64 A2.conv2|B2.conv2 [fused F(2x2)]",
@@ -919,11 +896,11 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     a.in = in; a.w = W + L.conv_w[id]; a.bias = W + L.conv_b[id];
     if (fast) {
       a.fast = 1;
-      a.overflow = c->overflow;
+      a.overflow = c->overflow.get();
       a.w = WS + SL.conv_ws[id];
       a.wscale = WS + SL.conv_sc[id];
-    } a.res = res; a.out = out; a.part = c->part; a.part_bytes = c->part_bytes;
-    a.sem = c->splitk_fused ? c->splitk_sem : nullptr;
+    } a.res = res; a.out = out; a.part = c->part.get(); a.part_bytes = c->part.count() * sizeof(float);
+    a.sem = c->splitk_fused ? c->splitk_sem.get() : nullptr;
     a.small_ok = c->small_kernels ? 1 : 0;
     a.skip_reduce = skip_reduce ? 1 : 0;
     a.in_ld = in_ld; a.res_ld = res_ld; a.out_ld = out_ld;
@@ -938,18 +915,18 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   };
   int rc;
   // 64-channel trunk: pool = a0|b0 ; t64 scratch ; q64 = a1|b1 -> a1|b2 (== torch.cat((a,b),1))
-  if ((rc = conv(L64_1, c->pool, 128, 64, nullptr, 0, 0, c->t64, 128, 64, S2, 1, 0, "conv64 A2.conv1|B2.conv1"))) return rc;
-  if ((rc = conv(L64_2, c->t64, 128, 64, c->pool, 128, 64, c->q64, 128, 64, S2, 1, 1, "conv64 A2.conv2|B2.conv2"))) return rc;
-  if ((rc = conv(L64_3, c->q64 + 64, 128, 0, nullptr, 0, 0, c->t64 + 64, 128, 0, S2, 1, 0, "conv64 B3.conv1"))) return rc;
-  if ((rc = conv(L64_4, c->t64 + 64, 128, 0, c->q64 + 64, 128, 0, c->q64 + 64, 128, 0, S2, 1, 1, "conv64 B3.conv2"))) return rc;
-  if ((rc = conv(LAB1, c->q64, 128, 0, nullptr, 0, 0, c->ab, 256, 0, S2, 2, 2, "convAB1 s2"))) return rc;
+  if ((rc = conv(L64_1, c->pool.get(), 128, 64, nullptr, 0, 0, c->t64.get(), 128, 64, S2, 1, 0, "conv64 A2.conv1|B2.conv1"))) return rc;
+  if ((rc = conv(L64_2, c->t64.get(), 128, 64, c->pool.get(), 128, 64, c->q64.get(), 128, 64, S2, 1, 1, "conv64 A2.conv2|B2.conv2"))) return rc;
+  if ((rc = conv(L64_3, c->q64.get() + 64, 128, 0, nullptr, 0, 0, c->t64.get() + 64, 128, 0, S2, 1, 0, "conv64 B3.conv1"))) return rc;
+  if ((rc = conv(L64_4, c->t64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, S2, 1, 1, "conv64 B3.conv2"))) return rc;
+  if ((rc = conv(LAB1, c->q64.get(), 128, 0, nullptr, 0, 0, c->ab.get(), 256, 0, S2, 2, 2, "convAB1 s2"))) return rc;
   // ResnetBasicBlocks of 256 / 512 channels: at n >= wino_min_batch with F(4x4) or F(6x6) the whole block runs through
   // launch_wino_block (conv1's out-transform fused with conv2's in-transform; the heads' last out-transform fused
   // with avg-pool + FC + tanh); otherwise conv by conv (direct / split-K / F(2x2) kernels)
   auto block_ok = [&](int which) -> bool {
     const int bt = tile_for(c, n, which);
-    const bool planes_ready = bt == 6 ? (!fast && c->wino_u6[0] && c->wino6_blob == c->blob) : (bt == 4 && c->wino_tile_derived == 4);
-    return c->wino_fuse && c->wino_min_batch > 0 && n >= c->wino_min_batch && c->wino_v && planes_ready &&
+    const bool planes_ready = bt == 6 ? (!fast && c->wino_u6[0].get() && c->wino6_blob == c->blob) : (bt == 4 && c->wino_tile_derived == 4);
+    return c->wino_fuse && c->wino_min_batch > 0 && n >= c->wino_min_batch && c->wino_v.get() && planes_ready &&
            (!fast || (c->wino_us_blob == c->blob && c->wino_us_tile == 4));
   };
   struct MarkCtx { se3tn_ctx* c; hipStream_t st; const char* name; };
@@ -959,9 +936,9 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     const Conv3& s = conv_specs()[id1];
     const int btile = tile_for(c, n, tl ? 1 : 0);
     WinoArgs w{};
-    float* const* Uset = btile == 6 ? c->wino_u6 : c->wino_u;
-    w.in = io; w.U = Uset[wino_slot(id1)]; w.bias = W + L.conv_b[id1]; w.res = nullptr; w.out = mid;
-    w.V = c->wino_v; w.Mw = c->wino_m;
+    const DeviceBuf<float>* Uset = btile == 6 ? c->wino_u6 : c->wino_u;
+    w.in = io; w.U = Uset[wino_slot(id1)].get(); w.bias = W + L.conv_b[id1]; w.res = nullptr; w.out = mid;
+    w.V = c->wino_v.get(); w.Mw = c->wino_m.get();
     w.in_ld = ld; w.res_ld = ld; w.out_ld = ld;
     w.m = btile; w.nf = (btile + 2) * (btile + 2);
     w.H = hin; w.W = hin; w.th = (hin + btile - 1) / btile; w.tw = w.th;
@@ -970,14 +947,14 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     w.in_gs = gs; w.res_gs = gs; w.out_gs = gs; w.bias_gs = s.cout;
     w.u_gs = (long long)w.nf * s.cin * s.cout;
     w.num_cus = c->num_cus; w.gemmp = c->gemmp;
-    const float *U2 = Uset[wino_slot(id2)], *usc2 = nullptr;
+    const float *U2 = Uset[wino_slot(id2)].get(), *usc2 = nullptr;
     float* keep2 = (tl && c->keep_intermediates) ? io : nullptr;
     if (fast) {   // f16x3: split-row activations / V / U, float32 M
       w.split = 1;
-      w.U = c->wino_us[wino_slot(id1)]; w.uscale = c->wino_usc[wino_slot(id1)];
-      U2 = c->wino_us[wino_slot(id2)]; usc2 = c->wino_usc[wino_slot(id2)];
-      w.overflow = c->overflow;
-      if (keep2) keep2 = c->head_f;   // the kept head activation is float32 (head itself holds split rows)
+      w.U = c->wino_us[wino_slot(id1)].get(); w.uscale = c->wino_usc[wino_slot(id1)].get();
+      U2 = c->wino_us[wino_slot(id2)].get(); usc2 = c->wino_usc[wino_slot(id2)].get();
+      w.overflow = c->overflow.get();
+      if (keep2) keep2 = c->head_f.get();   // the kept head activation is float32 (head itself holds split rows)
     }
     MarkCtx mc{c, st, c->prof ? algo_name(name1, btile, true) : name1};
     hipError_t e = launch_wino_block(w, U2, usc2, W + L.conv_b[id2], io, c->keep_intermediates ? 1 : 0, keep2, tl, st, mark_fn, &mc);
@@ -987,40 +964,40 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   // f16x3 mode: the batched GEMMs of the 256-channel block are bandwidth-bound at the f16 matrix rate (41 FLOP per byte of V / M
   // traffic) and lose to the direct f16x3 kernels (0.247 vs 0.220 ms at batch 64); the 512-channel heads win (0.349 vs 0.427 ms)
   if (block_ok(0) && !fast) {
-    if ((rc = block(LAB2_1, LAB2_2, c->ab, c->ab_t, 256, 0, S3, nullptr, "convAB2.conv1", "convAB2.conv2"))) return rc;
+    if ((rc = block(LAB2_1, LAB2_2, c->ab.get(), c->ab_t.get(), 256, 0, S3, nullptr, "convAB2.conv1", "convAB2.conv2"))) return rc;
     if (c->keep_intermediates) written |= STAGE_AB_T;
   } else {
-    if ((rc = conv(LAB2_1, c->ab, 256, 0, nullptr, 0, 0, c->ab_t, 256, 0, S3, 1, 0, "convAB2.conv1"))) return rc;
-    if ((rc = conv(LAB2_2, c->ab_t, 256, 0, c->ab, 256, 0, c->ab, 256, 0, S3, 1, 1, "convAB2.conv2"))) return rc;
+    if ((rc = conv(LAB2_1, c->ab.get(), 256, 0, nullptr, 0, 0, c->ab_t.get(), 256, 0, S3, 1, 0, "convAB2.conv1"))) return rc;
+    if ((rc = conv(LAB2_2, c->ab_t.get(), 256, 0, c->ab.get(), 256, 0, c->ab.get(), 256, 0, S3, 1, 1, "convAB2.conv2"))) return rc;
     written |= STAGE_AB_T;
   }
-  if ((rc = conv(LH1, c->ab, 256, 0, nullptr, 0, 0, c->head, 1024, 0, S3, 2, 2, "trans|rot conv1 s2"))) return rc;
+  if ((rc = conv(LH1, c->ab.get(), 256, 0, nullptr, 0, 0, c->head.get(), 1024, 0, S3, 2, 2, "trans|rot conv1 s2"))) return rc;
   if (block_ok(1)) {
-    TailArgs tl{W + L.fc_w, W + L.fc_b, c->logits, c->fcpart, trans, rot, poseA, poseB, c->tn, c->rn};
-    if ((rc = block(LH2_1, LH2_2, c->head, c->head_t, 1024, 512, S4, &tl, "trans|rot conv2.conv1",
+    TailArgs tl{W + L.fc_w, W + L.fc_b, c->logits.get(), c->fcpart.get(), trans, rot, poseA, poseB, c->tn, c->rn};
+    if ((rc = block(LH2_1, LH2_2, c->head.get(), c->head_t.get(), 1024, 512, S4, &tl, "trans|rot conv2.conv1",
                     "trans|rot conv2.conv2 + avgpool+fc+tanh+pose"))) return rc;
     if (c->keep_intermediates) written |= STAGE_HEAD_T | STAGE_HEAD;
   } else {
-    if ((rc = conv(LH2_1, c->head, 1024, 512, nullptr, 0, 0, c->head_t, 1024, 512, S4, 1, 0, "trans|rot conv2.conv1"))) return rc;
+    if ((rc = conv(LH2_1, c->head.get(), 1024, 512, nullptr, 0, 0, c->head_t.get(), 1024, 512, S4, 1, 0, "trans|rot conv2.conv1"))) return rc;
     written |= STAGE_HEAD_T;
-    float* head_out = fast ? c->head_f : c->head;
+    float* head_out = fast ? c->head_f.get() : c->head.get();
     // batch 1-5 (conv_slices_small: 8 partial-sum slices per output) may leave the slices to the tail -- no conv_reduce launch, the final
     // head map not written (se3tn_keep_intermediates keeps it).  Whether it did is what launch_conv3x3 reports: any other route the conv
     // takes (Winograd, split-K, ...) writes head_out and ignores the permission.
     skip_reduce = c->tail_parts && !c->keep_intermediates;
-    rc = conv(LH2_2, c->head_t, 1024, 512, c->head, 1024, 512, head_out, 1024, 512, S4, 1, 1, "trans|rot conv2.conv2");
+    rc = conv(LH2_2, c->head_t.get(), 1024, 512, c->head.get(), 1024, 512, head_out, 1024, 512, S4, 1, 1, "trans|rot conv2.conv2");
     skip_reduce = false;
     if (rc) return rc;
     if (route.algo == ConvRoute::SLICES && !route.reduced) {
       const int M = n * S4 * S4;
-      HIPCHK(launch_tail_parts(c->part, route.slices, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head, 1024, W + L.fc_w, W + L.fc_b,
-                               c->logits, trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart, c->tail_arrive, c->tail_flag, c->tail_seq,
+      HIPCHK(launch_tail_parts(c->part.get(), route.slices, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head.get(), 1024, W + L.fc_w, W + L.fc_b,
+                               c->logits.get(), trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart.get(), c->tail_arrive.get(), c->tail_flag, c->tail_seq,
                                c->tail_parts_ch));
       c->tail_flag = nullptr;   // consumed: this tail stores the word (se3tn_on_track polls only then)
       HIPCHK((hipError_t)prof_mark(c, st, "tail slices+avgpool+fc+tanh+pose", false));
     } else {
       written |= STAGE_HEAD;
-      HIPCHK(launch_tail(head_out, W + L.fc_w, W + L.fc_b, c->logits, trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart, c->tail_arrive, c->tail_flag, c->tail_seq));
+      HIPCHK(launch_tail(head_out, W + L.fc_w, W + L.fc_b, c->logits.get(), trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart.get(), c->tail_arrive.get(), c->tail_flag, c->tail_seq));
       c->tail_flag = nullptr;   // consumed
       HIPCHK((hipError_t)prof_mark(c, st, "tail avgpool+fc+tanh+pose", false));
     }
@@ -1032,20 +1009,20 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
 
 int se3tn_get_feature(se3tn_ctx* c, int n, float* feature_nchw, void* stream) {
   if (!c || c->device < 0 || !feature_nchw || n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_get_feature: bad argument");
-  HIPCHK(launch_padded_nhwc_to_nchw(c->ab, feature_nchw, n, S3, S3, 256, c->last_fast ? 1 : 0, (hipStream_t)stream));
+  HIPCHK(launch_padded_nhwc_to_nchw(c->ab.get(), feature_nchw, n, S3, S3, 256, c->last_fast ? 1 : 0, (hipStream_t)stream));
   return SE3TN_OK;
 }
 
-const float* se3tn_logits(se3tn_ctx* c) { return c ? c->logits : nullptr; }
+const float* se3tn_logits(se3tn_ctx* c) { return c ? c->logits.get() : nullptr; }
 
 int se3tn_debug_buffer(se3tn_ctx* c, const char* name, const float** ptr, int32_t dims[3]) {
   if (!c || !name || !ptr || !dims) return fail(SE3TN_E_ARG, "se3tn_debug_buffer: bad argument");
   struct { const char* n; const float* p; int h, w, ch; unsigned stage; } t[] = {   // (stage 0: the inputs, whoever filled them)
-      {"inA", c->inA, IN_P, IN_P, 4, 0},    {"inB", c->inB, IN_P, IN_P, 4, 0},     {"stem", c->stem, S1, S1, 128, STAGE_STEM},
-      {"pool", c->pool, S2 + 2, S2 + 2, 128, STAGE_POOL},    {"t64", c->t64, S2 + 2, S2 + 2, 128, STAGE_T64},
-      {"q64", c->q64, S2 + 2, S2 + 2, 128, STAGE_Q64},       {"ab", c->ab, S3 + 2, S3 + 2, 256, STAGE_AB},
-      {"ab_t", c->ab_t, S3 + 2, S3 + 2, 256, STAGE_AB_T},    {"head", c->last_fast ? c->head_f : c->head, S4 + 2, S4 + 2, 1024, STAGE_HEAD},
-      {"head_t", c->head_t, S4 + 2, S4 + 2, 1024, STAGE_HEAD_T}};
+      {"inA", c->inA.get(), IN_P, IN_P, 4, 0},    {"inB", c->inB.get(), IN_P, IN_P, 4, 0},     {"stem", c->stem.get(), S1, S1, 128, STAGE_STEM},
+      {"pool", c->pool.get(), S2 + 2, S2 + 2, 128, STAGE_POOL},    {"t64", c->t64.get(), S2 + 2, S2 + 2, 128, STAGE_T64},
+      {"q64", c->q64.get(), S2 + 2, S2 + 2, 128, STAGE_Q64},       {"ab", c->ab.get(), S3 + 2, S3 + 2, 256, STAGE_AB},
+      {"ab_t", c->ab_t.get(), S3 + 2, S3 + 2, 256, STAGE_AB_T},    {"head", c->last_fast ? c->head_f.get() : c->head.get(), S4 + 2, S4 + 2, 1024, STAGE_HEAD},
+      {"head_t", c->head_t.get(), S4 + 2, S4 + 2, 1024, STAGE_HEAD_T}};
   for (auto& e : t)
     if (std::strcmp(e.n, name) == 0) {
       if (e.stage && !(c->written & e.stage))
@@ -1066,16 +1043,16 @@ int se3tn_mesh_create(se3tn_ctx* c, const float* verts, const float* normals, co
     if (faces[i] < 0 || faces[i] >= V) return fail(SE3TN_E_ARG, "se3tn_mesh_create: face index out of range");
   se3tn_mesh* m = new se3tn_mesh();
   m->V = V; m->F = F;
-  struct { void** p; const void* src; size_t bytes; } up[] = {
-      {(void**)&m->verts, verts, sizeof(float) * 3 * V},     {(void**)&m->normals, normals, sizeof(float) * 3 * V},
-      {(void**)&m->colors, colors01, sizeof(float) * 3 * V}, {(void**)&m->faces, faces, sizeof(int) * 3 * F},
-      {(void**)&m->vpost, nullptr, sizeof(float4) * V},      {(void**)&m->vsnap, nullptr, sizeof(int4) * V},
-      {(void**)&m->big, nullptr, sizeof(int) * (1 + (size_t)F)}, {(void**)&m->clipq, nullptr, sizeof(int) * (1 + (size_t)F)}};
+  struct { DeviceBuf<float>* p; const float* src; } up[] = {{&m->verts, verts}, {&m->normals, normals}, {&m->colors, colors01}};
+  hipError_t e = hipSuccess;
   for (auto& u : up) {
-    hipError_t e = hipMalloc(u.p, u.bytes);
-    if (e == hipSuccess && u.src) e = hipMemcpy(*u.p, u.src, u.bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { se3tn_mesh_destroy(m); return hipfail(e, "se3tn_mesh_create"); }
+    if (e == hipSuccess) e = u.p->alloc((size_t)3 * V);
+    if (e == hipSuccess) e = hipMemcpy(u.p->get(), u.src, sizeof(float) * 3 * V, hipMemcpyHostToDevice);
   }
+  if (e == hipSuccess) e = m->faces.alloc((size_t)3 * F);
+  if (e == hipSuccess) e = hipMemcpy(m->faces.get(), faces, sizeof(int) * 3 * F, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = m->scratch.alloc(V, F, 1);
+  if (e != hipSuccess) { delete m; return hipfail(e, "se3tn_mesh_create"); }
   *out = m;
   return SE3TN_OK;
 }
@@ -1084,8 +1061,8 @@ int se3tn_mesh_set_texture(se3tn_mesh* m, const float* uv, const uint8_t* rgb, i
   if (!m || (rgb && (!uv || tw < 1 || th < 1))) return fail(SE3TN_E_ARG, "se3tn_mesh_set_texture: bad argument");
   if (kd) { m->kd[0] = kd[0]; m->kd[1] = kd[1]; m->kd[2] = kd[2]; }
   if (m->uv || m->tex) (void)hipDeviceSynchronize();   // a render may still be reading the old material
-  if (m->uv) { (void)hipFree(m->uv); m->uv = nullptr; }
-  if (m->tex) { (void)hipFree(m->tex); m->tex = nullptr; }
+  m->uv.reset();
+  m->tex.reset();
   m->tlevels = 0;
   m->has_material = true;
   if (!rgb) return SE3TN_OK;
@@ -1093,35 +1070,25 @@ int se3tn_mesh_set_texture(se3tn_mesh* m, const float* uv, const uint8_t* rgb, i
   std::vector<uint8_t> pyr;
   const int levels = se3tn_build_mip_pyramid(rgb, tw, th, pyr, m->tex_off);
   // both buffers exist and are filled before either is published: the resolve kernel reads uv whenever tex is set
-  uint8_t* d_tex = nullptr;
-  float* d_uv = nullptr;
-  hipError_t e = hipMalloc((void**)&d_tex, pyr.size());
-  if (e == hipSuccess) e = hipMemcpy(d_tex, pyr.data(), pyr.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_uv, sizeof(float) * 2 * m->V);
-  if (e == hipSuccess) e = hipMemcpy(d_uv, uv, sizeof(float) * 2 * m->V, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (d_tex) (void)hipFree(d_tex);
-    if (d_uv) (void)hipFree(d_uv);
-    return hipfail(e, "se3tn_mesh_set_texture");
-  }
-  m->tex = d_tex; m->uv = d_uv;
+  DeviceBuf<uint8_t> d_tex;
+  DeviceBuf<float> d_uv;
+  hipError_t e = d_tex.alloc(pyr.size());
+  if (e == hipSuccess) e = hipMemcpy(d_tex.get(), pyr.data(), pyr.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = d_uv.alloc((size_t)2 * m->V);
+  if (e == hipSuccess) e = hipMemcpy(d_uv.get(), uv, sizeof(float) * 2 * m->V, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hipfail(e, "se3tn_mesh_set_texture");
+  m->tex = std::move(d_tex); m->uv = std::move(d_uv);
   m->tw = tw; m->th = th; m->tlevels = levels;
   return SE3TN_OK;
 }
 
-void se3tn_mesh_destroy(se3tn_mesh* m) {
-  if (!m) return;
-  void* bufs[] = {m->verts, m->normals, m->colors, m->faces, m->vpost, m->vsnap, m->big, m->clipq, m->uv, m->tex,
-                  m->b_vpost, m->b_vsnap, m->b_big, m->b_clipq};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete m;
-}
+void se3tn_mesh_destroy(se3tn_mesh* m) { delete m; }
 
 // what both renderers share
 static void raster_common(RasterArgs& a, se3tn_ctx* c, se3tn_mesh* m, uint8_t* rgb, uint16_t* depth) {
-  a.verts = m->verts; a.normals = m->normals; a.colors = m->colors; a.faces = m->faces; a.vpost = m->vpost; a.vsnap = m->vsnap;
-  a.zbuf = c->zbuf; a.big = m->big; a.clipq = m->clipq; a.rgb = rgb; a.depth = depth; a.V = m->V; a.F = m->F;
+  a.verts = m->verts.get(); a.normals = m->normals.get(); a.colors = m->colors.get(); a.faces = m->faces.get();
+  raster_scratch(a, m->scratch);
+  a.zbuf = c->zbuf.get(); a.rgb = rgb; a.depth = depth; a.V = m->V; a.F = m->F;
   a.numpy_rule = c->offset_rule; a.sub_bits = c->raster_sub_bits;
 }
 // proj * view as the vertex shader evaluates it (vispy_renderer.py:92): per column of the result, products accumulated left to
@@ -1212,7 +1179,7 @@ int se3tn_render(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[16], const 
 // formed in float64 and uploaded as ONE float32 matrix; the vertex shader multiplies it with the position
 static void frame_uniforms(RasterArgs& a, const se3tn_mesh* m, const double ob_in_cam[16], const double K[9], int W, int H) {
   a.rw = W; a.rh = H; a.mode = 1;
-  a.uv = m->uv; a.tex = m->tex; a.tw = m->tw; a.th = m->th; a.tlevels = m->tlevels;
+  a.uv = m->uv.get(); a.tex = m->tex.get(); a.tw = m->tw; a.th = m->th; a.tlevels = m->tlevels;
   for (int i = 0; i < 16; ++i) a.tex_off[i] = m->tex_off[i];
   a.kd[0] = m->kd[0]; a.kd[1] = m->kd[1]; a.kd[2] = m->kd[2];
   const double n = R_NEAR_D, f = R_FAR_D;
@@ -1236,14 +1203,11 @@ static void rect_to_scissor(const int32_t rect[4], int H, int s[4]) {
 static int reserve_frame_route(se3tn_ctx* c, size_t px) {
   if (px <= c->fr_px) return SE3TN_OK;
   DeviceGuard dg(c->device);
-  if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
-  HIPCHK(hipDeviceSynchronize());
-  if (c->fr_sub) HIPCHK(hipFree(c->fr_sub));
-  if (c->fr_zbuf) HIPCHK(hipFree(c->fr_zbuf));
-  c->fr_sub = nullptr; c->fr_zbuf = nullptr; c->fr_px = 0;
-  HIPCHK(hipMalloc((void**)&c->fr_sub, 64 + ((px * 3 + 63) & ~(size_t)63) + px * 2 + 64));
-  HIPCHK(hipMalloc((void**)&c->fr_zbuf, sizeof(unsigned long long) * px));
-  HIPCHK(hipMemset(c->fr_sub, 0, 64));
+  if (int rc = begin_growth(dg)) return rc;
+  c->fr_px = 0;
+  HIPCHK(c->fr_sub.alloc(64 + ((px * 3 + 63) & ~(size_t)63) + px * 2 + 64));
+  HIPCHK(c->fr_zbuf.alloc(px));
+  HIPCHK(hipMemset(c->fr_sub.get(), 0, 64));
   c->fr_px = px;
   return SE3TN_OK;
 }
@@ -1263,11 +1227,7 @@ int se3tn_render_frame_rect(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[
   if (rect[2] <= rect[0] || rect[3] <= rect[1]) return fail(SE3TN_E_ARG, "se3tn_render_frame_rect: empty rectangle");
   if (rect[0] < 0 || rect[1] < 0 || rect[2] > W || rect[3] > H) return fail(SE3TN_E_ARG, "se3tn_render_frame_rect: rectangle outside the frame");
   const size_t px = (size_t)(rect[2] - rect[0]) * (size_t)(rect[3] - rect[1]);
-  if (px > c->zbuf_px) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
-    if (stream_is_capturing((hipStream_t)stream))
-      return fail(SE3TN_E_STATE, "se3tn_render_frame_rect: z-buffer too small for this rectangle inside a stream capture: call se3tn_reserve(ctx, H, W) first");
-    if (int rc = reserve_zbuf(c, px)) return rc;
-  }
+  if (int rc = grow_now_or_refuse(c, "se3tn_render_frame_rect", false, "rectangle", px, stream)) return rc;
   RasterArgs a{};
   raster_common(a, c, m, rgb_sub, depth_sub);
   frame_uniforms(a, m, ob_in_cam, K, W, H);
@@ -1301,6 +1261,12 @@ struct StagedUpload {
   void done() { copy = nullptr; }
 };
 static int upload_staged(se3tn_ctx* c, uint8_t* dev, const uint8_t* host, size_t bytes, hipStream_t st);
+// the copy stream of upload_staged and its event, made by the first tracking call (under that call's DeviceGuard)
+static int copy_stream(se3tn_ctx* c) {
+  if (!c->trk_copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->trk_copy_stream, hipStreamNonBlocking));
+  if (!c->trk_copy_event) HIPCHK(hipEventCreateWithFlags(&c->trk_copy_event, hipEventDisableTiming));
+  return SE3TN_OK;
+}
 static int fit_check_stage(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* est, const double K[9], int H, int W,
                            const se3tn::TrackWindow* windows, bool frame_route, const uint8_t* b_base, hipStream_t st, const std::string& who);
 
@@ -1330,34 +1296,25 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   // start-up allocations (first call / larger frame): pinned staging for a whole frame, its device mirror, outputs
   // (live: pose | window rgb | one zero pixel | RAW depth frame | the window's filled depth, written on the device)
   const size_t need = live ? 256 + a64(fpx * 3) + 64 + a64(fpx * 2) + fpx * 2 + 64 : 256 + fpx * 5 + 64;
-  if (live && fpx > c->fd_pixels) {
-    DeviceGuard dg(c->device);
-    if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+  if (live)
     if (int rc = reserve_fill_depth(c, fpx)) return rc;
-  }
-  if (need > c->trk_bytes) {
-    DeviceGuard dg(c->device);                     //  staging buffers belong to the context's device, whatever the caller's current one
-    if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
-    HIPCHK(hipDeviceSynchronize());
-    if (c->trk_host) HIPCHK(hipHostFree(c->trk_host));
-    if (c->trk_dev) HIPCHK(hipFree(c->trk_dev));
-    c->trk_host = nullptr; c->trk_dev = nullptr; c->trk_bytes = 0;
-    HIPCHK(hipHostMalloc((void**)&c->trk_host, need, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&c->trk_dev, need));
+  if (need > c->trk_bytes) {   //  staging buffers belong to the context's device, whatever the caller's current one
+    DeviceGuard dg(c->device);
+    if (int rc = begin_growth(dg)) return rc;
+    c->trk_bytes = 0;
+    HIPCHK(c->trk_host.alloc(need));
+    HIPCHK(c->trk_dev.alloc(need));
     c->trk_bytes = need;
   }
-  if (!c->trk_out_host) {
+  if (!c->trk_depthA) {   // (the first call; trk_depthA is made last, so a first call that failed half-way is made up for by the next)
     DeviceGuard dg(c->device);
-    if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+    if (int rc = begin_growth(dg)) return rc;
+    if (int rc = copy_stream(c)) return rc;
     // pose | trans | rot | completion word in MAPPED pinned host memory: the tail kernel writes them across the bus itself and the
     // host polls the word -- no device-to-host copy, no stream wake-up on the per-frame critical path
-    HIPCHK(hipHostMalloc((void**)&c->trk_out_host, 256, hipHostMallocMapped));
-    std::memset(c->trk_out_host, 0, 256);
-    HIPCHK(hipHostGetDevicePointer((void**)&c->trk_out_dev, c->trk_out_host, 0));
-    HIPCHK(hipMalloc((void**)&c->trk_rgbA, (size_t)RES * RES * 3));
-    HIPCHK(hipMalloc((void**)&c->trk_depthA, (size_t)RES * RES * 2));
-    HIPCHK(hipStreamCreateWithFlags(&c->trk_copy_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->trk_copy_event, hipEventDisableTiming));
+    HIPCHK(c->trk_out.alloc(256, true, true));
+    HIPCHK(c->trk_rgbA.alloc((size_t)RES * RES * 3));
+    HIPCHK(c->trk_depthA.alloc((size_t)RES * RES));
   }
   // the windows of the pair and the part of the frame that travels (track_plan.h; host float64, round half to even), behind the pose
   TrackWindow w;
@@ -1366,8 +1323,8 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   if (ps == PlanStatus::NOT_IN_FRONT) return fail(SE3TN_E_ARG, std::string(who) + ": pose is not in front of the camera (z <= 0 or not finite)");
   if (ps == PlanStatus::EMPTY_WINDOW) return fail(SE3TN_E_ARG, std::string(who) + ": empty crop window (pose behind the camera?)");
   // image A first: its four launches run on the device while the host stages the frame
-  uint8_t* rA = rgbA_dev ? rgbA_dev : c->trk_rgbA;
-  uint16_t* dA = depthA_dev ? depthA_dev : c->trk_depthA;
+  uint8_t* rA = rgbA_dev ? rgbA_dev : c->trk_rgbA.get();
+  uint16_t* dA = depthA_dev ? depthA_dev : c->trk_depthA.get();
   const bool frame_route = m->route == SE3TN_ROUTE_FRAME;
   size_t subA_d_off = 0;   // frame route: offset of the sub-image's depth in c->fr_sub
   if (frame_route) {
@@ -1379,8 +1336,8 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
       const size_t px = (size_t)w.sw * w.sh;
       subA_d_off = 64 + a64(px * 3);
       RasterArgs ra{};
-      raster_common(ra, c, m, c->fr_sub + 64, (uint16_t*)(c->fr_sub + subA_d_off));
-      ra.zbuf = c->fr_zbuf;
+      raster_common(ra, c, m, c->fr_sub.get() + 64, (uint16_t*)(c->fr_sub.get() + subA_d_off));
+      ra.zbuf = c->fr_zbuf.get();
       frame_uniforms(ra, m, prev_pose, K, W, H);
       const int32_t rectA[4] = {w.x0, w.y0, w.x0 + w.sw, w.y0 + w.sh};
       int s[4];
@@ -1394,7 +1351,7 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   const double t1 = trace ? now() : 0.0;
   // only the part of the frame the window covers travels: rows / columns [y0, y1) x [x0, x1) into pinned memory, ONE copy
   // with the pose in front, on a copy stream of its own (beside the rasteriser, not behind it)
-  uint8_t* hp = c->trk_host;
+  uint8_t* hp = c->trk_host.get();
   std::memcpy(hp, prev_pose, 128);
   size_t bytes, raw_off = 0;
   const bool fill = live && (!w.miss || live->depth_filled);
@@ -1413,13 +1370,13 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
     bytes = w.off_d + (size_t)w.sw * w.sh * 2;
   }
   StagedUpload up{c->trk_copy_stream};
-  if (int rc = upload_staged(c, c->trk_dev, hp, bytes, st)) return rc;
+  if (int rc = upload_staged(c, c->trk_dev.get(), hp, bytes, st)) return rc;
   const double t2 = trace ? now() : 0.0;
   if (fill) {   // predict_ros.py:38-41 for the pixels the crop reads (the whole frame when the caller wants it)
     const int32_t whole[4] = {0, 0, W, H}, sub[4] = {w.x0, w.y0, w.x0 + w.sw, w.y0 + w.sh};
-    const int rc = fill_depth_rect_enqueue(c, (const uint16_t*)(c->trk_dev + raw_off), H, W, live->max_depth_m,
+    const int rc = fill_depth_rect_enqueue(c, (const uint16_t*)(c->trk_dev.get() + raw_off), H, W, live->max_depth_m,
                                            live->extrapolate, live->blur, live->depth_filled ? whole : sub, live->depth_filled, sub,
-                                           w.miss ? nullptr : (uint16_t*)(c->trk_dev + w.off_d), st);
+                                           w.miss ? nullptr : (uint16_t*)(c->trk_dev.get() + w.off_d), st);
     if (rc) return rc;
   }
   const double t2f = trace ? now() : 0.0;
@@ -1429,23 +1386,23 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   std::memcpy(a.stdv, c->stdv, sizeof(a.stdv));
   // frame route: image A = the rendered rectangle (a window that misses the frame: the 1 x 1 zero image in front of the buffer); the same
   // launch writes its raw crop = Tracker.render_window (the one not given goes to the internal buffer)
-  const ImageA imgA = frame_route ? ImageA{c->fr_sub + 64, (const uint16_t*)(c->fr_sub + subA_d_off), c->fr_sub} : ImageA{rA, dA, nullptr};
-  crop_pair(w, prev_pose[11] * 1000, imgA, c->trk_dev, a.c[0], a.c[1]);
+  const ImageA imgA = frame_route ? ImageA{c->fr_sub.get() + 64, (const uint16_t*)(c->fr_sub.get() + subA_d_off), c->fr_sub.get()} : ImageA{rA, dA, nullptr};
+  crop_pair(w, prev_pose[11] * 1000, imgA, c->trk_dev.get(), a.c[0], a.c[1]);
   if (frame_route && (rgbA_dev || depthA_dev)) { a.raw_rgb = rA; a.raw_depth = dA; }
-  a.n = 2; a.n_first = 1; a.out = c->inA; a.out2 = c->inB; a.padded = 1;
+  a.n = 2; a.n_first = 1; a.out = c->inA.get(); a.out2 = c->inB.get(); a.padded = 1;
   a.split = c->prec == SE3TN_PREC_F16X3 ? 1 : 0;
-  a.overflow = c->overflow; a.offset_rule = c->offset_rule;
+  a.overflow = c->overflow.get(); a.offset_rule = c->offset_rule;
   c->in_split[0] = c->in_split[1] = a.split;
   if (const hipError_t e = launch_preprocess(a, st)) return hipfail(e, "launch_preprocess");
   const double t3 = trace ? now() : 0.0;
-  float* trans_d = (float*)(c->trk_out_dev + 128);
-  float* rot_d = (float*)(c->trk_out_dev + 144);
-  int* flag_d = (int*)(c->trk_out_dev + 192);
-  volatile int* flag_h = (volatile int*)(c->trk_out_host + 192);
+  float* trans_d = (float*)(c->trk_out.dev() + 128);
+  float* rot_d = (float*)(c->trk_out.dev() + 144);
+  int* flag_d = (int*)(c->trk_out.dev() + 192);
+  volatile int* flag_h = (volatile int*)(c->trk_out.get() + 192);
   const bool poll = !c->use_graphs && !c->prof;   // (a captured graph would replay a stale sequence number)
   const int seq = ++c->tail_seq == 0 ? ++c->tail_seq : c->tail_seq;
   c->tail_flag = poll ? flag_d : nullptr;
-  const int rc_inf = se3tn_infer(c, c->inA, c->inB, 1, SE3TN_NHWC, trans_d, rot_d, (const double*)c->trk_dev, (double*)c->trk_out_dev, stream);
+  const int rc_inf = se3tn_infer(c, c->inA.get(), c->inB.get(), 1, SE3TN_NHWC, trans_d, rot_d, (const double*)c->trk_dev.get(), (double*)c->trk_out.dev(), stream);
   // only launch_tail / launch_tail_parts take the word (and clear tail_flag when they do): the fused heads' tail (TailArgs) never stores
   // it, and polling for it would spin for the whole 5 ms before the stream wait
   const bool stored = poll && c->tail_flag == nullptr;
@@ -1477,13 +1434,13 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
       for (int i = 0; i < 7; ++i) acc[i] = 0;
     }
   }
-  std::memcpy(pose_out, c->trk_out_host, 128);
-  if (trans_out) std::memcpy(trans_out, c->trk_out_host + 128, 12);
-  if (rot_out) std::memcpy(rot_out, c->trk_out_host + 144, 12);
+  std::memcpy(pose_out, c->trk_out.get(), 128);
+  if (trans_out) std::memcpy(trans_out, c->trk_out.get() + 128, 12);
+  if (rot_out) std::memcpy(rot_out, c->trk_out.get() + 144, 12);
   if (bbox_vu) std::memcpy(bbox_vu, w.vu, sizeof(w.vu));
   if (c->fit_tol) {
     const se3tn_mesh* mm = m;
-    return fit_check_stage(c, 1, &mm, pose_out, K, H, W, &w, frame_route, c->trk_dev, st, who);
+    return fit_check_stage(c, 1, &mm, pose_out, K, H, W, &w, frame_route, c->trk_dev.get(), st, who);
   }
   return SE3TN_OK;
 }
@@ -1510,49 +1467,31 @@ int se3tn_on_track_live(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16],
 static int reserve_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, size_t stage_bytes) {
   if (n <= c->tb_cap && (!m || n <= m->batch_cap) && stage_bytes <= c->tb_stage_bytes) return SE3TN_OK;
   DeviceGuard dg(c->device);
-  if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
-  HIPCHK(hipDeviceSynchronize());
+  if (int rc = begin_growth(dg)) return rc;
+  const int cap = n > c->max_batch ? n : c->max_batch;
   if (n > c->tb_cap) {
-    if (c->tb_inst_host) HIPCHK(hipHostFree(c->tb_inst_host));
-    if (c->tb_out_host) HIPCHK(hipHostFree(c->tb_out_host));
-    for (void* b : {(void*)c->tb_inst_dev, (void*)c->tb_zbuf, (void*)c->tb_rgbA, (void*)c->tb_depthA, (void*)c->tb_out_dev})
-      if (b) HIPCHK(hipFree(b));
-    c->tb_inst_host = nullptr; c->tb_out_host = nullptr; c->tb_inst_dev = nullptr; c->tb_zbuf = nullptr; c->tb_rgbA = nullptr;
-    c->tb_depthA = nullptr; c->tb_out_dev = nullptr; c->tb_cap = 0;
-    const int cap = n > c->max_batch ? n : c->max_batch;
-    HIPCHK(hipHostMalloc((void**)&c->tb_inst_host, (sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&c->tb_out_host, (size_t)cap * 160, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&c->tb_inst_dev, (sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap));
-    HIPCHK(hipMalloc((void**)&c->tb_zbuf, sizeof(unsigned long long) * RES * RES * cap));
-    HIPCHK(hipMalloc((void**)&c->tb_rgbA, (size_t)RES * RES * 3 * cap));
-    HIPCHK(hipMalloc((void**)&c->tb_depthA, (size_t)RES * RES * 2 * cap));
-    HIPCHK(hipMalloc((void**)&c->tb_out_dev, (size_t)cap * 160));
+    c->tb_cap = 0;
+    HIPCHK(c->tb_inst_host.alloc((sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap));
+    HIPCHK(c->tb_out_host.alloc((size_t)cap * 160));
+    HIPCHK(c->tb_inst_dev.alloc((sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap));
+    HIPCHK(c->tb_zbuf.alloc((size_t)RES * RES * cap));
+    HIPCHK(c->tb_rgbA.alloc((size_t)RES * RES * 3 * cap));
+    HIPCHK(c->tb_depthA.alloc((size_t)RES * RES * cap));
+    HIPCHK(c->tb_out_dev.alloc((size_t)cap * 160));
     c->tb_cap = cap;
   }
   if (m && n > m->batch_cap) {
-    for (void* b : {(void*)m->b_vpost, (void*)m->b_vsnap, (void*)m->b_big, (void*)m->b_clipq})
-      if (b) HIPCHK(hipFree(b));
-    m->b_vpost = nullptr; m->b_vsnap = nullptr; m->b_big = nullptr; m->b_clipq = nullptr; m->batch_cap = 0;
-    const int cap = n > c->max_batch ? n : c->max_batch;
-    HIPCHK(hipMalloc((void**)&m->b_vpost, sizeof(float4) * (size_t)m->V * cap));
-    HIPCHK(hipMalloc((void**)&m->b_vsnap, sizeof(int4) * (size_t)m->V * cap));
-    HIPCHK(hipMalloc((void**)&m->b_big, sizeof(int) * (size_t)(1 + m->F) * cap));
-    HIPCHK(hipMalloc((void**)&m->b_clipq, sizeof(int) * (size_t)(1 + m->F) * cap));
+    m->batch_cap = 0;
+    HIPCHK(m->batch.alloc(m->V, m->F, cap));
     m->batch_cap = cap;
   }
   if (stage_bytes > c->tb_stage_bytes) {
-    if (c->tb_stage_host) HIPCHK(hipHostFree(c->tb_stage_host));
-    if (c->tb_stage_dev) HIPCHK(hipFree(c->tb_stage_dev));
-    c->tb_stage_host = nullptr; c->tb_stage_dev = nullptr; c->tb_stage_bytes = 0;
-    HIPCHK(hipHostMalloc((void**)&c->tb_stage_host, stage_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&c->tb_stage_dev, stage_bytes));
+    c->tb_stage_bytes = 0;
+    HIPCHK(c->tb_stage_host.alloc(stage_bytes));
+    HIPCHK(c->tb_stage_dev.alloc(stage_bytes));
     c->tb_stage_bytes = stage_bytes;
   }
-  if (!c->trk_copy_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->trk_copy_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->trk_copy_event, hipEventDisableTiming));
-  }
-  return SE3TN_OK;
+  return copy_stream(c);
 }
 
 // SE3TN_ROUTE_FRAME (predict.py:209-213): per pair the rectangle of the full-frame render its crop window covers -- the same rectangle as
@@ -1573,7 +1512,7 @@ static int reserve_frame_rects(se3tn_ctx* c, int n, const TrackWindow* windows, 
 
 // image A of pair i of n: its 176 x 176 render in the stack rA / dA, or (frame route) its rectangle in c->fr_sub
 static ImageA image_a(const se3tn_ctx* c, bool frame_route, int i, const uint8_t* rA, const uint16_t* dA, size_t maxpx, size_t fr_d_off) {
-  if (frame_route) return ImageA{c->fr_sub + 64 + (size_t)i * maxpx * 3, (const uint16_t*)(c->fr_sub + fr_d_off) + (size_t)i * maxpx, c->fr_sub};
+  if (frame_route) return ImageA{c->fr_sub.get() + 64 + (size_t)i * maxpx * 3, (const uint16_t*)(c->fr_sub.get() + fr_d_off) + (size_t)i * maxpx, c->fr_sub.get()};
   return ImageA{rA + (size_t)i * RES * RES * 3, dA + (size_t)i * RES * RES, nullptr};
 }
 
@@ -1609,11 +1548,11 @@ static int upload_staged(se3tn_ctx* c, uint8_t* dev, const uint8_t* host, size_t
 // [n poses | n trans | n rot] of c->tb_out_dev back to the caller (waits for `st`), and the bboxes of the windows
 static int read_back_tracks(se3tn_ctx* c, int n, hipStream_t st, double* pose_out, float* trans_out, float* rot_out, int32_t* bbox_vu,
                             const TrackWindow* windows) {
-  HIPCHK(hipMemcpyAsync(c->tb_out_host, c->tb_out_dev, (size_t)n * 152, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(c->tb_out_host.get(), c->tb_out_dev.get(), (size_t)n * 152, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(pose_out, c->tb_out_host, (size_t)n * 128);
-  if (trans_out) std::memcpy(trans_out, c->tb_out_host + (size_t)n * 128, (size_t)n * 12);
-  if (rot_out) std::memcpy(rot_out, c->tb_out_host + (size_t)n * 140, (size_t)n * 12);
+  std::memcpy(pose_out, c->tb_out_host.get(), (size_t)n * 128);
+  if (trans_out) std::memcpy(trans_out, c->tb_out_host.get() + (size_t)n * 128, (size_t)n * 12);
+  if (rot_out) std::memcpy(rot_out, c->tb_out_host.get() + (size_t)n * 140, (size_t)n * 12);
   if (bbox_vu)
     for (int i = 0; i < n; ++i) std::memcpy(bbox_vu + 8 * (size_t)i, windows[i].vu, sizeof(windows[i].vu));
   return SE3TN_OK;
@@ -1633,7 +1572,7 @@ int se3tn_fit_stats(se3tn_ctx* c, const se3tn_crop* model, const se3tn_crop* obs
     FitArgs a;
     std::memcpy(a.m, model + g0, sizeof(se3tn_crop) * k);
     std::memcpy(a.o, observed + g0, sizeof(se3tn_crop) * k);
-    a.counters = c->fit_counters + (size_t)FitArgs::WORDS * g0;
+    a.counters = c->fit_counters.get() + (size_t)FitArgs::WORDS * g0;
     a.out = out_dev + g0;
     a.tol = tol_mm;
     HIPCHK(launch_fit_stats(a, k, (hipStream_t)stream));
@@ -1652,19 +1591,22 @@ int se3tn_last_fit(se3tn_ctx* c, int n, se3tn_fit* out_host) {
   if (!c || !out_host || n < 1) return fail(SE3TN_E_ARG, "se3tn_last_fit: bad argument");
   if (c->fit_last_n == 0) return fail(SE3TN_E_STATE, "se3tn_last_fit: the last tracking call of this context left no records (se3tn_set_fit_check off, or the call failed)");
   if (c->fit_last_n != n) return fail(SE3TN_E_STATE, "se3tn_last_fit: the last tracking call held " + std::to_string(c->fit_last_n) + " pairs, not " + std::to_string(n));
-  std::memcpy(out_host, c->fit_host, sizeof(se3tn_fit) * (size_t)n);
+  std::memcpy(out_host, c->fit_host.get(), sizeof(se3tn_fit) * (size_t)n);
   return SE3TN_OK;
 }
 
 int se3tn_last_fit_images(se3tn_ctx* c, const uint8_t** rgb_dev, const uint16_t** depth_dev) {
   if (!c) return fail(SE3TN_E_ARG, "se3tn_last_fit_images: null ctx");
   if (c->fit_last_n == 0) return fail(SE3TN_E_STATE, "se3tn_last_fit_images: the last tracking call of this context left no estimate renders (se3tn_set_fit_check off, or the call failed)");
-  if (rgb_dev) *rgb_dev = c->fit_rgb;
-  if (depth_dev) *depth_dev = c->fit_depth;
+  if (rgb_dev) *rgb_dev = c->fit_rgb.get();
+  if (depth_dev) *depth_dev = c->fit_depth.get();
   return SE3TN_OK;
 }
 
-static int reserve_objects_raster(se3tn_ctx* c, int n, int V, int F);
+static int reserve_objects_raster(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes);
+static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* poses, const double K[9], int H, int W,
+                            const TrackWindow* windows, bool frame_route, uint8_t* rgb, uint16_t* depth, size_t maxpx, size_t fr_d_off,
+                            hipStream_t st, int* singular);
 
 // se3tn_set_fit_check's stage of the three bodies, after their pose read-back (so `st` is idle and the instance table, the rasteriser
 // scratch and, on the frame route, the rectangles' sub-images and z-buffers of image A are free again): every pair's mesh rendered at
@@ -1676,75 +1618,36 @@ static int reserve_objects_raster(se3tn_ctx* c, int n, int V, int F);
 // the call waits for `st` once more
 static int fit_check_stage(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* est, const double K[9], int H, int W,
                            const TrackWindow* windows, bool frame_route, const uint8_t* b_base, hipStream_t st, const std::string& who) {
-  int maxV = 0, maxF = 0;
-  for (int i = 0; i < n; ++i) {
-    maxV = meshes[i]->V > maxV ? meshes[i]->V : maxV;
-    maxF = meshes[i]->F > maxF ? meshes[i]->F : maxF;
-  }
   if (n > c->fit_cap) {   // first call with the check on (or a larger n than max_batch: never)
     DeviceGuard dg(c->device);
-    if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
-    HIPCHK(hipDeviceSynchronize());
-    for (void* b : {(void*)c->fit_rgb, (void*)c->fit_depth})
-      if (b) HIPCHK(hipFree(b));
-    if (c->fit_host) HIPCHK(hipHostFree(c->fit_host));
-    c->fit_rgb = nullptr; c->fit_depth = nullptr; c->fit_host = nullptr; c->fit_host_dev = nullptr; c->fit_cap = 0;
+    if (int rc = begin_growth(dg)) return rc;
+    c->fit_cap = 0;
     const int cap = n > c->max_batch ? n : c->max_batch;
-    HIPCHK(hipMalloc((void**)&c->fit_rgb, (size_t)RES * RES * 3 * cap));
-    HIPCHK(hipMalloc((void**)&c->fit_depth, (size_t)RES * RES * 2 * cap));
-    HIPCHK(hipHostMalloc((void**)&c->fit_host, sizeof(se3tn_fit) * cap, hipHostMallocMapped));
-    std::memset(c->fit_host, 0, sizeof(se3tn_fit) * cap);
-    HIPCHK(hipHostGetDevicePointer((void**)&c->fit_host_dev, c->fit_host, 0));
+    HIPCHK(c->fit_rgb.alloc((size_t)RES * RES * 3 * cap));
+    HIPCHK(c->fit_depth.alloc((size_t)RES * RES * cap));
+    HIPCHK(c->fit_host.alloc(cap, true, true));
     c->fit_cap = cap;
   }
   if (int rc = reserve_track_batch(c, nullptr, n, 0)) return rc;
-  if (int rc = reserve_objects_raster(c, n, maxV, maxF)) return rc;
+  if (int rc = reserve_objects_raster(c, n, meshes)) return rc;
   size_t maxpx = 0, fr_d_off = 0;
   if (frame_route)
     if (int rc = reserve_frame_rects(c, n, windows, H, W, &maxpx, &fr_d_off)) return rc;
-  RasterArgs ra{};
-  raster_common(ra, c, const_cast<se3tn_mesh*>(meshes[0]), c->fit_rgb, c->fit_depth);
-  ra.rw = RES; ra.rh = RES; ra.mode = 0;
-  ra.vpost = c->mo_vpost; ra.vsnap = c->mo_vsnap; ra.big = c->mo_big; ra.clipq = c->mo_clipq; ra.zbuf = c->tb_zbuf;
-  ra.V = maxV; ra.F = maxF; ra.inst_mesh = 1;
-  RasterMaterial* mat_host = (RasterMaterial*)(c->tb_inst_host + n);
-  if (frame_route) {
-    ra.rw = W; ra.rh = H; ra.mode = 1;
-    ra.rgb = c->fr_sub + 64; ra.depth = (uint16_t*)(c->fr_sub + fr_d_off);
-    ra.zbuf = c->fr_zbuf;
-    ra.scissor = 1; ra.spx = (int)maxpx;
-    ra.inst_mesh = 2;
-  }
-  for (int i = 0; i < n; ++i) {
-    const se3tn_mesh* m = meshes[i];
-    RasterInstance& I = c->tb_inst_host[i];
-    if (!fill_instance(I, frame_route, m, est + 16 * (size_t)i, K, W, H, windows[i]))
-      return fail(SE3TN_E_ARG, who + ": fit check: singular pose estimate");
-    I.verts = m->verts; I.normals = m->normals; I.colors = m->colors; I.faces = m->faces; I.V = m->V; I.F = m->F;
-    if (frame_route) {
-      RasterMaterial& M = mat_host[i];
-      M.uv = m->uv; M.tex = m->tex; M.tw = m->tw; M.th = m->th; M.tlevels = m->tlevels;
-      std::memcpy(M.kd, m->kd, sizeof(M.kd));
-      std::memcpy(M.tex_off, m->tex_off, sizeof(M.tex_off));
-    }
-  }
-  if (!frame_route || maxpx > 0) {   // (frame route with every window off the frame: nothing to render)
-    const size_t tab_bytes = sizeof(RasterInstance) * n + (frame_route ? sizeof(RasterMaterial) * n : 0);
-    HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, tab_bytes, hipMemcpyHostToDevice, st));
-    ra.inst = c->tb_inst_dev;
-    HIPCHK(launch_raster(ra, st, n));
-  }
+  int singular = -1;
+  if (int rc = raster_instances(c, n, meshes, est, K, H, W, windows, frame_route, c->fit_rgb.get(), c->fit_depth.get(), maxpx, fr_d_off, st,
+                                &singular))
+    return singular >= 0 ? fail(SE3TN_E_ARG, who + ": fit check: singular pose estimate") : rc;
   for (int g0 = 0; g0 < n; g0 += FitArgs::MAX) {
     const int k = n - g0 < FitArgs::MAX ? n - g0 : FitArgs::MAX;
     FitArgs a;
     for (int j = 0; j < k; ++j)
-      crop_pair(windows[g0 + j], 0.0, image_a(c, frame_route, g0 + j, c->fit_rgb, c->fit_depth, maxpx, fr_d_off), b_base, a.m[j], a.o[j]);
-    a.counters = c->fit_counters + (size_t)FitArgs::WORDS * g0;
-    a.out = c->fit_host_dev + g0;
+      crop_pair(windows[g0 + j], 0.0, image_a(c, frame_route, g0 + j, c->fit_rgb.get(), c->fit_depth.get(), maxpx, fr_d_off), b_base, a.m[j], a.o[j]);
+    a.counters = c->fit_counters.get() + (size_t)FitArgs::WORDS * g0;
+    a.out = c->fit_host.dev() + g0;
     a.tol = c->fit_tol;
     if (frame_route) {
-      a.raw_rgb = c->fit_rgb + (size_t)g0 * RES * RES * 3;
-      a.raw_depth = c->fit_depth + (size_t)g0 * RES * RES;
+      a.raw_rgb = c->fit_rgb.get() + (size_t)g0 * RES * RES * 3;
+      a.raw_depth = c->fit_depth.get() + (size_t)g0 * RES * RES;
     }
     HIPCHK(launch_fit_stats(a, k, st));
   }
@@ -1779,8 +1682,8 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   }
   if (int rc = reserve_track_batch(c, m, n, bytes)) return rc;
   // image A of all n poses: the instance table goes up on the launch stream, then FOUR launches (grid.y = pose)
-  uint8_t* rA = rgbA_dev ? rgbA_dev : c->tb_rgbA;
-  uint16_t* dA = depthA_dev ? depthA_dev : c->tb_depthA;
+  uint8_t* rA = rgbA_dev ? rgbA_dev : c->tb_rgbA.get();
+  uint16_t* dA = depthA_dev ? depthA_dev : c->tb_depthA.get();
   const bool frame_route = m->route == SE3TN_ROUTE_FRAME;
   size_t maxpx = 0, fr_d_off = 0;
   if (frame_route) {
@@ -1792,21 +1695,23 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   ra.rw = RES; ra.rh = RES; ra.mode = 0;
   if (frame_route) {
     frame_uniforms(ra, m, prev_poses, K, W, H);   // material, frame size (the matrix comes from the instance table)
-    ra.rgb = c->fr_sub + 64; ra.depth = (uint16_t*)(c->fr_sub + fr_d_off);
+    ra.rgb = c->fr_sub.get() + 64; ra.depth = (uint16_t*)(c->fr_sub.get() + fr_d_off);
     ra.scissor = 1; ra.spx = (int)maxpx;
   }
-  ra.vpost = m->b_vpost; ra.vsnap = m->b_vsnap; ra.big = m->b_big; ra.clipq = m->b_clipq; ra.zbuf = frame_route ? c->fr_zbuf : c->tb_zbuf;
+  raster_scratch(ra, m->batch);
+  ra.zbuf = frame_route ? c->fr_zbuf.get() : c->tb_zbuf.get();
+  RasterInstance* inst_host = (RasterInstance*)c->tb_inst_host.get();
   for (int i = 0; i < n; ++i)
-    if (!fill_instance(c->tb_inst_host[i], frame_route, m, prev_poses + 16 * (size_t)i, K, W, H, windows[i]))
+    if (!fill_instance(inst_host[i], frame_route, m, prev_poses + 16 * (size_t)i, K, W, H, windows[i]))
       return fail(SE3TN_E_ARG, "se3tn_on_track_batch: singular pose");
   if (!frame_route || maxpx > 0) {
-    HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, sizeof(RasterInstance) * n, hipMemcpyHostToDevice, st));
-    ra.inst = c->tb_inst_dev;
+    HIPCHK(hipMemcpyAsync(c->tb_inst_dev.get(), inst_host, sizeof(RasterInstance) * n, hipMemcpyHostToDevice, st));
+    ra.inst = (const RasterInstance*)c->tb_inst_dev.get();
     HIPCHK(launch_raster(ra, st, n));
   }
   const double t1 = trace ? now() : 0.0;
   // the frames' windows: staged through pinned memory while the rasteriser runs, ONE copy with the poses in front
-  uint8_t* hp = c->tb_stage_host;
+  uint8_t* hp = c->tb_stage_host.get();
   std::memcpy(hp, prev_poses, (size_t)n * 128);
   auto stage_pairs = [&](int i0, int i1) {
     for (int i = i0; i < i1; ++i) stage_window(windows[i], rgb[i], depth[i], W, hp);
@@ -1830,20 +1735,20 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   }
   const double t2 = trace ? now() : 0.0;
   StagedUpload up{c->trk_copy_stream};
-  if (int rc = upload_staged(c, c->tb_stage_dev, hp, bytes, st)) return rc;
+  if (int rc = upload_staged(c, c->tb_stage_dev.get(), hp, bytes, st)) return rc;
   // both crops of every pair (data_augmentation.py:124-189 with poseA's z), 64 descriptors per launch
   std::vector<se3tn_crop> crops(2 * (size_t)n);
   for (int i = 0; i < n; ++i)
-    crop_pair(windows[i], prev_poses[16 * (size_t)i + 11] * 1000, image_a(c, frame_route, i, rA, dA, maxpx, fr_d_off), c->tb_stage_dev, crops[i],
+    crop_pair(windows[i], prev_poses[16 * (size_t)i + 11] * 1000, image_a(c, frame_route, i, rA, dA, maxpx, fr_d_off), c->tb_stage_dev.get(), crops[i],
               crops[(size_t)n + i]);
   // frame route: the crops of image A also leave their raw pixels (crop_bbox of the render = Tracker.render_window) in rgbA_dev / depthA_dev
   const bool rawA = frame_route && (rgbA_dev || depthA_dev);
-  int rc = preprocess_impl(c, crops.data(), n, c->inA, rawA ? rA : nullptr, rawA ? dA : nullptr, stream);
-  if (rc == SE3TN_OK) rc = se3tn_preprocess(c, crops.data() + n, n, c->inB, stream);
-  float* trans_d = (float*)(c->tb_out_dev + (size_t)n * 128);
+  int rc = preprocess_impl(c, crops.data(), n, c->inA.get(), rawA ? rA : nullptr, rawA ? dA : nullptr, stream);
+  if (rc == SE3TN_OK) rc = se3tn_preprocess(c, crops.data() + n, n, c->inB.get(), stream);
+  float* trans_d = (float*)(c->tb_out_dev.get() + (size_t)n * 128);
   float* rot_d = trans_d + 3 * (size_t)n;
   if (rc == SE3TN_OK)
-    rc = se3tn_infer(c, c->inA, c->inB, n, SE3TN_NHWC, trans_d, rot_d, (const double*)c->tb_stage_dev, (double*)c->tb_out_dev, stream);
+    rc = se3tn_infer(c, c->inA.get(), c->inB.get(), n, SE3TN_NHWC, trans_d, rot_d, (const double*)c->tb_stage_dev.get(), (double*)c->tb_out_dev.get(), stream);
   if (rc != SE3TN_OK) return rc;
   const double t3 = trace ? now() : 0.0;
   if ((rc = read_back_tracks(c, n, st, pose_out, trans_out, rot_out, bbox_vu, windows.data()))) return rc;
@@ -1861,30 +1766,79 @@ int se3tn_on_track_batch(se3tn_ctx* c, se3tn_mesh* m, int n, const double* prev_
   }
   if (c->fit_tol) {
     const std::vector<const se3tn_mesh*> meshes(n, m);
-    return fit_check_stage(c, n, meshes.data(), pose_out, K, H, W, windows.data(), frame_route, c->tb_stage_dev, st, "se3tn_on_track_batch");
+    return fit_check_stage(c, n, meshes.data(), pose_out, K, H, W, windows.data(), frame_route, c->tb_stage_dev.get(), st, "se3tn_on_track_batch");
   }
   return SE3TN_OK;
 }
 
 // ---- n objects (n models) in one camera frame per call ------------------------------------------------------------------------------
 // rasteriser scratch for n instances of meshes of up to V vertices / F triangles (se3tn_on_track_objects; grown at first use)
-static int reserve_objects_raster(se3tn_ctx* c, int n, int V, int F) {
+static void largest_mesh(const se3tn_mesh* const* meshes, int n, int* V, int* F) {
+  *V = *F = 0;
+  for (int i = 0; i < n; ++i) {
+    *V = meshes[i]->V > *V ? meshes[i]->V : *V;
+    *F = meshes[i]->F > *F ? meshes[i]->F : *F;
+  }
+}
+static int reserve_objects_raster(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes) {
+  int V, F;
+  largest_mesh(meshes, n, &V, &F);
   if (n <= c->mo_cap && V <= c->mo_V && F <= c->mo_F) return SE3TN_OK;
   DeviceGuard dg(c->device);
-  if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
-  HIPCHK(hipDeviceSynchronize());
-  for (void* b : {(void*)c->mo_vpost, (void*)c->mo_vsnap, (void*)c->mo_big, (void*)c->mo_clipq})
-    if (b) HIPCHK(hipFree(b));
-  c->mo_vpost = nullptr; c->mo_vsnap = nullptr; c->mo_big = nullptr; c->mo_clipq = nullptr; c->mo_cap = 0;
+  if (int rc = begin_growth(dg)) return rc;
   const int cap = n > c->max_batch ? n : c->max_batch;
   V = V > c->mo_V ? V : c->mo_V;
   F = F > c->mo_F ? F : c->mo_F;
-  c->mo_V = 0; c->mo_F = 0;
-  HIPCHK(hipMalloc((void**)&c->mo_vpost, sizeof(float4) * (size_t)V * cap));
-  HIPCHK(hipMalloc((void**)&c->mo_vsnap, sizeof(int4) * (size_t)V * cap));
-  HIPCHK(hipMalloc((void**)&c->mo_big, sizeof(int) * (size_t)(1 + F) * cap));
-  HIPCHK(hipMalloc((void**)&c->mo_clipq, sizeof(int) * (size_t)(1 + F) * cap));
+  c->mo_cap = 0; c->mo_V = 0; c->mo_F = 0;
+  HIPCHK(c->mo.alloc(V, F, cap));
   c->mo_cap = cap; c->mo_V = V; c->mo_F = F;
+  return SE3TN_OK;
+}
+
+// n instances in the rasteriser's FOUR launches (grid.y = instance), every one with its own mesh, pose and window and, on the frame
+// route, its own material: the instance table (the materials behind the n instance records) goes up in one copy on `st`.  Window
+// route: the 176 x 176 renders land in the stacks rgb / depth; frame route: every rectangle in c->fr_sub (maxpx, fr_d_off:
+// reserve_frame_rects).  The scratch, the table and the z-buffers are reserved.  A singular pose: SE3TN_E_ARG with *singular = its
+// index and no text (the refusal is the caller's)
+static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* poses, const double K[9], int H, int W,
+                            const TrackWindow* windows, bool frame_route, uint8_t* rgb, uint16_t* depth, size_t maxpx, size_t fr_d_off,
+                            hipStream_t st, int* singular) {
+  RasterArgs ra{};
+  raster_common(ra, c, const_cast<se3tn_mesh*>(meshes[0]), rgb, depth);
+  ra.rw = RES; ra.rh = RES; ra.mode = 0;
+  raster_scratch(ra, c->mo);
+  ra.zbuf = c->tb_zbuf.get();
+  largest_mesh(meshes, n, &ra.V, &ra.F);
+  ra.inst_mesh = 1;
+  RasterInstance* inst_host = (RasterInstance*)c->tb_inst_host.get();
+  RasterMaterial* mat_host = (RasterMaterial*)(inst_host + n);
+  if (frame_route) {
+    ra.rw = W; ra.rh = H; ra.mode = 1;   // (matrix, mesh, material and rectangle come from the tables)
+    ra.rgb = c->fr_sub.get() + 64; ra.depth = (uint16_t*)(c->fr_sub.get() + fr_d_off);
+    ra.zbuf = c->fr_zbuf.get();
+    ra.scissor = 1; ra.spx = (int)maxpx;
+    ra.inst_mesh = 2;   // every instance with its own material: the table behind the n instance records
+  }
+  for (int i = 0; i < n; ++i) {
+    const se3tn_mesh* m = meshes[i];
+    RasterInstance& I = inst_host[i];
+    if (!fill_instance(I, frame_route, m, poses + 16 * (size_t)i, K, W, H, windows[i])) {
+      *singular = i;
+      return SE3TN_E_ARG;
+    }
+    I.verts = m->verts.get(); I.normals = m->normals.get(); I.colors = m->colors.get(); I.faces = m->faces.get(); I.V = m->V; I.F = m->F;
+    if (frame_route) {
+      RasterMaterial& M = mat_host[i];
+      M.uv = m->uv.get(); M.tex = m->tex.get(); M.tw = m->tw; M.th = m->th; M.tlevels = m->tlevels;
+      std::memcpy(M.kd, m->kd, sizeof(M.kd));
+      std::memcpy(M.tex_off, m->tex_off, sizeof(M.tex_off));
+    }
+  }
+  if (frame_route && maxpx == 0) return SE3TN_OK;   // (every window off the frame: nothing to render)
+  const size_t tab_bytes = sizeof(RasterInstance) * n + (frame_route ? sizeof(RasterMaterial) * n : 0);
+  HIPCHK(hipMemcpyAsync(c->tb_inst_dev.get(), inst_host, tab_bytes, hipMemcpyHostToDevice, st));
+  ra.inst = (const RasterInstance*)c->tb_inst_dev.get();
+  HIPCHK(launch_raster(ra, st, n));
   return SE3TN_OK;
 }
 
@@ -1896,13 +1850,13 @@ static int infer_small_objects(se3tn_ctx* c, const float* W, const ImgParams& ip
                                float* rot, const double* poseA, double* poseB, hipStream_t st) {
   const BlobLayout& L = c->L;
   c->written = 0;
-  HIPCHK(launch_stem_pool_small_multi(A, B, W + L.stem_w, W + L.stem_b, c->pool, k, ip.off, st));
+  HIPCHK(launch_stem_pool_small_multi(A, B, W + L.stem_w, W + L.stem_b, c->pool.get(), k, ip.off, st));
   auto conv = [&](ConvId id, const float* in, int in_ld, int in_gs, const float* res, int res_ld, int res_gs, float* out, int out_ld,
                   int out_gs, int hin, int stride, int epi, bool skip_reduce, const char* name) -> int {
     const Conv3& s = conv_specs()[id];
     ConvArgs a{};
     a.in = in; a.w = W + L.conv_w[id]; a.bias = W + L.conv_b[id]; a.res = res; a.out = out;
-    a.part = c->part; a.part_bytes = c->part_bytes; a.small_ok = 1; a.skip_reduce = skip_reduce ? 1 : 0;
+    a.part = c->part.get(); a.part_bytes = c->part.count() * sizeof(float); a.small_ok = 1; a.skip_reduce = skip_reduce ? 1 : 0;
     a.in_ld = in_ld; a.res_ld = res_ld; a.out_ld = out_ld;
     a.H = hin; a.W = hin; a.Ho = (hin - 1) / stride + 1; a.Wo = a.Ho;
     a.M = k * a.Ho * a.Wo;
@@ -1915,22 +1869,22 @@ static int infer_small_objects(se3tn_ctx* c, const float* W, const ImgParams& ip
     return e == hipSuccess ? SE3TN_OK : hipfail(e, name);
   };
   int rc;
-  if ((rc = conv(L64_1, c->pool, 128, 64, nullptr, 0, 0, c->t64, 128, 64, S2, 1, 0, false, "conv64 A2.conv1|B2.conv1"))) return rc;
-  if ((rc = conv(L64_2, c->t64, 128, 64, c->pool, 128, 64, c->q64, 128, 64, S2, 1, 1, false, "conv64 A2.conv2|B2.conv2"))) return rc;
-  if ((rc = conv(L64_3, c->q64 + 64, 128, 0, nullptr, 0, 0, c->t64 + 64, 128, 0, S2, 1, 0, false, "conv64 B3.conv1"))) return rc;
-  if ((rc = conv(L64_4, c->t64 + 64, 128, 0, c->q64 + 64, 128, 0, c->q64 + 64, 128, 0, S2, 1, 1, false, "conv64 B3.conv2"))) return rc;
-  if ((rc = conv(LAB1, c->q64, 128, 0, nullptr, 0, 0, c->ab, 256, 0, S2, 2, 2, false, "convAB1 s2"))) return rc;
-  if ((rc = conv(LAB2_1, c->ab, 256, 0, nullptr, 0, 0, c->ab_t, 256, 0, S3, 1, 0, false, "convAB2.conv1"))) return rc;
-  if ((rc = conv(LAB2_2, c->ab_t, 256, 0, c->ab, 256, 0, c->ab, 256, 0, S3, 1, 1, false, "convAB2.conv2"))) return rc;
-  if ((rc = conv(LH1, c->ab, 256, 0, nullptr, 0, 0, c->head, 1024, 0, S3, 2, 2, false, "trans|rot conv1 s2"))) return rc;
-  if ((rc = conv(LH2_1, c->head, 1024, 512, nullptr, 0, 0, c->head_t, 1024, 512, S4, 1, 0, false, "trans|rot conv2.conv1"))) return rc;
+  if ((rc = conv(L64_1, c->pool.get(), 128, 64, nullptr, 0, 0, c->t64.get(), 128, 64, S2, 1, 0, false, "conv64 A2.conv1|B2.conv1"))) return rc;
+  if ((rc = conv(L64_2, c->t64.get(), 128, 64, c->pool.get(), 128, 64, c->q64.get(), 128, 64, S2, 1, 1, false, "conv64 A2.conv2|B2.conv2"))) return rc;
+  if ((rc = conv(L64_3, c->q64.get() + 64, 128, 0, nullptr, 0, 0, c->t64.get() + 64, 128, 0, S2, 1, 0, false, "conv64 B3.conv1"))) return rc;
+  if ((rc = conv(L64_4, c->t64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, S2, 1, 1, false, "conv64 B3.conv2"))) return rc;
+  if ((rc = conv(LAB1, c->q64.get(), 128, 0, nullptr, 0, 0, c->ab.get(), 256, 0, S2, 2, 2, false, "convAB1 s2"))) return rc;
+  if ((rc = conv(LAB2_1, c->ab.get(), 256, 0, nullptr, 0, 0, c->ab_t.get(), 256, 0, S3, 1, 0, false, "convAB2.conv1"))) return rc;
+  if ((rc = conv(LAB2_2, c->ab_t.get(), 256, 0, c->ab.get(), 256, 0, c->ab.get(), 256, 0, S3, 1, 1, false, "convAB2.conv2"))) return rc;
+  if ((rc = conv(LH1, c->ab.get(), 256, 0, nullptr, 0, 0, c->head.get(), 1024, 0, S3, 2, 2, false, "trans|rot conv1 s2"))) return rc;
+  if ((rc = conv(LH2_1, c->head.get(), 1024, 512, nullptr, 0, 0, c->head_t.get(), 1024, 512, S4, 1, 0, false, "trans|rot conv2.conv1"))) return rc;
   // the last head conv leaves its 8 partial-sum slices to the tail (conv_slices_small_count(512, 1, S4) == 8)
-  if ((rc = conv(LH2_2, c->head_t, 1024, 512, c->head, 1024, 512, c->head, 1024, 512, S4, 1, 1, true, "trans|rot conv2.conv2"))) return rc;
+  if ((rc = conv(LH2_2, c->head_t.get(), 1024, 512, c->head.get(), 1024, 512, c->head.get(), 1024, 512, S4, 1, 1, true, "trans|rot conv2.conv2"))) return rc;
   c->written = STAGE_POOL | STAGE_T64 | STAGE_Q64 | STAGE_AB | STAGE_AB_T | STAGE_HEAD_T;   // (not the stem map, not the final head map)
   c->last_fast = false;
   const int M = k * S4 * S4;
-  HIPCHK(launch_tail_parts(c->part, 8, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head, 1024, W + L.fc_w, W + L.fc_b, c->logits, trans,
-                           rot, poseA, poseB, 0.0, 0.0, k, st, c->fcpart, c->tail_arrive, nullptr, 0, 16, &ip));
+  HIPCHK(launch_tail_parts(c->part.get(), 8, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head.get(), 1024, W + L.fc_w, W + L.fc_b, c->logits.get(), trans,
+                           rot, poseA, poseB, 0.0, 0.0, k, st, c->fcpart.get(), c->tail_arrive.get(), nullptr, 0, 16, &ip));
   return SE3TN_OK;
 }
 
@@ -1950,7 +1904,7 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
   if (stream_is_capturing((hipStream_t)stream)) return fail(SE3TN_E_STATE, fn + ": synchronous call, not capturable");
   c->fit_last_n = 0;
   const std::string who = fn + ": object ";
-  int maxV = 0, maxF = 0;
+  std::vector<const se3tn_mesh*> meshes(n > 0 ? n : 0);
   // one rasteriser mode per launch, so one route per call: all objects on SE3TN_ROUTE_WINDOW (vertex-colour meshes) or all on
   // SE3TN_ROUTE_FRAME (meshes with a material: a texture, or a Kd over the vertex colours)
   bool frame_route = false;
@@ -1959,7 +1913,7 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
     const std::string id = who + std::to_string(i);
     if (!o.mesh) return fail(SE3TN_E_ARG, id + ": null mesh");
     const bool fr = o.mesh->route == SE3TN_ROUTE_FRAME;
-    if (!fr && (o.mesh->tex || o.mesh->uv))
+    if (!fr && (o.mesh->tex.get() || o.mesh->uv.get()))
       return fail(SE3TN_E_ARG, id + ": textured mesh on SE3TN_ROUTE_WINDOW (the full-frame renderer's route: se3tn_mesh_set_route)");
     if (fr && !o.mesh->has_material)
       return fail(SE3TN_E_ARG, id + ": mesh on SE3TN_ROUTE_FRAME without a material (se3tn_mesh_set_texture: a texture, or a Kd over the vertex colours)");
@@ -1977,8 +1931,7 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
     if (m->raster_sub_bits != c->raster_sub_bits) return fail(SE3TN_E_STATE, id + ": model's raster rule differs from ctx's (se3tn_set_raster_rule)");
     if (((uintptr_t)m->blob - (uintptr_t)objs[0].model->blob) % sizeof(float) != 0)
       return fail(SE3TN_E_STATE, id + ": model's weight blob is not float-aligned to the others'");
-    maxV = o.mesh->V > maxV ? o.mesh->V : maxV;
-    maxF = o.mesh->F > maxF ? o.mesh->F : maxF;
+    meshes[i] = o.mesh;
   }
   if (frame_route && H > 2048)
     return fail(SE3TN_E_ARG, fn + ": frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
@@ -2000,59 +1953,25 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
     lay = plan_live(n, windows.data(), H, W, win_off);
     fill = lay.fills > 0 || live->depth_filled;
     bytes = lay.total;
-    if ((size_t)H * W > c->fd_pixels) {
-      DeviceGuard dg(c->device);
-      if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
-      if (int rc = reserve_fill_depth(c, (size_t)H * W)) return rc;
-    }
+    if (int rc = reserve_fill_depth(c, (size_t)H * W)) return rc;
   }
   if (int rc = reserve_track_batch(c, nullptr, n, bytes)) return rc;
-  if (int rc = reserve_objects_raster(c, n, maxV, maxF)) return rc;
+  if (int rc = reserve_objects_raster(c, n, meshes.data())) return rc;
   size_t maxpx = 0, fr_d_off = 0;
   if (frame_route)
     if (int rc = reserve_frame_rects(c, n, windows.data(), H, W, &maxpx, &fr_d_off)) return rc;
   if (c->rearm_counters) {   // (as se3tn_infer: a launch sequence that failed half-way may have left the tail's counters non-zero)
-    HIPCHK(hipMemsetAsync(c->tail_arrive, 0, sizeof(int) * c->max_batch, st));
+    HIPCHK(hipMemsetAsync(c->tail_arrive.get(), 0, sizeof(int) * c->max_batch, st));
     c->rearm_counters = false;
   }
   // image A of all n objects: FOUR launches (grid.y = object), every instance with its own mesh
-  uint8_t* rA = rgbA_dev ? rgbA_dev : c->tb_rgbA;
-  uint16_t* dA = depthA_dev ? depthA_dev : c->tb_depthA;
-  RasterArgs ra{};
-  raster_common(ra, c, objs[0].mesh, rA, dA);
-  ra.rw = RES; ra.rh = RES; ra.mode = 0;
-  ra.vpost = c->mo_vpost; ra.vsnap = c->mo_vsnap; ra.big = c->mo_big; ra.clipq = c->mo_clipq; ra.zbuf = c->tb_zbuf;
-  ra.V = maxV; ra.F = maxF; ra.inst_mesh = 1;
-  // frame route: the materials travel behind the n instances, in the same copy
-  RasterMaterial* mat_host = (RasterMaterial*)(c->tb_inst_host + n);
-  if (frame_route) {
-    ra.rw = W; ra.rh = H; ra.mode = 1;   // (matrix, mesh, material and rectangle come from the tables)
-    ra.rgb = c->fr_sub + 64; ra.depth = (uint16_t*)(c->fr_sub + fr_d_off);
-    ra.zbuf = c->fr_zbuf;
-    ra.scissor = 1; ra.spx = (int)maxpx;
-    ra.inst_mesh = 2;   // every instance with its own material: the table behind the n instance records
-  }
-  for (int i = 0; i < n; ++i) {
-    const se3tn_mesh* m = objs[i].mesh;
-    RasterInstance& I = c->tb_inst_host[i];
-    if (!fill_instance(I, frame_route, m, prev_poses + 16 * (size_t)i, K, W, H, windows[i]))
-      return fail(SE3TN_E_ARG, who + std::to_string(i) + ": singular pose");
-    I.verts = m->verts; I.normals = m->normals; I.colors = m->colors; I.faces = m->faces; I.V = m->V; I.F = m->F;
-    if (frame_route) {
-      RasterMaterial& M = mat_host[i];
-      M.uv = m->uv; M.tex = m->tex; M.tw = m->tw; M.th = m->th; M.tlevels = m->tlevels;
-      std::memcpy(M.kd, m->kd, sizeof(M.kd));
-      std::memcpy(M.tex_off, m->tex_off, sizeof(M.tex_off));
-    }
-  }
-  if (!frame_route || maxpx > 0) {   // (frame route with every window off the frame: nothing to render)
-    const size_t tab_bytes = sizeof(RasterInstance) * n + (frame_route ? sizeof(RasterMaterial) * n : 0);
-    HIPCHK(hipMemcpyAsync(c->tb_inst_dev, c->tb_inst_host, tab_bytes, hipMemcpyHostToDevice, st));
-    ra.inst = c->tb_inst_dev;
-    HIPCHK(launch_raster(ra, st, n));
-  }
+  uint8_t* rA = rgbA_dev ? rgbA_dev : c->tb_rgbA.get();
+  uint16_t* dA = depthA_dev ? depthA_dev : c->tb_depthA.get();
+  int singular = -1;
+  if (int rc = raster_instances(c, n, meshes.data(), prev_poses, K, H, W, windows.data(), frame_route, rA, dA, maxpx, fr_d_off, st, &singular))
+    return singular >= 0 ? fail(SE3TN_E_ARG, who + std::to_string(singular) + ": singular pose") : rc;
   // the poses, every object's mean | std and the frame's n windows: staged through pinned memory while the rasteriser runs, ONE copy
-  uint8_t* hp = c->tb_stage_host;
+  uint8_t* hp = c->tb_stage_host.get();
   std::memcpy(hp, prev_poses, (size_t)n * 128);
   double* norm_h = (double*)(hp + norm_off);
   for (int i = 0; i < n; ++i) {
@@ -2067,7 +1986,7 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
     for (int i = 0; i < n; ++i) stage_window(windows[i], rgb, depth, W, hp);
   }
   StagedUpload up{c->trk_copy_stream};
-  if (int rc = upload_staged(c, c->tb_stage_dev, hp, !live ? bytes : fill ? lay.upload_bytes : lay.raw_off, st)) return rc;
+  if (int rc = upload_staged(c, c->tb_stage_dev.get(), hp, !live ? bytes : fill ? lay.upload_bytes : lay.raw_off, st)) return rc;
   if (fill) {   // predict_ros.py:38-41 ONCE for the frame, then the pixels each object's crop reads (and the whole frame when the caller wants it)
     std::vector<int32_t> rects(4 * (size_t)n, 0);   // (a miss keeps the empty rectangle: skipped)
     std::vector<size_t> offs(n, 0);
@@ -2077,8 +1996,8 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
       rects[4 * (size_t)i] = t.x0; rects[4 * (size_t)i + 1] = t.y0; rects[4 * (size_t)i + 2] = t.x0 + t.sw; rects[4 * (size_t)i + 3] = t.y0 + t.sh;
       offs[i] = t.off_d / 2;
     }
-    if (int rc = fill_depth_rects_enqueue(c, (const uint16_t*)(c->tb_stage_dev + lay.raw_off), H, W, live->max_depth_m, live->extrapolate,
-                                          live->blur, n, rects.data(), offs.data(), (uint16_t*)c->tb_stage_dev, live->depth_filled, st))
+    if (int rc = fill_depth_rects_enqueue(c, (const uint16_t*)(c->tb_stage_dev.get() + lay.raw_off), H, W, live->max_depth_m, live->extrapolate,
+                                          live->blur, n, rects.data(), offs.data(), (uint16_t*)c->tb_stage_dev.get(), live->depth_filled, st))
       return rc;
   }
   // both crops of every object, each normalised with its own model's mean / std (the device table staged above); up to 32 objects
@@ -2092,7 +2011,7 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
     std::memcpy(a.stdv, c->stdv, sizeof(a.stdv));
     for (int j = 0; j < kg; ++j) {
       const int i = g0 + j;
-      crop_pair(windows[i], prev_poses[16 * (size_t)i + 11] * 1000, image_a(c, frame_route, i, rA, dA, maxpx, fr_d_off), c->tb_stage_dev,
+      crop_pair(windows[i], prev_poses[16 * (size_t)i + 11] * 1000, image_a(c, frame_route, i, rA, dA, maxpx, fr_d_off), c->tb_stage_dev.get(),
                 a.c[j], a.c[kg + j]);
     }
     // frame route: the crops of image A also leave their raw pixels (crop_bbox of the render = Tracker.render_window) in rgbA_dev /
@@ -2102,14 +2021,14 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
       a.raw_depth = dA + (size_t)g0 * RES * RES;
     }
     a.n = 2 * kg; a.n_first = kg;
-    a.out = c->inA + (size_t)g0 * img_floats; a.out2 = c->inB + (size_t)g0 * img_floats; a.padded = 1; a.split = 0;
-    a.overflow = c->overflow; a.offset_rule = c->offset_rule;
-    a.norm = (const double*)(c->tb_stage_dev + norm_off) + 16 * (size_t)g0;
+    a.out = c->inA.get() + (size_t)g0 * img_floats; a.out2 = c->inB.get() + (size_t)g0 * img_floats; a.padded = 1; a.split = 0;
+    a.overflow = c->overflow.get(); a.offset_rule = c->offset_rule;
+    a.norm = (const double*)(c->tb_stage_dev.get() + norm_off) + 16 * (size_t)g0;
     if (const hipError_t e = launch_preprocess(a, st)) rc = hipfail(e, "launch_preprocess");
   }
   c->in_split[0] = c->in_split[1] = 0;
   // the network, chunks of at most 5 objects; image j of a chunk reads its model's blob at off[j] floats from the chunk's first blob
-  float* trans_d = (float*)(c->tb_out_dev + (size_t)n * 128);
+  float* trans_d = (float*)(c->tb_out_dev.get() + (size_t)n * 128);
   float* rot_d = trans_d + 3 * (size_t)n;
   for (int i0 = 0; i0 < n && rc == SE3TN_OK; i0 += SE3TN_SLICES_SMALL_MAX_N) {
     const int k = n - i0 < SE3TN_SLICES_SMALL_MAX_N ? n - i0 : SE3TN_SLICES_SMALL_MAX_N;
@@ -2121,16 +2040,14 @@ static int on_track_objects_frame(se3tn_ctx* c, int n, const se3tn_object* objs,
       ip.tn[j] = m->tn;
       ip.rn[j] = m->rn;
     }
-    rc = infer_small_objects(c, W0, ip, c->inA + (size_t)i0 * img_floats, c->inB + (size_t)i0 * img_floats, k, trans_d + 3 * (size_t)i0,
-                             rot_d + 3 * (size_t)i0, (const double*)c->tb_stage_dev + 16 * (size_t)i0, (double*)c->tb_out_dev + 16 * (size_t)i0, st);
+    rc = infer_small_objects(c, W0, ip, c->inA.get() + (size_t)i0 * img_floats, c->inB.get() + (size_t)i0 * img_floats, k, trans_d + 3 * (size_t)i0,
+                             rot_d + 3 * (size_t)i0, (const double*)c->tb_stage_dev.get() + 16 * (size_t)i0, (double*)c->tb_out_dev.get() + 16 * (size_t)i0, st);
   }
   if (rc != SE3TN_OK) { c->rearm_counters = true; return rc; }
   if ((rc = read_back_tracks(c, n, st, pose_out, trans_out, rot_out, bbox_vu, windows.data()))) return rc;
   up.done();
   if (c->fit_tol) {
-    std::vector<const se3tn_mesh*> meshes(n);
-    for (int i = 0; i < n; ++i) meshes[i] = objs[i].mesh;
-    return fit_check_stage(c, n, meshes.data(), pose_out, K, H, W, windows.data(), frame_route, c->tb_stage_dev, st, fn);
+    return fit_check_stage(c, n, meshes.data(), pose_out, K, H, W, windows.data(), frame_route, c->tb_stage_dev.get(), st, fn);
   }
   return SE3TN_OK;
 }
@@ -2157,9 +2074,9 @@ static FillDepthArgs fill_depth_args(se3tn_ctx* c, const uint16_t* depth_mm, int
   FillDepthArgs f{};
   f.depth_mm = depth_mm; f.H = H; f.W = W; f.max_depth = max_depth_m; f.extrapolate = extrapolate; f.blur = blur;
   f.sigma_color = 1.5; f.sigma_space = 2.0;
-  f.buf0 = c->fd_buf; f.buf1 = c->fd_buf + px; f.buf2 = c->fd_buf + 2 * px;
-  f.minmax = reinterpret_cast<unsigned*>(c->fd_buf + 3 * px);
-  f.lut = c->fd_buf + 3 * px + 2;
+  f.buf0 = c->fd_buf.get(); f.buf1 = c->fd_buf.get() + px; f.buf2 = c->fd_buf.get() + 2 * px;
+  f.minmax = reinterpret_cast<unsigned*>(c->fd_buf.get() + 3 * px);
+  f.lut = c->fd_buf.get() + 3 * px + 2;
   return f;
 }
 
@@ -2168,11 +2085,7 @@ int se3tn_fill_depth(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, doubl
   if (!c || c->device < 0 || !depth_mm || H < 1 || W < 1 || (!out_mm && !out_m) || blur < 0 || blur > 2)
     return fail(SE3TN_E_ARG, "se3tn_fill_depth: bad argument");
   const size_t px = (size_t)H * W;
-  if (px > c->fd_pixels) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
-    if (stream_is_capturing((hipStream_t)stream))
-      return fail(SE3TN_E_STATE, "se3tn_fill_depth: scratch too small for this frame inside a stream capture: call se3tn_reserve(ctx, H, W) first");
-    if (int rc = reserve_fill_depth(c, px)) return rc;
-  }
+  if (int rc = grow_now_or_refuse(c, "se3tn_fill_depth", true, "frame", px, stream)) return rc;
   FillDepthArgs a = fill_depth_args(c, depth_mm, H, W, max_depth_m, extrapolate, blur);
   a.out_mm = out_mm; a.out_m = out_m;
   HIPCHK(launch_fill_depth(a, (hipStream_t)stream));
@@ -2199,11 +2112,7 @@ int se3tn_fill_depth_rect(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W, 
   if (rect[2] <= rect[0] || rect[3] <= rect[1]) return fail(SE3TN_E_ARG, "se3tn_fill_depth_rect: empty rectangle");
   if (rect[0] < 0 || rect[1] < 0 || rect[2] > W || rect[3] > H) return fail(SE3TN_E_ARG, "se3tn_fill_depth_rect: rectangle outside the frame");
   const size_t px = (size_t)H * W;
-  if (px > c->fd_pixels) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
-    if (stream_is_capturing((hipStream_t)stream))
-      return fail(SE3TN_E_STATE, "se3tn_fill_depth_rect: scratch too small for this frame inside a stream capture: call se3tn_reserve(ctx, H, W) first");
-    if (int rc = reserve_fill_depth(c, px)) return rc;
-  }
+  if (int rc = grow_now_or_refuse(c, "se3tn_fill_depth_rect", true, "frame", px, stream)) return rc;
   return fill_depth_rect_enqueue(c, depth_mm, H, W, max_depth_m, extrapolate, blur, rect, nullptr, rect, out_mm_sub, (hipStream_t)stream);
 }
 
@@ -2231,11 +2140,7 @@ int se3tn_fill_depth_rects(se3tn_ctx* c, const uint16_t* depth_mm, int H, int W,
   }
   if (!any) return SE3TN_OK;
   const size_t px = (size_t)H * W;
-  if (px > c->fd_pixels) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
-    if (stream_is_capturing((hipStream_t)stream))
-      return fail(SE3TN_E_STATE, "se3tn_fill_depth_rects: scratch too small for this frame inside a stream capture: call se3tn_reserve(ctx, H, W) first");
-    if (int rc = reserve_fill_depth(c, px)) return rc;
-  }
+  if (int rc = grow_now_or_refuse(c, "se3tn_fill_depth_rects", true, "frame", px, stream)) return rc;
   return fill_depth_rects_enqueue(c, depth_mm, H, W, max_depth_m, extrapolate, blur, n, rects, out_offsets, out_mm_base, nullptr,
                                   (hipStream_t)stream);
 }
@@ -2245,11 +2150,7 @@ int se3tn_render_frame(se3tn_ctx* c, se3tn_mesh* m, const double ob_in_cam[16], 
   if (!c || c->device < 0 || !m || !ob_in_cam || !K || !rgb || !depth || W < 1 || H < 1)
     return fail(SE3TN_E_ARG, "se3tn_render_frame: bad argument");
   const size_t px = (size_t)W * H;
-  if (px > c->zbuf_px) {   // not reserved (se3tn_reserve): grow now -- impossible inside a stream capture
-    if (stream_is_capturing((hipStream_t)stream))
-      return fail(SE3TN_E_STATE, "se3tn_render_frame: z-buffer too small for this frame inside a stream capture: call se3tn_reserve(ctx, H, W) first");
-    if (int rc = reserve_zbuf(c, px)) return rc;
-  }
+  if (int rc = grow_now_or_refuse(c, "se3tn_render_frame", false, "frame", px, stream)) return rc;
   if (H > 2048) return fail(SE3TN_E_ARG, "se3tn_render_frame: frames of more than 2048 rows are not supported");
   RasterArgs a{};
   raster_common(a, c, m, rgb, depth);

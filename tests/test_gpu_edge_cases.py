@@ -522,3 +522,87 @@ def test_tracker_init_with_a_ycb_size_mesh_is_bounded(se3, tmp_path):
     assert trk.renderer is not None and len(trk.renderer.mesh["faces"]) == len(f)
     rgbA, depthA = trk.render_window(Fx.pose(3))
     assert rgbA.shape == (176, 176, 3) and (depthA > 0).any()
+
+
+def test_create_use_everything_destroy_create_again(se3):
+    """Every buffer of a context and a mesh has one owner that frees it (csrc/hip_buffers.h), and every lazily allocated one is made by
+    the first call that needs it.  One cycle creates its own contexts and meshes and drives each lazily allocating entry point once, at
+    the smallest shapes that reach the allocation: se3tn_reserve(64, 48), se3tn_on_track and se3tn_on_track_live on a 64 x 48 frame,
+    se3tn_on_track_batch with n = 2, se3tn_on_track_objects with n = 2 on the window route and on the frame route (meshes with a 2 x 2
+    texture), a tracking call with se3tn_set_fit_check on, se3tn_profile_enable(1), se3tn_enable_graphs with three identical
+    se3tn_infer calls (eager, capture, replay) -- then destroys the meshes and the contexts, so the destructors run with every buffer,
+    the copy stream and its event, the profile events and a graph held.  Two such cycles; then a plain se3tn_infer on a third, fresh
+    context must have the bits of the first cycle's.  (Nothing is asserted about free device memory: the card is shared.)"""
+    H, W = 64, 48
+    K = Fx.K_YCB.copy()
+    K[0] *= W / 640
+    K[1] *= H / 480
+    info = dict(Fx.DATASET_INFO, object_width=150.0,
+                camera=dict(height=H, width=W, focalX=K[0, 0], focalY=K[1, 1], centerX=K[0, 2], centerY=K[1, 2]))
+    sd = O.make_state_dict(0, head_gain=0.01)
+    mean, std = Fx.mean_std(0)
+    rgb, depth = Fx.synthetic_frame(70, H, W)
+    raw = Fx.depth_frame_with_holes(70, H, W)
+    tex = Fx.textured_sphere(1, tex_hw=(2, 2))
+    assert tex["texture"].shape == (2, 2, 3)
+    P = Fx.pose(3, (0.0, 0.0, 0.8))
+    A, B = (x.cuda() for x in Fx.net_inputs(4, 1))
+
+    def plain_infer(eng, out=None):
+        t, r = out if out is not None else (torch.empty((1, 3), device="cuda"), torch.empty((1, 3), device="cuda"))
+        eng.infer(A, B, 1, se3.NCHW, t, r)
+        torch.cuda.synchronize()
+        return t.cpu().numpy(), r.cpu().numpy()
+
+    def cycle():
+        trk = se3.Tracker(info, mean, std, {"state_dict": sd}, max_samples=2)              # se3tn_create, se3tn_reserve(64, 48)
+        trk.renderer = se3.HipRenderer(trk.engine, Fx.icosphere(1))                          # se3tn_mesh_create
+        trk_t = se3.Tracker(info, mean, std, {"state_dict": sd}, max_samples=2)
+        trk_t.renderer = se3.HipRenderer(trk_t.engine, tex, mode="pyrender", frame_size=(H, W))   # se3tn_mesh_set_texture, frame route
+        multi = multi_t = None
+        try:
+            first = plain_infer(trk.engine)
+            outs = [trk.on_track(P, rgb, depth), trk.on_track_live(P, rgb, raw), trk.on_track_batch([P, P], [rgb] * 2, [depth] * 2)]
+            multi = se3.MultiTracker([trk, trk])
+            outs.append(multi.on_track([P, P], rgb, depth))                                   # se3tn_on_track_objects, window route
+            multi_t = se3.MultiTracker([trk_t, trk_t])
+            outs.append(multi_t.on_track([P, P], rgb, depth))                                 # ... frame route
+            outs.append(trk_t.on_track_batch([P, P], [rgb] * 2, [depth] * 2))                 # (the batch's frame-route rectangles)
+            trk.fit_check = 30
+            outs.append(trk.on_track(P, rgb, depth))
+            assert trk.last_fit_ratio is not None
+            trk.fit_check = None
+            assert all(np.isfinite(np.asarray(o)).all() for o in outs)
+            eng = trk.engine
+            eng.profile_enable(1)
+            plain_infer(eng)
+            assert len(eng.profile_launches(0)) > 0
+            eng.profile_enable(0)
+            eng.enable_graphs(True)
+            out = (torch.empty((1, 3), device="cuda"), torch.empty((1, 3), device="cuda"))   # the same arguments three times
+            torch.cuda.synchronize()
+            with torch.cuda.stream(torch.cuda.Stream()):
+                replays = [plain_infer(eng, out) for _ in range(3)]
+            for g in replays:
+                assert np.array_equal(g[0], first[0]) and np.array_equal(g[1], first[1])
+            return first
+        finally:
+            for m in (multi, multi_t):
+                if m is not None:
+                    m.close()
+            for t in (trk, trk_t):
+                r, t.renderer = t.renderer, None
+                r.__del__()              # the mesh handle goes before its context
+                t.engine.close()
+
+    first = cycle()
+    again = cycle()
+    assert np.isfinite(first[0]).all() and np.abs(first[0]).max() > 0
+    assert np.array_equal(again[0], first[0]) and np.array_equal(again[1], first[1])
+    eng = se3.Engine(0, 2)
+    try:
+        eng.load_state_dict(sd)
+        third = plain_infer(eng)
+    finally:
+        eng.close()
+    assert np.array_equal(third[0], first[0]) and np.array_equal(third[1], first[1])

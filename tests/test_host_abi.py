@@ -289,6 +289,30 @@ def test_track_plan_host_arithmetic_under_sanitizers(tmp_path):
     assert "track_plan_check: ok" in out.stdout
 
 
+def test_hip_buffers_ownership_under_sanitizers(tmp_path):
+    """csrc/hip_buffers.h (the owners of every device and pinned buffer of a context and a mesh) in a stand-alone host program built
+    with AddressSanitizer + UBSan.  The program defines the six HIP runtime functions the header calls over malloc / free with a count
+    of live blocks and a switch that fails the k-th allocation, so it links no HIP library and touches no device: destruction frees
+    everything, alloc over a held block frees it, a failed alloc leaves the object empty, the rasteriser's group of four survives a
+    failure of each of its allocations (grown again, destroyed: no leak, no double free), a move leaves the source empty, a mapped
+    pinned block reports its device alias."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    rocm_inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
+    if not os.path.exists(os.path.join(rocm_inc, "hip", "hip_runtime_api.h")):
+        pytest.skip("no ROCm headers")
+    exe = str(tmp_path / "hip_buffers_check")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-D__HIP_PLATFORM_AMD__", "-I" + rocm_inc, "-I" + os.path.join(ROOT, "iros20-6d-pose-tracking_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c_abi", "hip_buffers_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    assert "hip_buffers_check: ok" in out.stdout
+
+
 def test_create_refuses_a_max_batch_above_the_limit(se3):
     """se3tn_create: SE3TN_E_ARG with a message above SE3TN_MAX_BATCH_LIMIT (the bound of the kernels' 32-bit byte offsets, derived by
     reading them; nothing is run at or near it), before a context exists; a normal create works afterwards.  The constant is the
