@@ -466,6 +466,42 @@ int se3tn_last_fit(se3tn_ctx* ctx, int n, se3tn_fit* out_host);
  * rectangle.  Either pointer may be NULL.  SE3TN_E_STATE as se3tn_last_fit. */
 int se3tn_last_fit_images(se3tn_ctx* ctx, const uint8_t** rgb_dev, const uint16_t** depth_dev);
 
+/* ---- ADD / ADD-S of n pose pairs in one call ----------------------------------------------------------------- */
+/* Utils.py:72-98 `add` / `adi`, the two errors every result of the reference is reported in (eval_ycb.py, eval_ycbineoat.py),
+ * which it computes one pose at a time with a KD-tree per frame.  For pair i, with the model points x_j (j < P),
+ * a_j = R_pred x_j + t_pred and b_j = R_gt x_j + t_gt:
+ *     add[i]  = mean_j |a_j - b_j|                 (Utils.py:72-82)
+ *     adds[i] = mean_j min_k |b_j - a_k|           (Utils.py:84-98: the tree holds the PRED cloud, the GT cloud queries it)
+ * float64 throughout, no tree: all pairs of points, n * P^2 distance evaluations for ADD-S (P = 2,620: 6.9 M per pose pair).
+ * Guarantees:
+ *   (a) equal poses give exactly 0.0 for both values: both clouds go through ONE transform function in one stated operation order
+ *       with no fused multiply-add, so a point has the same bits on both sides;
+ *   (b) a pair's two doubles depend on (points, pred_i, gt_i) only -- not on n, on the pair's place in the call, on how the call is
+ *       cut into chunks, or on the run: every sum is formed in a fixed order, without floating-point atomics;
+ *   (c) the device-pointer entry point allocates nothing.
+ * A points handle holds the model points on the device (uploaded once) and the partial-sum scratch of one chunk of
+ * SE3TN_POSE_ERRORS_CHUNK pairs; larger n are cut into chunks inside the call.  Calls that share a handle share that scratch: issue
+ * them on one stream (as every compute call of a context). */
+#define SE3TN_POSE_ERRORS_CHUNK 256          /* pose pairs per launch */
+#define SE3TN_POSE_ERRORS_MAX_POINTS 1048576 /* 2^20 */
+typedef struct se3tn_points se3tn_points;
+/* xyz: HOST float64 [P,3] metres (copied).  SE3TN_E_ARG: a NULL pointer, P outside [1, SE3TN_POSE_ERRORS_MAX_POINTS], a coordinate
+ * that is not finite, a host-only context (device = -1) -- all checked before anything is allocated. */
+int se3tn_points_create(se3tn_ctx* ctx, const double* xyz, int P, se3tn_points** out);
+void se3tn_points_destroy(se3tn_points* points);
+int se3tn_points_count(const se3tn_points* points);   /* -1 for NULL */
+/* pred_dev / gt_dev: device float64 [n,16], row-major 4x4 poses (metres); row 3 is not read.  add_dev / adds_dev: device (or mapped
+ * pinned host) float64 [n]; either may be NULL (not both), and with adds_dev NULL the all-pairs loop is not run -- add has the same
+ * bits either way.  Any n >= 1.  Stream-ordered, capturable, allocates nothing.  The poses are not inspected: a pose that is not
+ * finite gives a result that is not finite for its pair (and for no other), which is the caller's business. */
+int se3tn_pose_errors(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* pred_dev, const double* gt_dev,
+                      double* add_dev, double* adds_dev, void* stream);
+/* The same from HOST memory: pred / gt float64 [n,16], add_out / adds_out float64 [n] (either may be NULL, not both): one upload, the
+ * launches, one read-back.  SYNCHRONOUS on `stream`, refused inside a stream capture (SE3TN_E_STATE); the pinned staging and its
+ * device mirror (34 doubles per pair) grow on a first or larger call.  SE3TN_E_ARG: a pose entry that is not finite. */
+int se3tn_pose_errors_host(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* pred, const double* gt,
+                           double* add_out, double* adds_out, void* stream);
+
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K
  * row-major 3x3, width in mm; out_vu[8] = 4 x (v,u) int32, np.round (half-to-even). */

@@ -21,6 +21,8 @@ BLUR_NONE, BLUR_BILATERAL, BLUR_GAUSSIAN = 0, 1, 2
 COLOR_RGB, COLOR_BGR = 0, 1        # se3tn_on_track_live's / se3tn_on_track_objects_live's color_order
 ROUTE_WINDOW, ROUTE_FRAME = 0, 1   # as include/se3tracknet.h: the renderer se3tn_on_track uses for a mesh's image A
 FIT_MAX_PAIRS = 32                 # as include/se3tracknet.h: pairs per launch of se3tn_fit_stats (larger n are chunked)
+POSE_ERRORS_CHUNK = 256            # as include/se3tracknet.h: pose pairs per launch of se3tn_pose_errors (larger n are chunked)
+POSE_ERRORS_MAX_POINTS = 1 << 20   # as include/se3tracknet.h: the largest model se3tn_points_create accepts
 MAX_BATCH_LIMIT = 1982             # as include/se3tracknet.h: the largest max_batch se3tn_create accepts
 RES = 176
 
@@ -133,6 +135,11 @@ _SIGS = {
     "se3tn_get_fit_check": (C.c_int, [C.c_void_p]),
     "se3tn_last_fit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "se3tn_last_fit_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "se3tn_points_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "se3tn_points_destroy": (None, [C.c_void_p]),
+    "se3tn_points_count": (C.c_int, [C.c_void_p]),
+    "se3tn_pose_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_pose_errors_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_compute_bbox": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(C.c_int32)]),
     "se3tn_pose_update_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float),

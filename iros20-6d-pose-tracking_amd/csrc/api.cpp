@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "hip_buffers.h"
+#include "pose_errors_plan.h"
 #include "se3tn_internal.h"
 #include "tex_pyramid.h"
 #include "track_plan.h"
@@ -141,6 +142,8 @@ struct se3tn_ctx {
   int fit_tol = 0, fit_last_n = 0, fit_cap = 0;
   DeviceBuf<uint8_t> fit_rgb; DeviceBuf<uint16_t> fit_depth;
   PinnedBuf<se3tn_fit> fit_host;
+  // se3tn_pose_errors_host: pinned staging [pred | gt | add | adds] (pose_errors_plan.h: pe_stage_*) for pe_cap pairs and its device mirror
+  PinnedBuf<double> pe_host; DeviceBuf<double> pe_dev; int pe_cap = 0;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive / splitk_sem before the next one
   DeviceBuf<int> tail_arrive;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
   int* tail_flag = nullptr; int tail_seq = 0;   // set around se3tn_on_track's infer: the tail kernel stores tail_seq to this (mapped) word
@@ -194,6 +197,13 @@ struct se3tn_mesh {
   float kd[3] = {1.f, 1.f, 1.f};
   bool has_material = false;        // se3tn_mesh_set_texture has been called (a texture, or a Kd over the vertex colours)
   int route = SE3TN_ROUTE_WINDOW;   // se3tn_mesh_set_route: the renderer se3tn_on_track / _batch use for image A
+};
+
+// se3tn_points_create: the model points of se3tn_pose_errors and the partial sums of one chunk of pairs
+struct se3tn_points {
+  int device = -1, P = 0;
+  DeviceBuf<double> xyz;    // [P,3]
+  DeviceBuf<double> part;   // [PE_CHUNK][tiles][2] (pose_errors_plan.h)
 };
 
 // Init-time entry points that allocate or launch (plane derivation, workspace growth) run on the CONTEXT's device whatever device the
@@ -1600,6 +1610,96 @@ int se3tn_last_fit_images(se3tn_ctx* c, const uint8_t** rgb_dev, const uint16_t*
   if (c->fit_last_n == 0) return fail(SE3TN_E_STATE, "se3tn_last_fit_images: the last tracking call of this context left no estimate renders (se3tn_set_fit_check off, or the call failed)");
   if (rgb_dev) *rgb_dev = c->fit_rgb.get();
   if (depth_dev) *depth_dev = c->fit_depth.get();
+  return SE3TN_OK;
+}
+
+// ---- ADD / ADD-S of n pose pairs ---------------------------------------------------------------------------------------------------
+int se3tn_points_create(se3tn_ctx* c, const double* xyz, int P, se3tn_points** out) {
+  if (!c || !xyz || !out) return fail(SE3TN_E_ARG, "se3tn_points_create: NULL argument");
+  if (c->device < 0) return fail(SE3TN_E_ARG, "se3tn_points_create: host-only context (device = -1) has no device to hold the points");
+  if (P < 1 || P > PE_MAX_POINTS)
+    return fail(SE3TN_E_ARG, "se3tn_points_create: P = " + std::to_string(P) + " outside [1, SE3TN_POSE_ERRORS_MAX_POINTS = " +
+                                 std::to_string(PE_MAX_POINTS) + "]");
+  for (size_t i = 0; i < (size_t)3 * P; ++i)
+    if (!std::isfinite(xyz[i])) return fail(SE3TN_E_ARG, "se3tn_points_create: coordinate " + std::to_string(i) + " is not finite");
+  DeviceGuard dg(c->device);
+  if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+  se3tn_points* p = new se3tn_points();
+  p->device = c->device; p->P = P;
+  hipError_t e = p->xyz.alloc((size_t)3 * P);
+  if (e == hipSuccess) e = hipMemcpy(p->xyz.get(), xyz, sizeof(double) * 3 * (size_t)P, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = p->part.alloc(pe_scratch_doubles(P), true);
+  if (e != hipSuccess) { delete p; return hipfail(e, "se3tn_points_create"); }
+  *out = p;
+  return SE3TN_OK;
+}
+
+void se3tn_points_destroy(se3tn_points* p) { delete p; }
+int se3tn_points_count(const se3tn_points* p) { return p ? p->P : -1; }
+
+// the chunks of one call, enqueued on st (both entry points)
+static int pose_errors_enqueue(const se3tn_points* p, int n, const double* pred, const double* gt, double* add, double* adds, hipStream_t st) {
+  for (int ch = 0, nch = pe_chunks(n); ch < nch; ++ch) {
+    const PeChunk k = pe_chunk(n, ch);
+    PoseErrArgs a;
+    a.pts = p->xyz.get(); a.P = p->P;
+    a.pred = pred + k.first * 16; a.gt = gt + k.first * 16;
+    a.part = p->part.get();
+    a.add = add ? add + k.first : nullptr;
+    a.adds = adds ? adds + k.first : nullptr;
+    HIPCHK(launch_pose_errors(a, k.count, st));
+  }
+  return SE3TN_OK;
+}
+
+static int pose_errors_check(const char* who, const se3tn_ctx* c, const se3tn_points* p, int n, const void* pred, const void* gt,
+                             const void* add, const void* adds) {
+  if (!c || c->device < 0 || !p) return fail(SE3TN_E_ARG, std::string(who) + ": NULL or host-only context, or NULL points");
+  if (p->device != c->device) return fail(SE3TN_E_ARG, std::string(who) + ": the points live on another device than the context");
+  if (n < 1) return fail(SE3TN_E_ARG, std::string(who) + ": n < 1");
+  if (!pred || !gt) return fail(SE3TN_E_ARG, std::string(who) + ": NULL poses");
+  if (!add && !adds) return fail(SE3TN_E_ARG, std::string(who) + ": both outputs NULL");
+  return SE3TN_OK;
+}
+
+int se3tn_pose_errors(se3tn_ctx* c, const se3tn_points* p, int n, const double* pred_dev, const double* gt_dev, double* add_dev,
+                      double* adds_dev, void* stream) {
+  if (int rc = pose_errors_check("se3tn_pose_errors", c, p, n, pred_dev, gt_dev, add_dev, adds_dev)) return rc;
+  return pose_errors_enqueue(p, n, pred_dev, gt_dev, add_dev, adds_dev, (hipStream_t)stream);
+}
+
+int se3tn_pose_errors_host(se3tn_ctx* c, const se3tn_points* p, int n, const double* pred, const double* gt, double* add_out,
+                           double* adds_out, void* stream) {
+  if (int rc = pose_errors_check("se3tn_pose_errors_host", c, p, n, pred, gt, add_out, adds_out)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_pose_errors_host: the call is synchronous, it cannot be captured");
+  for (size_t i = 0; i < (size_t)n * 16; ++i)
+    if (!std::isfinite(pred[i]) || !std::isfinite(gt[i]))
+      return fail(SE3TN_E_ARG, "se3tn_pose_errors_host: pose " + std::to_string(i / 16) + " has an entry that is not finite");
+  if (n > c->pe_cap) {   // first / larger call: the staging belongs to the context's device
+    DeviceGuard dg(c->device);
+    if (int rc = begin_growth(dg)) return rc;
+    c->pe_cap = 0;
+    HIPCHK(c->pe_host.alloc(pe_stage_doubles(n)));
+    HIPCHK(c->pe_dev.alloc(pe_stage_doubles(n)));
+    c->pe_cap = n;
+  }
+  // the staging is laid out for THIS n (pe_stage_*): poses and results are each one contiguous run
+  double* h = c->pe_host.get();
+  double* d = c->pe_dev.get();
+  std::memcpy(h, pred, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(h + pe_stage_gt(n), gt, sizeof(double) * 16 * (size_t)n);
+  HIPCHK(hipMemcpyAsync(d, h, sizeof(double) * 32 * (size_t)n, hipMemcpyHostToDevice, st));
+  if (int rc = pose_errors_enqueue(p, n, d, d + pe_stage_gt(n), add_out ? d + pe_stage_add(n) : nullptr,
+                                   adds_out ? d + pe_stage_adds(n) : nullptr, st))
+    return rc;
+  // one read-back: [add | adds], or the one that was asked for
+  const size_t r0 = add_out ? pe_stage_add(n) : pe_stage_adds(n);
+  const size_t rn = (size_t)n * ((add_out ? 1 : 0) + (adds_out ? 1 : 0));
+  HIPCHK(hipMemcpyAsync(h + r0, d + r0, sizeof(double) * rn, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (add_out) std::memcpy(add_out, h + pe_stage_add(n), sizeof(double) * (size_t)n);
+  if (adds_out) std::memcpy(adds_out, h + pe_stage_adds(n), sizeof(double) * (size_t)n);
   return SE3TN_OK;
 }
 

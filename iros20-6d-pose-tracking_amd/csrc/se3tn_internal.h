@@ -258,6 +258,18 @@ struct FitArgs {
 static_assert(sizeof(FitArgs) <= 4096, "FitArgs travels as kernel arguments: HIP's limit is 4 KB");
 hipError_t launch_fit_stats(const FitArgs& a, int n, hipStream_t st);
 
+// ADD / ADD-S of one chunk of pose pairs (pose_errors.hip; the index arithmetic is pose_errors_plan.h)
+struct PoseErrArgs {
+  const double* pts;    // [P,3] model points
+  int P;
+  const double* pred;   // [.,16] row-major poses of the chunk's FIRST pair onwards (rows 0-2 are read)
+  const double* gt;
+  double* part;         // [PE_CHUNK][tiles][2] partial sums of this chunk
+  double* add;          // [count] results of the chunk, or nullptr
+  double* adds;         // [count] or nullptr: the all-pairs loop is skipped
+};
+hipError_t launch_pose_errors(const PoseErrArgs& a, int count, hipStream_t st);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per DEVICE: a launcher remembers which device
 // ordinals it has already raised the limit on (several contexts on different GPUs in one process).
 struct PerDeviceOnce {

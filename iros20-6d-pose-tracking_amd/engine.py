@@ -32,6 +32,34 @@ def pack_crops(rgb, depth, windows, z_offset_mm, stats):
     return rec
 
 
+class ModelPoints:
+    """se3tn_points: the model points of Engine.pose_errors on the device (uploaded once) with the scratch of one chunk of pairs.
+    ``points`` keeps the host copy (float64 [P,3]), so the handle also serves the CPU evaluators of metrics.py."""
+
+    def __init__(self, engine, pts):
+        self.points = np.ascontiguousarray(np.asarray(pts.points if hasattr(pts, "points") else pts, np.float64).reshape(-1, 3))
+        self.engine = engine
+        self._h = None
+        h = C.c_void_p()
+        check(engine.lib.se3tn_points_create(engine._h, C.c_void_p(self.points.ctypes.data), int(self.points.shape[0]), C.byref(h)),
+              "se3tn_points_create")
+        self._h = h
+
+    def __len__(self):
+        return int(self.points.shape[0])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.engine.lib.se3tn_points_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, device=0, max_batch=64):
         self.lib = _lib.load()
@@ -303,6 +331,43 @@ class Engine:
         check(self.lib.se3tn_memcpy_d2d(C.c_void_p(rgb.data_ptr()), rgb_p, n * RES * RES * 3, _stream_ptr()), "se3tn_memcpy_d2d")
         check(self.lib.se3tn_memcpy_d2d(C.c_void_p(dep.data_ptr()), dep_p, n * RES * RES * 2, _stream_ptr()), "se3tn_memcpy_d2d")
         return rgb, dep
+
+    # ---- ADD / ADD-S of n pose pairs -------------------------------------------------------------
+    def model_points(self, pts):
+        """Upload model points (float64 [P,3] metres, or an object with ``.points``) for pose_errors: a ModelPoints handle."""
+        return ModelPoints(self, pts)
+
+    def pose_errors(self, points, preds, gts, adds=True):
+        """se3tn_pose_errors: ADD and ADD-S (Utils.py:72-98) of n (pred, gt) pose pairs against the model `points` (ModelPoints) in one
+        call -> (add[n], adds[n]) in metres; adds=False skips the all-pairs loop and returns (add[n], None).
+        preds / gts: [n,4,4] (or [n,16]) numpy arrays -> float64 numpy arrays, synchronous (se3tn_pose_errors_host); or cuda float64
+        tensors -> cuda tensors, stream-ordered on the current stream, nothing allocated by the library (se3tn_pose_errors)."""
+        if not isinstance(points, ModelPoints) or not points._h:
+            raise Se3tnError("pose_errors: points must be an open ModelPoints handle (Engine.model_points)")
+        if torch.is_tensor(preds) or torch.is_tensor(gts):
+            if not (torch.is_tensor(preds) and torch.is_tensor(gts)):
+                raise Se3tnError("pose_errors: preds and gts must both be tensors or both be arrays")
+            for x in (preds, gts):
+                assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.numel() % 16 == 0
+            n = preds.numel() // 16
+            assert gts.numel() == preds.numel()
+            add = torch.empty((n,), dtype=torch.float64, device=preds.device)
+            ads = torch.empty((n,), dtype=torch.float64, device=preds.device) if adds else None
+            check(self.lib.se3tn_pose_errors(self._h, points._h, n, C.c_void_p(preds.data_ptr()), C.c_void_p(gts.data_ptr()),
+                                             C.c_void_p(add.data_ptr()), C.c_void_p(ads.data_ptr()) if adds else None, _stream_ptr()),
+                  "se3tn_pose_errors")
+            return add, ads
+        p = np.ascontiguousarray(np.asarray(preds, np.float64).reshape(-1, 16))
+        g = np.ascontiguousarray(np.asarray(gts, np.float64).reshape(-1, 16))
+        if p.shape != g.shape:
+            raise ValueError("pose_errors: %d predicted and %d ground-truth poses" % (p.shape[0], g.shape[0]))
+        n = int(p.shape[0])
+        add = np.empty(n, np.float64)
+        ads = np.empty(n, np.float64) if adds else None
+        check(self.lib.se3tn_pose_errors_host(self._h, points._h, n, C.c_void_p(p.ctypes.data), C.c_void_p(g.ctypes.data),
+                                              C.c_void_p(add.ctypes.data), C.c_void_p(ads.ctypes.data) if adds else None, _stream_ptr()),
+              "se3tn_pose_errors_host")
+        return add, ads
 
     def fill_depth(self, depth_mm, max_depth=2.0, extrapolate=False, blur_type="bilateral", return_metres=False):
         """Utils.py:455-514 fill_depth as predict_ros.py:38-41 applies it: uint16 millimetre frame (numpy [H,W] or a

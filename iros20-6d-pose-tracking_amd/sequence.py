@@ -102,7 +102,7 @@ def poserbpf_pose(ycb_dir, class_id, seq_id):
 
 
 def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, reinit=None, max_frames=None, init="gt",
-                         reinit_frames=None, ycb_dir=None, seq_id=None, reinit_below=None):
+                         reinit_frames=None, ycb_dir=None, seq_id=None, reinit_below=None, device_metrics=False):
     """tracker: se3tracknet_amd.Tracker.
     init: 'gt' (what predict.py:447 hard-codes) | 'posecnn' (:480-496: start at the keyframe nearest to start_frame) | 'poserbpf'.
     reinit_frames: the reference's --reinit_frames, a comma-separated string or list of 'SSSS/FFFFFF': before tracking the image
@@ -113,7 +113,9 @@ def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, rei
     estimate nearest to frame number i - 1 -- the reference's rule for a listed frame -- whenever the previous call's
     ``tracker.last_fit_ratio`` (inlier_px / model_px of its estimate against the observed depth) was below it: the list
     --reinit_frames takes from somebody who watched the canvas, decided by the fit.  The indices come back as res["reinit_at"].
-    None (default): nothing changes."""
+    None (default): nothing changes.
+    device_metrics (extension): True scores all frames after tracking in ONE ``tracker.pose_errors`` call on the tracker's engine
+    (se3tn_pose_errors_host) instead of a KD-tree per frame on the CPU; the errors agree within 1e-12 m, the files are the same."""
     rgb_files = sorted(glob.glob(os.path.join(seq_dir, "color", "*")))
     depth_files = sorted(glob.glob(os.path.join(seq_dir, "depth_filled", "*")))
     gt_files = sorted(glob.glob(os.path.join(seq_dir, "pose_gt", str(class_id), "*")))
@@ -177,14 +179,16 @@ def predict_sequence_ycb(tracker, seq_dir, class_id, out_dir, start_frame=0, rei
     for k in range(len(pred_poses)):
         np.savetxt(os.path.join(out_dir, "%05d.txt" % k), pred_poses[k])
         np.savetxt(os.path.join(out_dir, "%05dgt.txt" % k), gt_poses[start_frame + k])
-        if tracker.object_cloud is not None:
+        if tracker.object_cloud is not None and not device_metrics:
             add_errs.append(metrics.add(pred_poses[k], gt_poses[start_frame + k], tracker.object_cloud))
             adi_errs.append(metrics.adi(pred_poses[k], gt_poses[start_frame + k], tracker.object_cloud))
+    if tracker.object_cloud is not None and device_metrics:
+        add_errs, adi_errs = tracker.pose_errors(pred_poses, np.array(gt_poses[start_frame:start_frame + len(pred_poses)]))
     res = {"poses": pred_poses, "frames": len(pred_poses) - 1,
            "hz": (len(pred_poses) - 1) / t_track if t_track > 0 else float("nan")}
     if reinit_below is not None:
         res["reinit_at"] = reinit_at
-    if adi_errs:
+    if len(adi_errs):
         res.update(add_errs=np.array(add_errs), adi_errs=np.array(adi_errs))
         res["add_auc"] = metrics.auc(add_errs)    # 0.0 when no frame is below 0.1 m (the reference's VOCap raises)
         res["adi_auc"] = metrics.auc(adi_errs)
@@ -310,17 +314,19 @@ def get_results_ycb_objects(trackers_by_class, ycb_dir, out_dirs_by_class, seq_i
     return done
 
 
-def eval_one_class(res_dir, ycb_dir, class_id):
+def eval_one_class(res_dir, ycb_dir, class_id, engine=None):
     """eval_ycb.py:67-119: ADD / ADD-S AUC (x100) of the keyframe poses found under res_dir/seq*/,
     against <ycb_dir>/data_organized/%04d/pose_gt/<class_id>/%06d.txt, with the class's
-    CADmodels/*/points.xyz as the model and YCB_Video_toolbox/keyframe.txt as the frame filter."""
+    CADmodels/*/points.xyz as the model and YCB_Video_toolbox/keyframe.txt as the frame filter.
+    engine (extension): an Engine -- every (pred, gt) of the class is collected first and scored in ONE device call
+    (metrics.pose_errors) instead of a KD-tree per frame on the CPU."""
     pose_files = sorted(glob.glob(os.path.join(res_dir, "**", "*.txt"), recursive=True))
     assert len(pose_files) > 0, "no pose files under %s" % res_dir
     model_files = sorted(glob.glob(os.path.join(ycb_dir, "CADmodels", "**", "points.xyz"), recursive=True))
     model_pts = np.loadtxt(model_files[class_id - 1]).reshape(-1, 3)
     with open(os.path.join(ycb_dir, "YCB_Video_toolbox", "keyframe.txt")) as ff:
         keyframes = set(line.rstrip() for line in ff)
-    adi_errs, add_errs = [], []
+    adi_errs, add_errs, pairs = [], [], []
     for pose_file in pose_files:
         rel = os.path.relpath(pose_file, res_dir).split(os.sep)
         seq_id = int(rel[0].replace("seq", ""))
@@ -329,8 +335,13 @@ def eval_one_class(res_dir, ycb_dir, class_id):
             continue
         pred = np.loadtxt(pose_file)
         gt = np.loadtxt(os.path.join(ycb_dir, "data_organized", "%04d" % seq_id, "pose_gt", str(class_id), "%06d.txt" % frame_id))
+        if engine is not None:
+            pairs.append((pred, gt))
+            continue
         adi_errs.append(metrics.adi(pred, gt, model_pts))
         add_errs.append(metrics.add(pred, gt, model_pts))
+    if pairs:
+        add_errs, adi_errs = metrics.pose_errors([p for p, _ in pairs], [g for _, g in pairs], model_pts, engine=engine)
     assert len(adi_errs) > 0, "no keyframe among the result files"
     adi_errs = np.sort(np.array(adi_errs)); add_errs = np.sort(np.array(add_errs))
     return {"add_auc": metrics.auc(add_errs), "adi_auc": metrics.auc(adi_errs),
@@ -366,17 +377,20 @@ def predict_sequence_ycbineoat(tracker, data_dir, out_dir, max_frames=None):
     return {"poses": np.array(poses), "frames": n, "hz": n / t_track if t_track > 0 else float("nan")}
 
 
-def eval_ycbineoat(res_dir, data_dir, ycb_dir, objects=YCBINEOAT_OBJECTS):
+def eval_ycbineoat(res_dir, data_dir, ycb_dir, objects=YCBINEOAT_OBJECTS, engine=None):
     """eval_ycbineoat.py:45-109 `eval_all`: every folder of res_dir (one per video, named after it) is
     matched to an object by substring, its %07d.txt poses are compared one-to-one with
     <data_dir>/<folder>/annotated_poses/*.txt, the model is the CADmodels/*/points.xyz whose path
-    contains the object name.  Returns per-object and overall ADD / ADD-S AUC (x100)."""
+    contains the object name.  Returns per-object and overall ADD / ADD-S AUC (x100).
+    engine (extension): an Engine -- the (pred, gt) pairs of an object are collected over its videos first and scored in ONE
+    device call per model (metrics.pose_errors) instead of a KD-tree per frame on the CPU."""
     models = {}
     for t in sorted(glob.glob(os.path.join(ycb_dir, "CADmodels", "*", "points.xyz"))):
         for obj in objects:
             if obj in t:
                 models[obj] = np.loadtxt(t).reshape(-1, 3)
     class_res = {obj: {"add": [], "add-s": []} for obj in objects}
+    pairs = {obj: [] for obj in objects}
     for folder in sorted(os.listdir(res_dir)):
         if ".tar.gz" in folder or not os.path.isdir(os.path.join(res_dir, folder)):
             continue
@@ -387,8 +401,15 @@ def eval_ycbineoat(res_dir, data_dir, ycb_dir, objects=YCBINEOAT_OBJECTS):
         assert len(pred_files) == len(gt_files), "#pred_files:%d, #gt_files:%d" % (len(pred_files), len(gt_files))
         for pf, gf in zip(pred_files, gt_files):
             pred, gt = np.loadtxt(pf), np.loadtxt(gf)
+            if engine is not None:
+                pairs[obj].append((pred, gt))
+                continue
             class_res[obj]["add"].append(metrics.add(pred, gt, models[obj]))
             class_res[obj]["add-s"].append(metrics.adi(pred, gt, models[obj]))
+    for obj in objects:
+        if pairs[obj]:
+            a, s_ = metrics.pose_errors([p for p, _ in pairs[obj]], [g for _, g in pairs[obj]], models[obj], engine=engine)
+            class_res[obj]["add"], class_res[obj]["add-s"] = a.tolist(), s_.tolist()
 
     auc = metrics.auc   # 0.0 when nothing is below 0.1 m (the reference's VOCap raises) or the list is empty
     out = {"per_object": {}, "n": 0}

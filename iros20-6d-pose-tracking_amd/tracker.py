@@ -111,6 +111,7 @@ class Tracker:
         self._poseB = self._out[:ms * 128].view(torch.float64).view(ms, 16)
         self._trans = self._out[ms * 128:ms * 140].view(torch.float32).view(ms, 3)
         self._rot = self._out[ms * 140:ms * 152].view(torch.float32).view(ms, 3)
+        self._model_points = None    # pose_errors: object_cloud on the device, uploaded at first use
         self.last_prediction = None
         self.last_fit_ratio = None   # fit_check set: inlier_px / model_px of the last call (float; on_track_batch: [n] array)
         self._fit_imgs = None
@@ -120,6 +121,15 @@ class Tracker:
         self._stream = torch.cuda.Stream(device=dev) if use_graphs else None
         if use_graphs:
             self.engine.enable_graphs(True)
+
+    def pose_errors(self, preds, gts):
+        """ADD / ADD-S (metres) of n (pred, gt) pose pairs against ``object_cloud`` in one device call (Engine.pose_errors) ->
+        (add[n], adds[n]).  The cloud is uploaded on the first call and kept."""
+        if self.object_cloud is None:
+            raise ValueError("pose_errors: this tracker has no object_cloud (no model_path was given)")
+        if self._model_points is None:
+            self._model_points = self.engine.model_points(self.object_cloud)
+        return self.engine.pose_errors(self._model_points, preds, gts)
 
     @property
     def fit_check(self):
