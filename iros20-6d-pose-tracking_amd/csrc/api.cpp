@@ -41,7 +41,7 @@ enum { MAX_LAUNCHES = 24, MAX_SLOTS = 64 };
 struct GraphKey {
   const void *A, *B, *trans, *rot, *poseA, *poseB, *blob;
   int n, layout, prec, wino_min_batch, wino_tile, keep, wino64, wino64_fill;
-  int small_kernels, splitk_fused, wino_fuse, gemmp, tail_parts;   // every switch that selects a kernel family (a graph captured under another
+  int small_kernels, wino_fuse, gemmp, tail_parts;   // every switch that selects a kernel family (a graph captured under another
                                                        // setting must not be replayed)
   double tn, rn;
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
@@ -77,16 +77,12 @@ struct se3tn_ctx {
   DeviceBuf<float> fcpart;                      // [mb,2,<=32,3] partial FC dot products (fused Winograd tail: 8 slices per head; tail_kernel 8; tail_parts_kernel 32)
   bool keep_intermediates = false;              // se3tn_keep_intermediates: fused blocks also store ab_t / head_t / head
   int auto_tile_override[2] = {0, 0};           // SE3TN_WINOGRAD_AUTO_TILE_AB2 / _HEADS = 4 | 6: what AUTO picks per block (rounding studies)
-  int trunk_kernel = 1;                         // SE3TN_TRUNK_KERNEL = 2: the register-V trunk experiment (only in -DSE3TN_TRUNK_REGV=1 builds)
   int gemmp = -1;                               // SE3TN_WINO_GEMMP = 0 | 1: never | always the persistent 128 x 256 Winograd GEMM (default: by tile count)
   bool wino_fuse = true;                        // whole residual blocks as one fused launch sequence (SE3TN_WINOGRAD_FUSE=0: conv by conv)
   DeviceBuf<float> part;                        // split-K partial sums (small-batch latency path)
-  DeviceBuf<int> splitk_sem;                    // [2 x SE3TN_SPLITK_MAX_TILES] arrival / seen counters of the fused split-K reduction (zero between launches)
   int tail_parts_ch = 16;                       // SE3TN_TAIL_PARTS=2: 32 workgroups x 32 channels per pair instead of 64 x 16 (developer A/B)
   bool tail_parts = true;                       // SE3TN_TAIL_PARTS=0 (developer switch): batch 1-5 keeps conv_reduce + tail_kernel after the last head conv
   bool small_kernels = true;                    // SE3TN_SMALL_KERNELS=0 (developer switch): batch 1-5 through the split-K kernels only
-  bool splitk_fused = false;                    // SE3TN_SPLITK_FUSED=1 (developer switch): the reduction inside the split-K launch -- bitwise the same results,
-                                                // but SLOWER on this chip (363 vs 268 us per batch-1 forward: EXPERIMENTS item 41), so off
   // Winograd F(m x m,3x3) path (wino_mfma.hip) of convAB2.* and trans|rot conv2.* at n >= wino_min_batch
   int wino_min_batch = SE3TN_WINOGRAD_DEFAULT_MIN_BATCH;  // 0 = never
   int wino_tile = SE3TN_WINOGRAD_DEFAULT_TILE;            // m = 2 | 4 | 6 | SE3TN_WINOGRAD_TILE_AUTO
@@ -144,7 +140,7 @@ struct se3tn_ctx {
   PinnedBuf<se3tn_fit> fit_host;
   // se3tn_pose_errors_host: pinned staging [pred | gt | add | adds] (pose_errors_plan.h: pe_stage_*) for pe_cap pairs and its device mirror
   PinnedBuf<double> pe_host; DeviceBuf<double> pe_dev; int pe_cap = 0;
-  bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive / splitk_sem before the next one
+  bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive before the next one
   DeviceBuf<int> tail_arrive;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
   int* tail_flag = nullptr; int tail_seq = 0;   // set around se3tn_on_track's infer: the tail kernel stores tail_seq to this (mapped) word
   hipStream_t trk_copy_stream = nullptr; hipEvent_t trk_copy_event = nullptr;
@@ -405,7 +401,6 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
   c->SL = split_layout();
   if (const char* e = std::getenv("SE3TN_WINOGRAD_AUTO_TILE_AB2")) c->auto_tile_override[0] = (std::atoi(e) == 4 || std::atoi(e) == 6) ? std::atoi(e) : 0;
   if (const char* e = std::getenv("SE3TN_WINOGRAD_AUTO_TILE_HEADS")) c->auto_tile_override[1] = (std::atoi(e) == 4 || std::atoi(e) == 6) ? std::atoi(e) : 0;
-  if (const char* e = std::getenv("SE3TN_TRUNK_KERNEL")) c->trunk_kernel = std::atoi(e) == 2 ? 2 : 1;
   if (const char* e = std::getenv("SE3TN_WINO_GEMMP")) c->gemmp = std::atoi(e) != 0 ? 1 : 0;
   if (const char* e = std::getenv("SE3TN_WINOGRAD_FUSE")) c->wino_fuse = std::atoi(e) != 0;      // developer A/B switch (and the tests'
                                                                                                   // bit-equality check of the two forms)
@@ -442,10 +437,8 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
     }
     // split-K workspace: 16 slices of the widest layer (1024 couts x 121 px) up to batch 16
     e = c->part.alloc((size_t)16 * 1024 * 121 * 16);
-    if (e == hipSuccess) e = c->splitk_sem.alloc(2 * SE3TN_SPLITK_MAX_TILES, true);
     if (e == hipSuccess) e = c->tail_arrive.alloc(c->max_batch, true);
     if (e == hipSuccess) e = c->fit_counters.alloc((size_t)FitArgs::WORDS * c->max_batch, true);
-    if (const char* sf = std::getenv("SE3TN_SPLITK_FUSED")) c->splitk_fused = std::atoi(sf) != 0;
     if (const char* sk = std::getenv("SE3TN_SMALL_KERNELS")) c->small_kernels = std::atoi(sk) != 0;
     if (const char* tp = std::getenv("SE3TN_TAIL_PARTS")) { c->tail_parts = std::atoi(tp) != 0; c->tail_parts_ch = std::atoi(tp) == 2 ? 32 : 16; }
     if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(split-K workspace)"); }
@@ -744,10 +737,9 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
 int se3tn_infer(se3tn_ctx* c, const float* A, const float* B, int n, int layout, float* trans, float* rot,
                 const double* poseA, double* poseB, void* stream) {
   if (c && c->rearm_counters && c->device >= 0 && !stream_is_capturing((hipStream_t)stream)) {
-    // a launch sequence that failed half-way can leave the tail's arrival counters / the split-K semaphores non-zero, and every
+    // a launch sequence that failed half-way can leave the tail's arrival counters non-zero, and every
     // later frame would then find no "last" workgroup: clear them, stream-ordered, before the next frame
     if (c->tail_arrive) HIPCHK(hipMemsetAsync(c->tail_arrive.get(), 0, sizeof(int) * c->max_batch, (hipStream_t)stream));
-    if (c->splitk_sem) HIPCHK(hipMemsetAsync(c->splitk_sem.get(), 0, sizeof(int) * 2 * SE3TN_SPLITK_MAX_TILES, (hipStream_t)stream));
     c->rearm_counters = false;
   }
   const int rc = infer_graph_or_launch(c, A, B, n, layout, trans, rot, poseA, poseB, stream);
@@ -765,7 +757,7 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
   key.n = n; key.layout = layout; key.prec = c->prec;
   key.wino_min_batch = c->wino_min_batch; key.wino_tile = c->wino_tile; key.keep = c->keep_intermediates ? 1 : 0;
   key.wino64 = c->wino64_min_batch; key.wino64_fill = c->wino64_min_fill; key.tn = c->tn; key.rn = c->rn;
-  key.small_kernels = c->small_kernels ? 1 : 0; key.splitk_fused = c->splitk_fused ? 1 : 0; key.wino_fuse = c->wino_fuse ? 1 : 0;
+  key.small_kernels = c->small_kernels ? 1 : 0; key.wino_fuse = c->wino_fuse ? 1 : 0;
   key.gemmp = c->gemmp; key.tail_parts = c->tail_parts ? c->tail_parts_ch : 0;
   hipStream_t st = (hipStream_t)stream;
   for (auto& g : c->graphs) {
@@ -860,9 +852,7 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
     else
       HIPCHK(launch_stem(A, B, W + L.stem_w, W + L.stem_b, nullptr, c->stem.get(), n, st));
     HIPCHK((hipError_t)prof_mark(c, st, "stem7x7_mfma", false));
-#if !defined(SE3TN_ABLATE_POOL)   // (timing-only variant build: what the step costs WITHOUT the pool pass -- EXPERIMENTS item 43)
     HIPCHK(launch_maxpool(c->stem.get(), c->pool.get(), n, fast ? 1 : 0, st));
-#endif
     HIPCHK((hipError_t)prof_mark(c, st, "maxpool3x3s2", false));
   }
 
@@ -896,7 +886,7 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
       const int slot64 = (int)id - (int)L64_1;
       route.algo = ConvRoute::WINO64;
       hipError_t e = launch_wino64(in, in_ld, in_gs, c->wino64_u[slot64].get(), (long long)16 * s.cin * s.cout, W + L.conv_b[id], s.cout, res,
-                                   res_ld, res_gs, out, out_ld, out_gs, n, s.groups, epi, c->trunk_kernel, st);
+                                   res_ld, res_gs, out, out_ld, out_gs, n, s.groups, epi, st);
       if (e != hipSuccess) return hipfail(e, name);
       static const char* const fused_names[4] = {"conv64 A2.conv1|B2.conv1 [fused F(2x2)]", "conv64 A2.conv2|B2.conv2 [fused F(2x2)]",
                                                  "conv64 B3.conv1 [fused F(2x2)]", "conv64 B3.conv2 [fused F(2x2)]"};
@@ -910,7 +900,6 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
       a.w = WS + SL.conv_ws[id];
       a.wscale = WS + SL.conv_sc[id];
     } a.res = res; a.out = out; a.part = c->part.get(); a.part_bytes = c->part.count() * sizeof(float);
-    a.sem = c->splitk_fused ? c->splitk_sem.get() : nullptr;
     a.small_ok = c->small_kernels ? 1 : 0;
     a.skip_reduce = skip_reduce ? 1 : 0;
     a.in_ld = in_ld; a.res_ld = res_ld; a.out_ld = out_ld;

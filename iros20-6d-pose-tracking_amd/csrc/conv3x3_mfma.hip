@@ -36,13 +36,6 @@
 //    tap (strided windows have no contiguous slab).
 #include "mfma_common.h"
 
-#ifndef SE3TN_PERSISTENT_SLAB
-#define SE3TN_PERSISTENT_SLAB 1  // 0: one workgroup per tile (A/B timing only)
-#endif
-#ifndef SE3TN_SLAB_RELAXED
-#define SE3TN_SLAB_RELAXED 0     // 1: the slab piece of the NEXT chunk stays in flight across the K-step barriers (counted vmcnt)
-#endif
-
 namespace se3tn {
 
 // shared epilogue: lane holds pixel l31 x couts {8q + 4hh + 0..3} of each 32x32 tile.
@@ -234,15 +227,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_slab_kernel(const ConvArgs a) 
         } else if (more) {
           WEIGHT_TILE(0, 0, wb ^ 1)
         }
-        // (the weight tile is issued BEFORE the slab piece: a counted wait that leaves one operation in flight leaves the
-        // slab piece, which nobody reads before the next chunk)
-        bool piece_in_flight = false;
         if (ch + 1 < NCH) {
           SLAB_PIECE(lo, npieces, ch + 1, sb ^ 1, tap)
-          piece_in_flight = (wid + 8 * tap) < npieces;
         } else if (more) {
           SLAB_PIECE(nlo, nnp, 0, 0, tap)
-          piece_in_flight = (wid + 8 * tap) < nnp;
         }
 
         const int r = tap / 3, s = tap - r * 3;
@@ -269,18 +257,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_slab_kernel(const ConvArgs a) 
         }
 #undef PXF
 #undef WTF
-        if (kt + 1 < NCH * 9 || more) {
-          if (SE3TN_SLAB_RELAXED && MM == MM_F32 && tap < 8) {
-            // next K-step reads only the weight tile just fetched: wait for it (operations retire in order), let this wave's
-            // slab piece fly on; the whole slab is drained (vmcnt(0)) at the chunk's last K-step, before anybody reads it
-            if (piece_in_flight) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-          } else {
-            wait_dma_and_barrier();
-          }
-        }
+        if (kt + 1 < NCH * 9 || more) wait_dma_and_barrier();
       }
     }
     store_tiles<PT, CT, EPI, MM, OUTF, RESF>(a, g, acc, opix, ok, n0 + wn * CT * 32, hh, PREFETCH_RES ? rpre : nullptr);
@@ -316,16 +293,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_gather_s2_kernel(const Con
   const int l31 = lane & 31, hh = lane >> 5;
 
   const int panels = a.groups * a.tiles_n;
-#if defined(SE3TN_GATHER_XCD_PIXELS)
-  // variant (EXPERIMENTS items 12, 42): an XCD owns a RANGE OF PIXEL TILES and walks every weight panel over it (its L2 keeps the
-  // input rows; the panels stream), instead of owning weight panels
-  const int tiles_m = (a.M + BM - 1) / BM, per_x = (tiles_m + 7) / 8;
-  const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int p = q % panels, mt = x * per_x + q / panels;
-  if (mt >= tiles_m) return;
-#else
   const int p = blockIdx.x % panels, mt = blockIdx.x / panels;
-#endif
   const int g = p / a.tiles_n, nt = p % a.tiles_n;
   const int m0 = mt * BM, n0 = nt * BN;
   const float* __restrict__ in = a.in + (size_t)g * a.in_gs;
@@ -411,34 +379,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_gather_s2_kernel(const Con
   store_tiles<PT, CT, EPI, MM, OUTF, FMT_F32>(a, g, acc, opix, ok, n0 + wn * CT * 32, hh);
 }
 
-// 16-byte store with device (agent) scope: written through the non-coherent per-XCD L2, visible to every compute unit once
-// s_waitcnt vmcnt(0) has returned
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store_agent_scope(float* p, const float4 v) {
-  f32x4_t t;
-  t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(t) : "memory");
-}
-
-#ifndef SE3TN_SPLITK_WT
-#define SE3TN_SPLITK_WT 1   // 1 (shipped): partial sums written through the L2 and device-scope counters -- correct under ANY workgroup ->
-                            // XCD mapping (CU masks, other partition modes: ADVICE r5); 0 (measurement builds only, EXPERIMENTS item 41):
-                            // left in the tile's own XCD's L2, which ASSUMES blockIdx % 8 is the XCD
-#endif
-// the arrival counters: device scope (memory side) with write-through partial sums, the XCD's own L2 otherwise
-#if SE3TN_SPLITK_WT
-#define SE3TN_SEM_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#else
-#define SE3TN_SEM_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-#endif
-__device__ __forceinline__ void store_partial(float* p, const float4 v) {
-#if SE3TN_SPLITK_WT
-  store_agent_scope(p, v);
-#else
-  *reinterpret_cast<float4*>(p) = v;
-#endif
-}
-
 // one float4 of the output: the slices' partial sums added in a FIXED order, then bias / residual / activation
 // PI (mixed-model batch, conv_slices_small only): the bias of output row m's image, img_off[m / (Ho Wo)] floats from a.bias -- a
 // per-lane index here (a workgroup may straddle two images), so the offset is selected from the table, not indexed
@@ -488,65 +428,6 @@ __global__ __launch_bounds__(256) void conv_reduce_kernel(const ConvArgs a, int 
   reduce_element<EPI, MM, OUTF, RESF, PI>(a, a.part + ((size_t)g * a.M + m) * cout + c, (size_t)a.groups * a.M * cout, g, m, c);
 }
 
-// The reduction INSIDE the split-K launch (a.sem != nullptr): the grid carries, after the conv workgroups, a.rpt reduce
-// workgroups per output tile (a power of two <= 32: each takes 128 / rpt rows).  A conv workgroup publishes its partial tile (device-scope release) and counts itself into sem[tile];
-// a reduce workgroup sleeps until the count reaches `slices`, then sums its rows of the tile in the same fixed slice order as
-// conv_reduce_kernel -- bitwise the same result, without the second launch.  MEASURED SLOWER (EXPERIMENTS item 41: 363 vs 268 us per
-// batch-1 forward): partial sums that another XCD must see inside the launch have to be written through / read around the per-XCD
-// L2, which costs more than the 5-6 us launch it saves.  Kept behind SE3TN_SPLITK_FUSED=1 with its bitwise A/B check.
-// No deadlock: conv workgroups never wait, and the reduce workgroups (rpt x tiles <= 256) cannot occupy every workgroup
-// slot of the device (launch_splitk checks), whatever order the dispatcher takes.
-template <int MM, int BM, int BN>
-__device__ __forceinline__ void splitk_reduce_part(const ConvArgs& a, int tile, int seg) {
-  const int panels = a.groups * a.tiles_n;
-  const int p = tile % panels, mt = tile / panels;
-  const int g = p / a.tiles_n, nt = p - g * a.tiles_n;
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    // (an atomic read-modify-write executes in the XCD's L2, where the conv workgroups' arrivals are counted: no stale L1 line)
-    while (__hip_atomic_fetch_add(a.sem + tile, 0, __ATOMIC_RELAXED, SE3TN_SEM_SCOPE) < a.slices) __builtin_amdgcn_s_sleep(1);
-    // the last reduce workgroup to see the tile complete re-arms both counters for the next launch
-    if (__hip_atomic_fetch_add(a.sem + SE3TN_SPLITK_MAX_TILES + tile, 1, __ATOMIC_RELAXED, SE3TN_SEM_SCOPE) == a.rpt - 1) {
-      __hip_atomic_exchange(a.sem + tile, 0, __ATOMIC_RELAXED, SE3TN_SEM_SCOPE);
-      __hip_atomic_exchange(a.sem + SE3TN_SPLITK_MAX_TILES + tile, 0, __ATOMIC_RELAXED, SE3TN_SEM_SCOPE);
-    }
-  }
-  __syncthreads();
-#if SE3TN_SPLITK_WT
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // every thread reads the partial sums other compute units stored
-#else
-  // the partial sums are in THIS XCD's L2 (written by its other compute units): only this compute unit's vector L1 may hold stale
-  // lines of the workspace (an agent-scope acquire would also drop the L2's clean lines under the conv workgroups still running)
-  asm volatile("buffer_inv sc0" ::: "memory");
-#endif
-  // the partial tiles are stored in ACCUMULATOR-FRAGMENT order (conv3x3_splitk_kernel): float4 number
-  //   f = (((wave * PT + i) * CT + j) * 4 + q) * 64 + lane   of tile `tile` of slice s at part[(s * tiles + tile) * BM * BN + 4 f]
-  // -- every store / load instruction of a wave moves one contiguous KB
-  constexpr int PT = 2, CT = BN / 64, E = BM * BN / 4;
-  const int tiles = ((a.M + BM - 1) / BM) * panels;
-  const int per = E / a.rpt;
-  const size_t slice_stride = (size_t)tiles * BM * BN;
-  for (int e = tid; e < per; e += 256) {
-    const int f = seg * per + e;
-    const int lane = f & 63, q = (f >> 6) & 3, t8 = f >> 8;
-    const int j = t8 % CT, i = (t8 / CT) % PT, wv = t8 / (CT * PT);
-    const int m = mt * BM + ((wv >> 1) * PT + i) * 32 + (lane & 31);
-    const int c = nt * BN + ((wv & 1) * CT + j) * 32 + q * 8 + (lane >> 5) * 4;
-    if (m >= a.M) continue;
-    const float* src = a.part + (size_t)tile * BM * BN + (size_t)f * 4;
-    if (MM == MM_F16X3) {
-      if (a.epi == 0) reduce_element<0, MM_F16X3, FMT_SPLIT, FMT_F32>(a, src, slice_stride, g, m, c);
-      else if (a.epi == 2) reduce_element<2, MM_F16X3, FMT_SPLIT, FMT_F32>(a, src, slice_stride, g, m, c);
-      else if (a.outf == FMT_SPLIT) reduce_element<1, MM_F16X3, FMT_SPLIT, FMT_SPLIT>(a, src, slice_stride, g, m, c);
-      else reduce_element<1, MM_F16X3, FMT_F32, FMT_SPLIT>(a, src, slice_stride, g, m, c);
-    } else {
-      if (a.epi == 0) reduce_element<0, MM_F32, FMT_F32, FMT_F32>(a, src, slice_stride, g, m, c);
-      else if (a.epi == 1) reduce_element<1, MM_F32, FMT_F32, FMT_F32>(a, src, slice_stride, g, m, c);
-      else reduce_element<2, MM_F32, FMT_F32, FMT_F32>(a, src, slice_stride, g, m, c);
-    }
-  }
-}
-
 // =================================================================================================
 // small-batch (latency) path: split-K.  At batch 1 the big-tile kernels above would occupy 8-64 of
 // the 256 CUs (M = 121..1936 rows), so the K dimension -- cin / 32 chunks x 9 taps K-steps -- is cut into `slices` runs of
@@ -572,23 +453,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_splitk_kernel(const ConvArgs a
   const int l31 = lane & 31, hh = lane >> 5;
 
   const int panels = a.groups * a.tiles_n;
-  int sl = blockIdx.x % a.slices, rest = blockIdx.x / a.slices;
-  if (a.sem) {   // (uniform) fused reduction: every workgroup of tile t -- its slices and its reduce workgroups -- has blockIdx = t (mod 8),
-    // i.e. runs on ONE XCD, whose L2 then holds the tile's partial sums; the workgroups behind the conv workgroups reduce
-    const int tiles = ((a.M + BM - 1) / BM) * panels, tg = (tiles + 7) / 8;
-    const int conv_wgs = tg * a.slices * 8;
-    const int b = (int)blockIdx.x;
-    if (b >= conv_wgs) {
-      const int rb = b - conv_wgs, q = rb >> 3;
-      const int t = (q / a.rpt) * 8 + (rb & 7);
-      if (t < tiles) splitk_reduce_part<MM, BM, BN>(a, t, q % a.rpt);
-      return;
-    }
-    const int q = b >> 3;
-    rest = (q / a.slices) * 8 + (b & 7);
-    sl = q % a.slices;
-    if (rest >= tiles) return;
-  }
+  const int sl = blockIdx.x % a.slices, rest = blockIdx.x / a.slices;
   const int p = rest % panels, mt = rest / panels;
   const int g = p / a.tiles_n, nt = p % a.tiles_n;
   const int m0 = mt * BM, n0 = nt * BN;
@@ -667,42 +532,21 @@ __global__ __launch_bounds__(256, 2) void conv3x3_splitk_kernel(const ConvArgs a
   }
 #undef ISSUE_TILE
 
-  // raw partial sums: part[slice][group][m][cout] for conv_reduce_kernel; with the fused reduction, accumulator-fragment order
-  // (splitk_reduce_part), written THROUGH the XCD's L2: another XCD's reduce workgroup reads it in this launch
+  // raw partial sums: part[slice][group][m][cout] for conv_reduce_kernel
   const int cout = a.tiles_n * BN;
-  if (a.sem) {
-    const int tiles = ((a.M + BM - 1) / BM) * panels;
-    float* __restrict__ ptile = a.part + ((size_t)sl * tiles + rest) * (BM * BN);
+  float* __restrict__ part = a.part + ((size_t)(sl * a.groups + g) * a.M) * cout;
 #pragma unroll
-    for (int i = 0; i < PT; ++i)
+  for (int i = 0; i < PT; ++i) {
+    const int m = m0 + (wm * PT + i) * 32 + l31;
+    if (m >= a.M) continue;
 #pragma unroll
-      for (int j = 0; j < CT; ++j)
+    for (int j = 0; j < CT; ++j)
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-          store_partial(ptile + (size_t)(((((wid * PT + i) * CT + j) * 4 + q) * 64 + lane) * 4),
-                        make_float4(acc[i][j][4 * q + 0], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]));
-  } else {
-    float* __restrict__ part = a.part + ((size_t)(sl * a.groups + g) * a.M) * cout;
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-      const int m = m0 + (wm * PT + i) * 32 + l31;
-      if (m >= a.M) continue;
-#pragma unroll
-      for (int j = 0; j < CT; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int c = n0 + (wn * CT + j) * 32 + q * 8 + hh * 4;
-          *reinterpret_cast<float4*>(part + (size_t)m * cout + c) =
-              make_float4(acc[i][j][4 * q + 0], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-        }
-    }
-  }
-  if (a.sem) {   // publish: the stores have been acknowledged by the device-coherent level, then ONE arrival per workgroup.
-    // (A release fence per thread -- __threadfence() -- writes the whole L2 back 256 times per workgroup: 864 us per forward
-    // instead of 268, measured.)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(a.sem + rest, 1, __ATOMIC_RELAXED, SE3TN_SEM_SCOPE);
+      for (int q = 0; q < 4; ++q) {
+        const int c = n0 + (wn * CT + j) * 32 + q * 8 + hh * 4;
+        *reinterpret_cast<float4*>(part + (size_t)m * cout + c) =
+            make_float4(acc[i][j][4 * q + 0], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+      }
   }
 }
 
@@ -729,7 +573,7 @@ static hipError_t launch_slab(const ConvArgs& a, hipStream_t st) {
   const int tiles_m = (a.M + BM - 1) / BM;
   // one workgroup per CU (LDS-bound); with more tiles than CUs the workgroups are persistent
   const int ntiles = tiles_m * a.tiles_n * a.groups;
-  const int grid = (SE3TN_PERSISTENT_SLAB && ntiles > 256) ? 256 : ntiles;
+  const int grid = ntiles > 256 ? 256 : ntiles;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
   return hipGetLastError();
 }
@@ -743,11 +587,7 @@ static hipError_t launch_gather_nw(const ConvArgs& a, hipStream_t st) {
   hipError_t e = set_lds(kern, lds, attr);
   if (e != hipSuccess) return e;
   const int tiles_m = (a.M + BM - 1) / BM;
-#if defined(SE3TN_GATHER_XCD_PIXELS)
-  hipLaunchKernelGGL(kern, dim3(((tiles_m + 7) / 8) * 8 * a.tiles_n * a.groups), dim3(NW * 64), lds, st, a);
-#else
   hipLaunchKernelGGL(kern, dim3(tiles_m * a.tiles_n * a.groups), dim3(NW * 64), lds, st, a);
-#endif
   return hipGetLastError();
 }
 
@@ -767,50 +607,40 @@ static void launch_reduce(const ConvArgs& a, int cout, hipStream_t st) {
   hipLaunchKernelGGL((conv_reduce_kernel<EPI, MM, OUTF, RESF, PI>), dim3((total + 255) / 256), dim3(256), 0, st, a, cout, total);
 }
 
-// the fused reduction's reduce workgroups: at most this many per launch (the launch holds 512 workgroup slots: 2 per compute unit)
-#ifndef SE3TN_SPLITK_MAX_REDUCE_WGS
-#define SE3TN_SPLITK_MAX_REDUCE_WGS 256
-#endif
-// outf / resf: FMT_* of the output and residual tensors (f16x3 mode: split rows except the last head conv)
+// The epilogue pass over the slices' partial sums, chosen once for every caller: epi 0 | 1 | 2, mm = MM_*, outf = FMT_* of the output
+// tensor.  f16x3 mode reads split-row residuals and writes split rows, except the last head conv (float32 out); per_img: ConvArgs.
+static hipError_t launch_reduce_for(const ConvArgs& a, int cout, int epi, int mm, int outf, bool per_img, hipStream_t st) {
+  if (mm == MM_F16X3) {
+    if (epi == 0) launch_reduce<0, MM_F16X3, FMT_SPLIT, FMT_F32>(a, cout, st);
+    else if (epi == 2) launch_reduce<2, MM_F16X3, FMT_SPLIT, FMT_F32>(a, cout, st);
+    else if (outf == FMT_SPLIT) launch_reduce<1, MM_F16X3, FMT_SPLIT, FMT_SPLIT>(a, cout, st);
+    else launch_reduce<1, MM_F16X3, FMT_F32, FMT_SPLIT>(a, cout, st);
+  } else if (per_img) {
+    if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
+    else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
+    else launch_reduce<2, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
+  } else {
+    if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
+    else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
+    else launch_reduce<2, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
+  }
+  return hipGetLastError();
+}
+
+// outf: FMT_* of the output tensor (f16x3 mode: split rows except the last head conv)
 template <int CIN, int STRIDE, int CT, int MM>
-static hipError_t launch_splitk(const ConvArgs& a0, int epi, int outf, int resf, hipStream_t st) {
+static hipError_t launch_splitk(const ConvArgs& a, int epi, int outf, hipStream_t st) {
   constexpr int BN = 64 * CT;
   constexpr size_t lds = (size_t)2 * (128 + BN) * 32 * sizeof(float);
   auto kern = conv3x3_splitk_kernel<CIN, STRIDE, CT, MM>;
   static PerDeviceOnce attr;
   hipError_t e = set_lds(kern, lds, attr);
   if (e != hipSuccess) return e;
-  const int tiles_m = (a0.M + 127) / 128;
-  const int tiles = tiles_m * a0.tiles_n * a0.groups;
-  if (a0.sem && tiles <= SE3TN_SPLITK_MAX_TILES && tiles * 4 <= SE3TN_SPLITK_MAX_REDUCE_WGS &&
-      (size_t)a0.slices * tiles * 128 * BN * sizeof(float) <= a0.part_bytes) {
-    // reduction inside this launch: rpt reduce workgroups per tile, ~128 in all (few tiles: more, thinner row bands)
-    ConvArgs a = a0;
-    int rpt = 4;
-    while (rpt < 32 && tiles * rpt * 2 <= SE3TN_SPLITK_MAX_REDUCE_WGS / 2) rpt *= 2;
-    a.rpt = rpt; a.epi = epi; a.outf = outf; a.resf = resf;
-    const int tg = (tiles + 7) / 8;
-    hipLaunchKernelGGL(kern, dim3(tg * 8 * (a.slices + rpt)), dim3(256), lds, st, a);
-    return hipGetLastError();
-  }
-  ConvArgs a = a0;
-  a.sem = nullptr;
+  const int tiles = ((a.M + 127) / 128) * a.tiles_n * a.groups;
   hipLaunchKernelGGL(kern, dim3(tiles * a.slices), dim3(256), lds, st, a);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int cout = a.tiles_n * BN;
-  if (MM == MM_F32) {
-    if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-    else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-    else launch_reduce<2, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-  } else {
-    if (epi == 0) launch_reduce<0, MM_F16X3, FMT_SPLIT, FMT_F32>(a, cout, st);
-    else if (epi == 2) launch_reduce<2, MM_F16X3, FMT_SPLIT, FMT_F32>(a, cout, st);
-    else if (outf == FMT_SPLIT) launch_reduce<1, MM_F16X3, FMT_SPLIT, FMT_SPLIT>(a, cout, st);
-    else launch_reduce<1, MM_F16X3, FMT_F32, FMT_SPLIT>(a, cout, st);
-  }
-  (void)resf;
-  return hipGetLastError();
+  return launch_reduce_for(a, a.tiles_n * BN, epi, MM, outf, false, st);
 }
 
 // Split-K is used when the big-tile grid would leave most of the 256 CUs idle and the partial-sum workspace is large enough.
@@ -872,7 +702,6 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
     if (sl > 0 && (size_t)sl * a.groups * a.M * cout * sizeof(float) <= a.part_bytes) {
       a.slices = sl;
       a.tiles_n = cout / 32;
-      a.sem = nullptr;
       r.algo = ConvRoute::SLICES;
       r.slices = sl;
       hipError_t e = launch_conv_slices_small(a, cin, stride, st);
@@ -881,10 +710,7 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
         r.reduced = false;
         return hipSuccess;
       }
-      if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-      else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-      else launch_reduce<2, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-      return hipGetLastError();
+      return launch_reduce_for(a, cout, epi, MM_F32, FMT_F32, false, st);
     }
   }
   a.slices = pick_slices(a, cin, cout, stride == 1 ? 256 : 128, cout >= 128 ? 128 : 64);
@@ -894,18 +720,18 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
     a.tiles_n = cout >= 128 ? cout / 128 : 1;
     if (a.fast) {  // f16x3: split rows everywhere, float32 out of the last head conv (cin 512, residual)
       const int outf = (cin == 512 && epi == 1) ? FMT_F32 : FMT_SPLIT;
-      if (cin == 64 && stride == 1) return launch_splitk<64, 1, 1, MM_F16X3>(a, epi, outf, FMT_SPLIT, st);
-      if (cin == 128 && stride == 2) return launch_splitk<128, 2, 2, MM_F16X3>(a, epi, outf, FMT_SPLIT, st);
-      if (cin == 256 && stride == 1) return launch_splitk<256, 1, 2, MM_F16X3>(a, epi, outf, FMT_SPLIT, st);
-      if (cin == 256 && stride == 2) return launch_splitk<256, 2, 2, MM_F16X3>(a, epi, outf, FMT_SPLIT, st);
-      if (cin == 512 && stride == 1) return launch_splitk<512, 1, 2, MM_F16X3>(a, epi, outf, FMT_SPLIT, st);
+      if (cin == 64 && stride == 1) return launch_splitk<64, 1, 1, MM_F16X3>(a, epi, outf, st);
+      if (cin == 128 && stride == 2) return launch_splitk<128, 2, 2, MM_F16X3>(a, epi, outf, st);
+      if (cin == 256 && stride == 1) return launch_splitk<256, 1, 2, MM_F16X3>(a, epi, outf, st);
+      if (cin == 256 && stride == 2) return launch_splitk<256, 2, 2, MM_F16X3>(a, epi, outf, st);
+      if (cin == 512 && stride == 1) return launch_splitk<512, 1, 2, MM_F16X3>(a, epi, outf, st);
       return hipErrorInvalidValue;
     }
-    if (cin == 64 && stride == 1) return launch_splitk<64, 1, 1, MM_F32>(a, epi, FMT_F32, FMT_F32, st);
-    if (cin == 128 && stride == 2) return launch_splitk<128, 2, 2, MM_F32>(a, epi, FMT_F32, FMT_F32, st);
-    if (cin == 256 && stride == 1) return launch_splitk<256, 1, 2, MM_F32>(a, epi, FMT_F32, FMT_F32, st);
-    if (cin == 256 && stride == 2) return launch_splitk<256, 2, 2, MM_F32>(a, epi, FMT_F32, FMT_F32, st);
-    if (cin == 512 && stride == 1) return launch_splitk<512, 1, 2, MM_F32>(a, epi, FMT_F32, FMT_F32, st);
+    if (cin == 64 && stride == 1) return launch_splitk<64, 1, 1, MM_F32>(a, epi, FMT_F32, st);
+    if (cin == 128 && stride == 2) return launch_splitk<128, 2, 2, MM_F32>(a, epi, FMT_F32, st);
+    if (cin == 256 && stride == 1) return launch_splitk<256, 1, 2, MM_F32>(a, epi, FMT_F32, st);
+    if (cin == 256 && stride == 2) return launch_splitk<256, 2, 2, MM_F32>(a, epi, FMT_F32, st);
+    if (cin == 512 && stride == 1) return launch_splitk<512, 1, 2, MM_F32>(a, epi, FMT_F32, st);
     return hipErrorInvalidValue;
   }
   r.algo = stride == 1 ? ConvRoute::SLAB : ConvRoute::GATHER;   // (the big-tile kernels: slab at stride 1, gather at stride 2)
@@ -965,20 +791,10 @@ hipError_t launch_conv_small(const ConvArgs& a0, int cin, int cout, int stride, 
   if (sl <= 0 || !a.part || (size_t)sl * a.groups * a.M * cout * sizeof(float) > a.part_bytes) return hipErrorInvalidValue;
   a.slices = sl;
   a.tiles_n = cout / 32;
-  a.sem = nullptr;
   hipError_t e = launch_conv_slices_small(a, cin, stride, st);
   if (e != hipSuccess) return e;
   if (a.skip_reduce) return hipSuccess;
-  if (a.per_img) {
-    if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
-    else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
-    else launch_reduce<2, MM_F32, FMT_F32, FMT_F32, true>(a, cout, st);
-  } else {
-    if (epi == 0) launch_reduce<0, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-    else if (epi == 1) launch_reduce<1, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-    else launch_reduce<2, MM_F32, FMT_F32, FMT_F32>(a, cout, st);
-  }
-  return hipGetLastError();
+  return launch_reduce_for(a, cout, epi, MM_F32, FMT_F32, a.per_img != 0, st);
 }
 
 }  // namespace se3tn

@@ -3,10 +3,6 @@
 #pragma once
 #include "se3tn_internal.h"
 
-#ifndef SE3TN_ABLATE
-#define SE3TN_ABLATE 0  // timing ablations only (wrong results): 1 = no DMA, 2 = no barrier
-#endif
-
 namespace se3tn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -56,9 +52,6 @@ __device__ __forceinline__ unsigned lds_addr_of(const float* p) {
 }
 template <int IMM>
 __device__ __forceinline__ void glds16(const float* sbase, unsigned voff_bytes, unsigned lds_byte_addr) {
-#if (SE3TN_ABLATE & 1)
-  return;
-#endif
   // both scalar operands are wave-uniform by construction; readfirstlane makes that provable to
   // the compiler (an "s" constraint on a value it believes divergent does not assemble)
   const unsigned long long b_ = (unsigned long long)sbase;
@@ -75,9 +68,7 @@ __device__ __forceinline__ void glds16(const float* sbase, unsigned voff_bytes, 
 }
 __device__ __forceinline__ void wait_dma_and_barrier() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if !(SE3TN_ABLATE & 2)
   __syncthreads();
-#endif
 }
 
 // One 8-k group of a K-step: PTN x CTN x 4 MFMAs.  PVEXPR may use `i`, WVEXPR may use `j`.

@@ -131,7 +131,6 @@ constexpr int PAD_SLACK_PX = 8;
 constexpr int IN_PAD = 3;
 constexpr int IN_P = RES + 2 * IN_PAD;  // 182
 constexpr int IN_SLACK_ROWS = 6;
-constexpr int SE3TN_SPLITK_MAX_TILES = 1024;   // output tiles (m tile x group x n tile) of a split-K launch with the fused reduction
 // batch 1-5 kernel family: most pairs a launch takes (stem + pool, trunk convs, channel-slice convs, and so the per-image tables below)
 #ifndef SE3TN_SLICES_SMALL_MAX_N
 #define SE3TN_SLICES_SMALL_MAX_N 5   // up to this many pairs the 128 .. 512-channel convs take conv_slices_small_kernel (0: never)
@@ -163,11 +162,6 @@ struct ConvArgs {
   float* part;
   size_t part_bytes;
   int slices;
-  // fused reduction of the split-K path: sem[tile] counts the slices of an output tile that have stored their partial sums,
-  // sem[SE3TN_SPLITK_MAX_TILES + tile] the reduce workgroups that have seen it complete (both are zero between launches).
-  // nullptr = separate conv_reduce_kernel launch.  epi / outf / resf: the epilogue the in-kernel reduction applies
-  int* sem;
-  int epi, outf, resf, rpt;   // rpt: reduce workgroups per output tile
   int skip_reduce;            // conv_slices_small only: the caller consumes the partial sums itself (tail_parts_kernel): no conv_reduce launch
   int small_ok;               // the batch-1-5 kernel family (conv64_small, conv_slices_small) may be used (SE3TN_SMALL_KERNELS=0 switches them off)
   // f16x3 mode: per-cout power-of-two weight scale (acc * wscale = true sum), overflow flag,
@@ -314,7 +308,7 @@ hipError_t launch_wino_conv(const WinoArgs& a, int epi, hipStream_t st);
 // fused Winograd F(2x2,3x3) of a 64 -> 64 channel convolution on the 44 x 44 maps (wino64_fused.hip); U: F(2x2) planes of launch_wino_weights
 hipError_t launch_wino64(const float* in, int in_ld, int in_gs, const float* U, long long u_gs, const float* bias, int bias_gs,
                          const float* res, int res_ld, int res_gs, float* out, int out_ld, int out_gs, int n, int groups, int epi,
-                         int variant, hipStream_t st);
+                         hipStream_t st);
 // a whole residual block on the Winograd F(4x4) path with the fused mid / tail transforms (wino_mfma.hip);
 // mark_after_mid: optional profiling hook called between conv1 and conv2 (returns non-zero on error)
 hipError_t launch_wino_block(const WinoArgs& c1, const float* U2, const float* uscale2, const float* bias2, float* out2, int keep_mid,

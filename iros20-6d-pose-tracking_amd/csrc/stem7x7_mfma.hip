@@ -20,10 +20,6 @@
 // Output: [n,88,88,128] NHWC, branch A in channels 0-63, branch B in 64-127.
 #include "se3tn_internal.h"
 
-#ifndef SE3TN_STEM_ABLATE
-#define SE3TN_STEM_ABLATE 0  // timing ablations only: 1 = no output stores, 2 = no slab DMA
-#endif
-
 namespace se3tn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -93,9 +89,6 @@ __global__ __launch_bounds__(512, 2) void stem7x7_slab_kernel(const StemArgs a) 
 
   // slab of tile t: padded input rows [2 h0, 2 h0 + 13) of image t / 31, h0 = first output row
   auto issue_slab = [&](int t, int buf) {
-#if (SE3TN_STEM_ABLATE & 2)
-    return;  // timing ablation: no slab DMA
-#endif
     const int img = t / TILES_PER_IMAGE, h0 = ((t - img * TILES_PER_IMAGE) * TILE) / S1;
     const float* src = in + ((size_t)img * IP * IP + (size_t)(2 * h0) * IP) * 4;
     const unsigned dst = lds0 + WBYTES + buf * SLAB_BYTES;
@@ -153,11 +146,7 @@ __global__ __launch_bounds__(512, 2) void stem7x7_slab_kernel(const StemArgs a) 
         v.y = selu_s(acc[j][4 * q + 1] * w.y + b.y);
         v.z = selu_s(acc[j][4 * q + 2] * w.z + b.z);
         v.w = selu_s(acc[j][4 * q + 3] * w.w + b.w);
-#if (SE3TN_STEM_ABLATE & 1)
-        asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));  // timing ablation: no stores
-#else
         *reinterpret_cast<float4*>(out + c) = v;
-#endif
       }
   };
 

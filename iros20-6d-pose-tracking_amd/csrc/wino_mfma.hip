@@ -459,19 +459,6 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs a) {
     ::se3tn_wg_trace[blockIdx.x * 8 + 3] = t_start_;
   }
 #endif
-#ifdef SE3TN_WINO_STAGGER
-  // experiment: the two workgroups of a CU start together and, tiles being equal, stay in lock step (both in their
-  // prologue, both in their epilogue): delay one of them by about half a tile
-  {
-#if SE3TN_WINO_STAGGER == 1
-    const bool late = blockIdx.x >= 256 && blockIdx.x < 512;
-#else
-    const bool late = blockIdx.x < 512 && (blockIdx.x & 1);
-#endif
-    if (late)
-      for (int i_ = 0; i_ < (CIN == 256 ? 3 : 6); ++i_) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   ISSUE_TILE(0, 0)
   wait_dma_and_barrier();
 
@@ -526,115 +513,6 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs a) {
   if (tid == 0 && blockIdx.x < 4096) ::se3tn_wg_trace[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_memrealtime();   // stores issued
 #endif
 }
-
-// -------------------------------------------------------------------------------------------------
-// wino_gemm8_kernel: the same 96 x 128 tile, LDS image and DMA as wino_gemm_kernel<CIN, 1, 4, 3, 1>, but EIGHT waves per
-// workgroup: waves 0-3 and 4-7 take the two 16-channel halves of every 32-channel K-step (intra-workgroup split-K), and the
-// two half sums are added through LDS at the end of the tile (fixed order: low half + high half).  Why: a WG-level trace of
-// the 4-wave kernel (scripts/wg_trace.py, profiles/r03_wg_trace.txt) shows that with 6.75 tiles per CU a CU spends ~21 % of
-// the launch with ONE resident workgroup = one wave per SIMD, which cannot keep the matrix pipe busy on its own (no
-// second wave to issue under its ds_reads / barrier / DMA wait).  With 8 waves a lone workgroup still has two waves per
-// SIMD, and two co-resident workgroups have four.
-template <int CIN>
-__global__ __launch_bounds__(512, 2) void wino_gemm8_kernel(const WinoArgs a) {
-  constexpr int PT = 3, BM = 96, BN = 128;
-  constexpr int NCH = CIN / 32;
-  constexpr int BUF = (BM + BN) * 32;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wn = wid & 3, kh = wid >> 2;
-  const int l31 = lane & 31, hh = lane >> 5;
-
-  const int panels = a.Cout / BN, mtiles = (a.T + BM - 1) / BM;
-  const int nt = blockIdx.x % panels, rest = blockIdx.x / panels;
-  const int mt = rest % mtiles, b = rest / mtiles;
-  const int g = b / a.nf, f = b - g * a.nf;
-  const int m0 = mt * BM, n0 = nt * BN;
-  const float* __restrict__ Vb = a.V + (size_t)b * a.T * CIN;
-  const float* __restrict__ Ub = a.U + (size_t)g * a.u_gs + ((size_t)f * a.Cout + n0) * 32;
-  const int mlast = a.T - 1;
-
-  // staging: thread t fills LDS slot (t & 7) of row (t >> 3) + 64 j with channel block (t & 7) ^ ((row >> 1) & 7);
-  // V rows 0..95: pass 0 all eight waves, pass 1 waves 0-3 (rows 64..95); U rows 0..127: two passes
-  const int r0 = tid >> 3;
-  const int c4 = (tid & 7) ^ ((r0 >> 1) & 7);
-  const unsigned pv0 = (unsigned)((min(m0 + r0, mlast) * CIN + c4 * 4) * 4);
-  const unsigned pv1 = (unsigned)((min(m0 + r0 + 64, mlast) * CIN + c4 * 4) * 4);
-  const unsigned wvoff = (unsigned)((r0 * 32 + c4 * 4) * 4);
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
-
-#define ISSUE_TILE8(CH, BUFI)                                                                        \
-  {                                                                                                  \
-    const float* pb_ = Vb + (CH) * 32;                                                               \
-    const unsigned lb_ = lds0 + (unsigned)(((BUFI) * BUF + wid * 256) * 4);                          \
-    glds16<0>(pb_, pv0, lb_);                                                                        \
-    if (wid < 4) glds16<0>(pb_, pv1, lb_ + 8192);                                                    \
-    const float* tb_ = Ub + (size_t)(CH) * a.nf * a.Cout * 32;                                       \
-    glds16<0>(tb_, wvoff, lb_ + BM * 128);                                                           \
-    glds16<0>(tb_ + 2048, wvoff, lb_ + BM * 128 + 8192);                                             \
-  }
-
-  const int X = (l31 >> 1) & 7;
-  const int lo = (hh ^ (X & 1)) * 4, xk = X >> 1;
-  // this wave's two 8-k groups of a K-step: 2 kh, 2 kh + 1
-  const int foA = (((2 * kh) ^ xk) << 3) + lo, foB = (((2 * kh + 1) ^ xk) << 3) + lo;
-
-  f32x16 acc[PT][1];
-#pragma unroll
-  for (int i = 0; i < PT; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][0][e] = 0.f;
-
-  ISSUE_TILE8(0, 0)
-  wait_dma_and_barrier();
-
-  for (int ch = 0; ch < NCH; ++ch) {
-    const int buf = ch & 1;
-    if (ch + 1 < NCH) ISSUE_TILE8(ch + 1, buf ^ 1)
-    const float* pP = smem + buf * BUF + l31 * 32;
-    const float* pW = smem + buf * BUF + (BM + wn * 32 + l31) * 32;
-#define PXF8(FO) *reinterpret_cast<const float4*>(pP + i * 1024 + (FO))
-#define WTF8(FO) *reinterpret_cast<const float4*>(pW + j * 1024 + (FO))
-    SE3TN_MMA_GROUP(PT, 1, PXF8(foA), WTF8(foA))
-    SE3TN_MMA_GROUP(PT, 1, PXF8(foB), WTF8(foB))
-#undef PXF8
-#undef WTF8
-    if (ch + 1 < NCH) wait_dma_and_barrier();
-  }
-#undef ISSUE_TILE8
-
-  // the two K halves meet in LDS (the operand buffers are free after this barrier): float4 slots [wn][i][q][lane]
-  __syncthreads();
-  float4* xch = reinterpret_cast<float4*>(smem);
-  if (kh == 1) {
-#pragma unroll
-    for (int i = 0; i < PT; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        xch[((wn * PT + i) * 4 + q) * 64 + lane] =
-            make_float4(acc[i][0][4 * q + 0], acc[i][0][4 * q + 1], acc[i][0][4 * q + 2], acc[i][0][4 * q + 3]);
-  }
-  __syncthreads();
-  if (kh == 1) return;
-  // lane holds row l31 x couts {8 q + 4 hh + 0..3} of each 32 x 32 block
-  float* __restrict__ Mb = a.Mw + (size_t)b * a.T * a.Cout;
-#pragma unroll
-  for (int i = 0; i < PT; ++i) {
-    const int m = m0 + i * 32 + l31;
-    if (m > mlast) continue;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 h = xch[((wn * PT + i) * 4 + q) * 64 + lane];
-      const int c = n0 + wn * 32 + q * 8 + hh * 4;
-      *reinterpret_cast<float4*>(Mb + (size_t)m * a.Cout + c) =
-          make_float4(acc[i][0][4 * q + 0] + h.x, acc[i][0][4 * q + 1] + h.y, acc[i][0][4 * q + 2] + h.z, acc[i][0][4 * q + 3] + h.w);
-    }
-  }
-}
-
 
 // -------------------------------------------------------------------------------------------------
 // wino_gemmp_kernel ("p" = persistent): 128 rows x 256 couts per tile, EIGHT waves (2 x 4, each 64 x 64 = 2 x 2 blocks), one
@@ -1091,22 +969,6 @@ static hipError_t launch_gemm(const WinoArgs& a, hipStream_t st) {
 }
 
 template <int CIN>
-static hipError_t launch_gemm8(const WinoArgs& a, hipStream_t st) {
-  static PerDeviceOnce attr;
-  auto kern = wino_gemm8_kernel<CIN>;
-  const size_t lds = 2 * (96 + 128) * 32 * sizeof(float);
-  bool* done = attr.current();
-  if (!done || !*done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (done) *done = true;
-  }
-  const int grid = (a.Cout / 128) * ((a.T + 95) / 96) * a.groups * a.nf;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-  return hipGetLastError();
-}
-
-template <int CIN>
 static hipError_t launch_gemmp(const WinoArgs& a, int total_tiles, int grid, hipStream_t st) {
   static PerDeviceOnce attr;
   auto kern = wino_gemmp_kernel<CIN>;
@@ -1121,12 +983,6 @@ static hipError_t launch_gemmp(const WinoArgs& a, int total_tiles, int grid, hip
   return hipGetLastError();
 }
 
-#ifndef SE3TN_WINO_GEMMP
-#define SE3TN_WINO_GEMMP 1   // 0: never take the persistent 128 x 256 kernel
-#endif
-#ifndef SE3TN_WINO_GEMM8
-#define SE3TN_WINO_GEMM8 0   // 1: 96-row tiles run as 8-wave workgroups with intra-workgroup split-K (wino_gemm8_kernel)
-#endif
 // 128- or 96-row tiles: whichever leaves the shorter per-CU queue (in 32 x 32 x K blocks) on 256 CUs
 template <int CIN>
 static hipError_t launch_gemm_auto(const WinoArgs& a, hipStream_t st) {
@@ -1138,7 +994,7 @@ static hipError_t launch_gemm_auto(const WinoArgs& a, hipStream_t st) {
   // and the plane count lets the XCD-local tile order cover them (groups nf % 8 == 0: 36 F(4x4) planes do not).
   // a.gemmp: -1 = that rule, 0 = never, 1 = whenever the shape allows (SE3TN_WINO_GEMMP at se3tn_create: A/B runs and the tests'
   // bit-equality check of the two kernels on ragged shapes)
-  if (SE3TN_WINO_GEMMP && a.gemmp != 0 && a.Cout % 256 == 0 && (a.groups * a.nf) % 8 == 0) {
+  if (a.gemmp != 0 && a.Cout % 256 == 0 && (a.groups * a.nf) % 8 == 0) {
     const int cus = a.num_cus > 0 ? a.num_cus : 256;
     const int tiles = (a.Cout / 256) * ((a.T + 127) / 128) * a.groups * a.nf;
     // the automatic rule takes it for the plane sets it was measured on (EXPERIMENTS item 27): F(6x6).  The two-group F(4x4) heads
@@ -1147,7 +1003,6 @@ static hipError_t launch_gemm_auto(const WinoArgs& a, hipStream_t st) {
     const bool measured_shape = a.nf == 64;
     if (a.gemmp == 1 || (tiles >= 2 * cus && measured_shape)) return launch_gemmp<CIN>(a, tiles, tiles < cus ? tiles : (cus / 8) * 8, st);
   }
-  if (SE3TN_WINO_GEMM8 && q96 < q128) return launch_gemm8<CIN>(a, st);
   return q96 < q128 ? launch_gemm<CIN, 1, 4, 3, 1>(a, st) : launch_gemm<CIN, 2, 2, 2, 2>(a, st);
 }
 

@@ -2,14 +2,14 @@
 
 se3tn_infer picks an algorithm per layer from the public switches (se3tn_set_winograd / _trunk_winograd / _small_kernels /
 _keep_intermediates / _precision / _normalizers / _enable_graphs) and the create-time developer switches (SE3TN_WINOGRAD_FUSE,
-SE3TN_TAIL_PARTS, SE3TN_SPLITK_FUSED, SE3TN_WINOGRAD_AUTO_TILE_AB2 / _HEADS).  Each case of CASES is one combination, run at the
+SE3TN_TAIL_PARTS, SE3TN_WINOGRAD_AUTO_TILE_AB2 / _HEADS).  Each case of CASES is one combination, run at the
 batch sizes around its switch points.  Per (case, n):
   * one call on another window of the 72-pair pool first, so that a route which reads the previous call's buffers fails;
   * the checked call: EVERY pair's logits against float64 within the case's tolerance class, every composed pose within 1e-5;
   * the profile names of that call: the algorithm the route table (`expected`) names ran for each conv and for the tail;
   * every stage se3tn_debug_buffer hands out against the float64 intermediates (first and last pair of the call), and the stages it
     refuses are exactly the ones the route does not write.
-Bit identity: SE3TN_SPLITK_FUSED=1 against 0, and graph replay (non-default stream, third call) against the eager call."""
+Bit identity: graph replay (non-default stream, third call) against the eager call."""
 import os
 import re
 
@@ -42,11 +42,10 @@ S15 = [1, 2, 3, 4, 5]
 EVERY_N = [1, 2, 3, 4, 5, 6, 7, 13, 14, 15, 17, 18, 33, 34, 64, 72]   # 5/6: batch 1-5 family | Winograd; 14: AUTO -> F(6x6); 18/34: trunk
 
 
-def case(cid, ns, env=None, ops=(), graph=False, twin=None):
-    return dict(id=cid, ns=ns, env=env or {}, ops=list(ops), graph=graph, twin=twin)
+def case(cid, ns, env=None, ops=(), graph=False):
+    return dict(id=cid, ns=ns, env=env or {}, ops=list(ops), graph=graph)
 
 
-SPLITK = {"SE3TN_SPLITK_FUSED": "1"}
 CASES = [case("default", EVERY_N),
          case("small-off", S15, ops=[("small", 0)]),
          case("keep", S15 + [6, 14], ops=[("keep", 1)])]
@@ -54,9 +53,7 @@ CASES += [case("wino1-F%s-keep%d" % (name, keep), S15 + [6, 14], ops=[("wino", 1
           for name, tile in (("2", 2), ("4", 4), ("6", 6), ("6_4", TILE_6_4), ("auto", TILE_AUTO)) for keep in (0, 1)]
 CASES += [case("fuse0-F%d" % tile, [1, 3, 5, 8, 20], env={"SE3TN_WINOGRAD_FUSE": "0"}, ops=[("wino", 1, tile)]) for tile in (4, 6)]
 CASES += [case("tail-parts%s" % v, S15, env={"SE3TN_TAIL_PARTS": v}) for v in ("0", "2")]
-CASES += [case("splitk-fused", S15, env=SPLITK, twin={}),
-          case("splitk-fused-small-off", S15, env=SPLITK, ops=[("small", 0)], twin={}),
-          case("splitk-fused-direct", [6, 9, 13], env=SPLITK, ops=[("wino", 0, 0)], twin={}),
+CASES += [case("wino-off", [6, 9, 13], ops=[("wino", 0, 0)]),
           case("trunk1-fill0", S15 + [8], ops=[("trunk", 1, 0)]),
           case("direct", EVERY_N, ops=[("wino", 0, 0), ("trunk", 0, 0)]),
           case("auto-rot0.3", [14], ops=[("norm", 0.03, 0.3)]),
@@ -349,17 +346,10 @@ def _check_call(se3, eng, ref, cfg, n, chk, lg, pose, names, cid, worst):
 def test_route_vs_float64(se3, ref, case):
     n_max = max(case["ns"])
     eng, cfg = _engine(se3, ref, case["env"], case["ops"], n_max)
-    twin = _engine(se3, ref, case["twin"], case["ops"], n_max)[0] if case["twin"] is not None else None
     try:
         run = _Runner(se3, eng, ref, n_max)
-        run_twin = _Runner(se3, twin, ref, n_max) if twin else None
         for n in case["ns"]:
             lg, pose, got_w = _check(se3, eng, run, ref, cfg, n, case["id"])
-            if twin:   # SE3TN_SPLITK_FUSED: "bitwise the same results" as the separate reduce launch
-                pre, chk = _windows(n)
-                run_twin(pre)
-                lg_t, pose_t = run_twin(chk)
-                assert np.array_equal(lg, lg_t) and np.array_equal(pose, pose_t), (case["id"], n)
             if case["graph"]:   # graph replay: first call eager, second captured, third replayed -- the eager bits
                 pre, chk = _windows(n)
                 s = torch.cuda.Stream()
@@ -377,8 +367,6 @@ def test_route_vs_float64(se3, ref, case):
                 assert w_g == got_w, (case["id"], n, w_g, got_w)
     finally:
         eng.close()
-        if twin:
-            twin.close()
 
 
 class _Render:
