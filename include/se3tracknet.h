@@ -121,10 +121,9 @@ int se3tn_split_weights_host(const void* packed_blob_host, size_t blob_bytes, vo
  * scripts/rounding_by_block.py): max |d logit| 4.9e-6 with tile 4 everywhere, 6.0e-6 with tile 6 on the 256-channel block only,
  * 1.3e-5 with tile 6 on the 512-channel heads as well -- the heads' products go straight into the average pool + FC.
  * SE3TN_WINOGRAD_TILE_6_4 = tile 6 for the 256-channel block, tile 4 for the heads.
- * SE3TN_WINOGRAD_TILE_AUTO (the default): tile 4 below SE3TN_WINOGRAD_TILE6_MIN_BATCH pairs; from there tile 6 for the 256-channel
- * block, and for the heads tile 6 while rot_normalizer (se3tn_set_normalizers) <= SE3TN_WINOGRAD_HEADS_TILE6_MAX_ROT, else tile 4: the
- * rotation logits' rounding reaches the composed pose multiplied by rot_normalizer (tolerance 1e-5; with the reference's default
- * 5 degrees the pose moves by < 1.2e-6 either way, with YCBInEOAT's 30 degrees by 3.1e-6 with tile 4 heads, 6.4e-6 with tile 6).
+ * SE3TN_WINOGRAD_TILE_AUTO (the default) picks tile 4 or 6 per block from the batch and, for the heads, from rot_normalizer
+ * (se3tn_set_normalizers): the rotation logits' rounding reaches the composed pose multiplied by it.  The rule -- with every other choice
+ * of kernel per conv -- is stated once, in csrc/infer_plan.h (tile_for, plan_infer); the constants below are its thresholds.
  * SE3TN_PREC_F16X3 has F(4x4) only and uses it whatever is selected. */
 #define SE3TN_WINOGRAD_TILE_AUTO 46
 #define SE3TN_WINOGRAD_TILE_6_4 64

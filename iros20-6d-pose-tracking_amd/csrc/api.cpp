@@ -2,12 +2,14 @@
 // the .hip files.  One context per (process, device).
 #include <cmath>
 #include <thread>
+#include <type_traits>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -37,24 +39,20 @@ static int hipfail(hipError_t e, const char* what) {
 
 enum { MAX_LAUNCHES = 24, MAX_SLOTS = 64 };
 
-// one captured se3tn_infer: every argument that is baked into the kernel launches
+// one captured se3tn_infer: every argument that is baked into the kernel launches -- the pointers, the layout, and the InferConfig the
+// route was planned from (infer_plan.h: a switch that influences the route is in the key because the plan could not have read it otherwise)
 struct GraphKey {
   const void *A, *B, *trans, *rot, *poseA, *poseB, *blob;
-  int n, layout, prec, wino_min_batch, wino_tile, keep, wino64, wino64_fill;
-  int small_kernels, wino_fuse, gemmp, tail_parts;   // every switch that selects a kernel family (a graph captured under another
-                                                       // setting must not be replayed)
-  double tn, rn;
+  int layout;
+  InferConfig cfg;
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
 struct GraphEntry {
   GraphKey key;
   hipGraphExec_t exec = nullptr;  // null: seen once (run eagerly, which also sets the kernels' LDS attributes)
-  bool fast = false;
-  unsigned written = 0;   // the stages the captured sequence writes (se3tn_ctx::written)
+  InferPlan plan;                 // what the captured sequence runs (its STAGE_* mask, its tail)
 };
-// the activation buffers se3tn_debug_buffer hands out, as bits of se3tn_ctx::written
-enum : unsigned { STAGE_STEM = 1, STAGE_POOL = 2, STAGE_T64 = 4, STAGE_Q64 = 8, STAGE_AB = 16, STAGE_AB_T = 32, STAGE_HEAD = 64,
-                  STAGE_HEAD_T = 128 };
+static_assert(std::is_trivially_copyable<GraphEntry>::value, "the graph cache moves its entries as bytes (GraphKey is compared as bytes)");
 
 struct se3tn_ctx {
   int device = -1, max_batch = 0;
@@ -73,6 +71,7 @@ struct se3tn_ctx {
   DeviceBuf<float> head_f;                      // f16x3 mode: float32 output of the last head conv (the
                                                 // in-place residual update cannot change format)
   unsigned written = 0;                         // STAGE_* the last infer wrote (the others hold older data: se3tn_debug_buffer refuses them)
+  InferPlan plan;                               // the route of the last forward pass that was planned (infer_plan.h)
   DeviceBuf<float> logits;                      // [mb,6]
   DeviceBuf<float> fcpart;                      // [mb,2,<=32,3] partial FC dot products (fused Winograd tail: 8 slices per head; tail_kernel 8; tail_parts_kernel 32)
   bool keep_intermediates = false;              // se3tn_keep_intermediates: fused blocks also store ab_t / head_t / head
@@ -241,24 +240,6 @@ static int wino_slot(ConvId id) {
 static size_t wino_ws_floats(int max_batch) {
   const size_t head = (size_t)16 * 36 * 1024, ab = (size_t)16 * 121 * 256;
   return (size_t)max_batch * (head > ab ? head : ab);
-}
-// The tile the 256 / 512-channel blocks of a batch of n pairs run with.  F(6x6) exists in float32 only (SE3TN_PREC_F16X3 keeps F(4x4)
-// and its fused head block on split operands) and pays from 14 pairs on (scripts/tile_sweep.sh: 0.511 vs 0.462 ms at n = 6, 0.701 vs
-// 0.718 at n = 16, 1.76 vs 1.86 at n = 64): SE3TN_WINOGRAD_TILE_AUTO switches there.  With tile 6 | AUTO selected both U sets are
-// resident: the F(4x4) planes in wino_u, the F(6x6) planes in wino_u6.
-// which: 0 = the 256-channel block (convAB2), 1 = the 512-channel heads
-static int tile_for(const se3tn_ctx* c, int n, int which) {
-  const int t = c->wino_tile;
-  if (t == 2 || t == 4) return t;
-  if (c->prec == SE3TN_PREC_F16X3) return 4;
-  if (t == 6) return 6;
-  if (t == SE3TN_WINOGRAD_TILE_6_4) return which == 0 ? 6 : 4;
-  if (c->auto_tile_override[which]) return c->auto_tile_override[which];   // developer switch: SE3TN_WINOGRAD_AUTO_TILE_AB2 / _HEADS
-  if (n < SE3TN_WINOGRAD_TILE6_MIN_BATCH) return 4;
-  // AUTO: F(6x6) where its rounding is cheap.  The heads' products feed the average pool + FC directly: F(6x6) there doubles the
-  // logits' rounding error (1.3e-5 vs 6.0e-6 in the batched 30-degree closed loop), and the rotation logits reach the composed pose
-  // multiplied by rot_normalizer -- with a large normaliser (YCBInEOAT's 30 degrees, predict.py:586) the heads stay on F(4x4)
-  return (which == 0 || c->rn <= SE3TN_WINOGRAD_HEADS_TILE6_MAX_ROT) ? 6 : 4;
 }
 static const ConvId kWino64Convs[4] = {L64_1, L64_2, L64_3, L64_4};
 static int wino64_prepare(se3tn_ctx* c, hipStream_t st) {
@@ -534,16 +515,6 @@ int se3tn_set_winograd(se3tn_ctx* c, int min_batch, int tile) {
   return split_prepare(c, nullptr);
 }
 
-// The fused trunk kernel occupies a CU per workgroup (126 KB of LDS) for ~52 us whatever the batch: it beats the direct kernels when
-// its 4 n groups workgroups fill the rounds of the CUs to more than half (measured, scripts/trunk_sweep.sh -> profiles/r03f_trunk_sweep.txt:
-// n = 64 -> 2 | 1 rounds, 108 | 56 us vs 155 | 80 us direct; n = 20 grouped = 0.63 round 53 vs 80; but n = 16 grouped and n = 32 single
-// = half a round 52 vs 45; the direct kernels step from one round of their own tiles to two at n = 17 grouped / n = 34 single).
-static bool wino64_pays(const se3tn_ctx* c, int n, int groups) {
-  if (c->wino64_min_batch <= 0 || n < c->wino64_min_batch) return false;
-  const long wgs = 4L * n * groups, rounds = (wgs + c->num_cus - 1) / c->num_cus;
-  return 100 * wgs >= (long)c->wino64_min_fill * rounds * c->num_cus;   // the rounds are at least min_fill % full
-}
-
 int se3tn_set_trunk_winograd(se3tn_ctx* c, int min_batch, int min_fill_percent) {
   if (!c || min_batch < 0 || min_fill_percent < 0 || min_fill_percent > 100)
     return fail(SE3TN_E_ARG, "se3tn_set_trunk_winograd: min_batch >= 0, 0 <= min_fill_percent <= 100");
@@ -692,31 +663,91 @@ static int prof_mark(se3tn_ctx* c, hipStream_t st, const char* name, bool is_con
   return (int)hipEventRecord(c->ev[c->n_launch], st);
 }
 
-// Profile names say which ALGORITHM a launch took ("convAB2.conv1 [F(6x6)]"): the tests assert from them that the path they mean to
-// check is the one that ran.  Interned once per (name, tile); the strings live as long as the library.
-static const char* algo_name(const char* name, int tile, bool fused_block = false) {
+// the labels of infer_plan.h's step_label, interned: the strings live as long as the library (only ever reached by a profiled call)
+static const char* intern_label(const std::string& label) {
   static std::mutex mu;
-  static std::map<std::pair<std::string, int>, std::string> names;
+  static std::set<std::string> names;
   std::lock_guard<std::mutex> lk(mu);
-  auto key = std::make_pair(std::string(name), tile * 2 + (fused_block ? 1 : 0));
-  auto it = names.find(key);
-  if (it == names.end()) {
-    const std::string t = std::to_string(tile);
-    it = names.emplace(key, std::string(name) + " [F(" + t + "x" + t + ")]" + (fused_block ? " fused block" : "")).first;
-  }
-  return it->second.c_str();
+  return names.insert(label).first->c_str();
 }
-// ... and the direct family's: "convAB1 s2 [slices]", "[split-K]", "[slab f16x3]" (keyed by the literal's address: no string work on a hit)
-static const char* direct_name(const char* name, const ConvRoute& r, bool fast) {
-  static const char* const tags[] = {"", "conv64 small", "slices", "split-K", "slab", "gather"};
-  if (r.algo < ConvRoute::SMALL64 || r.algo > ConvRoute::GATHER) return name;
-  static std::mutex mu;
-  static std::map<std::pair<const char*, int>, std::string> names;
-  std::lock_guard<std::mutex> lk(mu);
-  auto key = std::make_pair(name, (int)r.algo * 2 + (fast ? 1 : 0));
-  auto it = names.find(key);
-  if (it == names.end()) it = names.emplace(key, std::string(name) + " [" + tags[r.algo] + (fast ? " f16x3]" : "]")).first;
-  return it->second.c_str();
+
+// Everything the route of a forward pass of n pairs depends on (infer_plan.h), read from the context in ONE place.  `f` is zeroed by the
+// caller: it is compared as bytes (GraphKey)
+static void fill_config(const se3tn_ctx* c, int n, bool small_family, InferConfig& f) {
+  f.n = n; f.prec = c->prec; f.keep_intermediates = c->keep_intermediates ? 1 : 0;
+  f.small_kernels = c->small_kernels ? 1 : 0; f.small_family = small_family ? 1 : 0;
+  f.tail_parts = c->tail_parts ? 1 : 0; f.tail_parts_ch = c->tail_parts_ch;
+  f.wino_min_batch = c->wino_min_batch; f.wino_tile = c->wino_tile;
+  f.auto_tile_override[0] = c->auto_tile_override[0]; f.auto_tile_override[1] = c->auto_tile_override[1];
+  f.wino_fuse = c->wino_fuse ? 1 : 0; f.gemmp = c->gemmp;
+  f.wino64_min_batch = c->wino64_min_batch; f.wino64_min_fill = c->wino64_min_fill; f.num_cus = c->num_cus;
+  f.part_bytes = c->part.count() * sizeof(float);
+  f.tn = c->tn; f.rn = c->rn;
+  f.ready = (c->wino_v.get() ? READY_WINO_VM : 0u) | (c->wino_tile_derived == 2 ? READY_U2 : c->wino_tile_derived == 4 ? READY_U4 : 0u) |
+            (c->wino_u6[0].get() && c->wino6_blob == c->blob ? READY_U6 : 0u) | (c->wino64_blob == c->blob ? READY_TRUNK : 0u) |
+            (c->split_blob == c->blob ? READY_SPLIT_W : 0u) | (c->wino_us_blob == c->blob && c->wino_us_tile == 4 ? READY_SPLIT_U4 : 0u);
+}
+
+// ---- executing a planned forward pass: conv_table() rows -> kernel argument blocks ----------------------------------------------------
+static float* tensor_ptr(se3tn_ctx* c, const TensorRef& t, bool fast) {
+  float* p = nullptr;
+  switch (t.buf) {
+    case BUF_POOL: p = c->pool.get(); break;
+    case BUF_T64: p = c->t64.get(); break;
+    case BUF_Q64: p = c->q64.get(); break;
+    case BUF_AB: p = c->ab.get(); break;
+    case BUF_AB_T: p = c->ab_t.get(); break;
+    case BUF_HEAD: p = c->head.get(); break;
+    case BUF_HEAD_T: p = c->head_t.get(); break;
+    case BUF_HEAD_OUT: p = fast ? c->head_f.get() : c->head.get(); break;
+    case BUF_NONE: return nullptr;
+  }
+  return p + t.ch;
+}
+// ip != nullptr: the mixed-model call (image i reads w / bias ip->off[i] floats from W)
+static void fill_conv_args(se3tn_ctx* c, const ConvRow& r, int n, const float* W, const ImgParams* ip, bool fast, ConvArgs& a) {
+  const Conv3& s = conv_specs()[r.id];
+  a = ConvArgs{};
+  a.in = tensor_ptr(c, r.in, fast); a.w = W + c->L.conv_w[r.id]; a.bias = W + c->L.conv_b[r.id];
+  if (fast) {
+    a.fast = 1;
+    a.overflow = c->overflow.get();
+    a.w = c->split_w.get() + c->SL.conv_ws[r.id];
+    a.wscale = c->split_w.get() + c->SL.conv_sc[r.id];
+  }
+  a.res = tensor_ptr(c, r.res, fast); a.out = tensor_ptr(c, r.out, fast);
+  a.part = c->part.get(); a.part_bytes = c->part.count() * sizeof(float);
+  a.in_ld = r.in.ld; a.res_ld = r.res.ld; a.out_ld = r.out.ld;
+  a.H = r.hin; a.W = r.hin; a.Ho = (r.hin - 1) / r.stride + 1; a.Wo = a.Ho;
+  a.M = n * a.Ho * a.Wo;
+  a.groups = s.groups;
+  a.in_gs = r.in.gs; a.res_gs = r.res.gs; a.out_gs = r.out.gs; a.bias_gs = s.cout;
+  a.w_gs = (long long)conv3_words(s.cin, s.cout);
+  if (ip) {
+    a.per_img = 1;
+    std::memcpy(a.img_off, ip->off, sizeof(a.img_off));
+  }
+}
+// split: the f16x3 form of a fused F(4x4) block (split-row activations / V / U, float32 M)
+static void fill_wino_args(se3tn_ctx* c, const ConvRow& r, int tile, int n, const float* W, bool split, WinoArgs& w) {
+  const Conv3& s = conv_specs()[r.id];
+  const int ws = wino_slot(r.id);
+  w = WinoArgs{};
+  w.in = tensor_ptr(c, r.in, split); w.bias = W + c->L.conv_b[r.id]; w.res = tensor_ptr(c, r.res, split); w.out = tensor_ptr(c, r.out, split);
+  w.U = tile == 6 ? c->wino_u6[ws].get() : c->wino_u[ws].get();
+  w.V = c->wino_v.get(); w.Mw = c->wino_m.get();
+  w.in_ld = r.in.ld; w.res_ld = r.res.ld; w.out_ld = r.out.ld;
+  w.m = tile; w.nf = (tile + 2) * (tile + 2);
+  w.H = r.hin; w.W = r.hin; w.th = (r.hin + tile - 1) / tile; w.tw = w.th;
+  w.n = n; w.T = n * w.th * w.tw;
+  w.C = s.cin; w.Cout = s.cout; w.groups = s.groups;
+  w.in_gs = r.in.gs; w.res_gs = r.res.gs; w.out_gs = r.out.gs; w.bias_gs = s.cout;
+  w.u_gs = (long long)w.nf * s.cin * s.cout;
+  if (split) {
+    w.split = 1;
+    w.U = c->wino_us[ws].get(); w.uscale = c->wino_usc[ws].get();
+    w.overflow = c->overflow.get();
+  }
 }
 
 static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int layout, float* trans, float* rot,
@@ -751,14 +782,12 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
                                  const double* poseA, double* poseB, void* stream) {
   if (!c || !c->use_graphs || c->prof || stream == nullptr)  // the null stream cannot be captured
     return infer_launch(c, A, B, n, layout, trans, rot, poseA, poseB, stream);
+  if (n < 1 || n > c->max_batch) return infer_launch(c, A, B, n, layout, trans, rot, poseA, poseB, stream);   // (refused there)
   GraphKey key;
   std::memset(&key, 0, sizeof(key));
   key.A = A; key.B = B; key.trans = trans; key.rot = rot; key.poseA = poseA; key.poseB = poseB; key.blob = c->blob;
-  key.n = n; key.layout = layout; key.prec = c->prec;
-  key.wino_min_batch = c->wino_min_batch; key.wino_tile = c->wino_tile; key.keep = c->keep_intermediates ? 1 : 0;
-  key.wino64 = c->wino64_min_batch; key.wino64_fill = c->wino64_min_fill; key.tn = c->tn; key.rn = c->rn;
-  key.small_kernels = c->small_kernels ? 1 : 0; key.wino_fuse = c->wino_fuse ? 1 : 0;
-  key.gemmp = c->gemmp; key.tail_parts = c->tail_parts ? c->tail_parts_ch : 0;
+  key.layout = layout;
+  fill_config(c, n, false, key.cfg);
   hipStream_t st = (hipStream_t)stream;
   for (auto& g : c->graphs) {
     if (!(g.key == key)) continue;
@@ -767,8 +796,9 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
       if ((A == c->inA.get() && c->in_split[0] != want_split) || (B == c->inB.get() && c->in_split[1] != want_split))
         return fail(SE3TN_E_STATE, "se3tn_infer: the input buffers were filled under a different precision mode");
       HIPCHK(hipGraphLaunch(g.exec, st));
-      c->last_fast = g.fast;
-      c->written = g.written;
+      c->last_fast = key.cfg.prec == SE3TN_PREC_F16X3;
+      c->plan = g.plan;
+      c->written = g.plan.written;
       return SE3TN_OK;
     }
     // second sighting: capture
@@ -781,8 +811,7 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
     const hipError_t e2 = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e2 != hipSuccess) { g.exec = nullptr; return hipfail(e2, "hipGraphInstantiate"); }
-    g.fast = c->last_fast;
-    g.written = c->written;
+    g.plan = c->plan;
     HIPCHK(hipGraphLaunch(g.exec, st));
     return SE3TN_OK;
   }
@@ -790,10 +819,87 @@ static int infer_graph_or_launch(se3tn_ctx* c, const float* A, const float* B, i
     if (c->graphs.front().exec) (void)hipGraphExecDestroy(c->graphs.front().exec);
     c->graphs.erase(c->graphs.begin());
   }
-  GraphEntry ge;
-  ge.key = key;
-  c->graphs.push_back(ge);
+  c->graphs.emplace_back();
+  std::memcpy(&c->graphs.back().key, &key, sizeof(key));   // (as bytes, the zeroed padding included: that is how it is compared)
   return infer_launch(c, A, B, n, layout, trans, rot, poseA, poseB, stream);
+}
+
+// One forward pass as planned: the stem, the ten convs of conv_table() in order (a fused block takes its two rows in one launch
+// sequence), the tail.  ip != nullptr: the mixed-model call -- image i reads its parameters ip->off[i] floats from W and composes its
+// pose with ip->tn[i] / rn[i]; it is never profiled
+static int run_plan(se3tn_ctx* c, const InferConfig& cfg, const InferPlan& p, const float* W, const ImgParams* ip, const float* A,
+                    const float* B, float* trans, float* rot, const double* poseA, double* poseB, hipStream_t st) {
+  const BlobLayout& L = c->L;
+  const int n = cfg.n;
+  const bool fast = cfg.prec == SE3TN_PREC_F16X3, keep = cfg.keep_intermediates != 0;  // fast: both the big-tile and the split-K kernels
+  const bool named = c->prof && !ip;
+  auto mark = [&](const char* name, bool is_conv) -> int { return ip ? 0 : prof_mark(c, st, name, is_conv); };
+  c->last_fast = fast;
+  c->written = 0;          // (until this sequence has been enqueued in full)
+  if (p.stem == InferPlan::STEM_SMALL) {
+    HIPCHK(launch_stem_pool_small_multi(A, B, W + L.stem_w, W + L.stem_b, c->pool.get(), n, ip ? ip->off : nullptr, st));
+    HIPCHK((hipError_t)mark(stem_label(p, 0), false));
+  } else {
+    if (fast)
+      HIPCHK(launch_stem(A, B, c->split_w.get() + c->SL.stem_ws, W + L.stem_b, c->split_w.get() + c->SL.stem_sc, c->stem.get(), n, st));
+    else
+      HIPCHK(launch_stem(A, B, W + L.stem_w, W + L.stem_b, nullptr, c->stem.get(), n, st));
+    HIPCHK((hipError_t)mark(stem_label(p, 0), false));
+    HIPCHK(launch_maxpool(c->stem.get(), c->pool.get(), n, fast ? 1 : 0, st));
+    HIPCHK((hipError_t)mark(stem_label(p, 1), false));
+  }
+  struct MarkCtx { se3tn_ctx* c; hipStream_t st; const char* name; };
+  auto mark_fn = [](void* m_) -> int { MarkCtx* m = (MarkCtx*)m_; return prof_mark(m->c, m->st, m->name, true); };
+  const ConvRow* rows = conv_table();
+  for (int i = 0; i < NUM_CONV3; ++i) {
+    const ConvRow& r = rows[i];
+    const ConvStep& s = p.conv[i];
+    const Conv3& sp = conv_specs()[r.id];
+    const int blk = wino_block_of(r.id);
+    const bool in_block = blk >= 0 && p.block[blk];
+    const char* name = named ? intern_label(step_label(r, s, fast, in_block, blk == 1)) : r.name;
+    hipError_t e;
+    if (in_block) {   // rows i, i + 1: conv1's out-transform fused with conv2's in-transform, the heads' last one with the tail
+      const ConvRow& r2 = rows[++i];
+      WinoArgs w, w2;   // (w2: conv2's planes, scales and bias; its tensors follow from conv1's inside launch_wino_block)
+      fill_wino_args(c, r, s.tile, n, W, fast, w);
+      fill_wino_args(c, r2, s.tile, n, W, fast, w2);
+      w.res_ld = w.in_ld; w.res_gs = w.in_gs;   // (conv2's residual is conv1's input)
+      const TailArgs tl{W + L.fc_w, W + L.fc_b, c->logits.get(), c->fcpart.get(), trans, rot, poseA, poseB, cfg.tn, cfg.rn};
+      // the kept head activation is float32 (in f16x3 mode head itself holds split rows)
+      float* keep2 = (blk == 1 && keep) ? tensor_ptr(c, r2.out, fast) : nullptr;
+      MarkCtx mc{c, st, name};
+      e = launch_wino_block(w, s.gemm, w2.U, w2.uscale, w2.bias, const_cast<float*>(w.in), keep ? 1 : 0, keep2, blk == 1 ? &tl : nullptr, st, mark_fn, &mc);
+      if (e != hipSuccess) return hipfail(e, r2.name);
+      name = named ? intern_label(step_label(r2, p.conv[i], fast, true, blk == 1)) : r2.name;
+    } else if (s.algo == ConvStep::WINO) {
+      WinoArgs w;
+      fill_wino_args(c, r, s.tile, n, W, false, w);
+      e = launch_wino_conv(w, s.gemm, r.epi, st);
+    } else if (s.algo == ConvStep::WINO64) {
+      e = launch_wino64(tensor_ptr(c, r.in, fast), r.in.ld, r.in.gs, c->wino64_u[(int)r.id - (int)L64_1].get(), (long long)16 * sp.cin * sp.cout,
+                        W + L.conv_b[r.id], sp.cout, tensor_ptr(c, r.res, fast), r.res.ld, r.res.gs, tensor_ptr(c, r.out, fast), r.out.ld,
+                        r.out.gs, n, sp.groups, r.epi, st);
+    } else {
+      ConvArgs a;
+      fill_conv_args(c, r, n, W, ip, fast, a);
+      e = launch_conv3x3(a, s, sp.cin, sp.cout, r.stride, r.epi, st);
+    }
+    if (e != hipSuccess) return hipfail(e, r.name);
+    if (int rc = mark(name, true)) return rc;
+  }
+  if (p.tail == InferPlan::TAIL_PARTS) {   // the slices of the last head conv go to the tail unreduced
+    const int M = n * S4 * S4;
+    HIPCHK(launch_tail_parts(c->part.get(), p.conv[LH2_2].slices, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head.get(), 1024, W + L.fc_w, W + L.fc_b,
+                             c->logits.get(), trans, rot, poseA, poseB, ip ? 0.0 : cfg.tn, ip ? 0.0 : cfg.rn, n, st, c->fcpart.get(), c->tail_arrive.get(),
+                             ip ? nullptr : c->tail_flag, ip ? 0 : c->tail_seq, p.tail_ch, ip));
+  } else if (p.tail == InferPlan::TAIL_PLAIN) {
+    HIPCHK(launch_tail(tensor_ptr(c, rows[LH2_2].out, fast), W + L.fc_w, W + L.fc_b, c->logits.get(), trans, rot, poseA, poseB, cfg.tn, cfg.rn, n, st,
+                       c->fcpart.get(), c->tail_arrive.get(), c->tail_flag, c->tail_seq));
+  }
+  if (const char* name = tail_label(p)) HIPCHK((hipError_t)mark(name, false));
+  c->written = p.written;
+  return SE3TN_OK;
 }
 
 static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int layout, float* trans, float* rot,
@@ -804,8 +910,6 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   if ((poseA == nullptr) != (poseB == nullptr)) return fail(SE3TN_E_ARG, "se3tn_infer: poseA and poseB go together");
   if (layout != SE3TN_NCHW && layout != SE3TN_NHWC) return fail(SE3TN_E_ARG, "se3tn_infer: bad layout");
   hipStream_t st = (hipStream_t)stream;
-  const float* W = c->blob;
-  const BlobLayout& L = c->L;
   c->n_launch = 0;
   int slot = 0;
   if (c->prof) {
@@ -831,177 +935,12 @@ static int infer_launch(se3tn_ctx* c, const float* A, const float* B, int n, int
   if (c->in_split[0] != want_split || c->in_split[1] != want_split)
     return fail(SE3TN_E_STATE, "se3tn_infer: the input buffers were filled under a different precision mode "
                                "(call se3tn_set_precision before se3tn_preprocess)");
-  if (want_split && c->split_blob != c->blob)
+  InferConfig cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  fill_config(c, n, false, cfg);
+  if (plan_infer(cfg, c->plan) != INFER_PLAN_OK)
     return fail(SE3TN_E_STATE, "se3tn_infer: f16x3 split panels not derived (se3tn_set_precision after the weights are bound)");
-  const float* WS = c->split_w.get();
-  const SplitLayout& SL = c->SL;
-  const bool fast = c->prec == SE3TN_PREC_F16X3;  // both the big-tile and the split-K kernels
-  c->last_fast = fast;
-  c->written = 0;          // (until this sequence has been enqueued in full)
-  unsigned written = STAGE_POOL | STAGE_T64 | STAGE_Q64 | STAGE_AB;   // every route writes these; the others are added where they are
-  // batch 1-2 (the per-frame regime): stem + max-pool of both branches in ONE launch of 16-pool-pixel tiles; the 88 x 88 x 128 stem
-  // map is not stored, so a caller who asked for the intermediates gets the batch-64 pair
-  const bool small_stem = c->small_kernels && !want_split && !c->keep_intermediates && n <= SE3TN_STEM_SMALL_MAX_N;
-  if (!small_stem) written |= STAGE_STEM;
-  if (small_stem) {
-    HIPCHK(launch_stem_pool_small(A, B, W + L.stem_w, W + L.stem_b, c->pool.get(), n, st));
-    HIPCHK((hipError_t)prof_mark(c, st, "stem7x7 + maxpool [small tiles]", false));
-  } else {
-    if (want_split)
-      HIPCHK(launch_stem(A, B, WS + SL.stem_ws, W + L.stem_b, WS + SL.stem_sc, c->stem.get(), n, st));
-    else
-      HIPCHK(launch_stem(A, B, W + L.stem_w, W + L.stem_b, nullptr, c->stem.get(), n, st));
-    HIPCHK((hipError_t)prof_mark(c, st, "stem7x7_mfma", false));
-    HIPCHK(launch_maxpool(c->stem.get(), c->pool.get(), n, fast ? 1 : 0, st));
-    HIPCHK((hipError_t)prof_mark(c, st, "maxpool3x3s2", false));
-  }
-
-  bool skip_reduce = false;   // set around the last head conv: tail_parts_kernel MAY consume its partial sums (what happened: `route`)
-  ConvRoute route;            // the algorithm the last conv() took
-  auto conv = [&](ConvId id, const float* in, int in_ld, int in_gs, const float* res, int res_ld, int res_gs,
-                  float* out, int out_ld, int out_gs, int hin, int stride, int epi, const char* name) -> int {
-    const Conv3& s = conv_specs()[id];
-    const int ws = wino_slot(id);
-    const int wtile = tile_for(c, n, ws >= 2 ? 1 : 0);
-    const bool u_ready = wtile == 6 ? (c->wino_u6[0].get() && c->wino6_blob == c->blob) : (c->wino_tile_derived == wtile);
-    route = ConvRoute{};
-    if (ws >= 0 && !fast && c->wino_min_batch > 0 && n >= c->wino_min_batch && c->wino_v.get() && u_ready) {
-      route.algo = ConvRoute::WINO;
-      WinoArgs w{};
-      w.in = in; w.U = wtile == 6 ? c->wino_u6[ws].get() : c->wino_u[ws].get(); w.bias = W + L.conv_b[id]; w.res = res; w.out = out;
-      w.V = c->wino_v.get(); w.Mw = c->wino_m.get();
-      w.in_ld = in_ld; w.res_ld = res_ld; w.out_ld = out_ld;
-      w.m = wtile; w.nf = (w.m + 2) * (w.m + 2);
-      w.H = hin; w.W = hin; w.th = (hin + w.m - 1) / w.m; w.tw = w.th;
-      w.n = n; w.T = n * w.th * w.tw;
-      w.C = s.cin; w.Cout = s.cout; w.groups = s.groups;
-      w.in_gs = in_gs; w.res_gs = res_gs; w.out_gs = out_gs; w.bias_gs = s.cout;
-      w.u_gs = (long long)w.nf * s.cin * s.cout;
-      w.num_cus = c->num_cus; w.gemmp = c->gemmp;
-      hipError_t e = launch_wino_conv(w, epi, st);
-      if (e != hipSuccess) return hipfail(e, name);
-      return prof_mark(c, st, c->prof ? algo_name(name, wtile) : name, true);
-    }
-    if (id <= L64_4 && !fast && wino64_pays(c, n, s.groups) && c->wino64_blob == c->blob && stride == 1 && hin == S2 && epi != 2) {
-      const int slot64 = (int)id - (int)L64_1;
-      route.algo = ConvRoute::WINO64;
-      hipError_t e = launch_wino64(in, in_ld, in_gs, c->wino64_u[slot64].get(), (long long)16 * s.cin * s.cout, W + L.conv_b[id], s.cout, res,
-                                   res_ld, res_gs, out, out_ld, out_gs, n, s.groups, epi, st);
-      if (e != hipSuccess) return hipfail(e, name);
-      static const char* const fused_names[4] = {"conv64 A2.conv1|B2.conv1 [fused F(2x2)]", "conv64 A2.conv2|B2.conv2 [fused F(2x2)]",
-                                                 "conv64 B3.conv1 [fused F(2x2)]", "conv64 B3.conv2 [fused F(2x2)]"};
-      return prof_mark(c, st, fused_names[slot64], true);   // (the profile says which algorithm a launch took)
-    }
-    ConvArgs a{};
-    a.in = in; a.w = W + L.conv_w[id]; a.bias = W + L.conv_b[id];
-    if (fast) {
-      a.fast = 1;
-      a.overflow = c->overflow.get();
-      a.w = WS + SL.conv_ws[id];
-      a.wscale = WS + SL.conv_sc[id];
-    } a.res = res; a.out = out; a.part = c->part.get(); a.part_bytes = c->part.count() * sizeof(float);
-    a.small_ok = c->small_kernels ? 1 : 0;
-    a.skip_reduce = skip_reduce ? 1 : 0;
-    a.in_ld = in_ld; a.res_ld = res_ld; a.out_ld = out_ld;
-    a.H = hin; a.W = hin; a.Ho = (hin - 1) / stride + 1; a.Wo = a.Ho;
-    a.M = n * a.Ho * a.Wo;
-    a.groups = s.groups;
-    a.in_gs = in_gs; a.res_gs = res_gs; a.out_gs = out_gs; a.bias_gs = s.cout;
-    a.w_gs = (long long)conv3_words(s.cin, s.cout);
-    hipError_t e = launch_conv3x3(a, s.cin, s.cout, stride, epi, st, &route);
-    if (e != hipSuccess) return hipfail(e, name);
-    return prof_mark(c, st, c->prof ? direct_name(name, route, fast) : name, true);
-  };
-  int rc;
-  // 64-channel trunk: pool = a0|b0 ; t64 scratch ; q64 = a1|b1 -> a1|b2 (== torch.cat((a,b),1))
-  if ((rc = conv(L64_1, c->pool.get(), 128, 64, nullptr, 0, 0, c->t64.get(), 128, 64, S2, 1, 0, "conv64 A2.conv1|B2.conv1"))) return rc;
-  if ((rc = conv(L64_2, c->t64.get(), 128, 64, c->pool.get(), 128, 64, c->q64.get(), 128, 64, S2, 1, 1, "conv64 A2.conv2|B2.conv2"))) return rc;
-  if ((rc = conv(L64_3, c->q64.get() + 64, 128, 0, nullptr, 0, 0, c->t64.get() + 64, 128, 0, S2, 1, 0, "conv64 B3.conv1"))) return rc;
-  if ((rc = conv(L64_4, c->t64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, S2, 1, 1, "conv64 B3.conv2"))) return rc;
-  if ((rc = conv(LAB1, c->q64.get(), 128, 0, nullptr, 0, 0, c->ab.get(), 256, 0, S2, 2, 2, "convAB1 s2"))) return rc;
-  // ResnetBasicBlocks of 256 / 512 channels: at n >= wino_min_batch with F(4x4) or F(6x6) the whole block runs through
-  // launch_wino_block (conv1's out-transform fused with conv2's in-transform; the heads' last out-transform fused
-  // with avg-pool + FC + tanh); otherwise conv by conv (direct / split-K / F(2x2) kernels)
-  auto block_ok = [&](int which) -> bool {
-    const int bt = tile_for(c, n, which);
-    const bool planes_ready = bt == 6 ? (!fast && c->wino_u6[0].get() && c->wino6_blob == c->blob) : (bt == 4 && c->wino_tile_derived == 4);
-    return c->wino_fuse && c->wino_min_batch > 0 && n >= c->wino_min_batch && c->wino_v.get() && planes_ready &&
-           (!fast || (c->wino_us_blob == c->blob && c->wino_us_tile == 4));
-  };
-  struct MarkCtx { se3tn_ctx* c; hipStream_t st; const char* name; };
-  auto mark_fn = [](void* p) -> int { MarkCtx* m = (MarkCtx*)p; return prof_mark(m->c, m->st, m->name, true); };
-  auto block = [&](ConvId id1, ConvId id2, float* io, float* mid, int ld, int gs, int hin, const TailArgs* tl,
-                   const char* name1, const char* name2) -> int {
-    const Conv3& s = conv_specs()[id1];
-    const int btile = tile_for(c, n, tl ? 1 : 0);
-    WinoArgs w{};
-    const DeviceBuf<float>* Uset = btile == 6 ? c->wino_u6 : c->wino_u;
-    w.in = io; w.U = Uset[wino_slot(id1)].get(); w.bias = W + L.conv_b[id1]; w.res = nullptr; w.out = mid;
-    w.V = c->wino_v.get(); w.Mw = c->wino_m.get();
-    w.in_ld = ld; w.res_ld = ld; w.out_ld = ld;
-    w.m = btile; w.nf = (btile + 2) * (btile + 2);
-    w.H = hin; w.W = hin; w.th = (hin + btile - 1) / btile; w.tw = w.th;
-    w.n = n; w.T = n * w.th * w.tw;
-    w.C = s.cin; w.Cout = s.cout; w.groups = s.groups;
-    w.in_gs = gs; w.res_gs = gs; w.out_gs = gs; w.bias_gs = s.cout;
-    w.u_gs = (long long)w.nf * s.cin * s.cout;
-    w.num_cus = c->num_cus; w.gemmp = c->gemmp;
-    const float *U2 = Uset[wino_slot(id2)].get(), *usc2 = nullptr;
-    float* keep2 = (tl && c->keep_intermediates) ? io : nullptr;
-    if (fast) {   // f16x3: split-row activations / V / U, float32 M
-      w.split = 1;
-      w.U = c->wino_us[wino_slot(id1)].get(); w.uscale = c->wino_usc[wino_slot(id1)].get();
-      U2 = c->wino_us[wino_slot(id2)].get(); usc2 = c->wino_usc[wino_slot(id2)].get();
-      w.overflow = c->overflow.get();
-      if (keep2) keep2 = c->head_f.get();   // the kept head activation is float32 (head itself holds split rows)
-    }
-    MarkCtx mc{c, st, c->prof ? algo_name(name1, btile, true) : name1};
-    hipError_t e = launch_wino_block(w, U2, usc2, W + L.conv_b[id2], io, c->keep_intermediates ? 1 : 0, keep2, tl, st, mark_fn, &mc);
-    if (e != hipSuccess) return hipfail(e, name2);
-    return prof_mark(c, st, c->prof ? algo_name(name2, btile, true) : name2, true);
-  };
-  // f16x3 mode: the batched GEMMs of the 256-channel block are bandwidth-bound at the f16 matrix rate (41 FLOP per byte of V / M
-  // traffic) and lose to the direct f16x3 kernels (0.247 vs 0.220 ms at batch 64); the 512-channel heads win (0.349 vs 0.427 ms)
-  if (block_ok(0) && !fast) {
-    if ((rc = block(LAB2_1, LAB2_2, c->ab.get(), c->ab_t.get(), 256, 0, S3, nullptr, "convAB2.conv1", "convAB2.conv2"))) return rc;
-    if (c->keep_intermediates) written |= STAGE_AB_T;
-  } else {
-    if ((rc = conv(LAB2_1, c->ab.get(), 256, 0, nullptr, 0, 0, c->ab_t.get(), 256, 0, S3, 1, 0, "convAB2.conv1"))) return rc;
-    if ((rc = conv(LAB2_2, c->ab_t.get(), 256, 0, c->ab.get(), 256, 0, c->ab.get(), 256, 0, S3, 1, 1, "convAB2.conv2"))) return rc;
-    written |= STAGE_AB_T;
-  }
-  if ((rc = conv(LH1, c->ab.get(), 256, 0, nullptr, 0, 0, c->head.get(), 1024, 0, S3, 2, 2, "trans|rot conv1 s2"))) return rc;
-  if (block_ok(1)) {
-    TailArgs tl{W + L.fc_w, W + L.fc_b, c->logits.get(), c->fcpart.get(), trans, rot, poseA, poseB, c->tn, c->rn};
-    if ((rc = block(LH2_1, LH2_2, c->head.get(), c->head_t.get(), 1024, 512, S4, &tl, "trans|rot conv2.conv1",
-                    "trans|rot conv2.conv2 + avgpool+fc+tanh+pose"))) return rc;
-    if (c->keep_intermediates) written |= STAGE_HEAD_T | STAGE_HEAD;
-  } else {
-    if ((rc = conv(LH2_1, c->head.get(), 1024, 512, nullptr, 0, 0, c->head_t.get(), 1024, 512, S4, 1, 0, "trans|rot conv2.conv1"))) return rc;
-    written |= STAGE_HEAD_T;
-    float* head_out = fast ? c->head_f.get() : c->head.get();
-    // batch 1-5 (conv_slices_small: 8 partial-sum slices per output) may leave the slices to the tail -- no conv_reduce launch, the final
-    // head map not written (se3tn_keep_intermediates keeps it).  Whether it did is what launch_conv3x3 reports: any other route the conv
-    // takes (Winograd, split-K, ...) writes head_out and ignores the permission.
-    skip_reduce = c->tail_parts && !c->keep_intermediates;
-    rc = conv(LH2_2, c->head_t.get(), 1024, 512, c->head.get(), 1024, 512, head_out, 1024, 512, S4, 1, 1, "trans|rot conv2.conv2");
-    skip_reduce = false;
-    if (rc) return rc;
-    if (route.algo == ConvRoute::SLICES && !route.reduced) {
-      const int M = n * S4 * S4;
-      HIPCHK(launch_tail_parts(c->part.get(), route.slices, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head.get(), 1024, W + L.fc_w, W + L.fc_b,
-                               c->logits.get(), trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart.get(), c->tail_arrive.get(), c->tail_flag, c->tail_seq,
-                               c->tail_parts_ch));
-      c->tail_flag = nullptr;   // consumed: this tail stores the word (se3tn_on_track polls only then)
-      HIPCHK((hipError_t)prof_mark(c, st, "tail slices+avgpool+fc+tanh+pose", false));
-    } else {
-      written |= STAGE_HEAD;
-      HIPCHK(launch_tail(head_out, W + L.fc_w, W + L.fc_b, c->logits.get(), trans, rot, poseA, poseB, c->tn, c->rn, n, st, c->fcpart.get(), c->tail_arrive.get(), c->tail_flag, c->tail_seq));
-      c->tail_flag = nullptr;   // consumed
-      HIPCHK((hipError_t)prof_mark(c, st, "tail avgpool+fc+tanh+pose", false));
-    }
-  }
-  c->written = written;
+  if (int rc = run_plan(c, cfg, c->plan, c->blob, nullptr, A, B, trans, rot, poseA, poseB, st)) return rc;
   if (c->prof) c->slot_launches[slot] = c->n_launch;
   return SE3TN_OK;
 }
@@ -1402,9 +1341,9 @@ static int on_track_frame(se3tn_ctx* c, se3tn_mesh* m, const double prev_pose[16
   const int seq = ++c->tail_seq == 0 ? ++c->tail_seq : c->tail_seq;
   c->tail_flag = poll ? flag_d : nullptr;
   const int rc_inf = se3tn_infer(c, c->inA.get(), c->inB.get(), 1, SE3TN_NHWC, trans_d, rot_d, (const double*)c->trk_dev.get(), (double*)c->trk_out.dev(), stream);
-  // only launch_tail / launch_tail_parts take the word (and clear tail_flag when they do): the fused heads' tail (TailArgs) never stores
-  // it, and polling for it would spin for the whole 5 ms before the stream wait
-  const bool stored = poll && c->tail_flag == nullptr;
+  // only launch_tail / launch_tail_parts take the word: the fused heads' tail (TailArgs) never stores it, and polling for it would spin
+  // for the whole 5 ms before the stream wait
+  const bool stored = poll && rc_inf == SE3TN_OK && c->plan.tail_stores_word;
   c->tail_flag = nullptr;
   if (rc_inf) return rc_inf;
   const double t4 = trace ? now() : 0.0;
@@ -1931,50 +1870,19 @@ static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes
   return SE3TN_OK;
 }
 
-// The network on k <= 5 pairs of (possibly) k models, through the batch 1-5 family chosen EXPLICITLY -- not through infer_launch's
-// predicates: stem + pool in one launch, the four trunk convs (conv64_small), the five 128 .. 512-channel convs as channel slices
-// (+ conv_reduce), the tail on the last conv's partial sums.  That is the sequence se3tn_infer runs for one pair of a default context;
-// every kernel of it works image by image in a layer-fixed order, and here image i reads its parameters ip.off[i] floats from W.
+// The network on k <= 5 pairs of (possibly) k models, through the batch 1-5 family chosen EXPLICITLY (InferConfig::small_family) -- not
+// through the predicates of a default context: stem + pool in one launch, the four trunk convs (conv64_small), the five 128 ..
+// 512-channel convs as channel slices (+ conv_reduce), the tail on the last conv's partial sums.  That is the plan of one pair of a
+// default context (tests/c_abi/infer_plan_check.cpp holds the two equal); every kernel of it works image by image in a layer-fixed
+// order, and here image i reads its parameters ip.off[i] floats from W.
 static int infer_small_objects(se3tn_ctx* c, const float* W, const ImgParams& ip, const float* A, const float* B, int k, float* trans,
                                float* rot, const double* poseA, double* poseB, hipStream_t st) {
-  const BlobLayout& L = c->L;
-  c->written = 0;
-  HIPCHK(launch_stem_pool_small_multi(A, B, W + L.stem_w, W + L.stem_b, c->pool.get(), k, ip.off, st));
-  auto conv = [&](ConvId id, const float* in, int in_ld, int in_gs, const float* res, int res_ld, int res_gs, float* out, int out_ld,
-                  int out_gs, int hin, int stride, int epi, bool skip_reduce, const char* name) -> int {
-    const Conv3& s = conv_specs()[id];
-    ConvArgs a{};
-    a.in = in; a.w = W + L.conv_w[id]; a.bias = W + L.conv_b[id]; a.res = res; a.out = out;
-    a.part = c->part.get(); a.part_bytes = c->part.count() * sizeof(float); a.small_ok = 1; a.skip_reduce = skip_reduce ? 1 : 0;
-    a.in_ld = in_ld; a.res_ld = res_ld; a.out_ld = out_ld;
-    a.H = hin; a.W = hin; a.Ho = (hin - 1) / stride + 1; a.Wo = a.Ho;
-    a.M = k * a.Ho * a.Wo;
-    a.groups = s.groups;
-    a.in_gs = in_gs; a.res_gs = res_gs; a.out_gs = out_gs; a.bias_gs = s.cout;
-    a.w_gs = (long long)conv3_words(s.cin, s.cout);
-    a.per_img = 1;
-    std::memcpy(a.img_off, ip.off, sizeof(a.img_off));
-    const hipError_t e = launch_conv_small(a, s.cin, s.cout, stride, epi, st);
-    return e == hipSuccess ? SE3TN_OK : hipfail(e, name);
-  };
-  int rc;
-  if ((rc = conv(L64_1, c->pool.get(), 128, 64, nullptr, 0, 0, c->t64.get(), 128, 64, S2, 1, 0, false, "conv64 A2.conv1|B2.conv1"))) return rc;
-  if ((rc = conv(L64_2, c->t64.get(), 128, 64, c->pool.get(), 128, 64, c->q64.get(), 128, 64, S2, 1, 1, false, "conv64 A2.conv2|B2.conv2"))) return rc;
-  if ((rc = conv(L64_3, c->q64.get() + 64, 128, 0, nullptr, 0, 0, c->t64.get() + 64, 128, 0, S2, 1, 0, false, "conv64 B3.conv1"))) return rc;
-  if ((rc = conv(L64_4, c->t64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, c->q64.get() + 64, 128, 0, S2, 1, 1, false, "conv64 B3.conv2"))) return rc;
-  if ((rc = conv(LAB1, c->q64.get(), 128, 0, nullptr, 0, 0, c->ab.get(), 256, 0, S2, 2, 2, false, "convAB1 s2"))) return rc;
-  if ((rc = conv(LAB2_1, c->ab.get(), 256, 0, nullptr, 0, 0, c->ab_t.get(), 256, 0, S3, 1, 0, false, "convAB2.conv1"))) return rc;
-  if ((rc = conv(LAB2_2, c->ab_t.get(), 256, 0, c->ab.get(), 256, 0, c->ab.get(), 256, 0, S3, 1, 1, false, "convAB2.conv2"))) return rc;
-  if ((rc = conv(LH1, c->ab.get(), 256, 0, nullptr, 0, 0, c->head.get(), 1024, 0, S3, 2, 2, false, "trans|rot conv1 s2"))) return rc;
-  if ((rc = conv(LH2_1, c->head.get(), 1024, 512, nullptr, 0, 0, c->head_t.get(), 1024, 512, S4, 1, 0, false, "trans|rot conv2.conv1"))) return rc;
-  // the last head conv leaves its 8 partial-sum slices to the tail (conv_slices_small_count(512, 1, S4) == 8)
-  if ((rc = conv(LH2_2, c->head_t.get(), 1024, 512, c->head.get(), 1024, 512, c->head.get(), 1024, 512, S4, 1, 1, true, "trans|rot conv2.conv2"))) return rc;
-  c->written = STAGE_POOL | STAGE_T64 | STAGE_Q64 | STAGE_AB | STAGE_AB_T | STAGE_HEAD_T;   // (not the stem map, not the final head map)
-  c->last_fast = false;
-  const int M = k * S4 * S4;
-  HIPCHK(launch_tail_parts(c->part.get(), 8, (size_t)2 * M * 512, M, W + L.conv_b[LH2_2], c->head.get(), 1024, W + L.fc_w, W + L.fc_b, c->logits.get(), trans,
-                           rot, poseA, poseB, 0.0, 0.0, k, st, c->fcpart.get(), c->tail_arrive.get(), nullptr, 0, 16, &ip));
-  return SE3TN_OK;
+  InferConfig cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  fill_config(c, k, true, cfg);
+  if (plan_infer(cfg, c->plan) != INFER_PLAN_OK)
+    return fail(SE3TN_E_ARG, "se3tn_on_track_objects: the batch 1-5 kernel family has no kernel for a launch of " + std::to_string(k) + " pairs");
+  return run_plan(c, cfg, c->plan, W, &ip, A, B, trans, rot, poseA, poseB, st);
 }
 
 // se3tn_on_track_objects (live == nullptr) and se3tn_on_track_objects_live: one body, two staging steps

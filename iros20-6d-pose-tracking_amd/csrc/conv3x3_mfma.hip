@@ -643,80 +643,22 @@ static hipError_t launch_splitk(const ConvArgs& a, int epi, int outf, hipStream_
   return launch_reduce_for(a, a.tiles_n * BN, epi, MM, outf, false, st);
 }
 
-// Split-K is used when the big-tile grid would leave most of the 256 CUs idle and the partial-sum workspace is large enough.
-// slices = the largest divisor of the K-step count (cin / 32 x 9) that leaves every workgroup >= SE3TN_SPLITK_MIN_STEPS K-steps and
-// the launch <= 512 workgroups (two per CU).  Up to SE3TN_SPLITK_FIXED_MAX_N images the workgroup count is taken from the ONE-image
-// geometry -- 6 / 12 / 24 / 24 / 48 slices of 3 steps for the 64-ch / convAB1 / convAB2 / trans|rot conv1 / conv2 layers -- so the
-// slice count is a function of the layer (the same summation order for one pair alone or two together); larger batches count the
-// real grid (fewer, longer slices), so from 3 pairs on a pair's last bits may depend on the batch it travels in -- as they do across
-// the algorithm switches at 6 / 14 pairs, and in the reference under cuDNN.
-#ifndef SE3TN_SPLITK_MIN_STEPS
-#define SE3TN_SPLITK_MIN_STEPS 3   // measured at batch 1: 2 -> 280 us, 3 -> 268 us, 4 -> 276 us per forward (whole chunks before: 321 us)
-#endif
-#ifndef SE3TN_SPLITK_MAX_WGS
-#define SE3TN_SPLITK_MAX_WGS 512
-#endif
-#ifndef SE3TN_SPLITK_FIXED_MAX_N
-#define SE3TN_SPLITK_FIXED_MAX_N 2  // (5 = up to the Winograd threshold was measured: 15 % slower at n = 4 -- 4 x the partial sums of 48 slices)
-#endif
-static int pick_slices(const ConvArgs& a, int cin, int cout, int big_tile_rows, int bn_big) {
-  const int big_blocks = ((a.M + big_tile_rows - 1) / big_tile_rows) * (cout / bn_big) * a.groups;
-  if (big_blocks >= 200 || a.part == nullptr) return 0;
-  const int bn = cout >= 128 ? 128 : 64;
-  const int hw = a.Ho * a.Wo;
-  const int rows = a.M <= SE3TN_SPLITK_FIXED_MAX_N * hw ? hw : a.M;          // one image's rows | the real grid
-  const int base = ((rows + 127) / 128) * (cout / bn) * a.groups;            // workgroups per slice
-  const int ks = cin / 32 * 9;
-  const size_t per_slice = (size_t)a.groups * a.M * cout * sizeof(float);
-  int best = 0;
-  for (int sl = 1; sl <= ks; ++sl) {
-    if (ks % sl != 0 || ks / sl < SE3TN_SPLITK_MIN_STEPS) continue;
-    if (per_slice * sl > a.part_bytes) break;
-    if (best > 0 && base * sl > SE3TN_SPLITK_MAX_WGS) break;
-    best = sl;
-  }
-  return best;
-}
-
 // Slab sizes (pixels, multiple of 8) = worst case of
 //   255 + 2 per row break + (2 Wp + 2) per image break + 2 (Wp + 1) + 1     (tests/test_slab_geometry.py)
 //   W = 44: 454 -> 464     W = 22: 378 -> 384     W = 11: 410 -> 424
-#ifndef SE3TN_CONV64_SMALL_MAX_N
-#define SE3TN_CONV64_SMALL_MAX_N 5   // the trunk convs of up to this many pairs take conv64_small_kernel (0: never).  Measured 2 vs 5:
-                                     // 8.6k -> 9.6k / 10.2k -> 11.0k / 10.8k -> 11.2k pairs/s at 3 / 4 / 5 pairs (one stream)
-#endif
-// (SE3TN_SLICES_SMALL_MAX_N: se3tn_internal.h)
-hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int epi, hipStream_t st, ConvRoute* route) {
+// Executes the step csrc/infer_plan.h planned for this conv (plan_conv): the template ladders below map (algorithm, shape) to an
+// instantiation and decide nothing
+hipError_t launch_conv3x3(const ConvArgs& a0, const ConvStep& step, int cin, int cout, int stride, int epi, hipStream_t st) {
   ConvArgs a = a0;
-  ConvRoute unused;
-  ConvRoute& r = route ? *route : unused;
-  r = ConvRoute{};
-  if (!a.fast && cin == 64 && cout == 64 && stride == 1 && a.W == 44 && a.H == 44 && epi != 2 && a.M % (44 * 44) == 0 &&
-      a.M / (44 * 44) <= SE3TN_CONV64_SMALL_MAX_N && a.small_ok) {
-    r.algo = ConvRoute::SMALL64;
-    return launch_conv64_small(a, a.M / (44 * 44), epi, st);
+  a.slices = step.slices;
+  if (step.algo == ConvStep::SMALL64) return launch_conv64_small(a, a.M / (44 * 44), epi, st);
+  if (step.algo == ConvStep::SLICES) {   // float32 only (per_img: the mixed-model call)
+    a.tiles_n = cout / 32;
+    hipError_t e = launch_conv_slices_small(a, cin, stride, st);
+    if (e != hipSuccess || !step.reduce) return e;      // (!reduce: the tail adds the slices: kernels_misc.hip tail_parts_kernel)
+    return launch_reduce_for(a, cout, epi, MM_F32, FMT_F32, a.per_img != 0, st);
   }
-  // batch 1-5, float32: the wide convs as one round of 128-pixel x 32-cout x channel-slice workgroups (conv_slices_small.hip)
-  if (!a.fast && a.small_ok && a.part && a.Ho * a.Wo > 0 && a.M % (a.Ho * a.Wo) == 0 && a.M / (a.Ho * a.Wo) <= SE3TN_SLICES_SMALL_MAX_N) {
-    const int sl = conv_slices_small_count(cin, stride, a.H);
-    if (sl > 0 && (size_t)sl * a.groups * a.M * cout * sizeof(float) <= a.part_bytes) {
-      a.slices = sl;
-      a.tiles_n = cout / 32;
-      r.algo = ConvRoute::SLICES;
-      r.slices = sl;
-      hipError_t e = launch_conv_slices_small(a, cin, stride, st);
-      if (e != hipSuccess) return e;
-      if (a.skip_reduce) {                               // (the tail adds the slices: kernels_misc.hip tail_parts_kernel)
-        r.reduced = false;
-        return hipSuccess;
-      }
-      return launch_reduce_for(a, cout, epi, MM_F32, FMT_F32, false, st);
-    }
-  }
-  a.slices = pick_slices(a, cin, cout, stride == 1 ? 256 : 128, cout >= 128 ? 128 : 64);
-  if (a.slices > 0) {
-    r.algo = ConvRoute::SPLITK;
-    r.slices = a.slices;
+  if (step.algo == ConvStep::SPLITK) {
     a.tiles_n = cout >= 128 ? cout / 128 : 1;
     if (a.fast) {  // f16x3: split rows everywhere, float32 out of the last head conv (cin 512, residual)
       const int outf = (cin == 512 && epi == 1) ? FMT_F32 : FMT_SPLIT;
@@ -734,7 +676,7 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
     if (cin == 512 && stride == 1) return launch_splitk<512, 1, 2, MM_F32>(a, epi, FMT_F32, st);
     return hipErrorInvalidValue;
   }
-  r.algo = stride == 1 ? ConvRoute::SLAB : ConvRoute::GATHER;   // (the big-tile kernels: slab at stride 1, gather at stride 2)
+  if (step.algo != (stride == 1 ? ConvStep::SLAB : ConvStep::GATHER)) return hipErrorInvalidValue;   // (the big-tile kernels)
   if (a.fast) {
     // f16x3 mode (se3tn_set_precision): every 3x3 conv runs on the f16 matrix cores with split-row
     // operands; the max-pool produces the first split-row tensor, the last conv of the heads writes
@@ -774,27 +716,6 @@ hipError_t launch_conv3x3(const ConvArgs& a0, int cin, int cout, int stride, int
   if (stride == 2 && cin == 128 && epi == 2) return launch_gather<128, 2>(a, st);
   if (stride == 2 && cin == 256 && epi == 2) return launch_gather<256, 2>(a, st);
   return hipErrorInvalidValue;
-}
-
-// The batch 1-5 family with no predicate to fall through: the caller (se3tn_on_track_objects: mixed-model batches, whose bits must
-// equal each model's batch-1 run) has chosen it, so a shape or batch it does not cover is an error, not another algorithm.
-hipError_t launch_conv_small(const ConvArgs& a0, int cin, int cout, int stride, int epi, hipStream_t st) {
-  ConvArgs a = a0;
-  if (a.fast || a.Ho * a.Wo <= 0 || a.M % (a.Ho * a.Wo) != 0) return hipErrorInvalidValue;
-  const int n = a.M / (a.Ho * a.Wo);
-  if (n < 1 || n > SE3TN_SLICES_SMALL_MAX_N) return hipErrorInvalidValue;
-  if (cin == 64 && cout == 64 && stride == 1 && a.W == 44 && a.H == 44 && epi != 2) {
-    if (n > SE3TN_CONV64_SMALL_MAX_N) return hipErrorInvalidValue;
-    return launch_conv64_small(a, n, epi, st);
-  }
-  const int sl = conv_slices_small_count(cin, stride, a.H);
-  if (sl <= 0 || !a.part || (size_t)sl * a.groups * a.M * cout * sizeof(float) > a.part_bytes) return hipErrorInvalidValue;
-  a.slices = sl;
-  a.tiles_n = cout / 32;
-  hipError_t e = launch_conv_slices_small(a, cin, stride, st);
-  if (e != hipSuccess) return e;
-  if (a.skip_reduce) return hipSuccess;
-  return launch_reduce_for(a, cout, epi, MM_F32, FMT_F32, a.per_img != 0, st);
 }
 
 }  // namespace se3tn

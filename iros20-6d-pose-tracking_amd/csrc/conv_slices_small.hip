@@ -287,15 +287,6 @@ static hipError_t launch_cs(const ConvArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// slices of the layer (0: this geometry has no kernel here)
-int conv_slices_small_count(int cin, int stride, int H) {
-  if (cin == 128 && stride == 2 && H == S2) return 4;
-  if (cin == 256 && stride == 1 && H == S3) return 8;
-  if (cin == 256 && stride == 2 && H == S3) return 8;
-  if (cin == 512 && stride == 1 && H == S4) return 8;
-  return 0;
-}
-
 // the conv part only: a.slices / a.tiles_n (= cout / 32) are set by the caller, who also launches the reduction
 hipError_t launch_conv_slices_small(const ConvArgs& a, int cin, int stride, hipStream_t st) {
   if (cin == 128 && stride == 2) return launch_cs<1, 2, 690, S3, 4, 8>(a, st);     // convAB1: 128 -> 256

@@ -6,14 +6,9 @@
 #include <stdint.h>
 
 #include "../../include/se3tracknet.h"
+#include "infer_plan.h"   // network geometry, ConvId / conv_specs, the planned steps the conv launchers execute
 
 namespace se3tn {
-
-constexpr int RES = SE3TN_RES;  // 176
-constexpr int S1 = 88;          // after the 7x7 s2 stems
-constexpr int S2 = 44;          // after maxpool 3x3 s2
-constexpr int S3 = 22;          // after convAB1 (s2)
-constexpr int S4 = 11;          // after {trans,rot}_conv1 (s2)
 
 // ---------------------------------------------------------------------------------------------
 // Packed weight blob (float32 words).  One contiguous allocation so that multi-GPU start-up is a
@@ -23,25 +18,6 @@ constexpr int S4 = 11;          // after {trans,rot}_conv1 (s2)
 // runs a lane reads with one ds_read_b128.  Stems: [Cout = 64][204], k = pair*8 + half*4 + c
 // (tap pairing: weights.cpp pack_stem / stem7x7_mfma.hip).
 // ---------------------------------------------------------------------------------------------
-struct Conv3 {
-  int cin, cout, groups;  // weights of `groups` independent convs stored back to back
-};
-constexpr size_t conv3_words(int cin, int cout) { return (size_t)9 * cin * cout; }
-
-enum ConvId {
-  L64_1 = 0,  // convA2.conv1 | convB2.conv1     (2 groups, 64->64)
-  L64_2,      // convA2.conv2 | convB2.conv2     (2 groups)
-  L64_3,      // convB3.conv1
-  L64_4,      // convB3.conv2
-  LAB1,       // convAB1 128->256 s2
-  LAB2_1,     // convAB2.conv1 256->256
-  LAB2_2,     // convAB2.conv2
-  LH1,        // trans_conv1 | rot_conv1 fused along Cout: 256->1024 s2
-  LH2_1,      // trans_conv2.conv1 | rot_conv2.conv1   (2 groups, 512->512)
-  LH2_2,      // trans_conv2.conv2 | rot_conv2.conv2   (2 groups)
-  NUM_CONV3
-};
-
 struct BlobLayout {
   // offsets in float32 words
   size_t stem_w;   // [2 branches][64][204]
@@ -67,13 +43,6 @@ struct SplitLayout {
   size_t conv_sc[NUM_CONV3];
   size_t total;    // words
 };
-
-inline const Conv3* conv_specs() {
-  static const Conv3 s[NUM_CONV3] = {
-      {64, 64, 2},   {64, 64, 2},   {64, 64, 1},   {64, 64, 1},  {128, 256, 1},
-      {256, 256, 1}, {256, 256, 1}, {256, 1024, 1}, {512, 512, 2}, {512, 512, 2}};
-  return s;
-}
 
 inline BlobLayout blob_layout() {
   BlobLayout L{};
@@ -131,12 +100,7 @@ constexpr int PAD_SLACK_PX = 8;
 constexpr int IN_PAD = 3;
 constexpr int IN_P = RES + 2 * IN_PAD;  // 182
 constexpr int IN_SLACK_ROWS = 6;
-// batch 1-5 kernel family: most pairs a launch takes (stem + pool, trunk convs, channel-slice convs, and so the per-image tables below)
-#ifndef SE3TN_SLICES_SMALL_MAX_N
-#define SE3TN_SLICES_SMALL_MAX_N 5   // up to this many pairs the 128 .. 512-channel convs take conv_slices_small_kernel (0: never)
-#endif
-constexpr int SMALL_MAX_IMG = 5;
-static_assert(SE3TN_SLICES_SMALL_MAX_N <= SMALL_MAX_IMG, "the per-image tables hold SMALL_MAX_IMG entries");
+// (SMALL_MAX_IMG, the most pairs a launch of the batch 1-5 kernel family takes: infer_plan.h)
 // Mixed-model launches of the batch 1-5 family (se3tn_on_track_objects): image i of a launch reads every weight / bias / FC tensor
 // img_off[i] floats away from the launch's own pointers (all blobs share one layout, so one offset per image serves every tensor),
 // and its pose update takes tn[i] / rn[i].  The offset is looked up once per workgroup from the image index of blockIdx (a scalar
@@ -162,8 +126,8 @@ struct ConvArgs {
   float* part;
   size_t part_bytes;
   int slices;
-  int skip_reduce;            // conv_slices_small only: the caller consumes the partial sums itself (tail_parts_kernel): no conv_reduce launch
-  int small_ok;               // the batch-1-5 kernel family (conv64_small, conv_slices_small) may be used (SE3TN_SMALL_KERNELS=0 switches them off)
+  int reserved[2];            // unused.  The words keep img_off (below) at its offset: the per-image conv_reduce kernels address that table
+                              // through vector immediates, which a shorter struct would change (profiles/EXPERIMENTS.md item 80)
   // f16x3 mode: per-cout power-of-two weight scale (acc * wscale = true sum), overflow flag,
   // fast = 0 (f32 everywhere) | 1 | 2 (see launch_conv3x3)
   const float* wscale;
@@ -191,8 +155,6 @@ struct WinoArgs {
   int C, Cout, groups;
   int in_gs, res_gs, out_gs, bias_gs;
   long long u_gs;     // floats per group of U
-  int num_cus;        // compute units of the device (0: 256); sizes the persistent GEMM grid
-  int gemmp;          // persistent 128 x 256 GEMM: -1 = when its tiles fill every CU twice, 0 = never, 1 = whenever the shape allows
   // f16x3 mode of the fused F(4x4) blocks (split != 0): in / res / out are split-row tensors, V is written as split rows, U points
   // at the split planes and uscale[g][f][Cout] holds their exact power-of-two scales (undone in the GEMM epilogue, M is float32)
   int split;
@@ -291,43 +253,29 @@ hipError_t launch_stem(const float* inA, const float* inB, const float* w, const
                        const float* wscale, float* out, int n, hipStream_t st);
 // split_out != 0: write split rows (f16 hi | f16 lo) for the f16x3 mode
 hipError_t launch_maxpool(const float* in, float* out, int n, int split_out, hipStream_t st);
-// conv3x3: cin/cout/stride select the instantiation; epi: 0 bias+relu, 1 bias+res+relu, 2 bias+selu.
-// route (optional out): the algorithm it took -- what the caller decides the next launch from (a.skip_reduce is a permission)
-struct ConvRoute {
-  enum Algo { NONE = 0, SMALL64, SLICES, SPLITK, SLAB, GATHER, WINO, WINO64 };   // (WINO / WINO64: set by the caller's own routes)
-  Algo algo = NONE;
-  int slices = 0;      // partial-sum slices left in a.part (SLICES / SPLITK)
-  bool reduced = true; // false: the output map was NOT written, the partial sums were left to the caller (a.skip_reduce)
-};
-hipError_t launch_conv3x3(const ConvArgs& a, int cin, int cout, int stride, int epi, hipStream_t st, ConvRoute* route = nullptr);
+// conv3x3: executes the planned step (SMALL64 .. GATHER; its slice count, whether it reduces them); cin/cout/stride select the
+// instantiation; epi: 0 bias+relu, 1 bias+res+relu, 2 bias+selu.  hipErrorInvalidValue: no kernel of that algorithm for the shape
+hipError_t launch_conv3x3(const ConvArgs& a, const ConvStep& step, int cin, int cout, int stride, int epi, hipStream_t st);
 // Winograd F(m x m,3x3): U = G g G^T (float64, rounded once) from the packed direct weights
 // [chunk][9][cout][32] -> [chunk][(m+2)^2][cout][32]; launch_wino_conv = input transform + nf x groups
 // batched MFMA GEMMs + output transform with the conv epilogue (epi 0 | 1)
 hipError_t launch_wino_weights(const float* packed, float* U, int cin, int cout, int m, hipStream_t st);
-hipError_t launch_wino_conv(const WinoArgs& a, int epi, hipStream_t st);
+hipError_t launch_wino_conv(const WinoArgs& a, const GemmPlan& gemm, int epi, hipStream_t st);
 // fused Winograd F(2x2,3x3) of a 64 -> 64 channel convolution on the 44 x 44 maps (wino64_fused.hip); U: F(2x2) planes of launch_wino_weights
 hipError_t launch_wino64(const float* in, int in_ld, int in_gs, const float* U, long long u_gs, const float* bias, int bias_gs,
                          const float* res, int res_ld, int res_gs, float* out, int out_ld, int out_gs, int n, int groups, int epi,
                          hipStream_t st);
 // a whole residual block on the Winograd F(4x4) path with the fused mid / tail transforms (wino_mfma.hip);
 // mark_after_mid: optional profiling hook called between conv1 and conv2 (returns non-zero on error)
-hipError_t launch_wino_block(const WinoArgs& c1, const float* U2, const float* uscale2, const float* bias2, float* out2, int keep_mid,
+hipError_t launch_wino_block(const WinoArgs& c1, const GemmPlan& gemm, const float* U2, const float* uscale2, const float* bias2, float* out2, int keep_mid,
                              float* keep_out2, const TailArgs* tl, hipStream_t st, int mark_after_mid(void*), void* mark_ctx);
 // stem + max-pool of both branches in one launch at batch 1-2 (stem_pool_small.hip)
-#ifndef SE3TN_STEM_SMALL_MAX_N
-#define SE3TN_STEM_SMALL_MAX_N 5
-#endif
 hipError_t launch_stem_pool_small(const float* inA, const float* inB, const float* w, const float* bias, float* pool, int n, hipStream_t st);
 // the 64 -> 64 trunk convs at batch 1-5 without a K split (conv64_small.hip)
 hipError_t launch_conv64_small(const ConvArgs& a, int n, int epi, hipStream_t st);
 // the 128 .. 512-channel convs at batch 1-5: 128 pixels x 32 couts x one channel slice with all nine taps per workgroup
-// (conv_slices_small.hip); partial sums for conv_reduce_kernel (SE3TN_SLICES_SMALL_MAX_N: above)
-int conv_slices_small_count(int cin, int stride, int H);
+// (conv_slices_small.hip); partial sums for conv_reduce_kernel (the slice count per shape: infer_plan.h conv_slices_small_count)
 hipError_t launch_conv_slices_small(const ConvArgs& a, int cin, int stride, hipStream_t st);
-// one conv of the batch 1-5 family, chosen explicitly (no fall-back): conv64_small for the 64-channel trunk, otherwise
-// conv_slices_small + conv_reduce_kernel (a.skip_reduce: the caller consumes the partial sums).  hipErrorInvalidValue when the
-// family has no kernel for the shape or the batch (conv3x3_mfma.hip)
-hipError_t launch_conv_small(const ConvArgs& a, int cin, int cout, int stride, int epi, hipStream_t st);
 // stem + max-pool with a per-image weight offset table (ImgParams::off; nullptr = the single-model kernel)
 hipError_t launch_stem_pool_small_multi(const float* inA, const float* inB, const float* w, const float* bias, float* pool, int n,
                                         const long long* img_off, hipStream_t st);

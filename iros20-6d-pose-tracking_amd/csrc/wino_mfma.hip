@@ -983,35 +983,25 @@ static hipError_t launch_gemmp(const WinoArgs& a, int total_tiles, int grid, hip
   return hipGetLastError();
 }
 
-// 128- or 96-row tiles: whichever leaves the shorter per-CU queue (in 32 x 32 x K blocks) on 256 CUs
+// the tiling csrc/infer_plan.h planned (plan_gemm): 96- or 128-row tiles, or the persistent 128 x 256 kernel
 template <int CIN>
-static hipError_t launch_gemm_auto(const WinoArgs& a, hipStream_t st) {
-  const long long per_b = (long long)(a.Cout / 128) * a.groups * a.nf;
-  const long long q128 = ((((a.T + 127) / 128) * per_b + 255) / 256) * 16;
-  const long long q96 = ((((a.T + 95) / 96) * per_b + 255) / 256) * 12;
-  if (a.split) return q96 < q128 ? launch_gemm<CIN, 1, 4, 3, 1, MM_F16X3>(a, st) : launch_gemm<CIN, 2, 2, 2, 2, MM_F16X3>(a, st);
-  // persistent 128 x 256 tiles, one 8-wave workgroup per CU: when they fill every CU at least twice (F(6x6) at batch 64: exactly 2.0)
-  // and the plane count lets the XCD-local tile order cover them (groups nf % 8 == 0: 36 F(4x4) planes do not).
-  // a.gemmp: -1 = that rule, 0 = never, 1 = whenever the shape allows (SE3TN_WINO_GEMMP at se3tn_create: A/B runs and the tests'
-  // bit-equality check of the two kernels on ragged shapes)
-  if (a.gemmp != 0 && a.Cout % 256 == 0 && (a.groups * a.nf) % 8 == 0) {
-    const int cus = a.num_cus > 0 ? a.num_cus : 256;
-    const int tiles = (a.Cout / 256) * ((a.T + 127) / 128) * a.groups * a.nf;
-    // the automatic rule takes it for the plane sets it was measured on (EXPERIMENTS item 27): F(6x6).  The two-group F(4x4) heads
-    // (72 planes, T = 576 at batch 64 = 4.5 row tiles) also pass the divisibility test above and would trade their exact-fit 96-row
-    // tiling for it unmeasured: they keep launch_gemm unless gemmp == 1 forces it.
-    const bool measured_shape = a.nf == 64;
-    if (a.gemmp == 1 || (tiles >= 2 * cus && measured_shape)) return launch_gemmp<CIN>(a, tiles, tiles < cus ? tiles : (cus / 8) * 8, st);
+static hipError_t launch_gemm_planned(const WinoArgs& a, const GemmPlan& g, hipStream_t st) {
+  if (g.kind == GemmPlan::PERSISTENT) {   // (the kernel decodes tile indices below g.tiles: a count of another shape would leave the planes)
+    if (a.split || a.Cout % 256 != 0 || g.grid < 1 || g.tiles != (a.Cout / 256) * ((a.T + 127) / 128) * a.groups * a.nf) return hipErrorInvalidValue;
+    return launch_gemmp<CIN>(a, g.tiles, g.grid, st);
   }
-  return q96 < q128 ? launch_gemm<CIN, 1, 4, 3, 1>(a, st) : launch_gemm<CIN, 2, 2, 2, 2>(a, st);
+  if (g.kind != GemmPlan::ROWS96 && g.kind != GemmPlan::ROWS128) return hipErrorInvalidValue;
+  const bool r96 = g.kind == GemmPlan::ROWS96;
+  if (a.split) return r96 ? launch_gemm<CIN, 1, 4, 3, 1, MM_F16X3>(a, st) : launch_gemm<CIN, 2, 2, 2, 2, MM_F16X3>(a, st);
+  return r96 ? launch_gemm<CIN, 1, 4, 3, 1>(a, st) : launch_gemm<CIN, 2, 2, 2, 2>(a, st);
 }
 
 template <int M, int VEC>
-static hipError_t launch_transformed(const WinoArgs& a, int epi, hipStream_t st) {
+static hipError_t launch_transformed(const WinoArgs& a, const GemmPlan& g, int epi, hipStream_t st) {
   hipLaunchKernelGGL((wino_input_kernel<M, VEC>), dim3((a.T * (a.C / VEC) + 255) / 256, a.groups), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = a.C == 256 ? launch_gemm_auto<256>(a, st) : launch_gemm_auto<512>(a, st);
+  e = a.C == 256 ? launch_gemm_planned<256>(a, g, st) : launch_gemm_planned<512>(a, g, st);
   if (e != hipSuccess) return e;
   const dim3 og((a.T * (a.Cout / VEC) + 255) / 256, a.groups);
   if (epi == 0) hipLaunchKernelGGL((wino_output_kernel<M, VEC, 0>), og, dim3(256), 0, st, a);
@@ -1050,7 +1040,7 @@ static hipError_t launch_mid(const WinoArgs& a, float* keep, hipStream_t st) {
 #define WINO6_MID_CS_H 64  // channels per workgroup of the F(6x6) mid transform on the 11 x 11 maps (LDS 14 x 14 x CS floats)
 #endif
 
-hipError_t launch_wino_block(const WinoArgs& c1, const float* U2, const float* uscale2, const float* bias2, float* out2, int keep_mid,
+hipError_t launch_wino_block(const WinoArgs& c1, const GemmPlan& gemm, const float* U2, const float* uscale2, const float* bias2, float* out2, int keep_mid,
                              float* keep_out2, const TailArgs* tl, hipStream_t st, int mark_after_mid(void*), void* mark_ctx) {
   if ((c1.m != 4 && c1.m != 6) || c1.nf != (c1.m + 2) * (c1.m + 2) || c1.C != c1.Cout || (c1.C != 256 && c1.C != 512))
     return hipErrorInvalidValue;
@@ -1067,7 +1057,7 @@ hipError_t launch_wino_block(const WinoArgs& c1, const float* U2, const float* u
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = ab ? launch_gemm_auto<256>(c1, st) : launch_gemm_auto<512>(c1, st);
+  e = ab ? launch_gemm_planned<256>(c1, gemm, st) : launch_gemm_planned<512>(c1, gemm, st);
   if (e != hipSuccess) return e;
   float* keep1 = keep_mid ? c1.out : nullptr;
   if (c1.m == 6) e = ab ? launch_mid<6, 4, WINO6_MID_CS_AB, WINO6_MID_VEC>(c1, keep1, st) : launch_mid<6, 2, WINO6_MID_CS_H, WINO6_MID_VEC>(c1, keep1, st);
@@ -1077,7 +1067,7 @@ hipError_t launch_wino_block(const WinoArgs& c1, const float* U2, const float* u
   if (mark_after_mid && mark_after_mid(mark_ctx)) return hipErrorUnknown;
   WinoArgs c2 = c1;
   c2.U = U2; c2.uscale = uscale2; c2.bias = bias2; c2.res = c1.in; c2.res_ld = c1.in_ld; c2.res_gs = c1.in_gs; c2.out = out2;
-  e = ab ? launch_gemm_auto<256>(c2, st) : launch_gemm_auto<512>(c2, st);
+  e = ab ? launch_gemm_planned<256>(c2, gemm, st) : launch_gemm_planned<512>(c2, gemm, st);
   if (e != hipSuccess) return e;
   if (tl) {
     if (ab || c1.groups != 2 || c1.Cout != 512) return hipErrorInvalidValue;
@@ -1100,11 +1090,11 @@ hipError_t launch_wino_block(const WinoArgs& c1, const float* U2, const float* u
   return hipGetLastError();
 }
 
-hipError_t launch_wino_conv(const WinoArgs& a, int epi, hipStream_t st) {
+hipError_t launch_wino_conv(const WinoArgs& a, const GemmPlan& gemm, int epi, hipStream_t st) {
   if ((a.C != 256 && a.C != 512) || a.Cout % 128 != 0 || (epi != 0 && epi != 1)) return hipErrorInvalidValue;
-  if (a.m == 2 && a.nf == 16) return launch_transformed<2, 4>(a, epi, st);
-  if (a.m == 4 && a.nf == 36) return launch_transformed<4, WINO4_VEC>(a, epi, st);
-  if (a.m == 6 && a.nf == 64 && !a.split) return launch_transformed<6, 2>(a, epi, st);
+  if (a.m == 2 && a.nf == 16) return launch_transformed<2, 4>(a, gemm, epi, st);
+  if (a.m == 4 && a.nf == 36) return launch_transformed<4, WINO4_VEC>(a, gemm, epi, st);
+  if (a.m == 6 && a.nf == 64 && !a.split) return launch_transformed<6, 2>(a, gemm, epi, st);
   return hipErrorInvalidValue;
 }
 

@@ -45,7 +45,7 @@ def stem_grid(n):
 
 
 def trunk_fused(n, groups, tmin=8, tfill=55):
-    """csrc/api.cpp:558 wino64_pays: the fused F(2x2) trunk kernel where the rounds of its 4 n groups workgroups are tfill % full"""
+    """csrc/infer_plan.h wino64_pays: the fused F(2x2) trunk kernel where the rounds of its 4 n groups workgroups are tfill % full"""
     if tmin <= 0 or n < tmin:
         return False
     wgs = 4 * n * groups
@@ -53,7 +53,7 @@ def trunk_fused(n, groups, tmin=8, tfill=55):
 
 
 def pick_slices(M, hw, cin, cout, groups, big_rows, bn_big):
-    """csrc/conv3x3_mfma.hip:832 pick_slices (0: the big-tile kernel)"""
+    """csrc/infer_plan.h pick_slices (0: the big-tile kernel)"""
     if cdiv(M, big_rows) * (cout // bn_big) * groups >= 200:
         return 0
     bn = 128 if cout >= 128 else 64
@@ -72,7 +72,7 @@ def pick_slices(M, hw, cin, cout, groups, big_rows, bn_big):
 
 
 def direct(n, cin, cout, groups, ho, stride):
-    """csrc/conv3x3_mfma.hip:890-949 launch_conv3x3 above 5 pairs: split-K (slices) | slab (one tile per workgroup | persistent, :732) at
+    """csrc/infer_plan.h plan_conv above 5 pairs: split-K (slices) | slab (one tile per workgroup | persistent, :732) at
     stride 1 | gather (8 | 4 waves, :758-761) at stride 2; f16x3 takes the 4-wave gather always"""
     M, bn = n * ho * ho, (128 if cout >= 128 else 64)
     sl = pick_slices(M, ho * ho, cin, cout, groups, 256 if stride == 1 else 128, bn)
@@ -91,7 +91,7 @@ def direct_f16(n, cin, cout, groups, ho, stride):
 
 
 def gemm(T, cout, groups, nf, split=False):
-    """csrc/wino_mfma.hip:1132 launch_gemm_auto: the persistent 128 x 256 kernel (F(6x6) planes, >= 2 tiles per CU; value: the
+    """csrc/infer_plan.h plan_gemm: the persistent 128 x 256 kernel (F(6x6) planes, >= 2 tiles per CU; value: the
     virtual-tile rounds a workgroup walks, :679) | 96- or 128-row tiles, whichever queue is shorter"""
     per_b = (cout // 128) * groups * nf
     q128 = cdiv(cdiv(T, 128) * per_b, 256) * 16
@@ -104,7 +104,7 @@ def gemm(T, cout, groups, nf, split=False):
 
 
 def tile(cfg, n, which):
-    """csrc/api.cpp:229 tile_for (rot_normalizer 5 degrees: AUTO takes F(6x6) for the heads too)"""
+    """csrc/infer_plan.h tile_for (rot_normalizer 5 degrees: AUTO takes F(6x6) for the heads too)"""
     if cfg == "F4" or cfg == "f16x3":
         return 4
     if cfg == "F6":
@@ -178,7 +178,7 @@ _SHARED = [7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 18, 22, 23, 24, 25, 26, 27, 32, 
 SIZES = {
     "default": sorted(set(_SHARED + NAMED + [250])),     # 250: the one residue mod 8 (2) the others leave out above 72
     "keep": _SHARED,
-    # F(4x4) at every n: the 96- | 128-row choice of launch_gemm_auto alternates 38 (convAB2) + 18 (heads) times up to 256
+    # F(4x4) at every n: the 96- | 128-row choice of plan_gemm (csrc/infer_plan.h) alternates 38 (convAB2) + 18 (heads) times up to 256
     "F4": [7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 21, 22, 23, 24, 25, 26, 27, 28, 29, 32, 33, 34, 35, 36, 45, 46, 49, 50, 51, 52, 53,
            54, 56, 57, 60, 61, 63, 64, 65, 67, 68, 70, 71, 72, 74, 75, 85, 86, 93, 94, 99, 100, 104, 105, 113, 114, 122, 123, 124, 125, 127,
            128, 130, 131, 138, 139, 141, 142, 143, 149, 150, 160, 161, 163, 164, 170, 171, 174, 175, 178, 179, 184, 185, 188, 189, 192, 193,

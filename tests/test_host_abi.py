@@ -289,6 +289,57 @@ def test_track_plan_host_arithmetic_under_sanitizers(tmp_path):
     assert "track_plan_check: ok" in out.stdout
 
 
+def test_infer_plan_routes_under_sanitizers(tmp_path):
+    """csrc/infer_plan.h (which kernel runs for which conv of a forward pass, decided on the host before anything is enqueued) in a
+    stand-alone host program built with AddressSanitizer + UBSan.  The program walks every configuration recorded in
+    tests/golden/infer_routes.json for n = 1 .. 72, and the default one up to SE3TN_MAX_BATCH_LIMIT, and asserts the plan's invariants
+    itself (tests/c_abi/infer_plan_check.cpp: workspace bounds, split-K divisibility, fused blocks only with their planes, fallbacks with
+    a readiness bit cleared, the mixed-model call's explicit family = the default plan of 1 .. 5 pairs and an error at 6).  It prints
+    the launch names and written stages of every cell; here they are held against
+      * the record of what the library launched on the device at the commit named in the file (scripts/record_infer_routes.py), exactly;
+      * the Python route model (tests/route_model.py `expected`), for every cell."""
+    import json
+    import shutil
+    import subprocess
+    from route_model import actual, expected
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "infer_routes.json")))
+    cases = rec["cases"]
+    assert cases[0]["id"] == "default" and rec["n_max"] == 72 and len({c["id"] for c in cases}) == len(cases)
+    cfgs = tmp_path / "configs.txt"
+    with open(cfgs, "w") as f:
+        for c in cases:
+            g = c["cfg"]
+            ch = 32 if c["env"].get("SE3TN_TAIL_PARTS") == "2" else 16
+            f.write("%s %d %d %d %d %d %d %d %.17g %d %d %d %d %d\n" % (c["id"], g["wmin"], g["tile"], g["tmin"], g["tfill"], g["small"], g["keep"],
+                                                                      g["f16"], g["rn"], g["fuse"], g["tail_parts"], ch, g["ovr"][0], g["ovr"][1]))
+    exe = str(tmp_path / "infer_plan_check")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "iros20-6d-pose-tracking_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c_abi", "infer_plan_check.cpp"), "-o", exe])
+    out = subprocess.run([exe, str(cfgs)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    assert "infer_plan_check: ok" in out.stdout
+    got = {}
+    for line in out.stdout.splitlines():
+        if line.startswith("R\t"):
+            _, cid, n, names, stages = line.split("\t")
+            got[(cid, int(n))] = (names.split(";"), stages.split(",") if stages else [])
+    assert len(got) == 72 * len(cases)
+    for c in cases:
+        seen = 0
+        for first, last, names, stages in c["rows"]:
+            for n in range(first, last + 1):
+                seen += 1
+                assert got[(c["id"], n)] == (names, stages), (c["id"], n, got[(c["id"], n)], names, stages)
+                want_r, written = expected(c["cfg"], n)
+                assert actual(got[(c["id"], n)][0]) == want_r, (c["id"], n)
+                assert {s: s in got[(c["id"], n)][1] for s in written} == written, (c["id"], n)
+        assert seen == 72, c["id"]
+
+
 def test_hip_buffers_ownership_under_sanitizers(tmp_path):
     """csrc/hip_buffers.h (the owners of every device and pinned buffer of a context and a mesh) in a stand-alone host program built
     with AddressSanitizer + UBSan.  The program defines the six HIP runtime functions the header calls over malloc / free with a count
