@@ -501,6 +501,61 @@ int se3tn_pose_errors(se3tn_ctx* ctx, const se3tn_points* points, int n, const d
 int se3tn_pose_errors_host(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* pred, const double* gt,
                            double* add_out, double* adds_out, void* stream);
 
+/* ---- re-acquiring a lost object: n candidate poses scored against one depth frame, the best k picked ------------------------- */
+/* The reference's only answer to a lost track is an external detector: predict.py:539-541 re-initialises from PoseCNN at the frames
+ * --reinit_frames lists.  Here the search is a call: project the model's points under each candidate pose into the observed depth
+ * frame and count how many land on the surface the sensor saw.  For candidate i (row-major 4x4 float64, metres; row 3 is not read)
+ * and model point x_j of a points handle, all in float64, in this order, without fused multiply-add:
+ *     c = R x + t                row r is ((r_r0 x + r_r1 y) + r_r2 z) + t_r: the transform of se3tn_pose_errors
+ *     in front    c.z > 0        (false for NaN)
+ *     uf = rint(c.x * K[0] / c.z + K[2]),  vf = rint(c.y * K[4] / c.z + K[5])      round half to even, as se3tn_compute_bbox
+ *     in frame    in front && 0 <= uf < W && 0 <= vf < H    decided on the doubles, before any integer cast: -0.5 rounds to -0.0
+ *                 (inside), W - 0.5 rounds to W for even W (outside); NaN, infinities and huge values are outside
+ *     d = depth[vf, uf] (uint16 mm),  m = rint(c.z * 1000.0)  (kept as a double)
+ *     seen        in frame && 100 < d < 2000               the validity rule of se3tn_fit_stats
+ *     inlier      seen && |d - m| <= tol_mm
+ *     front       seen && d < m - tol_mm                    something stands in front of the point
+ *     behind      seen && d > m + tol_mm                    the sensor sees through where the point would be
+ * A candidate at the truth does not score P inliers: the far side of the object lies behind its near side and counts as `front`.
+ * Guarantees:
+ *   (a) every count is an integer sum: a record depends on (points, pose_i, depth, K, tol_mm) only -- not on n, on the pose's place
+ *       in the call, or on the run -- and equals the same rule evaluated in IEEE float64 anywhere else (tests/pose_search_oracle.py);
+ *   (b) a pose is read by its own workgroup alone: one that is not finite harms no other (with a NaN in it, in_frame_pts = 0);
+ *   (c) the device-pointer entry points allocate nothing, use no scratch and no atomics.
+ * Cost: n * P projections of about 40 float64 operations and one 2-byte gather each, one workgroup per pose (9,317 candidates of a
+ * 2,620-point model: 24 M projections); the ranking reads the n records k times with one workgroup. */
+#define SE3TN_POSE_SEARCH_MAX_POSES 1048576   /* 2^20 candidates per call */
+#define SE3TN_POSE_RANK_MAX 64                /* the largest k */
+typedef struct se3tn_point_fit {   /* all uint32, 32 bytes */
+  uint32_t points;        /* P                                            */
+  uint32_t in_frame_pts;  /* #{in frame}                                  */
+  uint32_t seen_pts;      /* #{in frame && valid(d)}                      */
+  uint32_t inlier_pts;    /* #{seen && |d - m| <= tol_mm}                 */
+  uint32_t front_pts;     /* #{seen && d <  m - tol_mm}                   */
+  uint32_t behind_pts;    /* #{seen && d >  m + tol_mm}                   */
+  uint32_t tol_mm;        /* echoed                                       */
+  uint32_t _reserved;     /* 0                                            */
+} se3tn_point_fit;        /* seen = inlier + front + behind <= in_frame <= points */
+/* poses_dev: device float64 [n,16]; depth_dev: device uint16 [H,W] millimetres; K: HOST row-major 3x3 (travels as kernel arguments);
+ * fit_dev: n records in device memory or mapped pinned host memory (every word stored once).  Stream-ordered, capturable.  The
+ * poses are not inspected.  SE3TN_E_ARG: a NULL pointer, a host-only context, points of another device, n outside
+ * [1, SE3TN_POSE_SEARCH_MAX_POSES], tol_mm outside [1, 65535], H or W < 1. */
+int se3tn_score_poses(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses_dev, const uint16_t* depth_dev,
+                      int H, int W, const double K[9], int tol_mm, se3tn_point_fit* fit_dev, void* stream);
+/* The indices of the k best of n records, best first, into idx_dev (device or mapped pinned host int32 [k]).  Record i has the key
+ *     inlier_pts * 2^40 + (2^20 - 1 - min(behind_pts, 2^20 - 1)) * 2^20 + (2^20 - 1 - i)
+ * -- more inliers, then fewer seen-through points, then the lower index; unique within a call -- and the k largest keys are written
+ * in descending order.  Selection without state: round r takes the largest key below round r - 1's winner (k passes over the n
+ * records by one workgroup), so the result is deterministic.  Stream-ordered, capturable.  SE3TN_E_ARG: a NULL pointer, a host-only
+ * context, n outside [1, SE3TN_POSE_SEARCH_MAX_POSES], k outside [1, min(n, SE3TN_POSE_RANK_MAX)]. */
+int se3tn_rank_poses(se3tn_ctx* ctx, int n, const se3tn_point_fit* fit_dev, int k, int32_t* idx_dev, void* stream);
+/* Both from HOST memory: poses float64 [n,16], depth uint16 [H,W]; idx_out int32 [k] and fit_out [k] receive the k best candidates'
+ * indices and records, best first.  One upload (the poses and the whole frame), the two launches, one read-back.  SYNCHRONOUS on
+ * `stream`, refused inside a stream capture (SE3TN_E_STATE); the pinned staging and its device mirror grow on a first or larger
+ * call.  SE3TN_E_ARG as the two above, and a pose entry or a K entry that is not finite. */
+int se3tn_search_poses_host(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses, const uint16_t* depth, int H, int W,
+                            const double K[9], int tol_mm, int k, int32_t* idx_out, se3tn_point_fit* fit_out, void* stream);
+
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K
  * row-major 3x3, width in mm; out_vu[8] = 4 x (v,u) int32, np.round (half-to-even). */

@@ -10,11 +10,12 @@ from .engine import Engine, ModelPoints, PipelinedEngine, NCHW, NHWC, compute_bb
 from .se3_tracknet import Se3TrackNet
 from .tracker import Tracker, MultiTracker
 from .utils import compute_bbox, crop_window
-from . import metrics, sequence
+from . import metrics, sequence, recover
+from .recover import pose_lattice
 from .renderer import HipRenderer
 from .live import LiveTracker, LiveMultiTracker, quaternion_from_matrix
 
 _lib.load()
 
 __all__ = ["Engine", "ModelPoints", "PipelinedEngine", "Se3TrackNet", "Tracker", "MultiTracker", "compute_bbox", "crop_window", "pack_crops", "pose_update_host", "frame_rect", "NCHW", "NHWC",
-           "metrics", "sequence", "HipRenderer", "LiveTracker", "LiveMultiTracker", "quaternion_from_matrix"]
+           "metrics", "sequence", "recover", "pose_lattice", "HipRenderer", "LiveTracker", "LiveMultiTracker", "quaternion_from_matrix"]

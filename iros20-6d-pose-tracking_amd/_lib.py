@@ -23,6 +23,8 @@ ROUTE_WINDOW, ROUTE_FRAME = 0, 1   # as include/se3tracknet.h: the renderer se3t
 FIT_MAX_PAIRS = 32                 # as include/se3tracknet.h: pairs per launch of se3tn_fit_stats (larger n are chunked)
 POSE_ERRORS_CHUNK = 256            # as include/se3tracknet.h: pose pairs per launch of se3tn_pose_errors (larger n are chunked)
 POSE_ERRORS_MAX_POINTS = 1 << 20   # as include/se3tracknet.h: the largest model se3tn_points_create accepts
+POSE_SEARCH_MAX_POSES = 1 << 20   # as include/se3tracknet.h: the most candidate poses one se3tn_score_poses / se3tn_rank_poses call takes
+POSE_RANK_MAX = 64                 # as include/se3tracknet.h: the largest k of se3tn_rank_poses
 MAX_BATCH_LIMIT = 1982             # as include/se3tracknet.h: the largest max_batch se3tn_create accepts
 RES = 176
 
@@ -49,6 +51,12 @@ class Fit(C.Structure):
                                           "_reserved")]
 
 
+class PointFit(C.Structure):
+    """se3tn_point_fit (include/se3tracknet.h): the record of one candidate pose of se3tn_score_poses."""
+    _fields_ = [(k, C.c_uint32) for k in ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm",
+                                          "_reserved")]
+
+
 # the same record as a numpy dtype, for building many descriptors without a Python loop
 import numpy as _np
 CROP_DTYPE = _np.dtype([("rgb", "<u8"), ("depth", "<u8"), ("H", "<i4"), ("W", "<i4"), ("left", "<i4"), ("top", "<i4"),
@@ -57,6 +65,9 @@ assert CROP_DTYPE.itemsize == C.sizeof(Crop)
 FIT_FIELDS = ("model_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm", "tol_mm")   # the seven that carry data
 FIT_DTYPE = _np.dtype([(k, "<u4") for k in FIT_FIELDS + ("_reserved",)])
 assert FIT_DTYPE.itemsize == C.sizeof(Fit) == 32
+POINT_FIT_FIELDS = ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm")   # the seven that carry data
+POINT_FIT_DTYPE = _np.dtype([(k, "<u4") for k in POINT_FIT_FIELDS + ("_reserved",)])
+assert POINT_FIT_DTYPE.itemsize == C.sizeof(PointFit) == 32
 
 
 _SIGS = {
@@ -140,6 +151,11 @@ _SIGS = {
     "se3tn_points_count": (C.c_int, [C.c_void_p]),
     "se3tn_pose_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_pose_errors_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_score_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                    C.c_void_p, C.c_void_p]),
+    "se3tn_rank_poses": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "se3tn_search_poses_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_compute_bbox": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(C.c_int32)]),
     "se3tn_pose_update_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float),

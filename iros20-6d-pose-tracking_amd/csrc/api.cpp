@@ -15,6 +15,7 @@
 
 #include "hip_buffers.h"
 #include "pose_errors_plan.h"
+#include "pose_search_plan.h"
 #include "se3tn_internal.h"
 #include "tex_pyramid.h"
 #include "track_plan.h"
@@ -139,6 +140,8 @@ struct se3tn_ctx {
   PinnedBuf<se3tn_fit> fit_host;
   // se3tn_pose_errors_host: pinned staging [pred | gt | add | adds] (pose_errors_plan.h: pe_stage_*) for pe_cap pairs and its device mirror
   PinnedBuf<double> pe_host; DeviceBuf<double> pe_dev; int pe_cap = 0;
+  // se3tn_search_poses_host: pinned staging (pose_search_plan.h: PsStage) of ps_cap bytes and its device mirror
+  PinnedBuf<unsigned char> ps_host; DeviceBuf<unsigned char> ps_dev; size_t ps_cap = 0;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive before the next one
   DeviceBuf<int> tail_arrive;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
   int* tail_flag = nullptr; int tail_seq = 0;   // set around se3tn_on_track's infer: the tail kernel stores tail_seq to this (mapped) word
@@ -1628,6 +1631,93 @@ int se3tn_pose_errors_host(se3tn_ctx* c, const se3tn_points* p, int n, const dou
   HIPCHK(hipStreamSynchronize(st));
   if (add_out) std::memcpy(add_out, h + pe_stage_add(n), sizeof(double) * (size_t)n);
   if (adds_out) std::memcpy(adds_out, h + pe_stage_adds(n), sizeof(double) * (size_t)n);
+  return SE3TN_OK;
+}
+
+// ---- n candidate poses against one depth frame, the best k ----------------------------------------------------------------------------
+// NULL pointers and a host-only context first (ok_ptrs: every pointer of the call), then the numbers
+static int pose_search_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, bool with_points, int n) {
+  if (!c || !ok_ptrs || (with_points && !p)) return fail(SE3TN_E_ARG, std::string(who) + ": NULL argument");
+  if (c->device < 0) return fail(SE3TN_E_ARG, std::string(who) + ": host-only context (device = -1) has no device to search on");
+  if (with_points && p->device != c->device) return fail(SE3TN_E_ARG, std::string(who) + ": the points live on another device than the context");
+  if (n < 1 || n > PS_MAX_POSES)
+    return fail(SE3TN_E_ARG, std::string(who) + ": n = " + std::to_string(n) + " outside [1, SE3TN_POSE_SEARCH_MAX_POSES = " +
+                                 std::to_string(PS_MAX_POSES) + "]");
+  return SE3TN_OK;
+}
+static int pose_score_check(const char* who, int H, int W, int tol_mm) {
+  if (tol_mm < 1 || tol_mm > 65535) return fail(SE3TN_E_ARG, std::string(who) + ": tol_mm = " + std::to_string(tol_mm) + " outside [1, 65535]");
+  if (H < 1 || W < 1) return fail(SE3TN_E_ARG, std::string(who) + ": empty frame (H or W < 1)");
+  return SE3TN_OK;
+}
+static int pose_rank_check(const char* who, int n, int k) {
+  const int kmax = n < PS_RANK_MAX ? n : PS_RANK_MAX;
+  if (k < 1 || k > kmax)
+    return fail(SE3TN_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " outside [1, min(n, SE3TN_POSE_RANK_MAX = " +
+                                 std::to_string(PS_RANK_MAX) + ") = " + std::to_string(kmax) + "]");
+  return SE3TN_OK;
+}
+static PoseScoreArgs pose_score_args(const se3tn_points* p, const double* poses, const uint16_t* depth, int H, int W, const double K[9],
+                                     int tol_mm, se3tn_point_fit* out) {
+  PoseScoreArgs a;
+  a.pts = p->xyz.get(); a.P = p->P; a.poses = poses; a.depth = depth; a.H = H; a.W = W; a.tol = tol_mm; a.out = out;
+  for (int i = 0; i < 9; ++i) a.K[i] = K[i];
+  return a;
+}
+
+int se3tn_score_poses(se3tn_ctx* c, const se3tn_points* p, int n, const double* poses_dev, const uint16_t* depth_dev, int H, int W,
+                      const double K[9], int tol_mm, se3tn_point_fit* fit_dev, void* stream) {
+  const char* who = "se3tn_score_poses";
+  if (int rc = pose_search_check(who, c, poses_dev && depth_dev && K && fit_dev, p, true, n)) return rc;
+  if (int rc = pose_score_check(who, H, W, tol_mm)) return rc;
+  HIPCHK(launch_pose_score(pose_score_args(p, poses_dev, depth_dev, H, W, K, tol_mm, fit_dev), n, (hipStream_t)stream));
+  return SE3TN_OK;
+}
+
+int se3tn_rank_poses(se3tn_ctx* c, int n, const se3tn_point_fit* fit_dev, int k, int32_t* idx_dev, void* stream) {
+  const char* who = "se3tn_rank_poses";
+  if (int rc = pose_search_check(who, c, fit_dev && idx_dev, nullptr, false, n)) return rc;
+  if (int rc = pose_rank_check(who, n, k)) return rc;
+  HIPCHK(launch_pose_rank(fit_dev, n, k, idx_dev, nullptr, (hipStream_t)stream));
+  return SE3TN_OK;
+}
+
+int se3tn_search_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const double* poses, const uint16_t* depth, int H, int W,
+                            const double K[9], int tol_mm, int k, int32_t* idx_out, se3tn_point_fit* fit_out, void* stream) {
+  const char* who = "se3tn_search_poses_host";
+  if (int rc = pose_search_check(who, c, poses && depth && K && idx_out && fit_out, p, true, n)) return rc;
+  if (int rc = pose_score_check(who, H, W, tol_mm)) return rc;
+  if (int rc = pose_rank_check(who, n, k)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_search_poses_host: the call is synchronous, it cannot be captured");
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(K[i])) return fail(SE3TN_E_ARG, "se3tn_search_poses_host: K entry " + std::to_string(i) + " is not finite");
+  for (size_t i = 0; i < (size_t)n * 16; ++i)
+    if (!std::isfinite(poses[i]))
+      return fail(SE3TN_E_ARG, "se3tn_search_poses_host: pose " + std::to_string(i / 16) + " has an entry that is not finite");
+  const PsStage s = ps_stage(n, H, W, k);
+  if (s.bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
+    DeviceGuard dg(c->device);
+    if (int rc = begin_growth(dg)) return rc;
+    c->ps_cap = 0;
+    HIPCHK(c->ps_host.alloc(s.bytes));
+    HIPCHK(c->ps_dev.alloc(s.bytes));
+    c->ps_cap = s.bytes;
+  }
+  // the staging is laid out for THIS (n, H, W, k): the upload is one contiguous run, and so is the read-back
+  unsigned char* h = c->ps_host.get();
+  unsigned char* d = c->ps_dev.get();
+  std::memcpy(h + s.poses, poses, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
+  HIPCHK(hipMemcpyAsync(d, h, s.upload_bytes, hipMemcpyHostToDevice, st));
+  se3tn_point_fit* fit_d = reinterpret_cast<se3tn_point_fit*>(d + s.fit);
+  HIPCHK(launch_pose_score(pose_score_args(p, reinterpret_cast<const double*>(d + s.poses), reinterpret_cast<const uint16_t*>(d + s.depth),
+                                           H, W, K, tol_mm, fit_d), n, st));
+  HIPCHK(launch_pose_rank(fit_d, n, k, reinterpret_cast<int32_t*>(d + s.idx), reinterpret_cast<se3tn_point_fit*>(d + s.top_fit), st));
+  HIPCHK(hipMemcpyAsync(h + s.top_fit, d + s.top_fit, s.readback_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(fit_out, h + s.top_fit, sizeof(se3tn_point_fit) * (size_t)k);
+  std::memcpy(idx_out, h + s.idx, sizeof(int32_t) * (size_t)k);
   return SE3TN_OK;
 }
 

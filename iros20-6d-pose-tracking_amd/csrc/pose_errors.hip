@@ -18,29 +18,12 @@
 //  (c) nothing is allocated: the scratch [PE_CHUNK][tiles][2] belongs to the points handle.
 // The inner loop keeps the minimum SQUARED distance; one sqrt per query point at the end (sqrt is monotone).
 #include "pose_errors_plan.h"
+#include "pose_transform.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
 
-struct Rigid {   // rows 0-2 of a row-major 4 x 4 pose
-  double r[3][3], t[3];
-};
-
-__device__ __forceinline__ Rigid load_pose(const double* p) {
-  Rigid T;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    T.r[i][0] = p[4 * i]; T.r[i][1] = p[4 * i + 1]; T.r[i][2] = p[4 * i + 2]; T.t[i] = p[4 * i + 3];
-  }
-  return T;
-}
-
-// THE transform of both clouds: row i is ((r_i0 x + r_i1 y) + r_i2 z) + t_i, five roundings in this order (no contraction)
-__device__ __forceinline__ void transform(const Rigid& T, double x, double y, double z, double& ox, double& oy, double& oz) {
-  ox = ((T.r[0][0] * x + T.r[0][1] * y) + T.r[0][2] * z) + T.t[0];
-  oy = ((T.r[1][0] * x + T.r[1][1] * y) + T.r[1][2] * z) + T.t[1];
-  oz = ((T.r[2][0] * x + T.r[2][1] * y) + T.r[2][2] * z) + T.t[2];
-}
+// Rigid, load_pose and THE transform of both clouds (pose_transform.h: shared with pose_search.hip, one operation order)
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -226,6 +226,21 @@ struct PoseErrArgs {
 };
 hipError_t launch_pose_errors(const PoseErrArgs& a, int count, hipStream_t st);
 
+// n candidate poses against one depth frame (pose_search.hip; key, geometry and staging: pose_search_plan.h)
+struct PoseScoreArgs {
+  const double* pts;       // [P,3] model points
+  int P;
+  const double* poses;     // [n,16] row-major candidates (rows 0-2 are read)
+  const uint16_t* depth;   // [H,W] millimetres
+  int H, W;
+  double K[9];             // row-major intrinsics: [0], [2], [4], [5] are read
+  int tol;                 // millimetres
+  se3tn_point_fit* out;    // [n] records, every word stored once
+};
+hipError_t launch_pose_score(const PoseScoreArgs& a, int n, hipStream_t st);
+// the indices of the k largest keys of n records, descending, into idx; top_fit (or nullptr) receives those k records
+hipError_t launch_pose_rank(const se3tn_point_fit* fit, int n, int k, int32_t* idx, se3tn_point_fit* top_fit, hipStream_t st);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per DEVICE: a launcher remembers which device
 // ordinals it has already raised the limit on (several contexts on different GPUs in one process).
 struct PerDeviceOnce {

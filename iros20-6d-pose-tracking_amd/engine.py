@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CROP_DTYPE, FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -368,6 +368,56 @@ class Engine:
                                               C.c_void_p(add.ctypes.data), C.c_void_p(ads.ctypes.data) if adds else None, _stream_ptr()),
               "se3tn_pose_errors_host")
         return add, ads
+
+    # ---- n candidate poses against one depth frame ------------------------------------------------
+    def score_poses(self, points, poses, depth, K, tol_mm, top=None):
+        """se3tn_score_poses (+ se3tn_rank_poses): project the model `points` (ModelPoints) under each of n candidate poses into the
+        depth frame (uint16 mm [H,W]) with the camera K (3x3) and count, per pose, the points in frame / seen / within tol_mm of the
+        observed surface / behind something / seen through -- the rule of include/se3tracknet.h, every counter an integer.
+        numpy in ([n,4,4] or [n,16] poses, [H,W] depth): top=None -> a structured array (_lib.POINT_FIT_DTYPE) of n records;
+        top=k -> (idx[k] int32, records[k]): the k best candidates, best first (more inliers, then fewer seen-through points, then
+        the lower index), ONE synchronous call (se3tn_search_poses_host: one upload, two launches, one read-back).
+        cuda tensors in (float64 poses, 16-bit depth): an int32 tensor [n,8] of records (``.cpu().numpy().view(POINT_FIT_DTYPE)``), or
+        with top=k (idx[k] int32, records[k,8]) -- stream-ordered on the current stream, nothing allocated by the library."""
+        if not isinstance(points, ModelPoints) or not points._h:
+            raise Se3tnError("score_poses: points must be an open ModelPoints handle (Engine.model_points)")
+        Kh = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        Kp = Kh.ctypes.data_as(C.POINTER(C.c_double))
+        if torch.is_tensor(poses) or torch.is_tensor(depth):
+            if not (torch.is_tensor(poses) and torch.is_tensor(depth)):
+                raise Se3tnError("score_poses: poses and depth must both be tensors or both be arrays")
+            return self._score_poses_device(points, poses, depth, Kp, tol_mm, top)
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("score_poses: depth must be [H,W]")
+        n = int(p.shape[0])
+        if top is None:   # all n records: the device entry point on uploaded copies (the host entry point returns the k best only)
+            dev = "cuda:%d" % self.device
+            fit = self._score_poses_device(points, torch.from_numpy(p).to(dev), torch.from_numpy(d.view(np.int16)).to(dev), Kp, tol_mm, None)
+            return fit.cpu().numpy().view(POINT_FIT_DTYPE).reshape(n)
+        k = int(top)
+        idx = np.empty(max(k, 0), np.int32)
+        fit = np.zeros(max(k, 0), POINT_FIT_DTYPE)
+        check(self.lib.se3tn_search_poses_host(self._h, points._h, n, C.c_void_p(p.ctypes.data), C.c_void_p(d.ctypes.data), int(d.shape[0]),
+                                               int(d.shape[1]), Kp, int(tol_mm), k, C.c_void_p(idx.ctypes.data), C.c_void_p(fit.ctypes.data),
+                                               _stream_ptr()), "se3tn_search_poses_host")
+        return idx, fit
+
+    def _score_poses_device(self, points, poses, depth, Kp, tol_mm, top):
+        assert poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous() and poses.numel() % 16 == 0
+        assert depth.is_cuda and depth.element_size() == 2 and depth.dim() == 2 and depth.is_contiguous()
+        n = poses.numel() // 16
+        fit = torch.empty((n, 8), dtype=torch.int32, device=poses.device)
+        check(self.lib.se3tn_score_poses(self._h, points._h, n, C.c_void_p(poses.data_ptr()), C.c_void_p(depth.data_ptr()),
+                                         int(depth.shape[0]), int(depth.shape[1]), Kp, int(tol_mm), C.c_void_p(fit.data_ptr()), _stream_ptr()),
+              "se3tn_score_poses")
+        if top is None:
+            return fit
+        idx = torch.empty((max(int(top), 0),), dtype=torch.int32, device=poses.device)
+        check(self.lib.se3tn_rank_poses(self._h, n, C.c_void_p(fit.data_ptr()), int(top), C.c_void_p(idx.data_ptr()), _stream_ptr()),
+              "se3tn_rank_poses")
+        return idx, fit[idx.long()]
 
     def fill_depth(self, depth_mm, max_depth=2.0, extrapolate=False, blur_type="bilateral", return_metres=False):
         """Utils.py:455-514 fill_depth as predict_ros.py:38-41 applies it: uint16 millimetre frame (numpy [H,W] or a

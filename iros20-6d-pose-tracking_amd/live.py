@@ -41,12 +41,18 @@ def quaternion_from_matrix(matrix):
 class LiveTracker:
     """predict_ros.py:19-66 `TrackerRos` minus the ROS plumbing."""
 
-    def __init__(self, tracker, pose_init, max_depth=2.0, extrapolate=False, blur_type="bilateral", one_call=False):
+    def __init__(self, tracker, pose_init, max_depth=2.0, extrapolate=False, blur_type="bilateral", one_call=False, recover_below=None):
         self.tracker = tracker
         self.color = None
         self._depth = None
         self.cur_time = None
         self.A_in_cam = np.asarray(pose_init, np.float64).copy()
+        # recover_below (extension): None (default) -- not one call more than before -- or a fit ratio: a frame whose estimate scores
+        # last_fit_ratio < recover_below is searched again (Tracker.recover around the pose the frame started from, the tracked
+        # estimate among the candidates) and the recovered pose is adopted.  Needs the fit check: the ratio comes from it.
+        if recover_below is not None and not tracker.fit_check:
+            raise ValueError("LiveTracker: recover_below needs tracker.fit_check to be set (the fit ratio comes from it)")
+        self.recover_below = recover_below
         self._fill = dict(max_depth=max_depth, extrapolate=extrapolate, blur_type=blur_type)
         from .renderer import HipRenderer
         # one library call per frame needs the built-in rasteriser (False by default: not measured on the MI355X yet)
@@ -124,6 +130,10 @@ class LiveTracker:
         else:
             ob_in_cam = self.tracker.on_track(self.A_in_cam, self.color.astype(np.uint8), self._depth,
                                               gt_A_in_cam=np.eye(4), gt_B_in_cam=np.eye(4), debug=False, samples=1)
+        if self.recover_below is not None and self.tracker.last_fit_ratio is not None and self.tracker.last_fit_ratio < self.recover_below:
+            # lost: search around the pose this frame started from; only here is the filled frame fetched on the one-call route
+            rgb = np.ascontiguousarray(self.color[:, :, ::-1]) if self.one_call else self.color.astype(np.uint8)
+            ob_in_cam = self.tracker.recover(self.A_in_cam, rgb, self.depth, extra=[ob_in_cam])
         self.A_in_cam = ob_in_cam.copy()
         trans = ob_in_cam[:3, 3]
         q_wxyz = quaternion_from_matrix(ob_in_cam)

@@ -113,6 +113,7 @@ class Tracker:
         self._rot = self._out[ms * 140:ms * 152].view(torch.float32).view(ms, 3)
         self._model_points = None    # pose_errors: object_cloud on the device, uploaded at first use
         self.last_prediction = None
+        self.last_recover = None     # recover(): what the last search found (dict)
         self.last_fit_ratio = None   # fit_check set: inlier_px / model_px of the last call (float; on_track_batch: [n] array)
         self._fit_imgs = None
         # optional hipGraph replay of the ~20 dependent launches of a frame on a dedicated stream (the
@@ -130,6 +131,60 @@ class Tracker:
         if self._model_points is None:
             self._model_points = self.engine.model_points(self.object_cloud)
         return self.engine.pose_errors(self._model_points, preds, gts)
+
+    def recover(self, prev_pose, rgb, depth, trans_radius=0.05, trans_step=0.01, rot_deg=(15.0,), tol_mm=10, top=None, refine=1,
+                points=None, extra=None):
+        """Extension: look for a lost object near where it was last seen.  The reference re-initialises from an external detector
+        (predict.py:539-541); this searches the observed depth frame instead and hands the track back:
+          1. the lattice of candidates around prev_pose (recover.pose_lattice; `extra`: a list of poses appended after it) is scored
+             against `depth` (HxW uint16 mm) in ONE device call with its `top` best picked (Engine.score_poses);
+          2. refine >= 1: the top poses go through on_track_batch(top_poses, [rgb] * k, [depth] * k), `refine` times -- the network
+             pulls a nearby hypothesis in;
+          3. [refined..., unrefined...] are scored once more and the pose with the largest key wins (recover.pose_key: more
+             inliers, then fewer seen-through points, then the lower index -- ties prefer the refined pose).
+        So the result never scores below the lattice's best.  refine=0 returns the top lattice candidate with no network call.
+        points: model points ([P,3], an object with .points, or a ModelPoints handle); default ``object_cloud``.  top defaults to
+        min(8, engine.max_batch).  ``last_recover`` keeps n, top_idx, top_fit, refined, final_fit, chosen and inlier_frac
+        (= inlier_pts / points of the returned pose).  With fit_check set, last_fit_ratio is whatever on_track_batch left."""
+        from .engine import ModelPoints
+        from .recover import pose_key, pose_lattice
+        if points is None:
+            if self.object_cloud is None:
+                raise ValueError("recover: this tracker has no object_cloud (no model_path was given) and no points were passed")
+            if self._model_points is None:
+                self._model_points = self.engine.model_points(self.object_cloud)
+            handle, own = self._model_points, False
+        elif isinstance(points, ModelPoints):
+            handle, own = points, False
+        else:
+            handle, own = self.engine.model_points(points), True
+        try:
+            k = min(8, self.engine.max_batch) if top is None else int(top)
+            cands = pose_lattice(prev_pose, trans_radius, trans_step, rot_deg)
+            if extra is not None and len(extra):
+                cands = np.concatenate([cands, np.asarray(extra, np.float64).reshape(-1, 4, 4)])
+            dep = np.ascontiguousarray(depth, dtype=np.uint16)
+            top_idx, top_fit = self.engine.score_poses(handle, cands, dep, self.K, tol_mm, top=k)
+            unrefined = cands[top_idx]
+            info = dict(n=len(cands), top_idx=top_idx, top_fit=top_fit, refined=None)
+            if int(refine) < 1:
+                info.update(final_fit=top_fit[:1].copy(), chosen=0, inlier_frac=float(top_fit["inlier_pts"][0]) / float(top_fit["points"][0]))
+                self.last_recover = info
+                return unrefined[0].copy()
+            refined = unrefined
+            for _ in range(int(refine)):
+                refined = np.asarray(self.on_track_batch(list(refined), [rgb] * k, [dep] * k), np.float64)
+            final = np.concatenate([refined, unrefined])
+            final_fit = self.engine.score_poses(handle, final, dep, self.K, tol_mm)
+            keys = pose_key(final_fit)
+            chosen = int(np.argmax(keys))             # keys are unique: the lower index wins a tie, and the refined poses come first
+            info.update(refined=refined, final_fit=final_fit, chosen=chosen,
+                        inlier_frac=float(final_fit["inlier_pts"][chosen]) / float(final_fit["points"][chosen]))
+            self.last_recover = info
+            return final[chosen].copy()
+        finally:
+            if own:
+                handle.close()
 
     @property
     def fit_check(self):
@@ -507,6 +562,7 @@ class MultiTracker:
         self._depthA = torch.empty((self.n, 176, 176), dtype=torch.int16, device=self._dev)
         self._C = C
         self.last_prediction = None
+        self.last_recover = None     # recover(): what the last search found (dict)
         self.last_fit_ratio = None   # fit_check set: inlier_px / model_px per object of the last call ([n] array)
         self._pred_rgb = self._pred_depth = None
         self.frame_cnt = 0
