@@ -556,6 +556,57 @@ int se3tn_rank_poses(se3tn_ctx* ctx, int n, const se3tn_point_fit* fit_dev, int 
 int se3tn_search_poses_host(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses, const uint16_t* depth, int H, int W,
                             const double K[9], int tol_mm, int k, int32_t* idx_out, se3tn_point_fit* fit_out, void* stream);
 
+/* ---- finding an object with no pose to start from: a product lattice of poses, counting only the points that face the camera --- */
+/* The reference takes its first pose from a file, from ground truth or from PoseCNN (predict.py:539-541); the search above is local
+ * to a pose the track once had.  Two things keep it local.  Its candidates travel as n x 16 doubles although a lattice is a product
+ * of a few rotations and a grid of translations; and its count includes the far side of the object, so inlier_pts / points has no
+ * fixed meaning and a wide search prefers poses that lay the model flat into a large plane.  Here the FACTORS travel -- n_rot
+ * rotations (row-major 3x3) and n_trans translations, candidate i = r * n_trans + t being the pose [R_r | t_t] -- and a points handle
+ * may carry one normal per point, so that only the points whose normal faces the camera are counted.
+ * For rotation R (rows R0, R1, R2), translation t, model point x and its normal n, all in float64, in this order, without fused
+ * multiply-add:
+ *     q = (R0 x + R1 y) + R2 z  per row,   c = q + t          the bits of the transform of se3tn_score_poses for the composed pose
+ *     with facing = 1:
+ *         n' = (R0 nx + R1 ny) + R2 nz  per row
+ *         f  = (n'x c.x + n'y c.y) + n'z c.z
+ *         facing      f < 0                                     false for NaN and for f == 0, the grazing point
+ *         a point that is not facing enters no counter, `points` included
+ *     in front, uf, vf, in frame, d, m, seen, inlier, front, behind                exactly as se3tn_score_poses states them
+ * With facing = 0 every word of record (r, t) equals the word se3tn_score_poses writes for the composed pose.  With facing = 1 the
+ * record's `points` word is the number of facing points, so inlier_pts / points is the share of the visible surface the sensor
+ * confirms; in_frame_pts <= points and seen = inlier + front + behind hold as before, _reserved stays 0.  Unit length of the normals
+ * is not required: only the sign of f is used.
+ * Guarantees:
+ *   (a) every count is an integer sum: a record depends on (points, normals, R_r, t_t, depth, K, tol_mm, facing) only -- not on the
+ *       grid it travels in, on its place in it, on the tiling or on the run -- and equals the same rule evaluated in IEEE float64
+ *       anywhere else (tests/pose_grid_oracle.py);
+ *   (b) a rotation or a translation that is not finite harms only its own candidates (with a NaN in it, in_frame_pts = 0);
+ *   (c) the device-pointer entry point allocates nothing and uses no atomics on global memory; it is stream-ordered and capturable.
+ * Cost: one workgroup per (rotation, 16 translations) rotates the model once into LDS, 1,024 points at a time, and adds each
+ * translation: n_rot * n_trans * P projections as above; 72 bytes per rotation and 24 per translation travel instead of 128 per pose. */
+/* nxyz: HOST float64 [P,3], one normal per point of the handle (copied and uploaded once); NULL removes the normals.  Synchronous.
+ * SE3TN_E_ARG: a NULL handle, a component that is not finite.  se3tn_points_create, se3tn_pose_errors*, se3tn_score_poses and
+ * se3tn_search_poses_host do not read the normals. */
+int se3tn_points_set_normals(se3tn_points* points, const double* nxyz);
+int se3tn_points_has_normals(const se3tn_points* points);   /* 1 | 0; -1 for NULL */
+/* rots_dev: device float64 [n_rot,9]; trans_dev: device float64 [n_trans,3]; depth_dev, K, tol_mm, fit_dev (n_rot * n_trans records,
+ * candidate order) and the stream as se3tn_score_poses.  The factors are not inspected.  SE3TN_E_ARG: a NULL pointer, n_rot or
+ * n_trans < 1, n_rot * n_trans > SE3TN_POSE_SEARCH_MAX_POSES (so se3tn_rank_poses serves the records unchanged), tol_mm outside
+ * [1, 65535], H or W < 1, facing neither 0 nor 1, a host-only context, points of another device.  SE3TN_E_STATE: facing = 1 and the
+ * handle has no normals. */
+int se3tn_score_pose_grid(se3tn_ctx* ctx, const se3tn_points* points, int n_rot, const double* rots_dev, int n_trans,
+                          const double* trans_dev, const uint16_t* depth_dev, int H, int W, const double K[9], int tol_mm, int facing,
+                          se3tn_point_fit* fit_dev, void* stream);
+/* The same from HOST memory with the k best picked (se3tn_rank_poses' order): rots float64 [n_rot,9], trans float64 [n_trans,3], depth
+ * uint16 [H,W]; idx_out int32 [k] and fit_out [k] receive the k best candidates' indices (r * n_trans + t) and records, best first.
+ * The staging is [rots | trans | depth | pad | fit n | top_fit k | idx k]: one upload, the two launches, one read-back.  SYNCHRONOUS
+ * on `stream`, refused inside a stream capture (SE3TN_E_STATE); the pinned staging and its device mirror (shared with
+ * se3tn_search_poses_host) grow on a first or larger call.  SE3TN_E_ARG as above, k outside [1, min(n_rot * n_trans,
+ * SE3TN_POSE_RANK_MAX)], and a rotation, translation or K entry that is not finite. */
+int se3tn_search_pose_grid_host(se3tn_ctx* ctx, const se3tn_points* points, int n_rot, const double* rots, int n_trans,
+                                const double* trans, const uint16_t* depth, int H, int W, const double K[9], int tol_mm, int facing,
+                                int k, int32_t* idx_out, se3tn_point_fit* fit_out, void* stream);
+
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K
  * row-major 3x3, width in mm; out_vu[8] = 4 x (v,u) int32, np.round (half-to-even). */

@@ -15,6 +15,7 @@
 
 #include "hip_buffers.h"
 #include "pose_errors_plan.h"
+#include "pose_grid_plan.h"
 #include "pose_search_plan.h"
 #include "se3tn_internal.h"
 #include "tex_pyramid.h"
@@ -140,7 +141,8 @@ struct se3tn_ctx {
   PinnedBuf<se3tn_fit> fit_host;
   // se3tn_pose_errors_host: pinned staging [pred | gt | add | adds] (pose_errors_plan.h: pe_stage_*) for pe_cap pairs and its device mirror
   PinnedBuf<double> pe_host; DeviceBuf<double> pe_dev; int pe_cap = 0;
-  // se3tn_search_poses_host: pinned staging (pose_search_plan.h: PsStage) of ps_cap bytes and its device mirror
+  // se3tn_search_poses_host / se3tn_search_pose_grid_host (both synchronous): pinned staging of ps_cap bytes, laid out per call
+  // (pose_search_plan.h: PsStage, pose_grid_plan.h: PgStage), and its device mirror
   PinnedBuf<unsigned char> ps_host; DeviceBuf<unsigned char> ps_dev; size_t ps_cap = 0;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive before the next one
   DeviceBuf<int> tail_arrive;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
@@ -202,6 +204,7 @@ struct se3tn_points {
   int device = -1, P = 0;
   DeviceBuf<double> xyz;    // [P,3]
   DeviceBuf<double> part;   // [PE_CHUNK][tiles][2] (pose_errors_plan.h)
+  DeviceBuf<double> nrm;    // [P,3] normals (se3tn_points_set_normals), or empty: read by se3tn_score_pose_grid with facing only
 };
 
 // Init-time entry points that allocate or launch (plane derivation, workspace growth) run on the CONTEXT's device whatever device the
@@ -1568,6 +1571,22 @@ int se3tn_points_create(se3tn_ctx* c, const double* xyz, int P, se3tn_points** o
 void se3tn_points_destroy(se3tn_points* p) { delete p; }
 int se3tn_points_count(const se3tn_points* p) { return p ? p->P : -1; }
 
+int se3tn_points_set_normals(se3tn_points* p, const double* nxyz) {
+  if (!p) return fail(SE3TN_E_ARG, "se3tn_points_set_normals: NULL points");
+  if (!nxyz) { p->nrm.reset(); return SE3TN_OK; }
+  for (size_t i = 0; i < (size_t)3 * p->P; ++i)
+    if (!std::isfinite(nxyz[i])) return fail(SE3TN_E_ARG, "se3tn_points_set_normals: component " + std::to_string(i) + " is not finite");
+  DeviceGuard dg(p->device);
+  if (dg.err != hipSuccess) return hipfail(dg.err, "hipSetDevice");
+  DeviceBuf<double> fresh;   // the handle keeps what it had unless the upload succeeds
+  hipError_t e = fresh.alloc((size_t)3 * p->P);
+  if (e == hipSuccess) e = hipMemcpy(fresh.get(), nxyz, sizeof(double) * 3 * (size_t)p->P, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hipfail(e, "se3tn_points_set_normals");
+  p->nrm = std::move(fresh);
+  return SE3TN_OK;
+}
+int se3tn_points_has_normals(const se3tn_points* p) { return p ? (p->nrm ? 1 : 0) : -1; }
+
 // the chunks of one call, enqueued on st (both entry points)
 static int pose_errors_enqueue(const se3tn_points* p, int n, const double* pred, const double* gt, double* add, double* adds, hipStream_t st) {
   for (int ch = 0, nch = pe_chunks(n); ch < nch; ++ch) {
@@ -1713,6 +1732,86 @@ int se3tn_search_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const do
   se3tn_point_fit* fit_d = reinterpret_cast<se3tn_point_fit*>(d + s.fit);
   HIPCHK(launch_pose_score(pose_score_args(p, reinterpret_cast<const double*>(d + s.poses), reinterpret_cast<const uint16_t*>(d + s.depth),
                                            H, W, K, tol_mm, fit_d), n, st));
+  HIPCHK(launch_pose_rank(fit_d, n, k, reinterpret_cast<int32_t*>(d + s.idx), reinterpret_cast<se3tn_point_fit*>(d + s.top_fit), st));
+  HIPCHK(hipMemcpyAsync(h + s.top_fit, d + s.top_fit, s.readback_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(fit_out, h + s.top_fit, sizeof(se3tn_point_fit) * (size_t)k);
+  std::memcpy(idx_out, h + s.idx, sizeof(int32_t) * (size_t)k);
+  return SE3TN_OK;
+}
+
+// ---- n_rot x n_trans candidate poses [R_r | t_t] against one depth frame, the best k ----------------------------------------------
+// NULL pointers first, then the numbers, then the context and the handle (which is not read before the context is known to have a
+// device): every refusal has its own message, on a host-only context too
+static int pose_grid_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, int n_rot, int n_trans, int H, int W,
+                           int tol_mm, int facing) {
+  if (!c || !ok_ptrs || !p) return fail(SE3TN_E_ARG, std::string(who) + ": NULL argument");
+  if (n_rot < 1 || n_trans < 1 || (long long)n_rot * (long long)n_trans > (long long)PS_MAX_POSES)
+    return fail(SE3TN_E_ARG, std::string(who) + ": n_rot = " + std::to_string(n_rot) + ", n_trans = " + std::to_string(n_trans) +
+                                 ": both must be >= 1 and their product <= SE3TN_POSE_SEARCH_MAX_POSES = " + std::to_string(PS_MAX_POSES));
+  if (int rc = pose_score_check(who, H, W, tol_mm)) return rc;
+  if (facing != 0 && facing != 1) return fail(SE3TN_E_ARG, std::string(who) + ": facing = " + std::to_string(facing) + " is neither 0 nor 1");
+  if (c->device < 0) return fail(SE3TN_E_ARG, std::string(who) + ": host-only context (device = -1) has no device to search on");
+  if (p->device != c->device) return fail(SE3TN_E_ARG, std::string(who) + ": the points live on another device than the context");
+  if (facing && !p->nrm)
+    return fail(SE3TN_E_STATE, std::string(who) + ": facing = 1 but the points handle has no normals (se3tn_points_set_normals)");
+  return SE3TN_OK;
+}
+static PoseGridArgs pose_grid_args(const se3tn_points* p, const double* rots, int n_trans, const double* trans, const uint16_t* depth, int H,
+                                   int W, const double K[9], int tol_mm, int facing, se3tn_point_fit* out) {
+  PoseGridArgs a;
+  a.pts = p->xyz.get(); a.nrm = p->nrm.get(); a.P = p->P; a.rots = rots; a.trans = trans; a.n_trans = n_trans;
+  a.depth = depth; a.H = H; a.W = W; a.tol = tol_mm; a.facing = facing; a.out = out;
+  for (int i = 0; i < 9; ++i) a.K[i] = K[i];
+  return a;
+}
+
+int se3tn_score_pose_grid(se3tn_ctx* c, const se3tn_points* p, int n_rot, const double* rots_dev, int n_trans, const double* trans_dev,
+                          const uint16_t* depth_dev, int H, int W, const double K[9], int tol_mm, int facing, se3tn_point_fit* fit_dev,
+                          void* stream) {
+  const char* who = "se3tn_score_pose_grid";
+  if (int rc = pose_grid_check(who, c, rots_dev && trans_dev && depth_dev && K && fit_dev, p, n_rot, n_trans, H, W, tol_mm, facing)) return rc;
+  HIPCHK(launch_pose_grid(pose_grid_args(p, rots_dev, n_trans, trans_dev, depth_dev, H, W, K, tol_mm, facing, fit_dev), n_rot,
+                          (hipStream_t)stream));
+  return SE3TN_OK;
+}
+
+int se3tn_search_pose_grid_host(se3tn_ctx* c, const se3tn_points* p, int n_rot, const double* rots, int n_trans, const double* trans,
+                                const uint16_t* depth, int H, int W, const double K[9], int tol_mm, int facing, int k, int32_t* idx_out,
+                                se3tn_point_fit* fit_out, void* stream) {
+  const char* who = "se3tn_search_pose_grid_host";
+  if (int rc = pose_grid_check(who, c, rots && trans && depth && K && idx_out && fit_out, p, n_rot, n_trans, H, W, tol_mm, facing)) return rc;
+  const int n = n_rot * n_trans;
+  if (int rc = pose_rank_check(who, n, k)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_search_pose_grid_host: the call is synchronous, it cannot be captured");
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(K[i])) return fail(SE3TN_E_ARG, "se3tn_search_pose_grid_host: K entry " + std::to_string(i) + " is not finite");
+  for (size_t i = 0; i < (size_t)n_rot * 9; ++i)
+    if (!std::isfinite(rots[i]))
+      return fail(SE3TN_E_ARG, "se3tn_search_pose_grid_host: rotation " + std::to_string(i / 9) + " has an entry that is not finite");
+  for (size_t i = 0; i < (size_t)n_trans * 3; ++i)
+    if (!std::isfinite(trans[i]))
+      return fail(SE3TN_E_ARG, "se3tn_search_pose_grid_host: translation " + std::to_string(i / 3) + " has an entry that is not finite");
+  const PgStage s = pg_stage(n_rot, n_trans, H, W, k);
+  if (s.bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
+    DeviceGuard dg(c->device);
+    if (int rc = begin_growth(dg)) return rc;
+    c->ps_cap = 0;
+    HIPCHK(c->ps_host.alloc(s.bytes));
+    HIPCHK(c->ps_dev.alloc(s.bytes));
+    c->ps_cap = s.bytes;
+  }
+  // the staging is laid out for THIS (n_rot, n_trans, H, W, k): the upload is one contiguous run, and so is the read-back
+  unsigned char* h = c->ps_host.get();
+  unsigned char* d = c->ps_dev.get();
+  std::memcpy(h + s.rots, rots, sizeof(double) * 9 * (size_t)n_rot);
+  std::memcpy(h + s.trans, trans, sizeof(double) * 3 * (size_t)n_trans);
+  std::memcpy(h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
+  HIPCHK(hipMemcpyAsync(d, h, s.upload_bytes, hipMemcpyHostToDevice, st));
+  se3tn_point_fit* fit_d = reinterpret_cast<se3tn_point_fit*>(d + s.fit);
+  HIPCHK(launch_pose_grid(pose_grid_args(p, reinterpret_cast<const double*>(d + s.rots), n_trans, reinterpret_cast<const double*>(d + s.trans),
+                                         reinterpret_cast<const uint16_t*>(d + s.depth), H, W, K, tol_mm, facing, fit_d), n_rot, st));
   HIPCHK(launch_pose_rank(fit_d, n, k, reinterpret_cast<int32_t*>(d + s.idx), reinterpret_cast<se3tn_point_fit*>(d + s.top_fit), st));
   HIPCHK(hipMemcpyAsync(h + s.top_fit, d + s.top_fit, s.readback_bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -1,0 +1,73 @@
+// Tiling, index arithmetic, LDS layout and staging layout of the product-lattice pose search (pose_grid.hip, api.cpp:
+// se3tn_score_pose_grid, se3tn_search_pose_grid_host).  Host and device; no HIP header is needed to read it
+// (tests/c_abi/pose_grid_plan_check.cpp runs it on the host under sanitizers).
+//
+// Candidate i = r * n_trans + t is the pose [R_r | t_t].  One workgroup of PG_THREADS threads scores one rotation against one tile
+// of PG_TT translations: workgroup b of the one-dimensional grid has rotation b / tiles and translation tile b % tiles, tiles =
+// ceil(n_trans / PG_TT).  (One dimension, not (tiles, n_rot): n_rot may reach 2^20 and a grid's y extent ends at 65,535; the product
+// n_rot * tiles <= n_rot * n_trans <= 2^20 always fits x.)  The workgroup walks the model in tiles of PG_PT points: all threads
+// rotate a tile into LDS, then wave w takes the translations w, w + PG_WAVES, ... of its tile and its lanes the points lane,
+// lane + 64, ... of the point tile.  A translation belongs to ONE wave, so its row of counters in LDS has one writer.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pose_search_plan.h"
+
+namespace se3tn {
+
+constexpr int PG_THREADS = 256;
+constexpr int PG_WAVES = PG_THREADS / 64;
+constexpr int PG_PT = 1024;        // model points rotated into LDS at a time
+constexpr int PG_TT = 16;          // translations per workgroup: PG_TT / PG_WAVES per wave
+constexpr int PG_ROW_WORDS = 6;    // counters of one translation: points (facing) | in frame, seen, inlier, front, behind
+static_assert(PG_TT % PG_WAVES == 0, "every wave walks the same number of translations of a full tile");
+static_assert(PG_TT * PG_ROW_WORDS <= PG_THREADS && PG_TT * PS_FIT_WORDS <= PG_THREADS, "one thread per counter / record word");
+
+SE3TN_PS_HD inline int pg_tiles(int n_trans) { return (n_trans + PG_TT - 1) / PG_TT; }           // translation tiles per rotation
+SE3TN_PS_HD inline int pg_point_tiles(int P) { return (P + PG_PT - 1) / PG_PT; }
+SE3TN_PS_HD inline long long pg_grid(int n_rot, int n_trans) { return (long long)n_rot * pg_tiles(n_trans); }
+// workgroup b: its rotation, the first translation of its tile and how many translations the tile holds
+SE3TN_PS_HD inline int pg_rot_of(int b, int n_trans) { return b / pg_tiles(n_trans); }
+SE3TN_PS_HD inline int pg_trans0_of(int b, int n_trans) { return (b % pg_tiles(n_trans)) * PG_TT; }
+SE3TN_PS_HD inline int pg_trans_count(int t0, int n_trans) { return n_trans - t0 < PG_TT ? n_trans - t0 : PG_TT; }
+SE3TN_PS_HD inline int pg_point_count(int p0, int P) { return P - p0 < PG_PT ? P - p0 : PG_PT; }
+// the wave that owns translation k of a tile (k < PG_TT)
+SE3TN_PS_HD inline int pg_wave_of(int k) { return k % PG_WAVES; }
+SE3TN_PS_HD inline size_t pg_candidate(int r, int t, int n_trans) { return (size_t)r * (size_t)n_trans + (size_t)t; }
+
+// LDS of a workgroup, in BYTES: [planes x PG_PT doubles | PG_TT rows of PG_ROW_WORDS uint32].  planes = 3 (qx | qy | qz of the
+// rotated points, each plane contiguous: lane l reads double l of a run of 64, no bank conflict) or 6 with `facing` (the rotated
+// normals n'x | n'y | n'z behind them).  24,960 / 49,536 bytes: six / three workgroups share a CU's 160 KiB.
+SE3TN_PS_HD inline int pg_planes(int facing) { return facing ? 6 : 3; }
+SE3TN_PS_HD inline size_t pg_lds_rows(int facing) { return (size_t)pg_planes(facing) * PG_PT * sizeof(double); }   // byte offset of the rows
+SE3TN_PS_HD inline size_t pg_lds_bytes(int facing) { return pg_lds_rows(facing) + (size_t)PG_TT * PG_ROW_WORDS * sizeof(uint32_t); }
+SE3TN_PS_HD inline size_t pg_lds_plane(int plane) { return (size_t)plane * PG_PT * sizeof(double); }               // byte offset of a plane
+SE3TN_PS_HD inline size_t pg_lds_row(int facing, int k) { return pg_lds_rows(facing) + (size_t)k * PG_ROW_WORDS * sizeof(uint32_t); }
+
+// Staging of se3tn_search_pose_grid_host, in BYTES, pinned host and device mirror alike:
+//   [rots n_rot x 9 doubles | trans n_trans x 3 doubles | depth H x W uint16 | pad to 8 | fit n records | top_fit k records |
+//    idx k int32 | pad to 8],  n = n_rot * n_trans
+// One upload covers [0, upload_bytes): the factors and the frame.  One read-back covers [top_fit, top_fit + k x 36).
+struct PgStage {
+  size_t rots, trans, depth, fit, top_fit, idx;   // byte offsets
+  size_t upload_bytes;                            // from 0
+  size_t readback_bytes;                          // from top_fit
+  size_t bytes;                                   // the whole buffer
+};
+SE3TN_PS_HD inline PgStage pg_stage(int n_rot, int n_trans, int H, int W, int k) {
+  PgStage s;
+  const size_t n = (size_t)n_rot * (size_t)n_trans;
+  s.rots = 0;
+  s.trans = (size_t)n_rot * 9 * sizeof(double);
+  s.depth = s.trans + (size_t)n_trans * 3 * sizeof(double);
+  s.upload_bytes = s.depth + (size_t)H * (size_t)W * sizeof(uint16_t);
+  s.fit = ps_align8(s.upload_bytes);
+  s.top_fit = s.fit + n * sizeof(se3tn_point_fit);
+  s.idx = s.top_fit + (size_t)k * sizeof(se3tn_point_fit);
+  s.readback_bytes = (size_t)k * (sizeof(se3tn_point_fit) + sizeof(int32_t));
+  s.bytes = ps_align8(s.idx + (size_t)k * sizeof(int32_t));
+  return s;
+}
+
+}  // namespace se3tn

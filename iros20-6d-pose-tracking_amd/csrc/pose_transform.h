@@ -1,6 +1,7 @@
 // THE rigid transform of a model point, shared by every float64 kernel that promises bits (pose_errors.hip, pose_search.hip): one
 // function, one operation order.  A file that includes this is compiled with -ffp-contract=off (csrc/Makefile): a fused multiply-add
-// formed in one place and not in another would give one point two sets of bits.
+// formed in one place and not in another would give one point two sets of bits.  (pose_grid.hip states the same five roundings cut
+// after the third: the rotated part once per rotation, the translation added per candidate.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -241,6 +241,23 @@ hipError_t launch_pose_score(const PoseScoreArgs& a, int n, hipStream_t st);
 // the indices of the k largest keys of n records, descending, into idx; top_fit (or nullptr) receives those k records
 hipError_t launch_pose_rank(const se3tn_point_fit* fit, int n, int k, int32_t* idx, se3tn_point_fit* top_fit, hipStream_t st);
 
+// n_rot x n_trans candidate poses [R_r | t_t] against one depth frame (pose_grid.hip; tiling, LDS and staging: pose_grid_plan.h)
+struct PoseGridArgs {
+  const double* pts;       // [P,3] model points
+  const double* nrm;       // [P,3] model normals (read with facing only)
+  int P;
+  const double* rots;      // [n_rot,9] row-major 3x3
+  const double* trans;     // [n_trans,3]
+  int n_trans;
+  const uint16_t* depth;   // [H,W] millimetres
+  int H, W;
+  double K[9];             // row-major intrinsics: [0], [2], [4], [5] are read
+  int tol;                 // millimetres
+  int facing;              // 0 | 1
+  se3tn_point_fit* out;    // [n_rot * n_trans] records, every word stored once
+};
+hipError_t launch_pose_grid(const PoseGridArgs& a, int n_rot, hipStream_t st);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per DEVICE: a launcher remembers which device
 // ordinals it has already raised the limit on (several contexts on different GPUs in one process).
 struct PerDeviceOnce {

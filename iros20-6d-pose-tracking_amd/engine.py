@@ -34,16 +34,29 @@ def pack_crops(rgb, depth, windows, z_offset_mm, stats):
 
 class ModelPoints:
     """se3tn_points: the model points of Engine.pose_errors on the device (uploaded once) with the scratch of one chunk of pairs.
-    ``points`` keeps the host copy (float64 [P,3]), so the handle also serves the CPU evaluators of metrics.py."""
+    ``points`` keeps the host copy (float64 [P,3]), so the handle also serves the CPU evaluators of metrics.py.  ``normals``
+    (optional float64 [P,3], one per point, any length) are what Engine.score_pose_grid(facing=True) reads
+    (se3tn_points_set_normals); ``.normals`` keeps the host copy, or None."""
 
-    def __init__(self, engine, pts):
+    def __init__(self, engine, pts, normals=None):
         self.points = np.ascontiguousarray(np.asarray(pts.points if hasattr(pts, "points") else pts, np.float64).reshape(-1, 3))
+        self.normals = None
         self.engine = engine
         self._h = None
         h = C.c_void_p()
         check(engine.lib.se3tn_points_create(engine._h, C.c_void_p(self.points.ctypes.data), int(self.points.shape[0]), C.byref(h)),
               "se3tn_points_create")
         self._h = h
+        if normals is not None:
+            nrm = np.ascontiguousarray(np.asarray(normals, np.float64).reshape(-1, 3))
+            if nrm.shape != self.points.shape:
+                self.close()
+                raise ValueError("ModelPoints: %d normals for %d points" % (nrm.shape[0], self.points.shape[0]))
+            rc = engine.lib.se3tn_points_set_normals(self._h, C.c_void_p(nrm.ctypes.data))
+            if rc != 0:
+                self.close()
+                check(rc, "se3tn_points_set_normals")
+            self.normals = nrm
 
     def __len__(self):
         return int(self.points.shape[0])
@@ -333,9 +346,10 @@ class Engine:
         return rgb, dep
 
     # ---- ADD / ADD-S of n pose pairs -------------------------------------------------------------
-    def model_points(self, pts):
-        """Upload model points (float64 [P,3] metres, or an object with ``.points``) for pose_errors: a ModelPoints handle."""
-        return ModelPoints(self, pts)
+    def model_points(self, pts, normals=None):
+        """Upload model points (float64 [P,3] metres, or an object with ``.points``) for pose_errors: a ModelPoints handle.
+        normals (optional float64 [P,3]): one per point, for score_pose_grid(facing=True)."""
+        return ModelPoints(self, pts, normals)
 
     def pose_errors(self, points, preds, gts, adds=True):
         """se3tn_pose_errors: ADD and ADD-S (Utils.py:72-98) of n (pred, gt) pose pairs against the model `points` (ModelPoints) in one
@@ -415,6 +429,61 @@ class Engine:
         if top is None:
             return fit
         idx = torch.empty((max(int(top), 0),), dtype=torch.int32, device=poses.device)
+        check(self.lib.se3tn_rank_poses(self._h, n, C.c_void_p(fit.data_ptr()), int(top), C.c_void_p(idx.data_ptr()), _stream_ptr()),
+              "se3tn_rank_poses")
+        return idx, fit[idx.long()]
+
+    def score_pose_grid(self, points, rots, trans, depth, K, tol_mm, facing=False, top=None):
+        """se3tn_score_pose_grid (+ se3tn_rank_poses): the n_rot x n_trans candidates [R_r | t_t] (candidate r * n_trans + t) of the
+        rotations `rots` ([n_rot,3,3] or [n_rot,9]) and translations `trans` ([n_trans,3]) scored as score_poses scores composed
+        poses, without materialising them.  facing=True counts only the points whose normal faces the camera (the handle must carry
+        normals: Engine.model_points(pts, normals)); a record's ``points`` is then the number of facing points.  facing=False gives
+        the words of score_poses on the composed poses.  Inputs and return values as score_poses: numpy in -> a structured array of
+        n_rot * n_trans records, or with top=k (idx[k] int32, records[k]) from ONE synchronous call (se3tn_search_pose_grid_host);
+        cuda tensors in (float64 rots / trans, 16-bit depth) -> int32 tensors, stream-ordered, nothing allocated by the library."""
+        if not isinstance(points, ModelPoints) or not points._h:
+            raise Se3tnError("score_pose_grid: points must be an open ModelPoints handle (Engine.model_points)")
+        Kh = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        Kp = Kh.ctypes.data_as(C.POINTER(C.c_double))
+        fc = 1 if facing else 0
+        tensors = [torch.is_tensor(x) for x in (rots, trans, depth)]
+        if any(tensors):
+            if not all(tensors):
+                raise Se3tnError("score_pose_grid: rots, trans and depth must all be tensors or all be arrays")
+            return self._score_pose_grid_device(points, rots, trans, depth, Kp, tol_mm, fc, top)
+        r = np.ascontiguousarray(np.asarray(rots, np.float64).reshape(-1, 9))
+        t = np.ascontiguousarray(np.asarray(trans, np.float64).reshape(-1, 3))
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("score_pose_grid: depth must be [H,W]")
+        n_rot, n_trans = int(r.shape[0]), int(t.shape[0])
+        if top is None:   # all records: the device entry point on uploaded copies (the host entry point returns the k best only)
+            dev = "cuda:%d" % self.device
+            fit = self._score_pose_grid_device(points, torch.from_numpy(r).to(dev), torch.from_numpy(t).to(dev),
+                                               torch.from_numpy(d.view(np.int16)).to(dev), Kp, tol_mm, fc, None)
+            return fit.cpu().numpy().view(POINT_FIT_DTYPE).reshape(n_rot * n_trans)
+        k = int(top)
+        idx = np.empty(max(k, 0), np.int32)
+        fit = np.zeros(max(k, 0), POINT_FIT_DTYPE)
+        check(self.lib.se3tn_search_pose_grid_host(self._h, points._h, n_rot, C.c_void_p(r.ctypes.data), n_trans, C.c_void_p(t.ctypes.data),
+                                                   C.c_void_p(d.ctypes.data), int(d.shape[0]), int(d.shape[1]), Kp, int(tol_mm), fc, k,
+                                                   C.c_void_p(idx.ctypes.data), C.c_void_p(fit.ctypes.data), _stream_ptr()),
+              "se3tn_search_pose_grid_host")
+        return idx, fit
+
+    def _score_pose_grid_device(self, points, rots, trans, depth, Kp, tol_mm, facing, top):
+        assert rots.is_cuda and rots.dtype == torch.float64 and rots.is_contiguous() and rots.numel() % 9 == 0
+        assert trans.is_cuda and trans.dtype == torch.float64 and trans.is_contiguous() and trans.numel() % 3 == 0
+        assert depth.is_cuda and depth.element_size() == 2 and depth.dim() == 2 and depth.is_contiguous()
+        n_rot, n_trans = rots.numel() // 9, trans.numel() // 3
+        n = n_rot * n_trans
+        fit = torch.empty((n, 8), dtype=torch.int32, device=rots.device)
+        check(self.lib.se3tn_score_pose_grid(self._h, points._h, n_rot, C.c_void_p(rots.data_ptr()), n_trans, C.c_void_p(trans.data_ptr()),
+                                             C.c_void_p(depth.data_ptr()), int(depth.shape[0]), int(depth.shape[1]), Kp, int(tol_mm),
+                                             int(facing), C.c_void_p(fit.data_ptr()), _stream_ptr()), "se3tn_score_pose_grid")
+        if top is None:
+            return fit
+        idx = torch.empty((max(int(top), 0),), dtype=torch.int32, device=rots.device)
         check(self.lib.se3tn_rank_poses(self._h, n, C.c_void_p(fit.data_ptr()), int(top), C.c_void_p(idx.data_ptr()), _stream_ptr()),
               "se3tn_rank_poses")
         return idx, fit[idx.long()]

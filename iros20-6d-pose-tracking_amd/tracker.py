@@ -49,9 +49,11 @@ class Tracker:
         self.dataset_info = dataset_info
         self.image_size = (dataset_info['resolution'], dataset_info['resolution'])
         self.object_cloud = None
+        self._normals = None         # object_normals: (model_path, vertices) until first read, then the array or None
         if model_path is not None:
             pts = U.load_model_points(model_path)
             self.object_cloud = U.PointCloud(U.voxel_down_sample(pts, 0.005))
+            self._normals = (model_path, pts)
         if 'object_width' not in dataset_info:
             if self.object_cloud is None:
                 raise ValueError("dataset_info has no 'object_width' and no model_path was given")
@@ -114,6 +116,8 @@ class Tracker:
         self._model_points = None    # pose_errors: object_cloud on the device, uploaded at first use
         self.last_prediction = None
         self.last_recover = None     # recover(): what the last search found (dict)
+        self.last_acquire = None     # acquire(): every hypothesis of the last search and what became of it (dict)
+        self._facing_points = None   # recover(facing=True) / acquire: object_cloud with object_normals on the device, at first use
         self.last_fit_ratio = None   # fit_check set: inlier_px / model_px of the last call (float; on_track_batch: [n] array)
         self._fit_imgs = None
         # optional hipGraph replay of the ~20 dependent launches of a frame on a dedicated stream (the
@@ -133,7 +137,7 @@ class Tracker:
         return self.engine.pose_errors(self._model_points, preds, gts)
 
     def recover(self, prev_pose, rgb, depth, trans_radius=0.05, trans_step=0.01, rot_deg=(15.0,), tol_mm=10, top=None, refine=1,
-                points=None, extra=None):
+                points=None, extra=None, facing=False):
         """Extension: look for a lost object near where it was last seen.  The reference re-initialises from an external detector
         (predict.py:539-541); this searches the observed depth frame instead and hands the track back:
           1. the lattice of candidates around prev_pose (recover.pose_lattice; `extra`: a list of poses appended after it) is scored
@@ -145,7 +149,16 @@ class Tracker:
         So the result never scores below the lattice's best.  refine=0 returns the top lattice candidate with no network call.
         points: model points ([P,3], an object with .points, or a ModelPoints handle); default ``object_cloud``.  top defaults to
         min(8, engine.max_batch).  ``last_recover`` keeps n, top_idx, top_fit, refined, final_fit, chosen and inlier_frac
-        (= inlier_pts / points of the returned pose).  With fit_check set, last_fit_ratio is whatever on_track_batch left."""
+        (= inlier_pts / points of the returned pose).  With fit_check set, last_fit_ratio is whatever on_track_batch left.
+        facing=True: only the model points whose normal faces the camera are counted (the rule of se3tn_score_pose_grid), in both
+        scorings, so inlier_frac is the share of the VISIBLE surface the sensor confirms and means the same for every object.  The
+        lattice then travels as its factors (recover.lattice_factors through Engine.score_pose_grid) and [refined, unrefined] are
+        rescored as the diagonal of a 2k x 2k grid.  Needs normals: ``object_normals``, or a ModelPoints handle that carries them
+        as `points`; `extra` cannot be combined with it (extra poses are no product): ValueError."""
+        if facing:
+            if extra is not None and len(extra):
+                raise ValueError("recover: extra poses cannot be combined with facing=True (the lattice is scored as a product)")
+            return self._recover_facing(prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points)
         from .engine import ModelPoints
         from .recover import pose_key, pose_lattice
         if points is None:
@@ -185,6 +198,135 @@ class Tracker:
         finally:
             if own:
                 handle.close()
+
+    @property
+    def object_normals(self):
+        """One normal per point of ``object_cloud`` (float64 [P,3], not of unit length), or None without a model: the normals the
+        .ply stores, else utils.vertex_normals of the model's triangles, down-sampled with the cloud
+        (utils.voxel_down_sample_normals: the mean normal of each voxel).  None for a model that has neither normals nor triangles.
+        Computed at first read -- only recover(facing=True) and acquire need them.  Assignable."""
+        if isinstance(self._normals, tuple):
+            model_path, pts = self._normals
+            nrm = U.load_model_normals(model_path, pts)
+            self._normals = None if nrm is None else U.voxel_down_sample_normals(pts, nrm, 0.005)[1]
+        return self._normals
+
+    @object_normals.setter
+    def object_normals(self, normals):
+        self._normals = None if normals is None else np.asarray(normals, np.float64).reshape(-1, 3)
+        self._facing_points = None
+
+    def _facing_handle(self, points, who):
+        """the ModelPoints handle with normals a facing search scores against"""
+        from .engine import ModelPoints
+        if points is None:
+            if self.object_cloud is None or self.object_normals is None:
+                raise ValueError("%s: this tracker has no object_normals (no model_path, or a model without normals and triangles) "
+                                 "and no ModelPoints handle with normals was passed" % who)
+            if self._facing_points is None:
+                self._facing_points = self.engine.model_points(self.object_cloud, self.object_normals)
+            return self._facing_points
+        if not isinstance(points, ModelPoints) or points.normals is None:
+            raise ValueError("%s: with facing=True `points` must be a ModelPoints handle that carries normals "
+                             "(Engine.model_points(pts, normals))" % who)
+        return points
+
+    def _score_diagonal(self, handle, poses, dep, tol_mm):
+        """the facing records of m poses: the diagonal of the m x m grid of their rotations and translations (one device call)"""
+        poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        m = len(poses)
+        fit = self.engine.score_pose_grid(handle, poses[:, :3, :3], poses[:, :3, 3], dep, self.K, tol_mm, facing=True)
+        return fit[np.arange(m) * m + np.arange(m)]
+
+    def _refine_and_choose(self, handle, unrefined, rgb, dep, tol_mm, refine):
+        """steps 2 and 3 of recover under the facing rule -> (final poses, refined, final_fit, chosen)"""
+        from .recover import pose_key
+        k = len(unrefined)
+        refined = unrefined
+        for _ in range(int(refine)):
+            refined = np.asarray(self.on_track_batch(list(refined), [rgb] * k, [dep] * k), np.float64)
+        final = np.concatenate([refined, unrefined])
+        final_fit = self._score_diagonal(handle, final, dep, tol_mm)
+        return final, refined, final_fit, int(np.argmax(pose_key(final_fit)))   # ties prefer the refined pose: the lower index
+
+    @staticmethod
+    def _compose(rots, trans, idx):
+        """candidates idx (r * n_trans + t) of the product rots x trans as [k,4,4] poses"""
+        idx = np.asarray(idx, np.int64)
+        out = np.tile(np.eye(4), (len(idx), 1, 1))
+        out[:, :3, :3] = rots[idx // len(trans)]
+        out[:, :3, 3] = trans[idx % len(trans)]
+        return out
+
+    @staticmethod
+    def _frac(rec):
+        return float(rec["inlier_pts"]) / float(rec["points"]) if int(rec["points"]) else 0.0
+
+    def _recover_facing(self, prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points):
+        from .recover import lattice_factors
+        handle = self._facing_handle(points, "recover")
+        k = min(8, self.engine.max_batch) if top is None else int(top)
+        rots, trans = lattice_factors(prev_pose, trans_radius, trans_step, rot_deg)
+        dep = np.ascontiguousarray(depth, dtype=np.uint16)
+        top_idx, top_fit = self.engine.score_pose_grid(handle, rots, trans, dep, self.K, tol_mm, facing=True, top=k)
+        unrefined = self._compose(rots, trans, top_idx)
+        info = dict(n=len(rots) * len(trans), top_idx=top_idx, top_fit=top_fit, refined=None, facing=True)
+        if int(refine) < 1:
+            info.update(final_fit=top_fit[:1].copy(), chosen=0, inlier_frac=self._frac(top_fit[0]))
+            self.last_recover = info
+            return unrefined[0].copy()
+        final, refined, final_fit, chosen = self._refine_and_choose(handle, unrefined, rgb, dep, tol_mm, refine)
+        info.update(refined=refined, final_fit=final_fit, chosen=chosen, inlier_frac=self._frac(final_fit[chosen]))
+        self.last_recover = info
+        return final[chosen].copy()
+
+    def acquire(self, rgb, depth, roi=None, views=40, inplane=12, stride=16, behind_m=0.03, tol_mm=10, top=None, refine=1):
+        """Extension with no reference counterpart (the reference takes its first pose from a file, from ground truth or from
+        PoseCNN): find the object in a frame with NO pose to start from.
+          1. recover.rotation_grid(views, inplane) x recover.depth_seeds(depth, K, stride, behind_m, roi) -- rotations that cover
+             SO(3) times one translation per valid pixel of a stride grid, pushed behind_m behind the seen surface -- scored as a
+             product in ONE device call counting only the points that face the camera (Engine.score_pose_grid(facing=True)), the
+             `top` best kept (default min(8, engine.max_batch)).  At most 2^20 candidates: ValueError otherwise (raise `stride`,
+             or pass a `roi` = (left, top, right, bottom));
+          2. around each of them the default lattice of recover(facing=True), its best candidate kept;
+          3. refine >= 1: those go through on_track_batch `refine` times; [refined..., unrefined...] are scored once more and the
+             pose with the largest key is returned (refine=0: the best of step 2, no network call).
+        Depth alone fixes WHERE the object is, not which way a near-symmetric object is turned: a box scores the same after half a
+        turn, and the true rotation may come second or fourth.  That is why ``last_acquire`` keeps ALL `top` hypotheses and not
+        just the winner: n, n_rot, n_trans, stage1_idx, stage1_fit, hypotheses (their poses), local, local_idx, local_fit (step 2),
+        refined, final_fit, chosen, inlier_frac (= inlier_pts / facing points of the returned pose).  Use colour, the network's
+        own fit check (fit_check) or a few tracked frames to tell them apart.  Needs ``object_normals``."""
+        from .recover import depth_seeds, lattice_factors, pose_key, rotation_grid
+        from ._lib import POSE_SEARCH_MAX_POSES, POINT_FIT_DTYPE
+        handle = self._facing_handle(None, "acquire")
+        dep = np.ascontiguousarray(depth, dtype=np.uint16)
+        rots = rotation_grid(views, inplane)
+        seeds = depth_seeds(dep, self.K, stride, behind_m, roi)
+        if len(seeds) == 0:
+            raise ValueError("acquire: no valid depth pixel (100 < d < 2000 mm) on the stride grid of the region searched")
+        n = len(rots) * len(seeds)
+        if n > POSE_SEARCH_MAX_POSES:
+            raise ValueError("acquire: %d rotations x %d seeds = %d candidates > 2^20: raise stride (now %d) or narrow roi"
+                             % (len(rots), len(seeds), n, int(stride)))
+        k = min(min(8, self.engine.max_batch) if top is None else int(top), n)
+        idx1, fit1 = self.engine.score_pose_grid(handle, rots, seeds, dep, self.K, tol_mm, facing=True, top=k)
+        hyps = self._compose(rots, seeds, idx1)
+        local, local_idx, local_fit = np.empty_like(hyps), np.empty(k, np.int32), np.zeros(k, POINT_FIT_DTYPE)
+        for i in range(k):
+            lr, lt = lattice_factors(hyps[i])
+            li, lf = self.engine.score_pose_grid(handle, lr, lt, dep, self.K, tol_mm, facing=True, top=1)
+            local[i], local_idx[i], local_fit[i] = self._compose(lr, lt, li)[0], li[0], lf[0]
+        info = dict(n=n, n_rot=len(rots), n_trans=len(seeds), stage1_idx=idx1, stage1_fit=fit1, hypotheses=hyps, local=local,
+                    local_idx=local_idx, local_fit=local_fit, refined=None)
+        if int(refine) < 1:
+            chosen = int(np.argmax(pose_key(local_fit)))
+            info.update(final_fit=local_fit.copy(), chosen=chosen, inlier_frac=self._frac(local_fit[chosen]))
+            self.last_acquire = info
+            return local[chosen].copy()
+        final, refined, final_fit, chosen = self._refine_and_choose(handle, local, rgb, dep, tol_mm, refine)
+        info.update(refined=refined, final_fit=final_fit, chosen=chosen, inlier_frac=self._frac(final_fit[chosen]))
+        self.last_acquire = info
+        return final[chosen].copy()
 
     @property
     def fit_check(self):

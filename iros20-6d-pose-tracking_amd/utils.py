@@ -380,6 +380,51 @@ def voxel_down_sample(points, voxel_size=0.005):
     return out / np.bincount(inv)[:, None]
 
 
+def voxel_down_sample_normals(points, normals, voxel_size=0.005):
+    """voxel_down_sample for a cloud with one normal per point -> (points, normals): the points are voxel_down_sample's, bit for
+    bit (the same statements on the same arrays), the normal of a voxel is the mean of its points' normals -- not of unit length, and
+    zero where opposite faces of a thin wall share a voxel (such a point never faces the camera: only the sign of a dot product is used)."""
+    pts = np.asarray(points, np.float64)
+    nrm = np.asarray(normals, np.float64)
+    if nrm.shape != pts.shape:
+        raise ValueError("voxel_down_sample_normals: %s normals for %s points" % (nrm.shape, pts.shape))
+    origin = pts.min(0) - voxel_size * 0.5
+    idx = np.floor((pts - origin) / voxel_size).astype(np.int64)
+    _, inv = np.unique(idx, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    out = np.zeros((inv.max() + 1, 3))
+    np.add.at(out, inv, pts)
+    cnt = np.bincount(inv)[:, None]
+    mean = np.zeros((inv.max() + 1, 3))
+    np.add.at(mean, inv, nrm)
+    return out / cnt, mean / cnt
+
+
+def load_model_normals(path, points):
+    """One normal per vertex of load_model_points(path) (`points`), float64 [V,3], or None when the file gives none: the normals a
+    .ply stores, else vertex_normals of the model's triangles.  An .obj is read through load_obj_mesh, which splits a vertex per
+    texture corner: the copies' normals are summed per position and scaled to unit length."""
+    mesh = load_obj_mesh(path) if path.endswith(".obj") else load_ply_mesh(path)
+    v = np.asarray(mesh["vertices"], np.float64)
+    nrm = mesh.get("normals")
+    if nrm is None:
+        if len(mesh["faces"]) == 0:
+            return None
+        nrm = vertex_normals(v, mesh["faces"])
+    nrm = np.asarray(nrm, np.float64)
+    pts = np.asarray(points, np.float64)
+    if v.shape == pts.shape and np.array_equal(v, pts):
+        return nrm
+    _, inv = np.unique(np.concatenate([pts, v]), axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    acc = np.zeros((inv.max() + 1, 3))
+    np.add.at(acc, inv[len(pts):], nrm)
+    out = acc[inv[:len(pts)]]
+    ln = np.linalg.norm(out, axis=1)
+    out[ln > 0] /= ln[ln > 0, None]
+    return out
+
+
 def compute_obj_max_width(points):
     """Utils.py:101-105,450-451: convex-hull diameter in millimetres."""
     from scipy.spatial import ConvexHull, distance_matrix
