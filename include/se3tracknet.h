@@ -607,6 +607,90 @@ int se3tn_search_pose_grid_host(se3tn_ctx* ctx, const se3tn_points* points, int 
                                 const double* trans, const uint16_t* depth, int H, int W, const double K[9], int tol_mm, int facing,
                                 int k, int32_t* idx_out, se3tn_point_fit* fit_out, void* stream);
 
+/* ---- from a lattice node to a pose: point-to-plane steps of n hypotheses against one depth frame (ICP) ------------------------- */
+/* The two searches above end at the resolution of their lattices (10 mm, 15 degrees); the network's reach is its normalisers (30 mm,
+ * 5 degrees by default), and it needs weights that track.  In between stands a depth-only refinement: a few damped Gauss-Newton steps
+ * that pull the model's FACING points onto the surface the sensor saw, for n poses in one launch.  The points handle must carry
+ * normals; a normal is used as given (one of length L weights its point by L^2).
+ * Per point x with normal n under the pose [R | t], all in float64, in this order, without fused multiply-add:
+ *     q  = (R0 x + R1 y) + R2 z  per row,   c = q + t            the transform of se3tn_score_pose_grid
+ *     n' = (R0 nx + R1 ny) + R2 nz  per row
+ *     f  = (n'x c.x + n'y c.y) + n'z c.z;    facing: f < 0
+ *     in front, uf, vf, in frame, d, m, seen                       exactly as se3tn_score_poses states them (facing points only)
+ *     paired   seen && |d - m| <= gate_mm
+ *     o.z = d / 1000.0;  o.x = ((uf - K[2]) * o.z) / K[0];  o.y = ((vf - K[5]) * o.z) / K[4]       the pixel's back-projection
+ *     r  = (n'x (o.x - c.x) + n'y (o.y - c.y)) + n'z (o.z - c.z)                                   the point-to-plane residual
+ *     J  = (q x n', n'):  J0 = q.y n'z - q.z n'y,  J1 = q.z n'x - q.x n'z,  J2 = q.x n'y - q.y n'x,  J3..5 = n'
+ *          -- the rotation is taken about the object's origin t (q = c - t), not about the camera: a plane seen from the front then
+ *          stays where it is along the directions depth cannot observe
+ *     fx(v) = (int64) rint(fmin(fmax(v, -256.0), 256.0) * 2^32)                                    (a NaN gives -256 * 2^32)
+ * Per pose and iteration, SE3TN_POSE_ALIGN_SUMS = 28 int64 sums over the paired points, in this order:
+ *     S_A[i][j], i <= j, row-major (21 words) = sum fx(J_i * J_j);   S_b[i] (6 words) = sum fx(J_i * r);   S_e (1 word) = sum fx(r * r)
+ * and two counts, pairs and facing_pts.  Every term is quantised BEFORE it is added, so the sums are integers and do not depend on
+ * the order of the reduction; the clamp makes overflow impossible (2^8 * 2^32 * 2^20 points = 2^60) and bounds what a normal may
+ * weigh: a product above 256 is cut, so keep normals within a length of about 10 (unit normals are the intended case).
+ *     pairs < min_pairs:  stop, status FEW.
+ *     solve:  A_ij = (double)S_A * 2^-32, b likewise, A_ii += damping * (double)pairs;  LDL^T without pivoting or square root:
+ *             d_j = A_jj - sum_k (L_jk L_jk) d_k,   L_ij = (A_ij - sum_k (L_ik L_jk) d_k) / d_j;   y_i = b_i - sum_k L_ik y_k;   y_i /= d_i;
+ *             delta_i = y_i - sum_{k > i} L_ki delta_k -- every inner sum starts from 0.0 and adds left to right over ascending k.
+ *             A pivot that is not > 0 (NaN included) or a component of delta = (w, v) that is not finite: stop, status SINGULAR, the
+ *             pose unchanged.
+ *     update (Cayley, no trigonometry):  a = 0.5 w,  s = (a0 a0 + a1 a1) + a2 a2,  C = ((1 - s) I + 2 a a^T + 2 [a]x) / (1 + s):
+ *             C_ii = ((1.0 - s) + 2.0 * (a_i * a_i)) / (1.0 + s),   C_ij = (2.0 * (a_i * a_j) + 2.0 * [a]x_ij) / (1.0 + s) with
+ *             [a]x_01 = -a2, _02 = a1, _10 = a2, _12 = -a0, _20 = -a1, _21 = a0 (a subtraction where the sign is minus);
+ *             R <- C R, entry (i, j) = (C_i0 R_0j + C_i1 R_1j) + C_i2 R_2j;   t <- t + v.
+ *     max_k |delta_k| <= stop:  stop, status CONVERGED (after the update).   After `iters` iterations: status ITERS.
+ * A pose that is not finite pairs nothing: FEW after one evaluation, rows 0-2 returned with the bits they came in with.  Row 3 of an
+ * input pose is not read; row 3 of an output pose is 0 0 0 1.
+ * Guarantees:
+ *   (a) a pose's output (pose, record, sums) depends on (points, normals, pose, depth, K, params) only -- not on n, on its place in
+ *       the call, on the thread count or on the run -- and equals the same rule evaluated in IEEE float64 anywhere else
+ *       (tests/pose_align_oracle.py; csrc/pose_align_math.h holds the statements, which tests/c_abi/pose_align_check.cpp runs on the host);
+ *   (b) a pose is read and written by its own workgroup alone: a bad one harms no other;
+ *   (c) the device-pointer entry point allocates nothing and uses no atomics on global memory; it is stream-ordered and capturable.
+ * Cost: ONE launch runs all iterations, one workgroup per pose; an iteration is P projections, 28 quantised products per paired
+ * point, a reduction through LDS and a 6 x 6 solve by one thread. */
+#define SE3TN_POSE_ALIGN_MAX_POSES 4096
+#define SE3TN_POSE_ALIGN_MAX_ITERS 64
+#define SE3TN_POSE_ALIGN_SUMS 28
+#define SE3TN_ALIGN_ITERS 0       /* `iters` iterations done                          */
+#define SE3TN_ALIGN_CONVERGED 1   /* max |delta| <= stop                              */
+#define SE3TN_ALIGN_FEW 2         /* pairs < min_pairs at the last evaluated pose     */
+#define SE3TN_ALIGN_SINGULAR 3    /* a pivot not > 0 or a step that is not finite     */
+typedef struct se3tn_align_params {
+  int32_t gate_mm;     /* pairing gate |d - m| <= gate_mm, [1, 65535]                 */
+  int32_t iters;       /* [1, SE3TN_POSE_ALIGN_MAX_ITERS]                              */
+  int32_t min_pairs;   /* [6, 2^20]                                                    */
+  int32_t _reserved;   /* 0                                                            */
+  double damping;      /* >= 0: added to the diagonal per paired point                 */
+  double stop;         /* >= 0: the step size that counts as converged                 */
+} se3tn_align_params;
+typedef struct se3tn_align_rec {   /* 40 bytes */
+  uint32_t iterations;   /* iterations evaluated                                       */
+  uint32_t status;       /* SE3TN_ALIGN_*                                              */
+  uint32_t pairs;        /* paired points at the last evaluated pose                   */
+  uint32_t facing_pts;   /* facing points at the last evaluated pose                   */
+  int64_t sum_r2;        /* S_e of the last evaluated pose (metres^2 * 2^32)           */
+  uint32_t pairs0;       /* paired points at the first evaluated pose                  */
+  uint32_t _reserved;    /* 0                                                          */
+  int64_t sum_r2_0;      /* S_e of the first evaluated pose                            */
+} se3tn_align_rec;       /* the last evaluated pose is the pose BEFORE the last update */
+/* poses_dev: device float64 [n,16]; poses_out_dev: device float64 [n,16], may equal poses_dev; rec_dev: n records; sums_dev: int64
+ * [n,28], the sums of the last evaluated iteration, or NULL; depth_dev, K and the stream as se3tn_score_poses.  The poses are not
+ * inspected.  SE3TN_E_ARG, each with a message of its own: a NULL pointer, n outside [1, SE3TN_POSE_ALIGN_MAX_POSES], gate_mm outside
+ * [1, 65535], iters outside [1, SE3TN_POSE_ALIGN_MAX_ITERS], min_pairs outside [6, 2^20], _reserved != 0, damping or stop negative or
+ * not finite, H or W < 1, a host-only context, points of another device.  SE3TN_E_STATE: the handle has no normals. */
+int se3tn_align_poses(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses_dev, const uint16_t* depth_dev, int H,
+                      int W, const double K[9], const se3tn_align_params* params, double* poses_out_dev, se3tn_align_rec* rec_dev,
+                      int64_t* sums_dev, void* stream);
+/* The same from HOST memory: poses float64 [n,16], depth uint16 [H,W]; poses_out [n,16], rec_out [n], sums_out int64 [n,28] or NULL.
+ * The staging is [poses | depth | pad | poses_out | rec | sums]: one upload, one launch, one read-back.  SYNCHRONOUS on `stream`,
+ * refused inside a stream capture (SE3TN_E_STATE); the pinned staging and its device mirror (shared with se3tn_search_poses_host) grow
+ * on a first or larger call.  SE3TN_E_ARG as above, and a pose entry (rows 0-2) or a K entry that is not finite. */
+int se3tn_align_poses_host(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses, const uint16_t* depth, int H, int W,
+                           const double K[9], const se3tn_align_params* params, double* poses_out, se3tn_align_rec* rec_out,
+                           int64_t* sums_out, void* stream);
+
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K
  * row-major 3x3, width in mm; out_vu[8] = 4 x (v,u) int32, np.round (half-to-even). */

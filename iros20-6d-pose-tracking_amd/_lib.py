@@ -25,6 +25,10 @@ POSE_ERRORS_CHUNK = 256            # as include/se3tracknet.h: pose pairs per la
 POSE_ERRORS_MAX_POINTS = 1 << 20   # as include/se3tracknet.h: the largest model se3tn_points_create accepts
 POSE_SEARCH_MAX_POSES = 1 << 20   # as include/se3tracknet.h: the most candidate poses one se3tn_score_poses / se3tn_rank_poses call takes
 POSE_RANK_MAX = 64                 # as include/se3tracknet.h: the largest k of se3tn_rank_poses
+POSE_ALIGN_MAX_POSES = 4096        # as include/se3tracknet.h: the most poses one se3tn_align_poses call takes
+POSE_ALIGN_MAX_ITERS = 64          # as include/se3tracknet.h: the most iterations of one se3tn_align_poses call
+POSE_ALIGN_SUMS = 28               # as include/se3tracknet.h: int64 sums per pose (21 of S_A | 6 of S_b | S_e)
+ALIGN_ITERS, ALIGN_CONVERGED, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2, 3   # as include/se3tracknet.h: se3tn_align_rec.status
 MAX_BATCH_LIMIT = 1982             # as include/se3tracknet.h: the largest max_batch se3tn_create accepts
 RES = 176
 
@@ -51,6 +55,18 @@ class Fit(C.Structure):
                                           "_reserved")]
 
 
+class AlignParams(C.Structure):
+    """se3tn_align_params (include/se3tracknet.h): gate, iteration and stop settings of se3tn_align_poses."""
+    _fields_ = [("gate_mm", C.c_int32), ("iters", C.c_int32), ("min_pairs", C.c_int32), ("_reserved", C.c_int32),
+                ("damping", C.c_double), ("stop", C.c_double)]
+
+
+class AlignRec(C.Structure):
+    """se3tn_align_rec (include/se3tracknet.h): what became of one pose of se3tn_align_poses."""
+    _fields_ = [("iterations", C.c_uint32), ("status", C.c_uint32), ("pairs", C.c_uint32), ("facing_pts", C.c_uint32),
+                ("sum_r2", C.c_int64), ("pairs0", C.c_uint32), ("_reserved", C.c_uint32), ("sum_r2_0", C.c_int64)]
+
+
 class PointFit(C.Structure):
     """se3tn_point_fit (include/se3tracknet.h): the record of one candidate pose of se3tn_score_poses."""
     _fields_ = [(k, C.c_uint32) for k in ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm",
@@ -68,6 +84,9 @@ assert FIT_DTYPE.itemsize == C.sizeof(Fit) == 32
 POINT_FIT_FIELDS = ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm")   # the seven that carry data
 POINT_FIT_DTYPE = _np.dtype([(k, "<u4") for k in POINT_FIT_FIELDS + ("_reserved",)])
 assert POINT_FIT_DTYPE.itemsize == C.sizeof(PointFit) == 32
+ALIGN_REC_DTYPE = _np.dtype([("iterations", "<u4"), ("status", "<u4"), ("pairs", "<u4"), ("facing_pts", "<u4"), ("sum_r2", "<i8"),
+                             ("pairs0", "<u4"), ("_reserved", "<u4"), ("sum_r2_0", "<i8")])
+assert ALIGN_REC_DTYPE.itemsize == C.sizeof(AlignRec) == 40 and C.sizeof(AlignParams) == 32
 
 
 _SIGS = {
@@ -162,6 +181,10 @@ _SIGS = {
                                         C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "se3tn_search_pose_grid_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                               C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_align_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                    C.POINTER(AlignParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_align_poses_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                         C.POINTER(AlignParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_compute_bbox": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(C.c_int32)]),
     "se3tn_pose_update_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float),

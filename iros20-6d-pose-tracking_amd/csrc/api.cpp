@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "hip_buffers.h"
+#include "pose_align_plan.h"
 #include "pose_errors_plan.h"
 #include "pose_grid_plan.h"
 #include "pose_search_plan.h"
@@ -141,7 +142,7 @@ struct se3tn_ctx {
   PinnedBuf<se3tn_fit> fit_host;
   // se3tn_pose_errors_host: pinned staging [pred | gt | add | adds] (pose_errors_plan.h: pe_stage_*) for pe_cap pairs and its device mirror
   PinnedBuf<double> pe_host; DeviceBuf<double> pe_dev; int pe_cap = 0;
-  // se3tn_search_poses_host / se3tn_search_pose_grid_host (both synchronous): pinned staging of ps_cap bytes, laid out per call
+  // se3tn_search_poses_host / se3tn_search_pose_grid_host / se3tn_align_poses_host (all synchronous): pinned staging of ps_cap bytes, laid out per call
   // (pose_search_plan.h: PsStage, pose_grid_plan.h: PgStage), and its device mirror
   PinnedBuf<unsigned char> ps_host; DeviceBuf<unsigned char> ps_dev; size_t ps_cap = 0;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive before the next one
@@ -1817,6 +1818,87 @@ int se3tn_search_pose_grid_host(se3tn_ctx* c, const se3tn_points* p, int n_rot, 
   HIPCHK(hipStreamSynchronize(st));
   std::memcpy(fit_out, h + s.top_fit, sizeof(se3tn_point_fit) * (size_t)k);
   std::memcpy(idx_out, h + s.idx, sizeof(int32_t) * (size_t)k);
+  return SE3TN_OK;
+}
+
+// ---- n pose hypotheses aligned to one depth frame: point-to-plane steps, all iterations in one launch ----------------------------------
+// NULL pointers first, then the numbers, then the context and the handle (which is not read before the context is known to have a
+// device): every refusal has its own message, on a host-only context too
+static int pose_align_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, int n, int H, int W,
+                            const se3tn_align_params* q) {
+  const std::string w(who);
+  if (!c || !ok_ptrs || !p || !q) return fail(SE3TN_E_ARG, w + ": NULL argument");
+  if (n < 1 || n > PA_MAX_POSES)
+    return fail(SE3TN_E_ARG, w + ": n = " + std::to_string(n) + " outside [1, SE3TN_POSE_ALIGN_MAX_POSES = " + std::to_string(PA_MAX_POSES) + "]");
+  if (q->gate_mm < 1 || q->gate_mm > 65535) return fail(SE3TN_E_ARG, w + ": gate_mm = " + std::to_string(q->gate_mm) + " outside [1, 65535]");
+  if (q->iters < 1 || q->iters > PA_MAX_ITERS)
+    return fail(SE3TN_E_ARG, w + ": iters = " + std::to_string(q->iters) + " outside [1, SE3TN_POSE_ALIGN_MAX_ITERS = " +
+                                 std::to_string(PA_MAX_ITERS) + "]");
+  if (q->min_pairs < 6 || q->min_pairs > (1 << 20))
+    return fail(SE3TN_E_ARG, w + ": min_pairs = " + std::to_string(q->min_pairs) + " outside [6, 2^20] (six unknowns)");
+  if (q->_reserved != 0) return fail(SE3TN_E_ARG, w + ": params._reserved = " + std::to_string(q->_reserved) + " is not 0");
+  if (!(q->damping >= 0.0) || !std::isfinite(q->damping)) return fail(SE3TN_E_ARG, w + ": damping is negative or not finite");
+  if (!(q->stop >= 0.0) || !std::isfinite(q->stop)) return fail(SE3TN_E_ARG, w + ": stop is negative or not finite");
+  if (H < 1 || W < 1) return fail(SE3TN_E_ARG, w + ": empty frame (H or W < 1)");
+  if (c->device < 0) return fail(SE3TN_E_ARG, w + ": host-only context (device = -1) has no device to align on");
+  if (p->device != c->device) return fail(SE3TN_E_ARG, w + ": the points live on another device than the context");
+  if (!p->nrm) return fail(SE3TN_E_STATE, w + ": the points handle has no normals (se3tn_points_set_normals)");
+  return SE3TN_OK;
+}
+static PoseAlignArgs pose_align_args(const se3tn_points* p, const double* poses, const uint16_t* depth, int H, int W, const double K[9],
+                                     const se3tn_align_params* q, double* poses_out, se3tn_align_rec* rec, int64_t* sums) {
+  PoseAlignArgs a;
+  a.pts = p->xyz.get(); a.nrm = p->nrm.get(); a.P = p->P; a.poses = poses; a.depth = depth; a.H = H; a.W = W; a.p = *q;
+  a.poses_out = poses_out; a.rec = rec; a.sums = sums;
+  for (int i = 0; i < 9; ++i) a.K[i] = K[i];
+  return a;
+}
+
+int se3tn_align_poses(se3tn_ctx* c, const se3tn_points* p, int n, const double* poses_dev, const uint16_t* depth_dev, int H, int W,
+                      const double K[9], const se3tn_align_params* params, double* poses_out_dev, se3tn_align_rec* rec_dev,
+                      int64_t* sums_dev, void* stream) {
+  const char* who = "se3tn_align_poses";
+  if (int rc = pose_align_check(who, c, poses_dev && depth_dev && K && poses_out_dev && rec_dev, p, n, H, W, params)) return rc;
+  HIPCHK(launch_pose_align(pose_align_args(p, poses_dev, depth_dev, H, W, K, params, poses_out_dev, rec_dev, sums_dev), n,
+                           (hipStream_t)stream));
+  return SE3TN_OK;
+}
+
+int se3tn_align_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const double* poses, const uint16_t* depth, int H, int W,
+                           const double K[9], const se3tn_align_params* params, double* poses_out, se3tn_align_rec* rec_out,
+                           int64_t* sums_out, void* stream) {
+  const char* who = "se3tn_align_poses_host";
+  if (int rc = pose_align_check(who, c, poses && depth && K && poses_out && rec_out, p, n, H, W, params)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_align_poses_host: the call is synchronous, it cannot be captured");
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(K[i])) return fail(SE3TN_E_ARG, "se3tn_align_poses_host: K entry " + std::to_string(i) + " is not finite");
+  for (size_t i = 0; i < (size_t)n * 16; ++i)
+    if (i % 16 < 12 && !std::isfinite(poses[i]))
+      return fail(SE3TN_E_ARG, "se3tn_align_poses_host: pose " + std::to_string(i / 16) + " has an entry that is not finite");
+  const PaStage s = pa_stage(n, H, W, sums_out ? 1 : 0);
+  if (s.bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
+    DeviceGuard dg(c->device);
+    if (int rc = begin_growth(dg)) return rc;
+    c->ps_cap = 0;
+    HIPCHK(c->ps_host.alloc(s.bytes));
+    HIPCHK(c->ps_dev.alloc(s.bytes));
+    c->ps_cap = s.bytes;
+  }
+  // the staging is laid out for THIS (n, H, W): the upload is one contiguous run, and so is the read-back
+  unsigned char* h = c->ps_host.get();
+  unsigned char* d = c->ps_dev.get();
+  std::memcpy(h + s.poses, poses, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
+  HIPCHK(hipMemcpyAsync(d, h, s.upload_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(launch_pose_align(pose_align_args(p, reinterpret_cast<const double*>(d + s.poses), reinterpret_cast<const uint16_t*>(d + s.depth), H, W,
+                                           K, params, reinterpret_cast<double*>(d + s.poses_out), reinterpret_cast<se3tn_align_rec*>(d + s.rec),
+                                           sums_out ? reinterpret_cast<int64_t*>(d + s.sums) : nullptr), n, st));
+  HIPCHK(hipMemcpyAsync(h + s.poses_out, d + s.poses_out, s.readback_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(poses_out, h + s.poses_out, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(rec_out, h + s.rec, sizeof(se3tn_align_rec) * (size_t)n);
+  if (sums_out) std::memcpy(sums_out, h + s.sums, sizeof(int64_t) * SE3TN_POSE_ALIGN_SUMS * (size_t)n);
   return SE3TN_OK;
 }
 

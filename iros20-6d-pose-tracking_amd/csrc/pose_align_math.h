@@ -1,0 +1,187 @@
+// The arithmetic of se3tn_align_poses (include/se3tracknet.h states the rule), host and device: the terms of one model point, their
+// quantisation, the 6 x 6 solve and the Cayley update.  pose_align.hip runs these statements on the device and
+// tests/c_abi/pose_align_check.cpp runs the very same ones on the host, so the two can be held to each other and to the numpy oracle
+// (tests/pose_align_oracle.py) word for word.  Whoever includes this compiles with -ffp-contract=off: every operation below is
+// rounded once, in the order written.  No HIP header is needed to read it.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include "pose_search_plan.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SE3TN_PA_UNROLL _Pragma("unroll")   // the sums and the 6 x 6 systems stay in registers on the device
+#else
+#define SE3TN_PA_UNROLL
+#endif
+
+namespace se3tn {
+
+constexpr int PA_SUMS = SE3TN_POSE_ALIGN_SUMS;   // 21 words of S_A (i <= j, row-major) | 6 of S_b | S_e
+constexpr int PA_B0 = 21, PA_E = 27;
+static_assert(PA_SUMS == 28, "21 + 6 + 1");
+
+struct PaPose {   // rows 0-2 of a row-major 4 x 4 pose
+  double r[3][3], t[3];
+};
+struct PaFrame {   // the observed frame and the camera
+  const uint16_t* depth;   // [H,W] millimetres
+  int H, W;
+  double k0, k2, k4, k5;   // K[0], K[2], K[4], K[5]
+  double gate;             // millimetres
+};
+
+// fx(v) = (int64) rint(min(max(v, -256), 256) * 2^32); fmax / fmin ignore a NaN, which therefore gives -256 * 2^32
+SE3TN_PS_HD inline int64_t pa_fx(double v) { return (int64_t)rint(fmin(fmax(v, -256.0), 256.0) * 4294967296.0); }
+
+// One model point x with normal n under pose T.  Returns bit 0: facing, bit 1: paired; with bit 1 set J[6] and r are the point's row
+// of the Jacobian and its residual (metres), otherwise they are not written.
+SE3TN_PS_HD inline int pa_point(const PaPose& T, const PaFrame& f, double x, double y, double z, double nx, double ny, double nz,
+                                double J[6], double& r) {
+  const double qx = (T.r[0][0] * x + T.r[0][1] * y) + T.r[0][2] * z;
+  const double qy = (T.r[1][0] * x + T.r[1][1] * y) + T.r[1][2] * z;
+  const double qz = (T.r[2][0] * x + T.r[2][1] * y) + T.r[2][2] * z;
+  const double cx = qx + T.t[0], cy = qy + T.t[1], cz = qz + T.t[2];
+  const double mx = (T.r[0][0] * nx + T.r[0][1] * ny) + T.r[0][2] * nz;
+  const double my = (T.r[1][0] * nx + T.r[1][1] * ny) + T.r[1][2] * nz;
+  const double mz = (T.r[2][0] * nx + T.r[2][1] * ny) + T.r[2][2] * nz;
+  const double face = (mx * cx + my * cy) + mz * cz;
+  if (!(face < 0.0)) return 0;   // turned away, grazing or NaN
+  const double uf = rint(cx * f.k0 / cz + f.k2);
+  const double vf = rint(cy * f.k4 / cz + f.k5);
+  // every comparison is false for NaN; +-inf and anything beyond the frame fail one of them: only an index reaches the cast
+  if (!(cz > 0.0 && uf >= 0.0 && uf < (double)f.W && vf >= 0.0 && vf < (double)f.H)) return 1;
+  const double d = (double)f.depth[(size_t)(int)vf * (size_t)f.W + (size_t)(int)uf];
+  const double m = rint(cz * 1000.0);
+  if (!(d > 100.0 && d < 2000.0 && fabs(d - m) <= f.gate)) return 1;
+  const double oz = d / 1000.0;
+  const double ox = ((uf - f.k2) * oz) / f.k0;
+  const double oy = ((vf - f.k5) * oz) / f.k4;
+  r = (mx * (ox - cx) + my * (oy - cy)) + mz * (oz - cz);
+  J[0] = qy * mz - qz * my;
+  J[1] = qz * mx - qx * mz;
+  J[2] = qx * my - qy * mx;
+  J[3] = mx; J[4] = my; J[5] = mz;
+  return 3;
+}
+
+// the 28 quantised terms of a paired point added to S
+SE3TN_PS_HD inline void pa_accumulate(const double J[6], double r, int64_t S[PA_SUMS]) {
+  int w = 0;
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i)
+    SE3TN_PA_UNROLL
+    for (int j = i; j < 6; ++j) S[w++] += pa_fx(J[i] * J[j]);
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i) S[PA_B0 + i] += pa_fx(J[i] * r);
+  S[PA_E] += pa_fx(r * r);
+}
+
+// (A + damping * pairs * I) delta = b by LDL^T without pivoting and without a square root; every inner sum starts from 0.0 and adds
+// left to right over ascending k.  Returns 0, or 1 (delta not to be used): a pivot that is not > 0 (NaN included) or a component of
+// delta that is not finite.
+SE3TN_PS_HD inline int pa_solve(const int64_t S[PA_SUMS], uint32_t pairs, double damping, double delta[6]) {
+  const double inv = 1.0 / 4294967296.0;
+  double A[6][6], b[6], L[6][6], D[6];
+  int w = 0;
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i)
+    SE3TN_PA_UNROLL
+    for (int j = i; j < 6; ++j) { A[i][j] = (double)S[w++] * inv; A[j][i] = A[i][j]; }
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i) b[i] = (double)S[PA_B0 + i] * inv;
+  const double lift = damping * (double)pairs;
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i) A[i][i] = A[i][i] + lift;
+  SE3TN_PA_UNROLL
+  for (int j = 0; j < 6; ++j) {
+    double s = 0.0;
+    SE3TN_PA_UNROLL
+    for (int k = 0; k < j; ++k) s = s + (L[j][k] * L[j][k]) * D[k];
+    D[j] = A[j][j] - s;
+    if (!(D[j] > 0.0)) return 1;
+    SE3TN_PA_UNROLL
+    for (int i = j + 1; i < 6; ++i) {
+      s = 0.0;
+      SE3TN_PA_UNROLL
+      for (int k = 0; k < j; ++k) s = s + (L[i][k] * L[j][k]) * D[k];
+      L[i][j] = (A[j][i] - s) / D[j];
+    }
+  }
+  double y[6];
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    double s = 0.0;
+    SE3TN_PA_UNROLL
+    for (int k = 0; k < i; ++k) s = s + L[i][k] * y[k];
+    y[i] = b[i] - s;
+  }
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i) y[i] = y[i] / D[i];
+  SE3TN_PA_UNROLL
+  for (int i = 5; i >= 0; --i) {
+    double s = 0.0;
+    SE3TN_PA_UNROLL
+    for (int k = i + 1; k < 6; ++k) s = s + L[k][i] * delta[k];
+    delta[i] = y[i] - s;
+  }
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 6; ++i)
+    if (!(fabs(delta[i]) <= 1.7976931348623157e308)) return 1;
+  return 0;
+}
+
+// R <- C R, t <- t + v with the Cayley rotation of w about the object's origin: a = 0.5 w, s = (a0 a0 + a1 a1) + a2 a2,
+// C = ((1 - s) I + 2 a a^T + 2 [a]x) / (1 + s) -- orthogonal for every w, no trigonometry
+SE3TN_PS_HD inline void pa_update(PaPose& T, const double delta[6]) {
+  const double a0 = 0.5 * delta[0], a1 = 0.5 * delta[1], a2 = 0.5 * delta[2];
+  const double s = (a0 * a0 + a1 * a1) + a2 * a2;
+  const double den = 1.0 + s;
+  double C[3][3];
+  C[0][0] = ((1.0 - s) + 2.0 * (a0 * a0)) / den;
+  C[0][1] = (2.0 * (a0 * a1) - 2.0 * a2) / den;
+  C[0][2] = (2.0 * (a0 * a2) + 2.0 * a1) / den;
+  C[1][0] = (2.0 * (a1 * a0) + 2.0 * a2) / den;
+  C[1][1] = ((1.0 - s) + 2.0 * (a1 * a1)) / den;
+  C[1][2] = (2.0 * (a1 * a2) - 2.0 * a0) / den;
+  C[2][0] = (2.0 * (a2 * a0) - 2.0 * a1) / den;
+  C[2][1] = (2.0 * (a2 * a1) + 2.0 * a0) / den;
+  C[2][2] = ((1.0 - s) + 2.0 * (a2 * a2)) / den;
+  double R[3][3];
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 3; ++i)
+    SE3TN_PA_UNROLL
+    for (int j = 0; j < 3; ++j) R[i][j] = (C[i][0] * T.r[0][j] + C[i][1] * T.r[1][j]) + C[i][2] * T.r[2][j];
+  SE3TN_PA_UNROLL
+  for (int i = 0; i < 3; ++i) {
+    SE3TN_PA_UNROLL
+    for (int j = 0; j < 3; ++j) T.r[i][j] = R[i][j];
+    T.t[i] = T.t[i] + delta[3 + i];
+  }
+}
+
+// max_k |delta_k| <= stop
+SE3TN_PS_HD inline bool pa_small(const double delta[6], double stop) {
+  double m = fabs(delta[0]);
+  SE3TN_PA_UNROLL
+  for (int i = 1; i < 6; ++i) m = fabs(delta[i]) > m ? fabs(delta[i]) : m;
+  return m <= stop;
+}
+
+// What one thread does after the sums of iteration `it` (0-based) are known: the record, the solve, the update.  Returns true when
+// the pose is finished (rec.status is then final); rec.iterations / pairs / facing_pts / sum_r2 describe the pose just evaluated.
+SE3TN_PS_HD inline bool pa_step(PaPose& T, const int64_t S[PA_SUMS], uint32_t pairs, uint32_t facing, int it,
+                                const se3tn_align_params& p, se3tn_align_rec& rec) {
+  rec.iterations = (uint32_t)(it + 1);
+  rec.pairs = pairs; rec.facing_pts = facing; rec.sum_r2 = S[PA_E];
+  if (it == 0) { rec.pairs0 = pairs; rec.sum_r2_0 = S[PA_E]; rec._reserved = 0u; }
+  rec.status = SE3TN_ALIGN_ITERS;
+  if (pairs < (uint32_t)p.min_pairs) { rec.status = SE3TN_ALIGN_FEW; return true; }
+  double delta[6];
+  if (pa_solve(S, pairs, p.damping, delta)) { rec.status = SE3TN_ALIGN_SINGULAR; return true; }
+  pa_update(T, delta);
+  if (pa_small(delta, p.stop)) { rec.status = SE3TN_ALIGN_CONVERGED; return true; }
+  return it + 1 >= p.iters;
+}
+
+}  // namespace se3tn

@@ -258,6 +258,23 @@ struct PoseGridArgs {
 };
 hipError_t launch_pose_grid(const PoseGridArgs& a, int n_rot, hipStream_t st);
 
+// n poses aligned to one depth frame, all iterations in one launch (pose_align.hip; geometry and staging: pose_align_plan.h, the
+// arithmetic: pose_align_math.h)
+struct PoseAlignArgs {
+  const double* pts;       // [P,3] model points
+  const double* nrm;       // [P,3] model normals
+  int P;
+  const double* poses;     // [n,16] row-major hypotheses (rows 0-2 are read)
+  const uint16_t* depth;   // [H,W] millimetres
+  int H, W;
+  double K[9];             // row-major intrinsics: [0], [2], [4], [5] are read
+  se3tn_align_params p;
+  double* poses_out;       // [n,16]; may be `poses`
+  se3tn_align_rec* rec;    // [n]
+  int64_t* sums;           // [n,28] or nullptr
+};
+hipError_t launch_pose_align(const PoseAlignArgs& a, int n, hipStream_t st);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per DEVICE: a launcher remembers which device
 // ordinals it has already raised the limit on (several contexts on different GPUs in one process).
 struct PerDeviceOnce {

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import ALIGN_REC_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -487,6 +487,50 @@ class Engine:
         check(self.lib.se3tn_rank_poses(self._h, n, C.c_void_p(fit.data_ptr()), int(top), C.c_void_p(idx.data_ptr()), _stream_ptr()),
               "se3tn_rank_poses")
         return idx, fit[idx.long()]
+
+    # ---- n pose hypotheses aligned to one depth frame ------------------------------------------------
+    def align_poses(self, points, poses, depth, K, gate_mm=20, iters=20, min_pairs=12, damping=1e-6, stop=1e-6, sums=False):
+        """se3tn_align_poses: up to `iters` damped point-to-plane steps of the facing points of the model `points` (a ModelPoints
+        handle WITH normals) against the depth frame (uint16 mm [H,W]), for each of n poses, in ONE launch -- the rule of
+        include/se3tracknet.h: points pair with the pixel they project to when it lies within gate_mm of them, every sum is an
+        integer, the rotation is taken about the object's origin.  A pose stops when fewer than min_pairs points pair (status
+        _lib.ALIGN_FEW), when the system cannot be solved (ALIGN_SINGULAR, the pose unchanged), when its step falls to `stop`
+        (ALIGN_CONVERGED) or after `iters` iterations (ALIGN_ITERS).
+        numpy in ([n,4,4] or [n,16] poses, [H,W] depth) -> (poses [n,4,4] float64, records [n] of _lib.ALIGN_REC_DTYPE), ONE synchronous
+        call (se3tn_align_poses_host: one upload, one launch, one read-back); cuda tensors in (float64 poses, 16-bit depth) -> (poses
+        [n,4,4] float64 tensor, records uint8 tensor [n,40]: ``.cpu().numpy().view(ALIGN_REC_DTYPE)``), stream-ordered on the current
+        stream, nothing allocated by the library.  sums=True appends the int64 [n,28] sums of each pose's last evaluated iteration."""
+        if not isinstance(points, ModelPoints) or not points._h:
+            raise Se3tnError("align_poses: points must be an open ModelPoints handle (Engine.model_points)")
+        Kh = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        Kp = Kh.ctypes.data_as(C.POINTER(C.c_double))
+        prm = _lib.AlignParams(int(gate_mm), int(iters), int(min_pairs), 0, float(damping), float(stop))
+        if torch.is_tensor(poses) or torch.is_tensor(depth):
+            if not (torch.is_tensor(poses) and torch.is_tensor(depth)):
+                raise Se3tnError("align_poses: poses and depth must both be tensors or both be arrays")
+            assert poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous() and poses.numel() % 16 == 0
+            assert depth.is_cuda and depth.element_size() == 2 and depth.dim() == 2 and depth.is_contiguous()
+            n = poses.numel() // 16
+            out = torch.empty((n, 4, 4), dtype=torch.float64, device=poses.device)
+            rec = torch.empty((n, ALIGN_REC_DTYPE.itemsize), dtype=torch.uint8, device=poses.device)
+            sm = torch.empty((n, _lib.POSE_ALIGN_SUMS), dtype=torch.int64, device=poses.device) if sums else None
+            check(self.lib.se3tn_align_poses(self._h, points._h, n, C.c_void_p(poses.data_ptr()), C.c_void_p(depth.data_ptr()),
+                                             int(depth.shape[0]), int(depth.shape[1]), Kp, C.byref(prm), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(rec.data_ptr()), C.c_void_p(sm.data_ptr()) if sums else None, _stream_ptr()),
+                  "se3tn_align_poses")
+            return (out, rec, sm) if sums else (out, rec)
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("align_poses: depth must be [H,W]")
+        n = int(p.shape[0])
+        out = np.empty((max(n, 0), 4, 4), np.float64)
+        rec = np.zeros(max(n, 0), ALIGN_REC_DTYPE)
+        sm = np.zeros((max(n, 0), _lib.POSE_ALIGN_SUMS), np.int64) if sums else None
+        check(self.lib.se3tn_align_poses_host(self._h, points._h, n, C.c_void_p(p.ctypes.data), C.c_void_p(d.ctypes.data), int(d.shape[0]),
+                                              int(d.shape[1]), Kp, C.byref(prm), C.c_void_p(out.ctypes.data), C.c_void_p(rec.ctypes.data),
+                                              C.c_void_p(sm.ctypes.data) if sums else None, _stream_ptr()), "se3tn_align_poses_host")
+        return (out, rec, sm) if sums else (out, rec)
 
     def fill_depth(self, depth_mm, max_depth=2.0, extrapolate=False, blur_type="bilateral", return_metres=False):
         """Utils.py:455-514 fill_depth as predict_ros.py:38-41 applies it: uint16 millimetre frame (numpy [H,W] or a

@@ -137,7 +137,7 @@ class Tracker:
         return self.engine.pose_errors(self._model_points, preds, gts)
 
     def recover(self, prev_pose, rgb, depth, trans_radius=0.05, trans_step=0.01, rot_deg=(15.0,), tol_mm=10, top=None, refine=1,
-                points=None, extra=None, facing=False):
+                points=None, extra=None, facing=False, align=0):
         """Extension: look for a lost object near where it was last seen.  The reference re-initialises from an external detector
         (predict.py:539-541); this searches the observed depth frame instead and hands the track back:
           1. the lattice of candidates around prev_pose (recover.pose_lattice; `extra`: a list of poses appended after it) is scored
@@ -154,11 +154,16 @@ class Tracker:
         scorings, so inlier_frac is the share of the VISIBLE surface the sensor confirms and means the same for every object.  The
         lattice then travels as its factors (recover.lattice_factors through Engine.score_pose_grid) and [refined, unrefined] are
         rescored as the diagonal of a 2k x 2k grid.  Needs normals: ``object_normals``, or a ModelPoints handle that carries them
-        as `points`; `extra` cannot be combined with it (extra poses are no product): ValueError."""
+        as `points`; `extra` cannot be combined with it (extra poses are no product): ValueError.
+        align = iters > 0: the top lattice candidates are first aligned to the depth frame (align(): up to `iters` point-to-plane
+        steps of the facing points, Engine.align_poses) and the network, if any, starts from the aligned poses; the final pool is
+        [refined..., aligned..., unaligned...] (refine=0: [aligned..., unaligned...]), scored as before, so the result never scores
+        below the one without alignment.  Needs ``object_normals`` (or a handle with normals as `points`) with or without facing --
+        the scoring of the plain search stays plain.  ``last_recover`` then also keeps aligned and align_rec."""
         if facing:
             if extra is not None and len(extra):
                 raise ValueError("recover: extra poses cannot be combined with facing=True (the lattice is scored as a product)")
-            return self._recover_facing(prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points)
+            return self._recover_facing(prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points, align)
         from .engine import ModelPoints
         from .recover import pose_key, pose_lattice
         if points is None:
@@ -172,6 +177,9 @@ class Tracker:
         else:
             handle, own = self.engine.model_points(points), True
         try:
+            if int(align) > 0:   # the alignment reads normals: the tracker's facing handle, or the caller's own when it carries them
+                with_normals = isinstance(points, ModelPoints) and points.normals is not None
+                facing_handle = points if with_normals else self._facing_handle(None, "recover")
             k = min(8, self.engine.max_batch) if top is None else int(top)
             cands = pose_lattice(prev_pose, trans_radius, trans_step, rot_deg)
             if extra is not None and len(extra):
@@ -180,18 +188,22 @@ class Tracker:
             top_idx, top_fit = self.engine.score_poses(handle, cands, dep, self.K, tol_mm, top=k)
             unrefined = cands[top_idx]
             info = dict(n=len(cands), top_idx=top_idx, top_fit=top_fit, refined=None)
-            if int(refine) < 1:
+            aligned = None
+            if int(align) > 0:
+                aligned, align_rec = self.engine.align_poses(facing_handle, unrefined, dep, self.K, iters=int(align))
+                info.update(aligned=aligned, align_rec=align_rec)
+            if int(refine) < 1 and aligned is None:
                 info.update(final_fit=top_fit[:1].copy(), chosen=0, inlier_frac=float(top_fit["inlier_pts"][0]) / float(top_fit["points"][0]))
                 self.last_recover = info
                 return unrefined[0].copy()
-            refined = unrefined
+            refined = unrefined if aligned is None else aligned
             for _ in range(int(refine)):
                 refined = np.asarray(self.on_track_batch(list(refined), [rgb] * k, [dep] * k), np.float64)
-            final = np.concatenate([refined, unrefined])
+            final = np.concatenate(([refined] if int(refine) >= 1 else []) + ([] if aligned is None else [aligned]) + [unrefined])
             final_fit = self.engine.score_poses(handle, final, dep, self.K, tol_mm)
             keys = pose_key(final_fit)
             chosen = int(np.argmax(keys))             # keys are unique: the lower index wins a tie, and the refined poses come first
-            info.update(refined=refined, final_fit=final_fit, chosen=chosen,
+            info.update(refined=refined if int(refine) >= 1 else None, final_fit=final_fit, chosen=chosen,
                         inlier_frac=float(final_fit["inlier_pts"][chosen]) / float(final_fit["points"][chosen]))
             self.last_recover = info
             return final[chosen].copy()
@@ -238,16 +250,28 @@ class Tracker:
         fit = self.engine.score_pose_grid(handle, poses[:, :3, :3], poses[:, :3, 3], dep, self.K, tol_mm, facing=True)
         return fit[np.arange(m) * m + np.arange(m)]
 
-    def _refine_and_choose(self, handle, unrefined, rgb, dep, tol_mm, refine):
-        """steps 2 and 3 of recover under the facing rule -> (final poses, refined, final_fit, chosen)"""
+    def _refine_and_choose(self, handle, unrefined, rgb, dep, tol_mm, refine, aligned=None):
+        """steps 2 and 3 of recover under the facing rule -> (final poses, refined, final_fit, chosen).  With `aligned` (the
+        unrefined poses after align()) the network starts from those and the pool is [refined..., aligned..., unrefined...];
+        refine < 1 leaves the refined part out (refined is then None)."""
         from .recover import pose_key
         k = len(unrefined)
-        refined = unrefined
+        refined = unrefined if aligned is None else aligned
         for _ in range(int(refine)):
             refined = np.asarray(self.on_track_batch(list(refined), [rgb] * k, [dep] * k), np.float64)
-        final = np.concatenate([refined, unrefined])
+        if int(refine) < 1:
+            refined = None
+        final = np.concatenate(([] if refined is None else [refined]) + ([] if aligned is None else [aligned]) + [unrefined])
         final_fit = self._score_diagonal(handle, final, dep, tol_mm)
-        return final, refined, final_fit, int(np.argmax(pose_key(final_fit)))   # ties prefer the refined pose: the lower index
+        return final, refined, final_fit, int(np.argmax(pose_key(final_fit)))   # ties prefer the earlier part of the pool: the lower index
+
+    def align(self, poses, depth, **kw):
+        """Align n pose hypotheses ([n,4,4]) to the depth frame (HxW uint16 mm): Engine.align_poses on ``object_cloud`` with
+        ``object_normals`` (uploaded at first use and kept) and this tracker's K -> (poses [n,4,4], records [n]); the keywords
+        (gate_mm, iters, min_pairs, damping, stop, sums) are Engine.align_poses'.  Needs ``object_normals``: ValueError otherwise."""
+        handle = self._facing_handle(None, "align")
+        dep = depth if torch.is_tensor(depth) else np.ascontiguousarray(depth, dtype=np.uint16)
+        return self.engine.align_poses(handle, poses, dep, self.K, **kw)
 
     @staticmethod
     def _compose(rots, trans, idx):
@@ -262,7 +286,7 @@ class Tracker:
     def _frac(rec):
         return float(rec["inlier_pts"]) / float(rec["points"]) if int(rec["points"]) else 0.0
 
-    def _recover_facing(self, prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points):
+    def _recover_facing(self, prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points, align=0):
         from .recover import lattice_factors
         handle = self._facing_handle(points, "recover")
         k = min(8, self.engine.max_batch) if top is None else int(top)
@@ -271,16 +295,20 @@ class Tracker:
         top_idx, top_fit = self.engine.score_pose_grid(handle, rots, trans, dep, self.K, tol_mm, facing=True, top=k)
         unrefined = self._compose(rots, trans, top_idx)
         info = dict(n=len(rots) * len(trans), top_idx=top_idx, top_fit=top_fit, refined=None, facing=True)
-        if int(refine) < 1:
+        aligned = None
+        if int(align) > 0:
+            aligned, align_rec = self.engine.align_poses(handle, unrefined, dep, self.K, iters=int(align))
+            info.update(aligned=aligned, align_rec=align_rec)
+        if int(refine) < 1 and aligned is None:
             info.update(final_fit=top_fit[:1].copy(), chosen=0, inlier_frac=self._frac(top_fit[0]))
             self.last_recover = info
             return unrefined[0].copy()
-        final, refined, final_fit, chosen = self._refine_and_choose(handle, unrefined, rgb, dep, tol_mm, refine)
+        final, refined, final_fit, chosen = self._refine_and_choose(handle, unrefined, rgb, dep, tol_mm, refine, aligned)
         info.update(refined=refined, final_fit=final_fit, chosen=chosen, inlier_frac=self._frac(final_fit[chosen]))
         self.last_recover = info
         return final[chosen].copy()
 
-    def acquire(self, rgb, depth, roi=None, views=40, inplane=12, stride=16, behind_m=0.03, tol_mm=10, top=None, refine=1):
+    def acquire(self, rgb, depth, roi=None, views=40, inplane=12, stride=16, behind_m=0.03, tol_mm=10, top=None, refine=1, align=0):
         """Extension with no reference counterpart (the reference takes its first pose from a file, from ground truth or from
         PoseCNN): find the object in a frame with NO pose to start from.
           1. recover.rotation_grid(views, inplane) x recover.depth_seeds(depth, K, stride, behind_m, roi) -- rotations that cover
@@ -295,7 +323,11 @@ class Tracker:
         turn, and the true rotation may come second or fourth.  That is why ``last_acquire`` keeps ALL `top` hypotheses and not
         just the winner: n, n_rot, n_trans, stage1_idx, stage1_fit, hypotheses (their poses), local, local_idx, local_fit (step 2),
         refined, final_fit, chosen, inlier_frac (= inlier_pts / facing points of the returned pose).  Use colour, the network's
-        own fit check (fit_check) or a few tracked frames to tell them apart.  Needs ``object_normals``."""
+        own fit check (fit_check) or a few tracked frames to tell them apart.  Needs ``object_normals``.
+        align = iters > 0: the hypotheses of step 2 are aligned to the depth frame before step 3 (align(): up to `iters`
+        point-to-plane steps each, one device call for all of them); the network, if any, starts from the aligned poses and the
+        pool of step 3 is [refined..., aligned..., unaligned...] (refine=0: [aligned..., unaligned...]).  ``last_acquire`` then
+        also keeps aligned and align_rec.  The lattices end 10 mm and 15 degrees apart; alignment ends on the surface."""
         from .recover import depth_seeds, lattice_factors, pose_key, rotation_grid
         from ._lib import POSE_SEARCH_MAX_POSES, POINT_FIT_DTYPE
         handle = self._facing_handle(None, "acquire")
@@ -318,12 +350,16 @@ class Tracker:
             local[i], local_idx[i], local_fit[i] = self._compose(lr, lt, li)[0], li[0], lf[0]
         info = dict(n=n, n_rot=len(rots), n_trans=len(seeds), stage1_idx=idx1, stage1_fit=fit1, hypotheses=hyps, local=local,
                     local_idx=local_idx, local_fit=local_fit, refined=None)
-        if int(refine) < 1:
+        aligned = None
+        if int(align) > 0:
+            aligned, align_rec = self.engine.align_poses(handle, local, dep, self.K, iters=int(align))
+            info.update(aligned=aligned, align_rec=align_rec)
+        if int(refine) < 1 and aligned is None:
             chosen = int(np.argmax(pose_key(local_fit)))
             info.update(final_fit=local_fit.copy(), chosen=chosen, inlier_frac=self._frac(local_fit[chosen]))
             self.last_acquire = info
             return local[chosen].copy()
-        final, refined, final_fit, chosen = self._refine_and_choose(handle, local, rgb, dep, tol_mm, refine)
+        final, refined, final_fit, chosen = self._refine_and_choose(handle, local, rgb, dep, tol_mm, refine, aligned)
         info.update(refined=refined, final_fit=final_fit, chosen=chosen, inlier_frac=self._frac(final_fit[chosen]))
         self.last_acquire = info
         return final[chosen].copy()
