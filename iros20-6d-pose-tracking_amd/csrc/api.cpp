@@ -140,10 +140,8 @@ struct se3tn_ctx {
   int fit_tol = 0, fit_last_n = 0, fit_cap = 0;
   DeviceBuf<uint8_t> fit_rgb; DeviceBuf<uint16_t> fit_depth;
   PinnedBuf<se3tn_fit> fit_host;
-  // se3tn_pose_errors_host: pinned staging [pred | gt | add | adds] (pose_errors_plan.h: pe_stage_*) for pe_cap pairs and its device mirror
-  PinnedBuf<double> pe_host; DeviceBuf<double> pe_dev; int pe_cap = 0;
-  // se3tn_search_poses_host / se3tn_search_pose_grid_host / se3tn_align_poses_host (all synchronous): pinned staging of ps_cap bytes, laid out per call
-  // (pose_search_plan.h: PsStage, pose_grid_plan.h: PgStage), and its device mirror
+  // the synchronous _host entry points of the pose family (StagedCall): pinned staging of ps_cap bytes and its device mirror, laid out
+  // per call (pose_errors_plan.h: pe_stage_*, pose_search_plan.h: PsStage, pose_grid_plan.h: PgStage, pose_align_plan.h: PaStage)
   PinnedBuf<unsigned char> ps_host; DeviceBuf<unsigned char> ps_dev; size_t ps_cap = 0;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive before the next one
   DeviceBuf<int> tail_arrive;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
@@ -371,6 +369,78 @@ static int grow_now_or_refuse(se3tn_ctx* c, const char* fn, bool fill, const cha
                                    " inside a stream capture: call se3tn_reserve(ctx, H, W) first");
   return fill ? reserve_fill_depth(c, px) : reserve_zbuf(c, px);
 }
+
+// ---- what the entry points of the pose family share ------------------------------------------------------------------------------------
+// The refusals, piece by piece; each entry point composes them in its own order
+static int refuse_if(bool bad, int code, const char* who, const std::string& msg) { return bad ? fail(code, std::string(who) + ": " + msg) : SE3TN_OK; }
+static int null_argument(const char* who) { return refuse_if(true, SE3TN_E_ARG, who, "NULL argument"); }
+static int device_check(const char* who, const se3tn_ctx* c, const char* verb) {
+  return refuse_if(c->device < 0, SE3TN_E_ARG, who, std::string("host-only context (device = -1) has no device to ") + verb + " on");
+}
+static int same_device_check(const char* who, const se3tn_ctx* c, const se3tn_points* p) {
+  return refuse_if(p->device != c->device, SE3TN_E_ARG, who, "the points live on another device than the context");
+}
+static int normals_check(const char* who, const se3tn_points* p, const char* lead) {
+  return refuse_if(!p->nrm, SE3TN_E_STATE, who, std::string(lead) + "the points handle has no normals (se3tn_points_set_normals)");
+}
+static int frame_check(const char* who, int H, int W) { return refuse_if(H < 1 || W < 1, SE3TN_E_ARG, who, "empty frame (H or W < 1)"); }
+static int mm_check(const char* who, const char* name, int mm) {   // tol_mm, gate_mm
+  return refuse_if(mm < 1 || mm > 65535, SE3TN_E_ARG, who, std::string(name) + " = " + std::to_string(mm) + " outside [1, 65535]");
+}
+static int count_check(const char* who, int n, int most, const char* most_name) {
+  return refuse_if(n < 1 || n > most, SE3TN_E_ARG, who,
+                   "n = " + std::to_string(n) + " outside [1, " + most_name + " = " + std::to_string(most) + "]");
+}
+// what a _host entry point asks of its arrays: the first `used` of every `stride` elements of a (and of b, if given) are finite.
+// (A row is tested without a branch per element: a branch each, or a modulus to find the row, costs 20-170 us per 9,317 poses.)
+static int finite_check(const char* who, const char* noun, const double* a, const double* b, size_t n, int stride, int used) {
+  for (size_t r = 0; r < n; ++r) {
+    bool bad = false;
+    for (int k = 0; k < used; ++k) bad |= !std::isfinite(a[r * stride + k]) || (b && !std::isfinite(b[r * stride + k]));
+    if (bad) return refuse_if(true, SE3TN_E_ARG, who, std::string(noun) + " " + std::to_string(r) + " has an entry that is not finite");
+  }
+  return SE3TN_OK;
+}
+static int finite_K_check(const char* who, const double K[9]) {
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(K[i])) return refuse_if(true, SE3TN_E_ARG, who, "K entry " + std::to_string(i) + " is not finite");
+  return SE3TN_OK;
+}
+// One synchronous _host call on the context's staging pair (ps_host / ps_dev), which is laid out for THIS call: the upload is one
+// contiguous run from 0, and so is the read-back.  The caller copies its inputs to h between grow() and upload(), enqueues its
+// launches on d between upload() and finish(), and copies its results from h after finish().  Nothing outlives the call, so no
+// call sees another's bytes.
+struct StagedCall {
+  se3tn_ctx* c;
+  const char* who;
+  hipStream_t st;
+  unsigned char* h = nullptr;   // pinned host
+  unsigned char* d = nullptr;   // its device mirror
+  int refuse_capture() const { return refuse_if(stream_is_capturing(st), SE3TN_E_STATE, who, "the call is synchronous, it cannot be captured"); }
+  int grow(size_t bytes) {
+    if (bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
+      DeviceGuard dg(c->device);
+      if (int rc = begin_growth(dg)) return rc;
+      c->ps_cap = 0;
+      HIPCHK(c->ps_host.alloc(bytes));
+      HIPCHK(c->ps_dev.alloc(bytes));
+      c->ps_cap = bytes;
+    }
+    h = c->ps_host.get();
+    d = c->ps_dev.get();
+    return SE3TN_OK;
+  }
+  int upload(size_t bytes) const {
+    HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+    return SE3TN_OK;
+  }
+  int finish(size_t at, size_t bytes) const {   // the read-back of [at, at + bytes), and the wait
+    HIPCHK(hipMemcpyAsync(h + at, d + at, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SE3TN_OK;
+  }
+  template <class T> T* dev(size_t at) const { return reinterpret_cast<T*>(d + at); }
+};
 
 extern "C" {
 
@@ -1606,7 +1676,7 @@ static int pose_errors_enqueue(const se3tn_points* p, int n, const double* pred,
 static int pose_errors_check(const char* who, const se3tn_ctx* c, const se3tn_points* p, int n, const void* pred, const void* gt,
                              const void* add, const void* adds) {
   if (!c || c->device < 0 || !p) return fail(SE3TN_E_ARG, std::string(who) + ": NULL or host-only context, or NULL points");
-  if (p->device != c->device) return fail(SE3TN_E_ARG, std::string(who) + ": the points live on another device than the context");
+  if (int rc = same_device_check(who, c, p)) return rc;
   if (n < 1) return fail(SE3TN_E_ARG, std::string(who) + ": n < 1");
   if (!pred || !gt) return fail(SE3TN_E_ARG, std::string(who) + ": NULL poses");
   if (!add && !adds) return fail(SE3TN_E_ARG, std::string(who) + ": both outputs NULL");
@@ -1621,34 +1691,25 @@ int se3tn_pose_errors(se3tn_ctx* c, const se3tn_points* p, int n, const double* 
 
 int se3tn_pose_errors_host(se3tn_ctx* c, const se3tn_points* p, int n, const double* pred, const double* gt, double* add_out,
                            double* adds_out, void* stream) {
-  if (int rc = pose_errors_check("se3tn_pose_errors_host", c, p, n, pred, gt, add_out, adds_out)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_pose_errors_host: the call is synchronous, it cannot be captured");
-  for (size_t i = 0; i < (size_t)n * 16; ++i)
-    if (!std::isfinite(pred[i]) || !std::isfinite(gt[i]))
-      return fail(SE3TN_E_ARG, "se3tn_pose_errors_host: pose " + std::to_string(i / 16) + " has an entry that is not finite");
-  if (n > c->pe_cap) {   // first / larger call: the staging belongs to the context's device
-    DeviceGuard dg(c->device);
-    if (int rc = begin_growth(dg)) return rc;
-    c->pe_cap = 0;
-    HIPCHK(c->pe_host.alloc(pe_stage_doubles(n)));
-    HIPCHK(c->pe_dev.alloc(pe_stage_doubles(n)));
-    c->pe_cap = n;
-  }
-  // the staging is laid out for THIS n (pe_stage_*): poses and results are each one contiguous run
-  double* h = c->pe_host.get();
-  double* d = c->pe_dev.get();
+  const char* who = "se3tn_pose_errors_host";
+  if (int rc = pose_errors_check(who, c, p, n, pred, gt, add_out, adds_out)) return rc;
+  StagedCall sc{c, who, (hipStream_t)stream};
+  if (int rc = sc.refuse_capture()) return rc;
+  if (int rc = finite_check(who, "pose", pred, gt, (size_t)n, 16, 16)) return rc;
+  if (int rc = sc.grow(sizeof(double) * pe_stage_doubles(n))) return rc;
+  // pe_stage_*, in doubles: poses and results are each one contiguous run
+  double* h = reinterpret_cast<double*>(sc.h);
+  double* d = sc.dev<double>(0);
   std::memcpy(h, pred, sizeof(double) * 16 * (size_t)n);
   std::memcpy(h + pe_stage_gt(n), gt, sizeof(double) * 16 * (size_t)n);
-  HIPCHK(hipMemcpyAsync(d, h, sizeof(double) * 32 * (size_t)n, hipMemcpyHostToDevice, st));
+  if (int rc = sc.upload(sizeof(double) * pe_stage_add(n))) return rc;
   if (int rc = pose_errors_enqueue(p, n, d, d + pe_stage_gt(n), add_out ? d + pe_stage_add(n) : nullptr,
-                                   adds_out ? d + pe_stage_adds(n) : nullptr, st))
+                                   adds_out ? d + pe_stage_adds(n) : nullptr, sc.st))
     return rc;
   // one read-back: [add | adds], or the one that was asked for
   const size_t r0 = add_out ? pe_stage_add(n) : pe_stage_adds(n);
   const size_t rn = (size_t)n * ((add_out ? 1 : 0) + (adds_out ? 1 : 0));
-  HIPCHK(hipMemcpyAsync(h + r0, d + r0, sizeof(double) * rn, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (int rc = sc.finish(sizeof(double) * r0, sizeof(double) * rn)) return rc;
   if (add_out) std::memcpy(add_out, h + pe_stage_add(n), sizeof(double) * (size_t)n);
   if (adds_out) std::memcpy(adds_out, h + pe_stage_adds(n), sizeof(double) * (size_t)n);
   return SE3TN_OK;
@@ -1657,18 +1718,15 @@ int se3tn_pose_errors_host(se3tn_ctx* c, const se3tn_points* p, int n, const dou
 // ---- n candidate poses against one depth frame, the best k ----------------------------------------------------------------------------
 // NULL pointers and a host-only context first (ok_ptrs: every pointer of the call), then the numbers
 static int pose_search_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, bool with_points, int n) {
-  if (!c || !ok_ptrs || (with_points && !p)) return fail(SE3TN_E_ARG, std::string(who) + ": NULL argument");
-  if (c->device < 0) return fail(SE3TN_E_ARG, std::string(who) + ": host-only context (device = -1) has no device to search on");
-  if (with_points && p->device != c->device) return fail(SE3TN_E_ARG, std::string(who) + ": the points live on another device than the context");
-  if (n < 1 || n > PS_MAX_POSES)
-    return fail(SE3TN_E_ARG, std::string(who) + ": n = " + std::to_string(n) + " outside [1, SE3TN_POSE_SEARCH_MAX_POSES = " +
-                                 std::to_string(PS_MAX_POSES) + "]");
-  return SE3TN_OK;
+  if (!c || !ok_ptrs || (with_points && !p)) return null_argument(who);
+  if (int rc = device_check(who, c, "search")) return rc;
+  if (with_points)
+    if (int rc = same_device_check(who, c, p)) return rc;
+  return count_check(who, n, PS_MAX_POSES, "SE3TN_POSE_SEARCH_MAX_POSES");
 }
 static int pose_score_check(const char* who, int H, int W, int tol_mm) {
-  if (tol_mm < 1 || tol_mm > 65535) return fail(SE3TN_E_ARG, std::string(who) + ": tol_mm = " + std::to_string(tol_mm) + " outside [1, 65535]");
-  if (H < 1 || W < 1) return fail(SE3TN_E_ARG, std::string(who) + ": empty frame (H or W < 1)");
-  return SE3TN_OK;
+  if (int rc = mm_check(who, "tol_mm", tol_mm)) return rc;
+  return frame_check(who, H, W);
 }
 static int pose_rank_check(const char* who, int n, int k) {
   const int kmax = n < PS_RANK_MAX ? n : PS_RANK_MAX;
@@ -1683,6 +1741,14 @@ static PoseScoreArgs pose_score_args(const se3tn_points* p, const double* poses,
   a.pts = p->xyz.get(); a.P = p->P; a.poses = poses; a.depth = depth; a.H = H; a.W = W; a.tol = tol_mm; a.out = out;
   for (int i = 0; i < 9; ++i) a.K[i] = K[i];
   return a;
+}
+// the tail of both searches: the k best of the n records at s.fit, read back and copied out
+static int rank_and_finish(const StagedCall& sc, const PsRankTail& s, int n, int k, int32_t* idx_out, se3tn_point_fit* fit_out) {
+  HIPCHK(launch_pose_rank(sc.dev<se3tn_point_fit>(s.fit), n, k, sc.dev<int32_t>(s.idx), sc.dev<se3tn_point_fit>(s.top_fit), sc.st));
+  if (int rc = sc.finish(s.top_fit, s.readback_bytes)) return rc;
+  std::memcpy(fit_out, sc.h + s.top_fit, sizeof(se3tn_point_fit) * (size_t)k);
+  std::memcpy(idx_out, sc.h + s.idx, sizeof(int32_t) * (size_t)k);
+  return SE3TN_OK;
 }
 
 int se3tn_score_poses(se3tn_ctx* c, const se3tn_points* p, int n, const double* poses_dev, const uint16_t* depth_dev, int H, int W,
@@ -1708,37 +1774,18 @@ int se3tn_search_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const do
   if (int rc = pose_search_check(who, c, poses && depth && K && idx_out && fit_out, p, true, n)) return rc;
   if (int rc = pose_score_check(who, H, W, tol_mm)) return rc;
   if (int rc = pose_rank_check(who, n, k)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_search_poses_host: the call is synchronous, it cannot be captured");
-  for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(K[i])) return fail(SE3TN_E_ARG, "se3tn_search_poses_host: K entry " + std::to_string(i) + " is not finite");
-  for (size_t i = 0; i < (size_t)n * 16; ++i)
-    if (!std::isfinite(poses[i]))
-      return fail(SE3TN_E_ARG, "se3tn_search_poses_host: pose " + std::to_string(i / 16) + " has an entry that is not finite");
+  StagedCall sc{c, who, (hipStream_t)stream};
+  if (int rc = sc.refuse_capture()) return rc;
+  if (int rc = finite_K_check(who, K)) return rc;
+  if (int rc = finite_check(who, "pose", poses, nullptr, (size_t)n, 16, 16)) return rc;
   const PsStage s = ps_stage(n, H, W, k);
-  if (s.bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
-    DeviceGuard dg(c->device);
-    if (int rc = begin_growth(dg)) return rc;
-    c->ps_cap = 0;
-    HIPCHK(c->ps_host.alloc(s.bytes));
-    HIPCHK(c->ps_dev.alloc(s.bytes));
-    c->ps_cap = s.bytes;
-  }
-  // the staging is laid out for THIS (n, H, W, k): the upload is one contiguous run, and so is the read-back
-  unsigned char* h = c->ps_host.get();
-  unsigned char* d = c->ps_dev.get();
-  std::memcpy(h + s.poses, poses, sizeof(double) * 16 * (size_t)n);
-  std::memcpy(h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
-  HIPCHK(hipMemcpyAsync(d, h, s.upload_bytes, hipMemcpyHostToDevice, st));
-  se3tn_point_fit* fit_d = reinterpret_cast<se3tn_point_fit*>(d + s.fit);
-  HIPCHK(launch_pose_score(pose_score_args(p, reinterpret_cast<const double*>(d + s.poses), reinterpret_cast<const uint16_t*>(d + s.depth),
-                                           H, W, K, tol_mm, fit_d), n, st));
-  HIPCHK(launch_pose_rank(fit_d, n, k, reinterpret_cast<int32_t*>(d + s.idx), reinterpret_cast<se3tn_point_fit*>(d + s.top_fit), st));
-  HIPCHK(hipMemcpyAsync(h + s.top_fit, d + s.top_fit, s.readback_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(fit_out, h + s.top_fit, sizeof(se3tn_point_fit) * (size_t)k);
-  std::memcpy(idx_out, h + s.idx, sizeof(int32_t) * (size_t)k);
-  return SE3TN_OK;
+  if (int rc = sc.grow(s.bytes)) return rc;
+  std::memcpy(sc.h + s.poses, poses, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(sc.h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
+  if (int rc = sc.upload(s.upload_bytes)) return rc;
+  HIPCHK(launch_pose_score(pose_score_args(p, sc.dev<double>(s.poses), sc.dev<uint16_t>(s.depth), H, W, K, tol_mm,
+                                           sc.dev<se3tn_point_fit>(s.fit)), n, sc.st));
+  return rank_and_finish(sc, s, n, k, idx_out, fit_out);
 }
 
 // ---- n_rot x n_trans candidate poses [R_r | t_t] against one depth frame, the best k ----------------------------------------------
@@ -1746,17 +1793,15 @@ int se3tn_search_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const do
 // device): every refusal has its own message, on a host-only context too
 static int pose_grid_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, int n_rot, int n_trans, int H, int W,
                            int tol_mm, int facing) {
-  if (!c || !ok_ptrs || !p) return fail(SE3TN_E_ARG, std::string(who) + ": NULL argument");
+  if (!c || !ok_ptrs || !p) return null_argument(who);
   if (n_rot < 1 || n_trans < 1 || (long long)n_rot * (long long)n_trans > (long long)PS_MAX_POSES)
     return fail(SE3TN_E_ARG, std::string(who) + ": n_rot = " + std::to_string(n_rot) + ", n_trans = " + std::to_string(n_trans) +
                                  ": both must be >= 1 and their product <= SE3TN_POSE_SEARCH_MAX_POSES = " + std::to_string(PS_MAX_POSES));
   if (int rc = pose_score_check(who, H, W, tol_mm)) return rc;
   if (facing != 0 && facing != 1) return fail(SE3TN_E_ARG, std::string(who) + ": facing = " + std::to_string(facing) + " is neither 0 nor 1");
-  if (c->device < 0) return fail(SE3TN_E_ARG, std::string(who) + ": host-only context (device = -1) has no device to search on");
-  if (p->device != c->device) return fail(SE3TN_E_ARG, std::string(who) + ": the points live on another device than the context");
-  if (facing && !p->nrm)
-    return fail(SE3TN_E_STATE, std::string(who) + ": facing = 1 but the points handle has no normals (se3tn_points_set_normals)");
-  return SE3TN_OK;
+  if (int rc = device_check(who, c, "search")) return rc;
+  if (int rc = same_device_check(who, c, p)) return rc;
+  return facing ? normals_check(who, p, "facing = 1 but ") : SE3TN_OK;
 }
 static PoseGridArgs pose_grid_args(const se3tn_points* p, const double* rots, int n_trans, const double* trans, const uint16_t* depth, int H,
                                    int W, const double K[9], int tol_mm, int facing, se3tn_point_fit* out) {
@@ -1784,41 +1829,20 @@ int se3tn_search_pose_grid_host(se3tn_ctx* c, const se3tn_points* p, int n_rot, 
   if (int rc = pose_grid_check(who, c, rots && trans && depth && K && idx_out && fit_out, p, n_rot, n_trans, H, W, tol_mm, facing)) return rc;
   const int n = n_rot * n_trans;
   if (int rc = pose_rank_check(who, n, k)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_search_pose_grid_host: the call is synchronous, it cannot be captured");
-  for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(K[i])) return fail(SE3TN_E_ARG, "se3tn_search_pose_grid_host: K entry " + std::to_string(i) + " is not finite");
-  for (size_t i = 0; i < (size_t)n_rot * 9; ++i)
-    if (!std::isfinite(rots[i]))
-      return fail(SE3TN_E_ARG, "se3tn_search_pose_grid_host: rotation " + std::to_string(i / 9) + " has an entry that is not finite");
-  for (size_t i = 0; i < (size_t)n_trans * 3; ++i)
-    if (!std::isfinite(trans[i]))
-      return fail(SE3TN_E_ARG, "se3tn_search_pose_grid_host: translation " + std::to_string(i / 3) + " has an entry that is not finite");
+  StagedCall sc{c, who, (hipStream_t)stream};
+  if (int rc = sc.refuse_capture()) return rc;
+  if (int rc = finite_K_check(who, K)) return rc;
+  if (int rc = finite_check(who, "rotation", rots, nullptr, (size_t)n_rot, 9, 9)) return rc;
+  if (int rc = finite_check(who, "translation", trans, nullptr, (size_t)n_trans, 3, 3)) return rc;
   const PgStage s = pg_stage(n_rot, n_trans, H, W, k);
-  if (s.bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
-    DeviceGuard dg(c->device);
-    if (int rc = begin_growth(dg)) return rc;
-    c->ps_cap = 0;
-    HIPCHK(c->ps_host.alloc(s.bytes));
-    HIPCHK(c->ps_dev.alloc(s.bytes));
-    c->ps_cap = s.bytes;
-  }
-  // the staging is laid out for THIS (n_rot, n_trans, H, W, k): the upload is one contiguous run, and so is the read-back
-  unsigned char* h = c->ps_host.get();
-  unsigned char* d = c->ps_dev.get();
-  std::memcpy(h + s.rots, rots, sizeof(double) * 9 * (size_t)n_rot);
-  std::memcpy(h + s.trans, trans, sizeof(double) * 3 * (size_t)n_trans);
-  std::memcpy(h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
-  HIPCHK(hipMemcpyAsync(d, h, s.upload_bytes, hipMemcpyHostToDevice, st));
-  se3tn_point_fit* fit_d = reinterpret_cast<se3tn_point_fit*>(d + s.fit);
-  HIPCHK(launch_pose_grid(pose_grid_args(p, reinterpret_cast<const double*>(d + s.rots), n_trans, reinterpret_cast<const double*>(d + s.trans),
-                                         reinterpret_cast<const uint16_t*>(d + s.depth), H, W, K, tol_mm, facing, fit_d), n_rot, st));
-  HIPCHK(launch_pose_rank(fit_d, n, k, reinterpret_cast<int32_t*>(d + s.idx), reinterpret_cast<se3tn_point_fit*>(d + s.top_fit), st));
-  HIPCHK(hipMemcpyAsync(h + s.top_fit, d + s.top_fit, s.readback_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(fit_out, h + s.top_fit, sizeof(se3tn_point_fit) * (size_t)k);
-  std::memcpy(idx_out, h + s.idx, sizeof(int32_t) * (size_t)k);
-  return SE3TN_OK;
+  if (int rc = sc.grow(s.bytes)) return rc;
+  std::memcpy(sc.h + s.rots, rots, sizeof(double) * 9 * (size_t)n_rot);
+  std::memcpy(sc.h + s.trans, trans, sizeof(double) * 3 * (size_t)n_trans);
+  std::memcpy(sc.h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
+  if (int rc = sc.upload(s.upload_bytes)) return rc;
+  HIPCHK(launch_pose_grid(pose_grid_args(p, sc.dev<double>(s.rots), n_trans, sc.dev<double>(s.trans), sc.dev<uint16_t>(s.depth), H, W, K,
+                                         tol_mm, facing, sc.dev<se3tn_point_fit>(s.fit)), n_rot, sc.st));
+  return rank_and_finish(sc, s, n, k, idx_out, fit_out);
 }
 
 // ---- n pose hypotheses aligned to one depth frame: point-to-plane steps, all iterations in one launch ----------------------------------
@@ -1827,10 +1851,9 @@ int se3tn_search_pose_grid_host(se3tn_ctx* c, const se3tn_points* p, int n_rot, 
 static int pose_align_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, int n, int H, int W,
                             const se3tn_align_params* q) {
   const std::string w(who);
-  if (!c || !ok_ptrs || !p || !q) return fail(SE3TN_E_ARG, w + ": NULL argument");
-  if (n < 1 || n > PA_MAX_POSES)
-    return fail(SE3TN_E_ARG, w + ": n = " + std::to_string(n) + " outside [1, SE3TN_POSE_ALIGN_MAX_POSES = " + std::to_string(PA_MAX_POSES) + "]");
-  if (q->gate_mm < 1 || q->gate_mm > 65535) return fail(SE3TN_E_ARG, w + ": gate_mm = " + std::to_string(q->gate_mm) + " outside [1, 65535]");
+  if (!c || !ok_ptrs || !p || !q) return null_argument(who);
+  if (int rc = count_check(who, n, PA_MAX_POSES, "SE3TN_POSE_ALIGN_MAX_POSES")) return rc;
+  if (int rc = mm_check(who, "gate_mm", q->gate_mm)) return rc;
   if (q->iters < 1 || q->iters > PA_MAX_ITERS)
     return fail(SE3TN_E_ARG, w + ": iters = " + std::to_string(q->iters) + " outside [1, SE3TN_POSE_ALIGN_MAX_ITERS = " +
                                  std::to_string(PA_MAX_ITERS) + "]");
@@ -1839,11 +1862,10 @@ static int pose_align_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, c
   if (q->_reserved != 0) return fail(SE3TN_E_ARG, w + ": params._reserved = " + std::to_string(q->_reserved) + " is not 0");
   if (!(q->damping >= 0.0) || !std::isfinite(q->damping)) return fail(SE3TN_E_ARG, w + ": damping is negative or not finite");
   if (!(q->stop >= 0.0) || !std::isfinite(q->stop)) return fail(SE3TN_E_ARG, w + ": stop is negative or not finite");
-  if (H < 1 || W < 1) return fail(SE3TN_E_ARG, w + ": empty frame (H or W < 1)");
-  if (c->device < 0) return fail(SE3TN_E_ARG, w + ": host-only context (device = -1) has no device to align on");
-  if (p->device != c->device) return fail(SE3TN_E_ARG, w + ": the points live on another device than the context");
-  if (!p->nrm) return fail(SE3TN_E_STATE, w + ": the points handle has no normals (se3tn_points_set_normals)");
-  return SE3TN_OK;
+  if (int rc = frame_check(who, H, W)) return rc;
+  if (int rc = device_check(who, c, "align")) return rc;
+  if (int rc = same_device_check(who, c, p)) return rc;
+  return normals_check(who, p, "");
 }
 static PoseAlignArgs pose_align_args(const se3tn_points* p, const double* poses, const uint16_t* depth, int H, int W, const double K[9],
                                      const se3tn_align_params* q, double* poses_out, se3tn_align_rec* rec, int64_t* sums) {
@@ -1869,36 +1891,21 @@ int se3tn_align_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const dou
                            int64_t* sums_out, void* stream) {
   const char* who = "se3tn_align_poses_host";
   if (int rc = pose_align_check(who, c, poses && depth && K && poses_out && rec_out, p, n, H, W, params)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (stream_is_capturing(st)) return fail(SE3TN_E_STATE, "se3tn_align_poses_host: the call is synchronous, it cannot be captured");
-  for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(K[i])) return fail(SE3TN_E_ARG, "se3tn_align_poses_host: K entry " + std::to_string(i) + " is not finite");
-  for (size_t i = 0; i < (size_t)n * 16; ++i)
-    if (i % 16 < 12 && !std::isfinite(poses[i]))
-      return fail(SE3TN_E_ARG, "se3tn_align_poses_host: pose " + std::to_string(i / 16) + " has an entry that is not finite");
+  StagedCall sc{c, who, (hipStream_t)stream};
+  if (int rc = sc.refuse_capture()) return rc;
+  if (int rc = finite_K_check(who, K)) return rc;
+  if (int rc = finite_check(who, "pose", poses, nullptr, (size_t)n, 16, 12)) return rc;   // row 3 is not read
   const PaStage s = pa_stage(n, H, W, sums_out ? 1 : 0);
-  if (s.bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
-    DeviceGuard dg(c->device);
-    if (int rc = begin_growth(dg)) return rc;
-    c->ps_cap = 0;
-    HIPCHK(c->ps_host.alloc(s.bytes));
-    HIPCHK(c->ps_dev.alloc(s.bytes));
-    c->ps_cap = s.bytes;
-  }
-  // the staging is laid out for THIS (n, H, W): the upload is one contiguous run, and so is the read-back
-  unsigned char* h = c->ps_host.get();
-  unsigned char* d = c->ps_dev.get();
-  std::memcpy(h + s.poses, poses, sizeof(double) * 16 * (size_t)n);
-  std::memcpy(h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
-  HIPCHK(hipMemcpyAsync(d, h, s.upload_bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(launch_pose_align(pose_align_args(p, reinterpret_cast<const double*>(d + s.poses), reinterpret_cast<const uint16_t*>(d + s.depth), H, W,
-                                           K, params, reinterpret_cast<double*>(d + s.poses_out), reinterpret_cast<se3tn_align_rec*>(d + s.rec),
-                                           sums_out ? reinterpret_cast<int64_t*>(d + s.sums) : nullptr), n, st));
-  HIPCHK(hipMemcpyAsync(h + s.poses_out, d + s.poses_out, s.readback_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(poses_out, h + s.poses_out, sizeof(double) * 16 * (size_t)n);
-  std::memcpy(rec_out, h + s.rec, sizeof(se3tn_align_rec) * (size_t)n);
-  if (sums_out) std::memcpy(sums_out, h + s.sums, sizeof(int64_t) * SE3TN_POSE_ALIGN_SUMS * (size_t)n);
+  if (int rc = sc.grow(s.bytes)) return rc;
+  std::memcpy(sc.h + s.poses, poses, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(sc.h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
+  if (int rc = sc.upload(s.upload_bytes)) return rc;
+  HIPCHK(launch_pose_align(pose_align_args(p, sc.dev<double>(s.poses), sc.dev<uint16_t>(s.depth), H, W, K, params, sc.dev<double>(s.poses_out),
+                                           sc.dev<se3tn_align_rec>(s.rec), sums_out ? sc.dev<int64_t>(s.sums) : nullptr), n, sc.st));
+  if (int rc = sc.finish(s.poses_out, s.readback_bytes)) return rc;
+  std::memcpy(poses_out, sc.h + s.poses_out, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(rec_out, sc.h + s.rec, sizeof(se3tn_align_rec) * (size_t)n);
+  if (sums_out) std::memcpy(sums_out, sc.h + s.sums, sizeof(int64_t) * SE3TN_POSE_ALIGN_SUMS * (size_t)n);
   return SE3TN_OK;
 }
 

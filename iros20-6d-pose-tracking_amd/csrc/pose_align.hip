@@ -33,19 +33,13 @@ __global__ __launch_bounds__(PA_THREADS) void pose_align_kernel(const PoseAlignA
   if (t < 12) sp[t] = a.poses[pose * 16 + t];   // rows 0-2: read before anything is written, so poses_out may be poses
   if (t == 0) done = 0;
   __syncthreads();
-  PaFrame f;
-  f.depth = a.depth; f.H = a.H; f.W = a.W;
-  f.k0 = a.K[0]; f.k2 = a.K[2]; f.k4 = a.K[4]; f.k5 = a.K[5];
-  f.gate = (double)a.p.gate_mm;
+  const DepthFrame f = depth_frame(a.depth, a.H, a.W, a.K);
+  const double gate = (double)a.p.gate_mm;
   se3tn_align_rec rec;   // thread 0's
   rec.iterations = 0u; rec.status = SE3TN_ALIGN_ITERS; rec.pairs = 0u; rec.facing_pts = 0u; rec.sum_r2 = 0;
   rec.pairs0 = 0u; rec._reserved = 0u; rec.sum_r2_0 = 0;
   for (int it = 0; it < a.p.iters; ++it) {
-    PaPose T;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      T.r[i][0] = sp[4 * i]; T.r[i][1] = sp[4 * i + 1]; T.r[i][2] = sp[4 * i + 2]; T.t[i] = sp[4 * i + 3];
-    }
+    Rigid T = load_pose(sp);
     int64_t S[PA_SUMS];
 #pragma unroll
     for (int w = 0; w < PA_SUMS; ++w) S[w] = 0;
@@ -54,7 +48,7 @@ __global__ __launch_bounds__(PA_THREADS) void pose_align_kernel(const PoseAlignA
       const double* x = a.pts + 3 * (size_t)j;
       const double* n = a.nrm + 3 * (size_t)j;
       double J[6], r;
-      const int k = pa_point(T, f, x[0], x[1], x[2], n[0], n[1], n[2], J, r);
+      const int k = pa_point(T, f, gate, x[0], x[1], x[2], n[0], n[1], n[2], J, r);
       facing += k & 1;
       if (k & 2) {
         pairs += 1;

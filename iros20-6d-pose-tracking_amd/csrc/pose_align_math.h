@@ -1,5 +1,6 @@
-// The arithmetic of se3tn_align_poses (include/se3tracknet.h states the rule), host and device: the terms of one model point, their
-// quantisation, the 6 x 6 solve and the Cayley update.  pose_align.hip runs these statements on the device and
+// The arithmetic of se3tn_align_poses (include/se3tracknet.h states the rule), host and device: the terms of one model point (which
+// pixel it pairs with is the rule of pose_point_rule.h), their quantisation, the 6 x 6 solve and the Cayley update.  pose_align.hip
+// runs these statements on the device and
 // tests/c_abi/pose_align_check.cpp runs the very same ones on the host, so the two can be held to each other and to the numpy oracle
 // (tests/pose_align_oracle.py) word for word.  Whoever includes this compiles with -ffp-contract=off: every operation below is
 // rounded once, in the order written.  No HIP header is needed to read it.
@@ -7,6 +8,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "pose_point_rule.h"
 #include "pose_search_plan.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -21,39 +23,23 @@ constexpr int PA_SUMS = SE3TN_POSE_ALIGN_SUMS;   // 21 words of S_A (i <= j, row
 constexpr int PA_B0 = 21, PA_E = 27;
 static_assert(PA_SUMS == 28, "21 + 6 + 1");
 
-struct PaPose {   // rows 0-2 of a row-major 4 x 4 pose
-  double r[3][3], t[3];
-};
-struct PaFrame {   // the observed frame and the camera
-  const uint16_t* depth;   // [H,W] millimetres
-  int H, W;
-  double k0, k2, k4, k5;   // K[0], K[2], K[4], K[5]
-  double gate;             // millimetres
-};
-
 // fx(v) = (int64) rint(min(max(v, -256), 256) * 2^32); fmax / fmin ignore a NaN, which therefore gives -256 * 2^32
 SE3TN_PS_HD inline int64_t pa_fx(double v) { return (int64_t)rint(fmin(fmax(v, -256.0), 256.0) * 4294967296.0); }
 
-// One model point x with normal n under pose T.  Returns bit 0: facing, bit 1: paired; with bit 1 set J[6] and r are the point's row
-// of the Jacobian and its residual (metres), otherwise they are not written.
-SE3TN_PS_HD inline int pa_point(const PaPose& T, const PaFrame& f, double x, double y, double z, double nx, double ny, double nz,
-                                double J[6], double& r) {
-  const double qx = (T.r[0][0] * x + T.r[0][1] * y) + T.r[0][2] * z;
-  const double qy = (T.r[1][0] * x + T.r[1][1] * y) + T.r[1][2] * z;
-  const double qz = (T.r[2][0] * x + T.r[2][1] * y) + T.r[2][2] * z;
+// One model point x with normal n under pose T, paired when it faces, its pixel is seen and |d - m| <= gate (millimetres).  Returns
+// bit 0: facing, bit 1: paired; with bit 1 set J[6] and r are the point's row of the Jacobian and its residual (metres), otherwise
+// they are not written.
+SE3TN_PS_HD inline int pa_point(const Rigid& T, const DepthFrame& f, double gate, double x, double y, double z, double nx, double ny,
+                                double nz, double J[6], double& r) {
+  double qx, qy, qz, mx, my, mz, uf, vf;
+  size_t q;
+  rotate(T.r, x, y, z, qx, qy, qz);
   const double cx = qx + T.t[0], cy = qy + T.t[1], cz = qz + T.t[2];
-  const double mx = (T.r[0][0] * nx + T.r[0][1] * ny) + T.r[0][2] * nz;
-  const double my = (T.r[1][0] * nx + T.r[1][1] * ny) + T.r[1][2] * nz;
-  const double mz = (T.r[2][0] * nx + T.r[2][1] * ny) + T.r[2][2] * nz;
-  const double face = (mx * cx + my * cy) + mz * cz;
-  if (!(face < 0.0)) return 0;   // turned away, grazing or NaN
-  const double uf = rint(cx * f.k0 / cz + f.k2);
-  const double vf = rint(cy * f.k4 / cz + f.k5);
-  // every comparison is false for NaN; +-inf and anything beyond the frame fail one of them: only an index reaches the cast
-  if (!(cz > 0.0 && uf >= 0.0 && uf < (double)f.W && vf >= 0.0 && vf < (double)f.H)) return 1;
-  const double d = (double)f.depth[(size_t)(int)vf * (size_t)f.W + (size_t)(int)uf];
-  const double m = rint(cz * 1000.0);
-  if (!(d > 100.0 && d < 2000.0 && fabs(d - m) <= f.gate)) return 1;
+  rotate(T.r, nx, ny, nz, mx, my, mz);
+  if (!faces(mx, my, mz, cx, cy, cz)) return 0;
+  if (!pixel_of(f, cx, cy, cz, uf, vf, q)) return 1;
+  const double d = (double)f.depth[q];
+  if (!(seen(d) && fabs(d - model_mm(cz)) <= gate)) return 1;
   const double oz = d / 1000.0;
   const double ox = ((uf - f.k2) * oz) / f.k0;
   const double oy = ((vf - f.k5) * oz) / f.k4;
@@ -133,7 +119,7 @@ SE3TN_PS_HD inline int pa_solve(const int64_t S[PA_SUMS], uint32_t pairs, double
 
 // R <- C R, t <- t + v with the Cayley rotation of w about the object's origin: a = 0.5 w, s = (a0 a0 + a1 a1) + a2 a2,
 // C = ((1 - s) I + 2 a a^T + 2 [a]x) / (1 + s) -- orthogonal for every w, no trigonometry
-SE3TN_PS_HD inline void pa_update(PaPose& T, const double delta[6]) {
+SE3TN_PS_HD inline void pa_update(Rigid& T, const double delta[6]) {
   const double a0 = 0.5 * delta[0], a1 = 0.5 * delta[1], a2 = 0.5 * delta[2];
   const double s = (a0 * a0 + a1 * a1) + a2 * a2;
   const double den = 1.0 + s;
@@ -170,7 +156,7 @@ SE3TN_PS_HD inline bool pa_small(const double delta[6], double stop) {
 
 // What one thread does after the sums of iteration `it` (0-based) are known: the record, the solve, the update.  Returns true when
 // the pose is finished (rec.status is then final); rec.iterations / pairs / facing_pts / sum_r2 describe the pose just evaluated.
-SE3TN_PS_HD inline bool pa_step(PaPose& T, const int64_t S[PA_SUMS], uint32_t pairs, uint32_t facing, int it,
+SE3TN_PS_HD inline bool pa_step(Rigid& T, const int64_t S[PA_SUMS], uint32_t pairs, uint32_t facing, int it,
                                 const se3tn_align_params& p, se3tn_align_rec& rec) {
   rec.iterations = (uint32_t)(it + 1);
   rec.pairs = pairs; rec.facing_pts = facing; rec.sum_r2 = S[PA_E];

@@ -42,22 +42,18 @@ SE3TN_PS_HD inline int pa_lds_row(int wave) { return wave * PA_ROW_WORDS; }
 SE3TN_PS_HD inline int pa_lds_total() { return PA_WAVES * PA_ROW_WORDS; }
 SE3TN_PS_HD inline int pa_lds_words() { return (PA_WAVES + 1) * PA_ROW_WORDS; }
 
-// Staging of se3tn_align_poses_host, in BYTES, pinned host and device mirror alike:
-//   [poses n x 16 doubles | depth H x W uint16 | pad to 8 | poses_out n x 16 doubles | rec n x 40 | sums n x 28 int64]
-// One upload covers [0, upload_bytes): the poses and the frame.  One read-back covers [poses_out, poses_out + readback_bytes): the
-// poses and the records, and the sums when they were asked for.
-struct PaStage {
-  size_t poses, depth, poses_out, rec, sums;   // byte offsets
-  size_t upload_bytes;                         // from 0
-  size_t readback_bytes;                       // from poses_out
-  size_t bytes;                                // the whole buffer
+// Staging of se3tn_align_poses_host (pose_search_plan.h has the head):
+//   [poses n x 16 doubles | frame | poses_out n x 16 doubles | rec n x 40 | sums n x 28 int64]
+// One read-back covers [poses_out, poses_out + readback_bytes): the poses and the records, and the sums when they were asked for.
+struct PaStage : PsHead {
+  size_t poses, poses_out, rec, sums;   // byte offsets
+  size_t readback_bytes;                // from poses_out
+  size_t bytes;                         // the whole buffer
 };
 SE3TN_PS_HD inline PaStage pa_stage(int n, int H, int W, int with_sums) {
   PaStage s;
   s.poses = 0;
-  s.depth = (size_t)n * 16 * sizeof(double);
-  s.upload_bytes = s.depth + (size_t)H * (size_t)W * sizeof(uint16_t);
-  s.poses_out = ps_align8(s.upload_bytes);
+  s.poses_out = ps_head(s, (size_t)n * 16 * sizeof(double), H, W);
   s.rec = s.poses_out + (size_t)n * 16 * sizeof(double);
   s.sums = s.rec + (size_t)n * sizeof(se3tn_align_rec);
   s.readback_bytes = (s.sums - s.poses_out) + (with_sums ? (size_t)n * SE3TN_POSE_ALIGN_SUMS * sizeof(int64_t) : 0);

@@ -3,13 +3,10 @@
 // (72 + 24 bytes per rotation / translation instead of 128 per pose), and the part of a point's transform that depends on the
 // rotation alone is computed once per rotation.
 //
-// The rule of a point x_j with normal n_j under candidate (r, t), float64, in this operation order (include/se3tracknet.h states it
-// in full):
-//     q  = (R0 x + R1 y) + R2 z  per row              the rotated part of transform() (pose_transform.h), its first three roundings
-//     c  = q + t                                      its last rounding: c has the bits transform() gives for the composed pose
-//     with facing:  n' = (R0 nx + R1 ny) + R2 nz per row,  f = (n'x c.x + n'y c.y) + n'z c.z,  the point counts only if f < 0
-//     in front / uf, vf / in frame / d, m / seen / inlier, front, behind     exactly as pose_search.hip
-// The file is compiled with -ffp-contract=off (csrc/Makefile) like pose_search.hip: every counter must EQUAL the numpy oracle's.
+// The rule of a point under candidate (r, t) lives in pose_point_rule.h: q = rotate(x) by R_r, c = q + t_t -- the bits transform()
+// gives for the composed pose, its five roundings cut after the third -- then faces() with the rotated normal where `facing` asks
+// for it, and count_point(); include/se3tracknet.h states it in full.  The file is compiled with -ffp-contract=off (csrc/Makefile):
+// every counter must EQUAL the numpy oracle's.
 //
 // One workgroup of PG_THREADS threads per (rotation, tile of PG_TT translations) -- pose_grid_plan.h has the index arithmetic.  Per
 // tile of PG_PT model points: all threads rotate the tile into LDS (three planes of doubles, six with the normals); then wave w
@@ -18,6 +15,7 @@
 // the last point tile the records are written once with plain vector stores.  Integer sums only, nothing allocated: a record
 // depends on (points, normals, R_r, t_t, depth, K, tol, facing) alone.
 #include "pose_grid_plan.h"
+#include "pose_point_rule.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
@@ -36,22 +34,18 @@ __global__ __launch_bounds__(PG_THREADS) void pose_grid_kernel(const PoseGridArg
   const int nt = pg_trans_count(t0, a.n_trans);
   if (t < PG_TT * PG_ROW_WORDS) rows[t] = 0u;   // (the first tile's barrier below orders this before any wave's first sum)
   const double* sr = a.rots + (size_t)r * 9;    // the rotation: nine uniform loads, kept in registers
-  const double r00 = sr[0], r01 = sr[1], r02 = sr[2], r10 = sr[3], r11 = sr[4], r12 = sr[5], r20 = sr[6], r21 = sr[7], r22 = sr[8];
-  const double W = (double)a.W, H = (double)a.H, tol = (double)a.tol;
-  const double fx = a.K[0], cx0 = a.K[2], fy = a.K[4], cy0 = a.K[5];
+  const double R[3][3] = {{sr[0], sr[1], sr[2]}, {sr[3], sr[4], sr[5]}, {sr[6], sr[7], sr[8]}};
+  const DepthFrame f = depth_frame(a.depth, a.H, a.W, a.K);
+  const double tol = (double)a.tol;
   for (int p0 = 0; p0 < a.P; p0 += PG_PT) {
     const int np = pg_point_count(p0, a.P);
     if (p0 > 0) __syncthreads();   // the previous tile's readers are done
     for (int j = t; j < np; j += PG_THREADS) {
       const double* x = a.pts + 3 * (size_t)(p0 + j);
-      qx[j] = (r00 * x[0] + r01 * x[1]) + r02 * x[2];
-      qy[j] = (r10 * x[0] + r11 * x[1]) + r12 * x[2];
-      qz[j] = (r20 * x[0] + r21 * x[1]) + r22 * x[2];
+      rotate(R, x[0], x[1], x[2], qx[j], qy[j], qz[j]);
       if (FACING) {
         const double* n = a.nrm + 3 * (size_t)(p0 + j);
-        qx[3 * PG_PT + j] = (r00 * n[0] + r01 * n[1]) + r02 * n[2];
-        qy[3 * PG_PT + j] = (r10 * n[0] + r11 * n[1]) + r12 * n[2];
-        qz[3 * PG_PT + j] = (r20 * n[0] + r21 * n[1]) + r22 * n[2];
+        rotate(R, n[0], n[1], n[2], qx[3 * PG_PT + j], qy[3 * PG_PT + j], qz[3 * PG_PT + j]);
       }
     }
     __syncthreads();
@@ -62,27 +56,11 @@ __global__ __launch_bounds__(PG_THREADS) void pose_grid_kernel(const PoseGridArg
 #pragma unroll 2
       for (int j = lane; j < np; j += 64) {
         const double cx = qx[j] + tx, cy = qy[j] + ty, cz = qz[j] + tz;
-        if (FACING) {
-          const double f = (qx[3 * PG_PT + j] * cx + qy[3 * PG_PT + j] * cy) + qz[3 * PG_PT + j] * cz;
-          if (!(f < 0.0)) continue;   // turned away, grazing (f == 0) or NaN: the point enters no counter
+        if (FACING) {   // turned away, grazing (f == 0) or NaN: the point enters no counter
+          if (!faces(qx[3 * PG_PT + j], qy[3 * PG_PT + j], qz[3 * PG_PT + j], cx, cy, cz)) continue;
           v[0] += 1u;
         }
-        const bool front = cz > 0.0;
-        const double uf = rint(cx * fx / cz + cx0);
-        const double vf = rint(cy * fy / cz + cy0);
-        // every comparison is false for NaN; +-inf and anything beyond the frame fail one of them: only an index reaches the cast
-        if (front && uf >= 0.0 && uf < W && vf >= 0.0 && vf < H) {
-          v[1] += 1u;
-          const size_t q = (size_t)(int)vf * (size_t)a.W + (size_t)(int)uf;
-          const double d = (double)a.depth[q];
-          if (d > 100.0 && d < 2000.0) {
-            const double m = rint(cz * 1000.0);
-            v[2] += 1u;
-            if (fabs(d - m) <= tol) v[3] += 1u;
-            if (d < m - tol) v[4] += 1u;
-            if (d > m + tol) v[5] += 1u;
-          }
-        }
+        count_point(f, tol, cx, cy, cz, v + 1);
       }
 #pragma unroll
       for (int c = 6 - NC; c < 6; ++c) {

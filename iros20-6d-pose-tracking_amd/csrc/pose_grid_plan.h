@@ -45,28 +45,16 @@ SE3TN_PS_HD inline size_t pg_lds_bytes(int facing) { return pg_lds_rows(facing) 
 SE3TN_PS_HD inline size_t pg_lds_plane(int plane) { return (size_t)plane * PG_PT * sizeof(double); }               // byte offset of a plane
 SE3TN_PS_HD inline size_t pg_lds_row(int facing, int k) { return pg_lds_rows(facing) + (size_t)k * PG_ROW_WORDS * sizeof(uint32_t); }
 
-// Staging of se3tn_search_pose_grid_host, in BYTES, pinned host and device mirror alike:
-//   [rots n_rot x 9 doubles | trans n_trans x 3 doubles | depth H x W uint16 | pad to 8 | fit n records | top_fit k records |
-//    idx k int32 | pad to 8],  n = n_rot * n_trans
-// One upload covers [0, upload_bytes): the factors and the frame.  One read-back covers [top_fit, top_fit + k x 36).
-struct PgStage {
-  size_t rots, trans, depth, fit, top_fit, idx;   // byte offsets
-  size_t upload_bytes;                            // from 0
-  size_t readback_bytes;                          // from top_fit
-  size_t bytes;                                   // the whole buffer
+// Staging of se3tn_search_pose_grid_host (pose_search_plan.h has the head and the rank tail):
+//   [rots n_rot x 9 doubles | trans n_trans x 3 doubles | frame | rank tail of n = n_rot * n_trans records]
+struct PgStage : PsHead, PsRankTail {
+  size_t rots, trans;   // byte offsets
 };
 SE3TN_PS_HD inline PgStage pg_stage(int n_rot, int n_trans, int H, int W, int k) {
   PgStage s;
-  const size_t n = (size_t)n_rot * (size_t)n_trans;
   s.rots = 0;
   s.trans = (size_t)n_rot * 9 * sizeof(double);
-  s.depth = s.trans + (size_t)n_trans * 3 * sizeof(double);
-  s.upload_bytes = s.depth + (size_t)H * (size_t)W * sizeof(uint16_t);
-  s.fit = ps_align8(s.upload_bytes);
-  s.top_fit = s.fit + n * sizeof(se3tn_point_fit);
-  s.idx = s.top_fit + (size_t)k * sizeof(se3tn_point_fit);
-  s.readback_bytes = (size_t)k * (sizeof(se3tn_point_fit) + sizeof(int32_t));
-  s.bytes = ps_align8(s.idx + (size_t)k * sizeof(int32_t));
+  ps_rank_tail(s, ps_head(s, s.trans + (size_t)n_trans * 3 * sizeof(double), H, W), (size_t)n_rot * (size_t)n_trans, k);
   return s;
 }
 

@@ -2,17 +2,9 @@
 // projecting the model's points, and the k best picked.  The reference's answer to a lost track is an external detector
 // (predict.py:539-541: PoseCNN at the frames --reinit_frames lists); a render per candidate would cost a rasteriser pass each.
 //
-// The rule of a point x_j under candidate i, float64, in this operation order (include/se3tracknet.h states it in full):
-//     c = R x + t                                   transform() of pose_transform.h, the one of pose_errors.hip
-//     in front   c.z > 0
-//     uf = rint(c.x * K[0] / c.z + K[2]),  vf = rint(c.y * K[4] / c.z + K[5])          half to even, the rule of track_plan.h
-//     in frame   in front && 0 <= uf < W && 0 <= vf < H                                on the doubles: nothing that is not an index is cast
-//     d = depth[vf, uf],  m = rint(c.z * 1000.0)
-//     seen       in frame && 100 < d < 2000
-//     inlier |d - m| <= tol      front d < m - tol      behind d > m + tol             (of the seen ones; exact: integers in doubles)
-// The file is compiled with -ffp-contract=off (csrc/Makefile): the numpy oracle of the tests states the same operations and the
-// counters must EQUAL its counters, which a fused multiply-add in the transform or in `c.x K[0] / c.z + K[2]` would break at a
-// pixel boundary.
+// The rule of a point under a candidate lives in pose_point_rule.h (count_point(), after transform() of pose_transform.h);
+// include/se3tracknet.h states it in full.  The file is compiled with -ffp-contract=off (csrc/Makefile): every counter must EQUAL
+// the numpy oracle's.
 //
 // Scoring: one workgroup of PS_THREADS threads per pose.  The pose's twelve doubles are loaded once (twelve lanes, through LDS);
 // thread t takes the points t, t + 256, ... and keeps five counters in registers; wave64 xor shuffles, the four waves through LDS,
@@ -20,8 +12,8 @@
 // record depends on (points, pose, depth, K, tol) alone.
 // Ranking: ONE workgroup; round r finds the largest key (pose_search_plan.h: ps_key) below round r - 1's winner -- k passes over
 // the n records, no scratch, the same result on every run because keys are unique.
+#include "pose_point_rule.h"
 #include "pose_search_plan.h"
-#include "pose_transform.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
@@ -34,27 +26,13 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_kernel(const PoseScoreA
   if (t < 12) sp[t] = a.poses[pose * 16 + t];   // rows 0-2 of the pose: loaded once per workgroup
   __syncthreads();
   const Rigid T = load_pose(sp);
-  const double W = (double)a.W, H = (double)a.H, tol = (double)a.tol;
+  const DepthFrame f = depth_frame(a.depth, a.H, a.W, a.K);
+  const double tol = (double)a.tol;
   unsigned v[5] = {0u, 0u, 0u, 0u, 0u};   // in frame, seen, inlier, front, behind
   for (int j = t; j < a.P; j += PS_THREADS) {
     double cx, cy, cz;
     transform(T, a.pts[3 * (size_t)j], a.pts[3 * (size_t)j + 1], a.pts[3 * (size_t)j + 2], cx, cy, cz);
-    const bool front = cz > 0.0;
-    const double uf = rint(cx * a.K[0] / cz + a.K[2]);
-    const double vf = rint(cy * a.K[4] / cz + a.K[5]);
-    // every comparison is false for NaN; +-inf and anything beyond the frame fail one of them: only an index reaches the cast
-    if (front && uf >= 0.0 && uf < W && vf >= 0.0 && vf < H) {
-      v[0] += 1u;
-      const size_t q = (size_t)(int)vf * (size_t)a.W + (size_t)(int)uf;
-      const double d = (double)a.depth[q];
-      if (d > 100.0 && d < 2000.0) {
-        const double m = rint(cz * 1000.0);
-        v[1] += 1u;
-        if (fabs(d - m) <= tol) v[2] += 1u;
-        if (d < m - tol) v[3] += 1u;
-        if (d > m + tol) v[4] += 1u;
-      }
-    }
+    count_point(f, tol, cx, cy, cz, v);
   }
 #pragma unroll
   for (int k = 0; k < 5; ++k) {

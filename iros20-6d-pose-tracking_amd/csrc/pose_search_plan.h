@@ -13,12 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/se3tracknet.h"
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define SE3TN_PS_HD __host__ __device__
-#else
-#define SE3TN_PS_HD
-#endif
+#include "pose_transform.h"   // SE3TN_PS_HD
 
 namespace se3tn {
 
@@ -44,27 +39,42 @@ SE3TN_PS_HD inline uint32_t ps_key_inliers(uint64_t key) { return (uint32_t)(key
 SE3TN_PS_HD inline uint32_t ps_key_behind(uint64_t key) { return PS_FIELD_MAX - (uint32_t)((key >> 20) & PS_FIELD_MAX); }   // clamped count
 SE3TN_PS_HD inline uint32_t ps_key_index(uint64_t key) { return PS_FIELD_MAX - (uint32_t)(key & PS_FIELD_MAX); }
 
-// Staging of se3tn_search_poses_host, in BYTES, pinned host and device mirror alike:
-//   [poses n x 16 doubles | depth H x W uint16 | pad to 8 | fit n records | top_fit k records | idx k int32 | pad to 8]
-// One upload covers [0, ps_stage_upload_bytes): poses and the frame.  One read-back covers [top_fit, top_fit + k x 36): the records
-// of the k winners, then their indices.  The n records in between stay on the device.
-struct PsStage {
-  size_t poses, depth, fit, top_fit, idx;   // byte offsets
-  size_t upload_bytes;                      // from 0
-  size_t readback_bytes;                    // from top_fit
-  size_t bytes;                             // the whole buffer
-};
+// Staging of the synchronous _host entry points of the pose family (api.cpp: StagedCall), in BYTES, pinned host and device mirror
+// alike.  Every layout starts with the HEAD [inputs | depth H x W uint16 | pad to 8]: one upload covers [0, upload_bytes), the inputs
+// and the frame.  The searches end with the RANK TAIL [fit n records | top_fit k records | idx k int32 | pad to 8]: one read-back
+// covers [top_fit, top_fit + k x 36), the records of the k winners, then their indices; the n records before them stay on the device.
 SE3TN_PS_HD inline size_t ps_align8(size_t b) { return (b + 7) & ~(size_t)7; }
-SE3TN_PS_HD inline PsStage ps_stage(int n, int H, int W, int k) {
-  PsStage s;
-  s.poses = 0;
-  s.depth = (size_t)n * 16 * sizeof(double);
+struct PsHead {
+  size_t depth;          // byte offset of the frame: the inputs end here
+  size_t upload_bytes;   // from 0
+};
+// fills the head for `input_bytes` of inputs and returns where the outputs begin
+SE3TN_PS_HD inline size_t ps_head(PsHead& s, size_t input_bytes, int H, int W) {
+  s.depth = input_bytes;
   s.upload_bytes = s.depth + (size_t)H * (size_t)W * sizeof(uint16_t);
-  s.fit = ps_align8(s.upload_bytes);
-  s.top_fit = s.fit + (size_t)n * sizeof(se3tn_point_fit);
+  return ps_align8(s.upload_bytes);
+}
+struct PsRankTail {
+  size_t fit, top_fit, idx;   // byte offsets
+  size_t readback_bytes;      // from top_fit
+  size_t bytes;               // the whole buffer
+};
+SE3TN_PS_HD inline void ps_rank_tail(PsRankTail& s, size_t at, size_t n, int k) {
+  s.fit = at;
+  s.top_fit = s.fit + n * sizeof(se3tn_point_fit);
   s.idx = s.top_fit + (size_t)k * sizeof(se3tn_point_fit);
   s.readback_bytes = (size_t)k * (sizeof(se3tn_point_fit) + sizeof(int32_t));
   s.bytes = ps_align8(s.idx + (size_t)k * sizeof(int32_t));
+}
+
+// se3tn_search_poses_host: [poses n x 16 doubles | frame | rank tail]
+struct PsStage : PsHead, PsRankTail {
+  size_t poses;   // byte offset
+};
+SE3TN_PS_HD inline PsStage ps_stage(int n, int H, int W, int k) {
+  PsStage s;
+  s.poses = 0;
+  ps_rank_tail(s, ps_head(s, (size_t)n * 16 * sizeof(double), H, W), (size_t)n, k);
   return s;
 }
 

@@ -141,10 +141,8 @@ static int run_case(const char* in, const char* out) {
   CHECK(read_n(f, pts, (size_t)P * 3) && read_n(f, nrm, (size_t)P * 3) && read_n(f, poses, (size_t)n * 16));
   CHECK(read_n(f, depth, (size_t)H * (size_t)W));
   std::fclose(f);
-  PaFrame fr;
-  fr.depth = depth.data(); fr.H = H; fr.W = W;
-  fr.k0 = dd[2 + 0]; fr.k2 = dd[2 + 2]; fr.k4 = dd[2 + 4]; fr.k5 = dd[2 + 5];
-  fr.gate = (double)prm.gate_mm;
+  const DepthFrame fr = depth_frame(depth.data(), H, W, dd.data() + 2);
+  const double gate = (double)prm.gate_mm;
   std::vector<double> poses_out((size_t)n * 16);
   std::vector<se3tn_align_rec> recs((size_t)n);
   std::vector<int64_t> sums((size_t)n * PA_SUMS);
@@ -155,8 +153,7 @@ static int run_case(const char* in, const char* out) {
     se3tn_align_rec rec;
     std::memset(&rec, 0, sizeof(rec));
     for (int it = 0; it < prm.iters; ++it) {
-      PaPose T;
-      for (int i = 0; i < 3; ++i) { T.r[i][0] = sp[4 * i]; T.r[i][1] = sp[4 * i + 1]; T.r[i][2] = sp[4 * i + 2]; T.t[i] = sp[4 * i + 3]; }
+      Rigid T = load_pose(sp);
       for (int w = 0; w < PA_WAVES; ++w)
         for (int k = 0; k < PA_ROW_WORDS; ++k) red[(size_t)(pa_lds_row(w) + k)] = 0;
       for (int t = 0; t < PA_THREADS; ++t) {   // a thread's registers, added to its wave's row (integer sums: any order)
@@ -164,7 +161,7 @@ static int run_case(const char* in, const char* out) {
         long long pairs = 0, facing = 0;
         for (int j = pa_first(t); j < P; j += pa_stride()) {
           double J[6], r;
-          const int k = pa_point(T, fr, pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2], nrm[3 * (size_t)j],
+          const int k = pa_point(T, fr, gate, pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2], nrm[3 * (size_t)j],
                                  nrm[3 * (size_t)j + 1], nrm[3 * (size_t)j + 2], J, r);
           facing += k & 1;
           if (k & 2) { pairs += 1; pa_accumulate(J, r, S); }

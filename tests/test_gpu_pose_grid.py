@@ -18,6 +18,7 @@ from scipy.spatial.transform import Rotation
 
 import pose_grid_oracle as PGO
 import pose_grid_scene as SC
+import pose_search_cases as PC
 import pose_search_oracle as PSO
 from oracle import fixtures as Fx
 from oracle import se3_oracle as O
@@ -25,10 +26,10 @@ from oracle import se3_oracle as O
 pytestmark = pytest.mark.gpu
 
 E_ARG, E_STATE = -1, -2
-H, W = 48, 64
-K = np.array([[100.0, 0, 31.5], [0, 101.0, 23.5], [0, 0, 1.0]])
+H, W = PC.GRID_HW
+K = PC.GRID_K
 TOL = 5
-TT = 16                                    # csrc/pose_grid_plan.h PG_TT: translations per workgroup
+TT = PC.GRID_TT                            # csrc/pose_grid_plan.h PG_TT: translations per workgroup
 P_EDGES = [1, 63, 64, 65, 1023, 1024, 1025, 2049]      # lanes of one wave, and the 1,024-point tile of LDS one short, full, one over, two and one
 NT_EDGES = [1, TT - 1, TT, TT + 1, 3 * TT + 5]
 NR_EDGES = [1, 3]
@@ -49,32 +50,15 @@ def eng(se3):
 
 @pytest.fixture(scope="module")
 def depth():
-    rng = np.random.default_rng(48)
-    yy, xx = np.mgrid[0:H, 0:W]
-    d = (500 + 0.6 * (xx - W / 2) - 0.4 * (yy - H / 2) + 12 * np.sin(xx / 5.0)).astype(np.uint16)
-    mask = rng.random((H, W)) < 0.1
-    d[mask] = rng.choice(np.array([0, 100, 101, 1999, 2000, 65535], np.uint16), int(mask.sum()))
-    return np.ascontiguousarray(d)
+    return PC.grid_depth()
 
 
 @pytest.fixture(scope="module")
 def factors():
-    """3 rotations and 53 translations: prefixes of these are the grids of the tiling tests.  Translation 7 is behind the camera,
-    translation 11 far off the frame"""
-    rng = np.random.default_rng(5)
-    rots = Rotation.from_rotvec(rng.normal(size=(3, 3))).as_matrix()
-    trans = np.array([0.0, 0.0, 0.5]) + rng.uniform(-0.05, 0.05, (3 * TT + 5, 3))
-    trans[7] = (0.0, 0.0, -0.5)
-    trans[11] = (2.0, 0.0, 0.5)
-    return np.ascontiguousarray(rots), np.ascontiguousarray(trans)
+    return PC.grid_factors()
 
 
-def blob(P):
-    """P points in a 90 mm ball and their normals: the direction from the centre (a convex blob: about half of it faces the camera)"""
-    rng = np.random.default_rng(P)
-    pts = rng.normal(size=(P, 3))
-    pts *= (0.045 * rng.uniform(0.3, 1.0, P) / np.linalg.norm(pts, axis=1))[:, None]
-    return np.ascontiguousarray(pts), np.ascontiguousarray(pts / np.linalg.norm(pts, axis=1)[:, None])
+blob = PC.blob
 
 
 def same_records(got, want, what):

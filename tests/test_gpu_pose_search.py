@@ -16,6 +16,7 @@ import pytest
 import torch
 from scipy.spatial.transform import Rotation
 
+import pose_search_cases as PC
 import pose_search_oracle as PSO
 from oracle import closed_loop as CL
 from oracle import fixtures as Fx
@@ -160,21 +161,16 @@ def test_exact_boundaries(se3, eng, hw, tol):
     v; two points are far beyond any integer.  m = 1000 exactly; the frame's pixels cycle through 0, 100, 101, 1999, 2000, 65535
     and 1000 -+ (tol - 1, tol, tol + 1) where a uint16 holds them, shifted one place per call so that every hit pixel takes every value."""
     Hh, Ww = hw
-    Kc = np.array([[1.0, 0, 0.5], [0, 1.0, 1.5], [0, 0, 1.0]])
-    xs = [-1.0, 0.0, Ww - 2.0, Ww - 1.0]
-    ys = [-2.0, -1.0, Hh - 3.0, Hh - 2.0]
-    pts = np.array([(x, y, 1.0) for x in xs for y in ys] + [(1e18, 0.0, 1.0), (0.0, -1e300, 1.0)])
-    poses = np.tile(np.eye(4), (3, 1, 1))
-    poses[1, 2, 3] = 0.0005     # c.z * 1000 = 1000.5: m rounds half to even
-    poses[2, 2, 3] = -2.0       # behind the camera
-    vals = [0, 100, 101, 1999, 2000, 65535] + [1000 + s * (tol + e) for s in (-1, 1) for e in (-1, 0, 1)]
-    vals = np.array([v for v in vals if 0 <= v <= 65535], np.uint16)
+    Kc = PC.BOUNDARY_K
+    pts = PC.boundary_points(hw)
+    poses = PC.boundary_poses()
+    vals = PC.boundary_values(tol)
     mp = eng.model_points(pts)
     n_in_x = 3 if Ww % 2 == 0 else 4
     n_in_y = 3 if Hh % 2 == 0 else 4
     seen_total = 0
     for shift in range(len(vals)):
-        depth = vals[(np.arange(Hh * Ww) + shift) % len(vals)].reshape(Hh, Ww)
+        depth = PC.boundary_depth(hw, vals, shift)
         want = PSO.score(pts, poses, depth, Kc, tol)
         # by hand, for the identity pose: which boundary points are inside does not depend on the depth
         assert want["in_frame_pts"][0] == n_in_x * n_in_y and want["in_frame_pts"][2] == 0, (hw, want)
