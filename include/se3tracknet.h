@@ -8,7 +8,7 @@
  * Conventions
  *   - plain C types only; device pointers are caller-owned (e.g. torch tensors' data_ptr());
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream);
- *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth, fit_stats) is stream-ordered and
+ *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth, fit_stats, color_stats) is stream-ordered and
  *     asynchronous: no hipMalloc, no hipDeviceSynchronize, no host<->device copy of results => hipGraph-capturable.
  *     All device memory is allocated by the init-time calls: se3tn_create (activations, 176x176 z-buffer),
  *     se3tn_upload_weights / se3tn_bind_weights / se3tn_set_winograd (Winograd planes), se3tn_set_precision (f16x3 split
@@ -464,6 +464,58 @@ int se3tn_last_fit(se3tn_ctx* ctx, int n, se3tn_fit* out_host);
  * cropped with, so that the two compare pixel by pixel.  On SE3TN_ROUTE_FRAME they are the raw 176 x 176 crop_bbox of the rendered
  * rectangle.  Either pointer may be NULL.  SE3TN_E_STATE as se3tn_last_fit. */
 int se3tn_last_fit_images(se3tn_ctx* ctx, const uint8_t** rgb_dev, const uint16_t** depth_dev);
+
+/* ---- how well a pose hypothesis fits the observed COLOUR ---------------------------------------------------- */
+/* The depth record above cannot tell a box from the same box after half a turn; the colours on it can.  A pixel of the 176 x 176
+ * crop is COMPARED exactly when it is an inlier of se3tn_fit: valid(m) && valid(o) && |o - m| <= tol_mm on the two depths -- the
+ * pixels where the sensor sees the model's surface, not an occluder and not the background.  Both images are read through se3tn_crop
+ * descriptors with se3tn_fit_stats' index rule (zero outside the image), the colour at the same source index as the depth.  With
+ * m_c(p) / o_c(p) the model / observed byte of channel c (R, G, B) at a compared pixel, the record holds the sums a zero-mean
+ * normalised cross-correlation needs.  No word can overflow: 176 * 176 * 255^2 = 2,014,214,400 < 2^32.  All integers: the record
+ * does not depend on the order the workgroups arrive in. */
+typedef struct se3tn_color_fit {   /* all uint32, 20 words, 80 bytes */
+  uint32_t px;          /* number of compared pixels (== se3tn_fit.inlier_px of the same pair) */
+  uint32_t tol_mm;      /* echoed                                                              */
+  uint32_t sum_m[3];    /* sum of m_c                                                          */
+  uint32_t sum_o[3];    /* sum of o_c                                                          */
+  uint32_t sum_mm[3];   /* sum of m_c^2                                                        */
+  uint32_t sum_oo[3];   /* sum of o_c^2                                                        */
+  uint32_t sum_mo[3];   /* sum of m_c * o_c                                                    */
+  uint32_t sum_abs[3];  /* sum of |o_c - m_c|                                                  */
+} se3tn_color_fit;
+/* The colour twin of se3tn_fit_stats: ONE pass over the crop pixels of n pairs accumulates both records.  `model` / `observed`: HOST
+ * arrays of n descriptors whose rgb AND depth are device images.  out_dev: n colour records; fit_out_dev (may be NULL): the n depth
+ * records, bit for bit what se3tn_fit_stats stores -- both in device memory or mapped pinned host memory (every word stored once).
+ * A launch takes SE3TN_FIT_MAX_PAIRS pairs; larger n are chunked.  Stream-ordered, capturable, allocates nothing (its counters belong
+ * to se3tn_create and are zero again when a launch ends).  SE3TN_E_ARG: n outside [1, se3tn_max_batch], tol_mm outside [1, 65535], a
+ * NULL pointer (a descriptor without rgb or depth included), an empty window or image. */
+int se3tn_color_stats(se3tn_ctx* ctx, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm,
+                      se3tn_fit* fit_out_dev /* may be NULL */, se3tn_color_fit* out_dev, void* stream);
+/* The score of a record: the mean over the channels of the zero-mean normalised cross-correlation, in [-1, 1]; it does not change
+ * under a gain or an offset of either image, which is what makes a Lambert-shaded render comparable with a camera image.  Host-only,
+ * pure, needs no context.  Operation order (utils.color_score returns the same double): per channel c, with n = px, in int64
+ *     cov = n * sum_mo - sum_m * sum_o,   vm = n * sum_mm - sum_m * sum_m,   vo = n * sum_oo - sum_o * sum_o
+ * (all three below 2^53: their conversion to double is exact);
+ *     z_c = (double)cov / (sqrt((double)vm) * sqrt((double)vo))   if vm > 0 && vo > 0, else 0 (a flat channel is no evidence);
+ *     score = ((z_0 + z_1) + z_2) / 3.0.
+ * The score is 0 when px < min_px or rec is NULL.  per_channel (may be NULL): z_0, z_1, z_2 (zeros when px < min_px). */
+double se3tn_color_score(const se3tn_color_fit* rec, int min_px, double per_channel[3] /* may be NULL */);
+/* ONE call for "which of these n hypotheses does the frame confirm": the front half of se3tn_on_track_batch with the hypothesis in
+ * the place of prev_pose, stopped before the network.  Per pose its own compute_bbox window; the frame's n windows staged through the
+ * pinned buffer in one copy; per pose its own image A (the n instances of the rasteriser's four launches: the window route, or the
+ * rectangle of the frame on SE3TN_ROUTE_FRAME, whichever `mesh` is on -- the bytes se3tn_on_track_batch renders for the same pose,
+ * through the per-instance rasteriser path and the context-owned scratch of se3tn_on_track_objects, with n instances of `mesh`);
+ * then se3tn_color_stats' kernel of image A against the window, and one read-back.  poses: HOST float64 [n,16]; rgb / depth: ONE HOST
+ * frame uint8 [H,W,3] / uint16 [H,W]; fit_out / color_out: HOST [n]; bbox_out: HOST [n,4,2] compute_bbox corners (v, u), may be NULL.
+ * A window that misses the frame compares nothing (px = 0).  SYNCHRONOUS on the default stream, SE3TN_E_STATE inside a stream capture
+ * the default stream takes part in (a blocking stream capturing; the capture of a non-blocking stream is not visible from here: a caller
+ * who has one open must not call -- Engine.verify_poses refuses under a capture of torch's current stream);
+ * SE3TN_E_ARG on a host-only context, for n outside [1, se3tn_max_batch], tol_mm outside [1, 65535], and for every pose
+ * se3tn_on_track_batch refuses (not in front of the camera, an empty window, singular).  Leaves no state behind: the tracking calls
+ * that follow return the bits they return on a fresh context. */
+int se3tn_verify_poses_host(se3tn_ctx* ctx, se3tn_mesh* mesh, const double* poses, int n, const double K[9], double object_width_mm,
+                            const uint8_t* rgb, const uint16_t* depth, int H, int W, int tol_mm, se3tn_fit* fit_out,
+                            se3tn_color_fit* color_out, int32_t* bbox_out /* [n,4,2], may be NULL */);
 
 /* ---- ADD / ADD-S of n pose pairs in one call ----------------------------------------------------------------- */
 /* Utils.py:72-98 `add` / `adi`, the two errors every result of the reference is reported in (eval_ycb.py, eval_ycbineoat.py),

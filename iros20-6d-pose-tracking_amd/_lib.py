@@ -55,6 +55,12 @@ class Fit(C.Structure):
                                           "_reserved")]
 
 
+class ColorFit(C.Structure):
+    """se3tn_color_fit (include/se3tracknet.h): the colour record of one (model, observed) pair."""
+    _fields_ = [("px", C.c_uint32), ("tol_mm", C.c_uint32)] + [(k, C.c_uint32 * 3) for k in ("sum_m", "sum_o", "sum_mm", "sum_oo", "sum_mo",
+                                                                                           "sum_abs")]
+
+
 class AlignParams(C.Structure):
     """se3tn_align_params (include/se3tracknet.h): gate, iteration and stop settings of se3tn_align_poses."""
     _fields_ = [("gate_mm", C.c_int32), ("iters", C.c_int32), ("min_pairs", C.c_int32), ("_reserved", C.c_int32),
@@ -81,6 +87,9 @@ assert CROP_DTYPE.itemsize == C.sizeof(Crop)
 FIT_FIELDS = ("model_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm", "tol_mm")   # the seven that carry data
 FIT_DTYPE = _np.dtype([(k, "<u4") for k in FIT_FIELDS + ("_reserved",)])
 assert FIT_DTYPE.itemsize == C.sizeof(Fit) == 32
+COLOR_FIT_SUMS = ("sum_m", "sum_o", "sum_mm", "sum_oo", "sum_mo", "sum_abs")   # three words each: R, G, B
+COLOR_FIT_DTYPE = _np.dtype([("px", "<u4"), ("tol_mm", "<u4")] + [(k, "<u4", (3,)) for k in COLOR_FIT_SUMS])
+assert COLOR_FIT_DTYPE.itemsize == C.sizeof(ColorFit) == 80
 POINT_FIT_FIELDS = ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm")   # the seven that carry data
 POINT_FIT_DTYPE = _np.dtype([(k, "<u4") for k in POINT_FIT_FIELDS + ("_reserved",)])
 assert POINT_FIT_DTYPE.itemsize == C.sizeof(PointFit) == 32
@@ -165,6 +174,10 @@ _SIGS = {
     "se3tn_get_fit_check": (C.c_int, [C.c_void_p]),
     "se3tn_last_fit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "se3tn_last_fit_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "se3tn_color_stats": (C.c_int, [C.c_void_p, C.POINTER(Crop), C.POINTER(Crop), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_color_score": (C.c_double, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "se3tn_verify_poses_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_points_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "se3tn_points_destroy": (None, [C.c_void_p]),
     "se3tn_points_count": (C.c_int, [C.c_void_p]),

@@ -21,6 +21,7 @@
 #include "se3tn_internal.h"
 #include "tex_pyramid.h"
 #include "track_plan.h"
+#include "verify_plan.h"
 #include "weights.h"
 
 using namespace se3tn;
@@ -140,6 +141,8 @@ struct se3tn_ctx {
   int fit_tol = 0, fit_last_n = 0, fit_cap = 0;
   DeviceBuf<uint8_t> fit_rgb; DeviceBuf<uint16_t> fit_depth;
   PinnedBuf<se3tn_fit> fit_host;
+  // se3tn_color_stats / se3tn_verify_poses_host: per-pair counters [max_batch][ColorFitArgs::WORDS] (se3tn_create; zero between launches)
+  DeviceBuf<unsigned> color_counters;
   // the synchronous _host entry points of the pose family (StagedCall): pinned staging of ps_cap bytes and its device mirror, laid out
   // per call (pose_errors_plan.h: pe_stage_*, pose_search_plan.h: PsStage, pose_grid_plan.h: PgStage, pose_align_plan.h: PaStage)
   PinnedBuf<unsigned char> ps_host; DeviceBuf<unsigned char> ps_dev; size_t ps_cap = 0;
@@ -497,6 +500,7 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
     e = c->part.alloc((size_t)16 * 1024 * 121 * 16);
     if (e == hipSuccess) e = c->tail_arrive.alloc(c->max_batch, true);
     if (e == hipSuccess) e = c->fit_counters.alloc((size_t)FitArgs::WORDS * c->max_batch, true);
+    if (e == hipSuccess) e = c->color_counters.alloc((size_t)ColorFitArgs::WORDS * c->max_batch, true);
     if (const char* sk = std::getenv("SE3TN_SMALL_KERNELS")) c->small_kernels = std::atoi(sk) != 0;
     if (const char* tp = std::getenv("SE3TN_TAIL_PARTS")) { c->tail_parts = std::atoi(tp) != 0; c->tail_parts_ch = std::atoi(tp) == 2 ? 32 : 16; }
     if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(split-K workspace)"); }
@@ -1618,6 +1622,47 @@ int se3tn_last_fit_images(se3tn_ctx* c, const uint8_t** rgb_dev, const uint16_t*
   return SE3TN_OK;
 }
 
+// ---- the colour record --------------------------------------------------------------------------------------------------------------
+int se3tn_color_stats(se3tn_ctx* c, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm, se3tn_fit* fit_out_dev,
+                      se3tn_color_fit* out_dev, void* stream) {
+  if (!c || c->device < 0 || !model || !observed || !out_dev) return fail(SE3TN_E_ARG, "se3tn_color_stats: bad argument");
+  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_color_stats: n outside [1, max_batch]");
+  if (tol_mm < 1 || tol_mm > 65535) return fail(SE3TN_E_ARG, "se3tn_color_stats: tol_mm outside [1, 65535]");
+  for (int i = 0; i < n; ++i)
+    for (const se3tn_crop* k : {model + i, observed + i})
+      if (!k->rgb || !k->depth || k->H < 1 || k->W < 1 || k->right <= k->left || k->bottom <= k->top)
+        return fail(SE3TN_E_ARG, "se3tn_color_stats: descriptor " + std::to_string(i) + ": NULL rgb or depth, empty image or empty window");
+  for (int g0 = 0; g0 < n; g0 += ColorFitArgs::MAX) {   // the descriptors travel as kernel arguments, ColorFitArgs::MAX pairs per launch
+    const int k = n - g0 < ColorFitArgs::MAX ? n - g0 : ColorFitArgs::MAX;
+    ColorFitArgs a;
+    std::memcpy(a.m, model + g0, sizeof(se3tn_crop) * k);
+    std::memcpy(a.o, observed + g0, sizeof(se3tn_crop) * k);
+    a.counters = c->color_counters.get() + (size_t)ColorFitArgs::WORDS * g0;
+    a.fit_out = fit_out_dev ? fit_out_dev + g0 : nullptr;
+    a.out = out_dev + g0;
+    a.tol = tol_mm;
+    HIPCHK(launch_color_fit(a, k, (hipStream_t)stream));
+  }
+  return SE3TN_OK;
+}
+
+// the operation order is the header's; utils.color_score states it again in NumPy
+double se3tn_color_score(const se3tn_color_fit* r, int min_px, double per_channel[3]) {
+  double z[3] = {0.0, 0.0, 0.0};
+  if (r && (long long)r->px >= (long long)min_px) {
+    const int64_t n = (int64_t)r->px;
+    for (int ch = 0; ch < 3; ++ch) {
+      const int64_t sm = r->sum_m[ch], so = r->sum_o[ch];
+      const int64_t cov = n * (int64_t)r->sum_mo[ch] - sm * so;
+      const int64_t vm = n * (int64_t)r->sum_mm[ch] - sm * sm;
+      const int64_t vo = n * (int64_t)r->sum_oo[ch] - so * so;
+      if (vm > 0 && vo > 0) z[ch] = (double)cov / (std::sqrt((double)vm) * std::sqrt((double)vo));
+    }
+  }
+  if (per_channel) { per_channel[0] = z[0]; per_channel[1] = z[1]; per_channel[2] = z[2]; }
+  return ((z[0] + z[1]) + z[2]) / 3.0;
+}
+
 // ---- ADD / ADD-S of n pose pairs ---------------------------------------------------------------------------------------------------
 int se3tn_points_create(se3tn_ctx* c, const double* xyz, int P, se3tn_points** out) {
   if (!c || !xyz || !out) return fail(SE3TN_E_ARG, "se3tn_points_create: NULL argument");
@@ -2145,6 +2190,86 @@ static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes
   HIPCHK(hipMemcpyAsync(c->tb_inst_dev.get(), inst_host, tab_bytes, hipMemcpyHostToDevice, st));
   ra.inst = (const RasterInstance*)c->tb_inst_dev.get();
   HIPCHK(launch_raster(ra, st, n));
+  return SE3TN_OK;
+}
+
+// ---- which of n hypotheses does the frame confirm ----------------------------------------------------------------------------------
+// The front half of se3tn_on_track_batch with the hypothesis in the place of prev_pose: windows, image A of every pose, the frame's
+// windows staged in one copy -- then the depth and colour records instead of the network.  The staging buffer carries the records in
+// front (verify_plan.h: where se3tn_on_track_batch carries its poses), written by the kernel and read back in one copy; the upload
+// starts behind them.  The stages are se3tn_on_track_batch's, the rasteriser path is se3tn_on_track_objects': raster_instances() with
+// n copies of the one mesh (inst_mesh = 1, or 2 on the frame route: mesh and material per instance from the table), on the CONTEXT's
+// scratch c->mo (reserve_objects_raster) -- not m->batch and not se3tn_on_track_batch's own launch, so the mesh is not touched.  The
+// bytes are those of that launch (tests/test_gpu_color_fit.py holds them equal).  What the call writes: c->mo, the instance table
+// (tb_inst_host / tb_inst_dev), tb_rgbA / tb_depthA / tb_zbuf or fr_sub / fr_zbuf, tb_stage_host / tb_stage_dev and the colour
+// counters (re-armed by the kernel) -- every one rewritten by a tracking call before it reads it
+int se3tn_verify_poses_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, int n, const double K[9], double object_width_mm,
+                            const uint8_t* rgb, const uint16_t* depth, int H, int W, int tol_mm, se3tn_fit* fit_out,
+                            se3tn_color_fit* color_out, int32_t* bbox_out) {
+  const char* who = "se3tn_verify_poses_host";
+  if (!c || !m || !poses || !K || !rgb || !depth || !fit_out || !color_out) return null_argument(who);
+  if (int rc = frame_check(who, H, W)) return rc;
+  if (int rc = refuse_if(!(object_width_mm > 0), SE3TN_E_ARG, who, "object_width_mm must be > 0")) return rc;
+  if (int rc = mm_check(who, "tol_mm", tol_mm)) return rc;
+  if (int rc = device_check(who, c, "verify")) return rc;
+  if (int rc = count_check(who, n, c->max_batch, "se3tn_max_batch")) return rc;
+  hipStream_t st = nullptr;
+  {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(st, &cs);   // (the default stream under another stream's capture: an error, refused too)
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (int rc = refuse_if(e != hipSuccess || cs != hipStreamCaptureStatusNone, SE3TN_E_STATE, who, "the call is synchronous, it cannot be captured"))
+      return rc;
+  }
+  if (int rc = finite_K_check(who, K)) return rc;
+  const std::string w(who);
+  std::vector<TrackWindow> windows(n);
+  const VerifyLayout L = plan_verify(n);
+  size_t bytes = L.begin;
+  for (int i = 0; i < n; ++i) {
+    const PlanStatus ps = plan_window(poses + 16 * (size_t)i, K, object_width_mm, H, W, bytes, windows[i]);
+    if (ps == PlanStatus::NOT_IN_FRONT) return fail(SE3TN_E_ARG, w + ": pose " + std::to_string(i) + " is not in front of the camera (z <= 0 or not finite)");
+    if (ps == PlanStatus::EMPTY_WINDOW) return fail(SE3TN_E_ARG, w + ": pose " + std::to_string(i) + ": empty crop window");
+  }
+  const bool frame_route = m->route == SE3TN_ROUTE_FRAME;
+  if (frame_route && H > 2048) return fail(SE3TN_E_ARG, w + ": frames of more than 2048 rows are not supported on SE3TN_ROUTE_FRAME");
+  if (int rc = reserve_track_batch(c, nullptr, n, bytes)) return rc;
+  const std::vector<const se3tn_mesh*> meshes(n, m);
+  if (int rc = reserve_objects_raster(c, n, meshes.data())) return rc;
+  size_t maxpx = 0, fr_d_off = 0;
+  if (frame_route)
+    if (int rc = reserve_frame_rects(c, n, windows.data(), H, W, &maxpx, &fr_d_off)) return rc;
+  // image A of all n poses: the instance table goes up on the launch stream, then FOUR launches (grid.y = pose)
+  uint8_t* rA = c->tb_rgbA.get();
+  uint16_t* dA = c->tb_depthA.get();
+  int singular = -1;
+  if (int rc = raster_instances(c, n, meshes.data(), poses, K, H, W, windows.data(), frame_route, rA, dA, maxpx, fr_d_off, st, &singular))
+    return singular >= 0 ? fail(SE3TN_E_ARG, w + ": pose " + std::to_string(singular) + " is singular") : rc;
+  // the frame's n windows: staged through pinned memory while the rasteriser runs, ONE copy
+  uint8_t* hp = c->tb_stage_host.get();
+  for (int i = 0; i < n; ++i) stage_window(windows[i], rgb, depth, W, hp);
+  StagedUpload up{c->trk_copy_stream};
+  if (int rc = upload_staged(c, c->tb_stage_dev.get() + L.begin, hp + L.begin, bytes - L.begin, st)) return rc;   // (every window stages >= 64 bytes)
+  se3tn_fit* fit_dev = (se3tn_fit*)(c->tb_stage_dev.get() + L.fit_off);
+  se3tn_color_fit* col_dev = (se3tn_color_fit*)(c->tb_stage_dev.get() + L.color_off);
+  for (int g0 = 0; g0 < n; g0 += ColorFitArgs::MAX) {
+    const int k = n - g0 < ColorFitArgs::MAX ? n - g0 : ColorFitArgs::MAX;
+    ColorFitArgs a;
+    for (int j = 0; j < k; ++j)
+      crop_pair(windows[g0 + j], 0.0, image_a(c, frame_route, g0 + j, rA, dA, maxpx, fr_d_off), c->tb_stage_dev.get(), a.m[j], a.o[j]);
+    a.counters = c->color_counters.get() + (size_t)ColorFitArgs::WORDS * g0;
+    a.fit_out = fit_dev + g0;
+    a.out = col_dev + g0;
+    a.tol = tol_mm;
+    HIPCHK(launch_color_fit(a, k, st));
+  }
+  HIPCHK(hipMemcpyAsync(hp, c->tb_stage_dev.get(), L.rec_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  up.done();
+  std::memcpy(fit_out, hp + L.fit_off, sizeof(se3tn_fit) * (size_t)n);
+  std::memcpy(color_out, hp + L.color_off, sizeof(se3tn_color_fit) * (size_t)n);
+  if (bbox_out)
+    for (int i = 0; i < n; ++i) std::memcpy(bbox_out + 8 * (size_t)i, windows[i].vu, sizeof(windows[i].vu));
   return SE3TN_OK;
 }
 

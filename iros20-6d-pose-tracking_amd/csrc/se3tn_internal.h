@@ -214,6 +214,21 @@ struct FitArgs {
 static_assert(sizeof(FitArgs) <= 4096, "FitArgs travels as kernel arguments: HIP's limit is 4 KB");
 hipError_t launch_fit_stats(const FitArgs& a, int n, hipStream_t st);
 
+// depth AND colour record of up to MAX (model, observed) pairs per launch (color_fit.hip): one pass, both records
+struct ColorFitArgs {
+  static constexpr int MAX = SE3TN_FIT_MAX_PAIRS;
+  static constexpr int SUMS = 24;                    // the six sums of se3tn_fit | sum_m .. sum_abs of se3tn_color_fit (px = inlier_px)
+  static constexpr int WORDS = 32;                   // counter words per pair: the SUMS | the arrival counter | unused
+  se3tn_crop m[MAX], o[MAX];  // model / observed image of pair i: rgb, depth, H, W, left .. bottom are read
+  unsigned* counters;         // [n][WORDS], zero between launches (the last workgroup of a pair to arrive re-arms them)
+  se3tn_fit* fit_out;         // [n] depth records or nullptr
+  se3tn_color_fit* out;       // [n] colour records: device memory, or mapped pinned host memory (each word stored once)
+  int tol;
+};
+static_assert(sizeof(ColorFitArgs) <= 4096, "ColorFitArgs travels as kernel arguments: HIP's limit is 4 KB");
+static_assert(sizeof(se3tn_color_fit) == 80 && sizeof(se3tn_fit) == 32, "the records are 20 / 8 words");
+hipError_t launch_color_fit(const ColorFitArgs& a, int n, hipStream_t st);
+
 // ADD / ADD-S of one chunk of pose pairs (pose_errors.hip; the index arithmetic is pose_errors_plan.h)
 struct PoseErrArgs {
   const double* pts;    // [P,3] model points

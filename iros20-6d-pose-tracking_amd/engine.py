@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ALIGN_REC_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -315,6 +315,64 @@ class Engine:
         check(self.lib.se3tn_fit_stats(self._h, arrs[0], arrs[1], n, int(tol_mm), C.c_void_p(out.data_ptr()), _stream_ptr()),
               "se3tn_fit_stats")
         return out.cpu().numpy().reshape(-1).view(FIT_DTYPE)[:n].copy()
+
+    # ---- how well a hypothesis fits the observed colour ------------------------------------------
+    def color_stats(self, model, observed, tol_mm, out=None):
+        """se3tn_color_stats: model / observed = n descriptors each, dict(rgb=cuda uint8 [H,W,3], depth=cuda 16-bit [H,W],
+        window=(left, top, right, bottom)); window defaults to the whole image.  ONE pass gives both records: returns (fit, color),
+        structured arrays of n records (_lib.FIT_DTYPE as fit_stats, _lib.COLOR_FIT_DTYPE: px, tol_mm, sum_m, sum_o, sum_mm, sum_oo,
+        sum_mo, sum_abs with three words each); synchronises on the current stream.  out: a cuda uint8 [>= n,112] tensor -- the call
+        is then only enqueued (capturable) and returns None; row-wise the first n * 32 bytes are the fit records, the n * 80 behind
+        them the colour records (color_records reads them)."""
+        n = len(model)
+        if len(observed) != n:
+            raise ValueError("color_stats: %d model and %d observed descriptors" % (n, len(observed)))
+        arrs = []
+        for group in (model, observed):
+            arr = (Crop * max(n, 1))()
+            for i, c in enumerate(group):
+                rgb, depth = c["rgb"], c["depth"]
+                assert depth.is_cuda and depth.element_size() == 2 and depth.is_contiguous() and depth.dim() == 2
+                assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous() and tuple(rgb.shape) == tuple(depth.shape) + (3,)
+                arr[i].rgb = rgb.data_ptr(); arr[i].depth = depth.data_ptr()
+                arr[i].H, arr[i].W = int(depth.shape[0]), int(depth.shape[1])
+                win = c.get("window") or (0, 0, int(depth.shape[1]), int(depth.shape[0]))
+                arr[i].left, arr[i].top, arr[i].right, arr[i].bottom = [int(v) for v in win]
+            arrs.append(arr)
+        buf = out if out is not None else torch.empty((max(n, 1), 112), dtype=torch.uint8, device="cuda:%d" % self.device)
+        assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and buf.numel() >= 112 * n
+        check(self.lib.se3tn_color_stats(self._h, arrs[0], arrs[1], n, int(tol_mm), C.c_void_p(buf.data_ptr()),
+                                         C.c_void_p(buf.data_ptr() + 32 * n), _stream_ptr()), "se3tn_color_stats")
+        return None if out is not None else self.color_records(buf, n)
+
+    @staticmethod
+    def color_records(buf, n):
+        """(fit, color) of the n pairs a color_stats(..., out=buf) call left in buf"""
+        host = buf.cpu().numpy().reshape(-1)
+        return host[:32 * n].view(FIT_DTYPE).copy(), host[32 * n:112 * n].view(COLOR_FIT_DTYPE).copy()
+
+    def verify_poses(self, mesh, poses, rgb, depth, K, object_width_mm, tol_mm=10):
+        """se3tn_verify_poses_host: "which of these n hypotheses does the frame confirm" in ONE call -- per pose its compute_bbox
+        window, its own image A (the renderer of `mesh`: a HipRenderer or its se3tn_mesh handle) and the depth and colour records of
+        that render against the frame's window.  poses [n,4,4]; rgb HxWx3 uint8, depth HxW uint16 mm (host arrays); K 3x3.
+        Returns (fit [n], color [n], bbox [n,4,2]).  Synchronous on the default stream: refused (Se3tnError, rc = SE3TN_E_STATE) while
+        the current stream is being captured -- here, since the library sees a capture only where the default stream takes part in it
+        (a blocking stream), and torch captures on non-blocking ones."""
+        if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
+            raise Se3tnError("se3tn_verify_poses_host refused (rc=-2): the call is synchronous, it cannot be captured")
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        n = len(p)
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        dep = np.ascontiguousarray(depth, dtype=np.uint16)
+        if rgb.ndim != 3 or rgb.shape[2] != 3 or dep.shape != rgb.shape[:2]:
+            raise ValueError("verify_poses: rgb must be HxWx3 uint8 and depth HxW")
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        fit, col, bb = np.zeros(max(n, 1), FIT_DTYPE), np.zeros(max(n, 1), COLOR_FIT_DTYPE), np.zeros((max(n, 1), 4, 2), np.int32)
+        check(self.lib.se3tn_verify_poses_host(
+            self._h, getattr(mesh, "_m", mesh), C.c_void_p(p.ctypes.data), n, Kc.ctypes.data_as(C.POINTER(C.c_double)),
+            C.c_double(float(object_width_mm)), C.c_void_p(rgb.ctypes.data), C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]),
+            int(tol_mm), C.c_void_p(fit.ctypes.data), C.c_void_p(col.ctypes.data), C.c_void_p(bb.ctypes.data)), "se3tn_verify_poses_host")
+        return fit[:n], col[:n], bb[:n]
 
     def set_fit_check(self, tol_mm):
         """se3tn_set_fit_check: every one-call tracking call this engine executes also scores its estimates against the observed

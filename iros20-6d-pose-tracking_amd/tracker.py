@@ -137,7 +137,7 @@ class Tracker:
         return self.engine.pose_errors(self._model_points, preds, gts)
 
     def recover(self, prev_pose, rgb, depth, trans_radius=0.05, trans_step=0.01, rot_deg=(15.0,), tol_mm=10, top=None, refine=1,
-                points=None, extra=None, facing=False, align=0):
+                points=None, extra=None, facing=False, align=0, colour=False, colour_within=0.9, color=None, color_within=None):
         """Extension: look for a lost object near where it was last seen.  The reference re-initialises from an external detector
         (predict.py:539-541); this searches the observed depth frame instead and hands the track back:
           1. the lattice of candidates around prev_pose (recover.pose_lattice; `extra`: a list of poses appended after it) is scored
@@ -159,11 +159,19 @@ class Tracker:
         steps of the facing points, Engine.align_poses) and the network, if any, starts from the aligned poses; the final pool is
         [refined..., aligned..., unaligned...] (refine=0: [aligned..., unaligned...]), scored as before, so the result never scores
         below the one without alignment.  Needs ``object_normals`` (or a handle with normals as `points`) with or without facing --
-        the scoring of the plain search stays plain.  ``last_recover`` then also keeps aligned and align_rec."""
+        the scoring of the plain search stays plain.  ``last_recover`` then also keeps aligned and align_rec.
+        colour=True (or color=True; off by default, and then not one call more is made): the final pool and its depth keys are
+        formed as above and D is their winner; the pool members with inlier_pts >= colour_within * inlier_pts[D] go through
+        verify() and the highest colour score wins (a tie: the larger depth key; every score 0: D).  Depth alone cannot tell a
+        near-symmetric object from its half turn; its colours can.  colour_within is a design choice, not a measured value.
+        ``last_recover`` then also keeps depth_chosen, color_fit, color_score and candidates."""
+        colour = bool(colour or color)
+        colour_within = colour_within if color_within is None else color_within
         if facing:
             if extra is not None and len(extra):
                 raise ValueError("recover: extra poses cannot be combined with facing=True (the lattice is scored as a product)")
-            return self._recover_facing(prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points, align)
+            return self._recover_facing(prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points, align,
+                                        colour, colour_within)
         from .engine import ModelPoints
         from .recover import pose_key, pose_lattice
         if points is None:
@@ -194,8 +202,11 @@ class Tracker:
                 info.update(aligned=aligned, align_rec=align_rec)
             if int(refine) < 1 and aligned is None:
                 info.update(final_fit=top_fit[:1].copy(), chosen=0, inlier_frac=float(top_fit["inlier_pts"][0]) / float(top_fit["points"][0]))
+                if colour:   # the pool is the ranked top of the lattice
+                    info.update(final_fit=top_fit.copy())
+                    self._choose_by_colour(info, unrefined, top_fit, rgb, dep, tol_mm, colour_within)
                 self.last_recover = info
-                return unrefined[0].copy()
+                return unrefined[info["chosen"]].copy()
             refined = unrefined if aligned is None else aligned
             for _ in range(int(refine)):
                 refined = np.asarray(self.on_track_batch(list(refined), [rgb] * k, [dep] * k), np.float64)
@@ -205,6 +216,8 @@ class Tracker:
             chosen = int(np.argmax(keys))             # keys are unique: the lower index wins a tie, and the refined poses come first
             info.update(refined=refined if int(refine) >= 1 else None, final_fit=final_fit, chosen=chosen,
                         inlier_frac=float(final_fit["inlier_pts"][chosen]) / float(final_fit["points"][chosen]))
+            if colour:
+                chosen = self._choose_by_colour(info, final, final_fit, rgb, dep, tol_mm, colour_within)
             self.last_recover = info
             return final[chosen].copy()
         finally:
@@ -265,6 +278,67 @@ class Tracker:
         final_fit = self._score_diagonal(handle, final, dep, tol_mm)
         return final, refined, final_fit, int(np.argmax(pose_key(final_fit)))   # ties prefer the earlier part of the pool: the lower index
 
+    def verify(self, poses, rgb, depth, tol_mm=10, min_px=64):
+        """Extension: which of these n pose hypotheses ([n,4,4]) does the frame (rgb HxWx3 uint8, depth HxW uint16 mm) confirm --
+        by colour, where depth cannot tell: per pose the model rendered in its own compute_bbox window against that window of the
+        frame, compared at the pixels where the two depths agree within tol_mm -> (fit [n], color [n], score [n]): the depth
+        records (as fit_stats), the colour records (_lib.COLOR_FIT_DTYPE) and utils.color_score of each (the zero-mean normalised
+        cross-correlation, mean of R, G, B; 0 below min_px compared pixels).  With the built-in HIP renderer ONE library call
+        (se3tn_verify_poses_host); with an injected renderer render_window per pose plus Engine.color_stats."""
+        from .renderer import HipRenderer
+        poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        n = len(poses)
+        if n > self.engine.max_batch:
+            raise ValueError("verify: %d poses > max_samples=%d given to Tracker()" % (n, self.engine.max_batch))
+        if n == 0:
+            from ._lib import COLOR_FIT_DTYPE, FIT_DTYPE
+            return np.zeros(0, FIT_DTYPE), np.zeros(0, COLOR_FIT_DTYPE), np.zeros(0, np.float64)
+        if self.one_call and isinstance(self.renderer, HipRenderer):
+            dep = _depth_u16(depth, rgb).view(np.uint16)   # the shape check and the reference's cast; the host call takes the uint16 itself
+            fit, color, _ = self.engine.verify_poses(self.renderer, poses, rgb, dep, self.K, self.object_width, tol_mm)
+        else:
+            fit, color = self._verify_stepwise(poses, rgb, depth, tol_mm)
+        return fit, color, np.atleast_1d(U.color_score(color, min_px))
+
+    def _verify_stepwise(self, poses, rgb, depth, tol_mm):
+        """verify on the step-by-step path: per pose render_window against the uploaded frame under the pose's own crop window,
+        through Engine.color_stats -- the records the one-call path gets from the library"""
+        rgb_d = torch.from_numpy(np.ascontiguousarray(rgb, dtype=np.uint8)).to(self._dev)
+        dep_d = torch.from_numpy(_depth_u16(depth, rgb)).to(self._dev)
+        model, observed = [], []
+        for pose in poses:
+            rgbA, depA = self.render_window(pose)
+            model.append(dict(rgb=torch.from_numpy(np.ascontiguousarray(rgbA, dtype=np.uint8)).to(self._dev),
+                              depth=torch.from_numpy(np.ascontiguousarray(depA).astype(np.uint16).view(np.int16)).to(self._dev)))
+            bb = U.compute_bbox(pose, self.K, self.object_width, scale=(1000, 1000, 1000))
+            observed.append(dict(rgb=rgb_d, depth=dep_d, window=U.crop_window(bb)))
+        return self.engine.color_stats(model, observed, tol_mm)
+
+    def _choose_by_colour(self, info, final, final_fit, rgb, dep, tol_mm, within, min_px=64):
+        """colour=True of acquire / recover: D = the depth winner (info['chosen']); the candidates are the pool members whose
+        inlier_pts reach `within` times D's -- colour never buys a pose the depth frame does not support; among them the highest
+        verify score wins, a tie goes to the larger depth key, and if every candidate scores 0, D stays.  `dep` is the uint16 frame
+        the depth stages of the caller read.  Updates info; returns the chosen index."""
+        from ._lib import COLOR_FIT_DTYPE
+        from .recover import pose_key
+        d = int(info["chosen"])
+        keys = pose_key(final_fit)
+        cand = np.flatnonzero(final_fit["inlier_pts"].astype(np.float64) >= float(within) * float(final_fit["inlier_pts"][d]))
+        score = np.zeros(len(final), np.float64)
+        color = np.zeros(len(final), COLOR_FIT_DTYPE)
+        mb = self.engine.max_batch
+        for i0 in range(0, len(cand), mb):   # (a pool of 3 x top poses may exceed the engine's batch)
+            part = cand[i0:i0 + mb]
+            _, col, sc = self.verify(final[part], rgb, dep, tol_mm, min_px)
+            color[part], score[part] = col, sc
+        chosen = d
+        if np.any(score[cand] != 0.0):
+            best = cand[score[cand] == score[cand].max()]
+            chosen = int(best[np.argmax(keys[best])])
+        info.update(depth_chosen=d, color_fit=color, color_score=score, candidates=cand, chosen=chosen,
+                    inlier_frac=self._frac(final_fit[chosen]))
+        return chosen
+
     def align(self, poses, depth, **kw):
         """Align n pose hypotheses ([n,4,4]) to the depth frame (HxW uint16 mm): Engine.align_poses on ``object_cloud`` with
         ``object_normals`` (uploaded at first use and kept) and this tracker's K -> (poses [n,4,4], records [n]); the keywords
@@ -286,7 +360,8 @@ class Tracker:
     def _frac(rec):
         return float(rec["inlier_pts"]) / float(rec["points"]) if int(rec["points"]) else 0.0
 
-    def _recover_facing(self, prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points, align=0):
+    def _recover_facing(self, prev_pose, rgb, depth, trans_radius, trans_step, rot_deg, tol_mm, top, refine, points, align=0,
+                        colour=False, colour_within=0.9):
         from .recover import lattice_factors
         handle = self._facing_handle(points, "recover")
         k = min(8, self.engine.max_batch) if top is None else int(top)
@@ -301,14 +376,20 @@ class Tracker:
             info.update(aligned=aligned, align_rec=align_rec)
         if int(refine) < 1 and aligned is None:
             info.update(final_fit=top_fit[:1].copy(), chosen=0, inlier_frac=self._frac(top_fit[0]))
+            if colour:   # the pool is the ranked top of the lattice
+                info.update(final_fit=top_fit.copy())
+                self._choose_by_colour(info, unrefined, top_fit, rgb, dep, tol_mm, colour_within)
             self.last_recover = info
-            return unrefined[0].copy()
+            return unrefined[info["chosen"]].copy()
         final, refined, final_fit, chosen = self._refine_and_choose(handle, unrefined, rgb, dep, tol_mm, refine, aligned)
         info.update(refined=refined, final_fit=final_fit, chosen=chosen, inlier_frac=self._frac(final_fit[chosen]))
+        if colour:
+            chosen = self._choose_by_colour(info, final, final_fit, rgb, dep, tol_mm, colour_within)
         self.last_recover = info
         return final[chosen].copy()
 
-    def acquire(self, rgb, depth, roi=None, views=40, inplane=12, stride=16, behind_m=0.03, tol_mm=10, top=None, refine=1, align=0):
+    def acquire(self, rgb, depth, roi=None, views=40, inplane=12, stride=16, behind_m=0.03, tol_mm=10, top=None, refine=1, align=0,
+                colour=False, colour_within=0.9, color=None, color_within=None):
         """Extension with no reference counterpart (the reference takes its first pose from a file, from ground truth or from
         PoseCNN): find the object in a frame with NO pose to start from.
           1. recover.rotation_grid(views, inplane) x recover.depth_seeds(depth, K, stride, behind_m, roi) -- rotations that cover
@@ -327,7 +408,14 @@ class Tracker:
         align = iters > 0: the hypotheses of step 2 are aligned to the depth frame before step 3 (align(): up to `iters`
         point-to-plane steps each, one device call for all of them); the network, if any, starts from the aligned poses and the
         pool of step 3 is [refined..., aligned..., unaligned...] (refine=0: [aligned..., unaligned...]).  ``last_acquire`` then
-        also keeps aligned and align_rec.  The lattices end 10 mm and 15 degrees apart; alignment ends on the surface."""
+        also keeps aligned and align_rec.  The lattices end 10 mm and 15 degrees apart; alignment ends on the surface.
+        colour=True (or color=True; off by default, and then not one call more is made): the pool of step 3 and its depth keys
+        are formed as above and D is their winner; the pool members with inlier_pts >= colour_within * inlier_pts[D] go through
+        verify() -- the model rendered at each against `rgb` -- and the highest colour score wins (a tie: the larger depth key;
+        every score 0: D).  Colour never buys a pose the depth frame does not support.  colour_within is a design choice, not a
+        measured value.  ``last_acquire`` then also keeps depth_chosen, color_fit, color_score and candidates."""
+        colour = bool(colour or color)
+        colour_within = colour_within if color_within is None else color_within
         from .recover import depth_seeds, lattice_factors, pose_key, rotation_grid
         from ._lib import POSE_SEARCH_MAX_POSES, POINT_FIT_DTYPE
         handle = self._facing_handle(None, "acquire")
@@ -357,10 +445,14 @@ class Tracker:
         if int(refine) < 1 and aligned is None:
             chosen = int(np.argmax(pose_key(local_fit)))
             info.update(final_fit=local_fit.copy(), chosen=chosen, inlier_frac=self._frac(local_fit[chosen]))
+            if colour:
+                chosen = self._choose_by_colour(info, local, local_fit, rgb, dep, tol_mm, colour_within)
             self.last_acquire = info
             return local[chosen].copy()
         final, refined, final_fit, chosen = self._refine_and_choose(handle, local, rgb, dep, tol_mm, refine, aligned)
         info.update(refined=refined, final_fit=final_fit, chosen=chosen, inlier_frac=self._frac(final_fit[chosen]))
+        if colour:
+            chosen = self._choose_by_colour(info, final, final_fit, rgb, dep, tol_mm, colour_within)
         self.last_acquire = info
         return final[chosen].copy()
 

@@ -469,6 +469,44 @@ def fit_stats(model_depth_u16, observed_depth_u16, tol_mm):
     return rec
 
 
+def color_stats(model_rgb, model_depth, observed_rgb, observed_depth, tol_mm):
+    """The colour record of se3tn_color_stats (include/se3tracknet.h) in NumPy: model / observed crops, rgb uint8 [..., 176, 176, 3]
+    and depth uint16 mm [..., 176, 176] -> a structured array of shape [...] with the fields of se3tn_color_fit.  A pixel is compared
+    exactly when it is an inlier of fit_stats: both depths valid (100 < d < 2000) and |o - m| <= tol_mm."""
+    from ._lib import COLOR_FIT_DTYPE
+    m = np.asarray(model_depth).astype(np.int64)
+    o = np.asarray(observed_depth).astype(np.int64)
+    tol = int(tol_mm)
+    cmp_ = ((m > 100) & (m < 2000) & (o > 100) & (o < 2000) & (np.abs(o - m) <= tol))[..., None]
+    mc = np.asarray(model_rgb).astype(np.int64) * cmp_
+    oc = np.asarray(observed_rgb).astype(np.int64) * cmp_
+    rec = np.zeros(m.shape[:-2], COLOR_FIT_DTYPE)
+    rec["px"] = cmp_.sum(axis=(-3, -2, -1))
+    rec["tol_mm"] = tol
+    for key, img in (("sum_m", mc), ("sum_o", oc), ("sum_mm", mc * mc), ("sum_oo", oc * oc), ("sum_mo", mc * oc), ("sum_abs", np.abs(oc - mc))):
+        rec[key] = img.sum(axis=(-3, -2))
+    return rec
+
+
+def color_score(rec, min_px=64, per_channel=False):
+    """se3tn_color_score (include/se3tracknet.h) in NumPy, the same double: the mean over R, G, B of the zero-mean normalised
+    cross-correlation of the compared pixels; 0 below min_px compared pixels, a flat channel counts 0.  float for one record, float64
+    array otherwise; per_channel=True: (score, z[..., 3])."""
+    rec = np.asarray(rec)
+    n = rec["px"].astype(np.int64)[..., None]
+    sm, so = rec["sum_m"].astype(np.int64), rec["sum_o"].astype(np.int64)
+    cov = n * rec["sum_mo"].astype(np.int64) - sm * so
+    vm = n * rec["sum_mm"].astype(np.int64) - sm * sm
+    vo = n * rec["sum_oo"].astype(np.int64) - so * so
+    ok = (vm > 0) & (vo > 0) & (n >= int(min_px))
+    den = np.sqrt(np.where(ok, vm, 1).astype(np.float64)) * np.sqrt(np.where(ok, vo, 1).astype(np.float64))
+    z = np.where(ok, cov.astype(np.float64) / den, 0.0)
+    s = ((z[..., 0] + z[..., 1]) + z[..., 2]) / 3.0
+    if s.ndim == 0:
+        s = float(s)
+    return (s, z) if per_channel else s
+
+
 def fit_ratio(rec):
     """inlier_px / model_px of fit records (0.0 where model_px == 0): float for one record, float64 array otherwise."""
     rec = np.asarray(rec)
