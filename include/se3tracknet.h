@@ -8,7 +8,7 @@
  * Conventions
  *   - plain C types only; device pointers are caller-owned (e.g. torch tensors' data_ptr());
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream);
- *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth, fit_stats, color_stats) is stream-ordered and
+ *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth, fit_stats, color_stats, scene_stats) is stream-ordered and
  *     asynchronous: no hipMalloc, no hipDeviceSynchronize, no host<->device copy of results => hipGraph-capturable.
  *     All device memory is allocated by the init-time calls: se3tn_create (activations, 176x176 z-buffer),
  *     se3tn_upload_weights / se3tn_bind_weights / se3tn_set_winograd (Winograd planes), se3tn_set_precision (f16x3 split
@@ -516,6 +516,86 @@ double se3tn_color_score(const se3tn_color_fit* rec, int min_px, double per_chan
 int se3tn_verify_poses_host(se3tn_ctx* ctx, se3tn_mesh* mesh, const double* poses, int n, const double K[9], double object_width_mm,
                             const uint8_t* rgb, const uint16_t* depth, int H, int W, int tol_mm, se3tn_fit* fit_out,
                             se3tn_color_fit* color_out, int32_t* bbox_out /* [n,4,2], may be NULL */);
+
+/* ---- the objects of one frame as ONE scene: tracked objects explain each other's occlusions -------------------------------- */
+/* se3tn_set_fit_check scores every object alone: where something stands in front of it the pixel is front_px, whatever that
+ * something is -- so an object tracked correctly BEHIND another tracked object looks lost.  The reference shows a person the renders
+ * beside the frame (cv2.imshow('AB', ...), predict.py:284-290); headless, the same look at the whole frame is one composition of the
+ * n objects' depth renders through a shared depth test: per object an integer record over the pixels where it is the nearest
+ * tracked surface, an id image of the frame (which tracked object a pixel belongs to) and the composed depth.
+ * Layer i (i < n) is a depth sub-image of the rectangle rect = {x0, y0, x1, y1} of the frame (se3tn_render_frame_rect's convention):
+ * uint16 millimetres, tightly packed [y1-y0, x1-x0]; x1 <= x0 or y1 <= y0 is a layer with no pixels.  For a frame pixel p:
+ *     m_i(p)    the layer's value if p is inside rect_i, else 0;      o(p)  the observed depth
+ *     valid(d)  100 < d < 2000, as everywhere in this library
+ *     owner(p)  the i with the smallest valid m_i(p), ties to the lowest i
+ *     ids(p)    owner + 1, or 0 if no layer is valid at p;            scene(p) = m_owner(p), or 0
+ * Always model_px == visible_px + hidden_px and seen_px == inlier_px + front_px + behind_px.  All integers: the record does not
+ * depend on the order the workgroups arrive in, and csrc/scene_fit_rule.h holds the statements both the kernel and a host program
+ * compile.  No word can overflow: two valid depths differ by at most 1999 - 101 = 1,898, a frame holds at most 2^21 pixels and
+ * 2^21 x 1,898 = 3,980,394,496 < 2^32; a frame with H * W > 2^21 is refused (1920 x 1080 fits).  hidden_by is one word and an id one
+ * byte: at most SE3TN_SCENE_MAX_OBJECTS layers. */
+#define SE3TN_SCENE_MAX_OBJECTS 32
+#define SE3TN_SCENE_MAX_PIXELS 2097152   /* 2^21 */
+/* (The record and the entry point that fills it share the name se3tn_scene_fit: the record is a struct TAG without a typedef, always
+ * written `struct se3tn_scene_fit`, which C and C++ both keep apart from the function.) */
+struct se3tn_scene_fit {   /* all uint32, 12 words, 48 bytes */
+  uint32_t model_px;     /* #{valid(m_i)}                                                      */
+  uint32_t visible_px;   /* #{valid(m_i) && owner == i}                                        */
+  uint32_t hidden_px;    /* #{valid(m_i) && owner != i}                                        */
+  uint32_t seen_px;      /* #{visible && valid(o)}                                             */
+  uint32_t inlier_px;    /* #{seen && |o - m_i| <= tol_mm}                                     */
+  uint32_t front_px;     /* #{seen && o <  m_i - tol_mm}   something UNTRACKED in front        */
+  uint32_t behind_px;    /* #{seen && o >  m_i + tol_mm}   the sensor sees through it          */
+  uint32_t sum_abs_mm;   /* sum of |o - m_i| over the inliers                                  */
+  uint32_t hidden_by;    /* bit j set iff object j owns at least one pixel where m_i is valid  */
+  uint32_t tol_mm;       /* echoed                                                             */
+  uint32_t n_objects;    /* echoed                                                             */
+  uint32_t _reserved;    /* 0                                                                  */
+};
+typedef struct se3tn_scene_layer {
+  const uint16_t* depth;   /* device, [y1-y0, x1-x0] uint16 millimetres (not read when the rectangle is empty) */
+  int32_t rect[4];         /* {x0, y0, x1, y1}: inside the frame, or empty                                     */
+} se3tn_scene_layer;
+/* The kernel alone (stands in for the eye that compares the pasted renders, predict.py:285-290).  layers: HOST array of n
+ * descriptors (copied into kernel arguments, no sync); observed_dev: device uint16 [H,W]; out_dev: n records in device memory or in
+ * mapped pinned host memory (every word is stored there once, not accumulated there); ids_dev (device uint8 [H,W]) and scene_dev
+ * (device uint16 [H,W]) may be NULL, and when given are defined for EVERY pixel of the frame (0 where there is no object).
+ * One launch: with ids_dev and scene_dev NULL its tiles cover the bounding box of the rectangles only.  Stream-ordered, capturable,
+ * allocates nothing (the counters belong to se3tn_create and are zero again when the launch ends).  As every compute call of a
+ * context: one stream.  SE3TN_E_ARG, all before anything is written: a NULL pointer (a layer that is not empty without depth
+ * included), n outside [1, min(SE3TN_SCENE_MAX_OBJECTS, se3tn_max_batch)], tol_mm outside [1, 65535], H or W < 1, H * W > 2^21, a
+ * rectangle that is not empty and not inside the frame, a host-only context. */
+int se3tn_scene_stats(se3tn_ctx* ctx, int n, const se3tn_scene_layer* layers /* host */, const uint16_t* observed_dev, int H, int W,
+                      int tol_mm, struct se3tn_scene_fit* out_dev, uint8_t* ids_dev /* [H,W], may be NULL */,
+                      uint16_t* scene_dev /* [H,W], may be NULL */, void* stream);
+/* Render, then the kernel (stands in for predict.py:284, render_window(final_estimate), done for every object of the frame at once).
+ * objects[i].mesh at poses[i] (HOST float64 [n,16] row-major) with objects[i].object_width_mm; objects[i].model is NOT read.  Per
+ * object the rectangle is se3tn_frame_rect's: the crop window of its pose intersected with the frame; all n rectangles are rendered
+ * by the per-instance rasteriser path of se3tn_on_track_objects in full-frame mode (FOUR launches), then the kernel above runs against
+ * depth_dev (device uint16 [H,W]).  EVERY mesh is rendered in full-frame mode, whatever its route and whether or not
+ * se3tn_mesh_set_texture was called on it: depth in that mode depends on the geometry only, so window-route and frame-route meshes
+ * share a call.  The layer is therefore the depth of se3tn_render_frame inside the rectangle (the model is rendered inside its
+ * rectangle only) -- NOT the depth se3tn_render gives a window-route mesh, which follows another read-back rule.  A window that
+ * misses the frame is an empty layer: all counts 0.  out_dev / ids_dev / scene_dev as se3tn_scene_stats.
+ * Stream-ordered; the poses travel through a pinned instance table of the scene stage's own, which a following call waits for (not
+ * for the launches).  The stage owns its buffers (instance table, rasteriser scratch, z-buffers, sub-images): a tracking call after
+ * a scene call returns the bits it returns on a fresh context, and a scene call between a tracking call and se3tn_last_fit /
+ * se3tn_last_fit_images leaves what those return unchanged.  The buffers grow on a first or larger call (draining the device);
+ * SE3TN_E_STATE inside a stream capture (the poses are host arguments: a replay could not carry new ones).
+ * SE3TN_E_ARG, all before anything is allocated or written: a NULL pointer or mesh, n outside [1, min(SE3TN_SCENE_MAX_OBJECTS,
+ * se3tn_max_batch)], tol_mm outside [1, 65535], H or W < 1, H > 2048, H * W > 2^21, object_width_mm <= 0, a pose not in front of the
+ * camera (z <= 0) or not finite, an empty crop window, a K entry that is not finite, a host-only context.  The context stays
+ * usable after a refusal. */
+int se3tn_scene_fit(se3tn_ctx* ctx, int n, const se3tn_object* objects, const double* poses /* host [n,16] */, const double K[9],
+                    const uint16_t* depth_dev, int H, int W, int tol_mm, struct se3tn_scene_fit* out_dev, uint8_t* ids_dev /* may be NULL */,
+                    uint16_t* scene_dev /* may be NULL */, void* stream);
+/* The same from a HOST depth frame (uint16 [H,W]) with the results to host memory: out [n] records, ids uint8 [H,W] and scene uint16
+ * [H,W] (either may be NULL).  The staging is [frame | records | ids | scene]: one upload, the launches, one read-back.  SYNCHRONOUS
+ * on `stream`, refused inside a stream capture (SE3TN_E_STATE) as se3tn_verify_poses_host refuses; the pinned staging and its device
+ * mirror (shared with se3tn_search_poses_host) grow on a first or larger call.  Refusals as se3tn_scene_fit. */
+int se3tn_scene_fit_host(se3tn_ctx* ctx, int n, const se3tn_object* objects, const double* poses /* host [n,16] */, const double K[9],
+                         const uint16_t* depth /* host [H,W] */, int H, int W, int tol_mm, struct se3tn_scene_fit* out,
+                         uint8_t* ids /* host [H,W], may be NULL */, uint16_t* scene /* host [H,W], may be NULL */, void* stream);
 
 /* ---- ADD / ADD-S of n pose pairs in one call ----------------------------------------------------------------- */
 /* Utils.py:72-98 `add` / `adi`, the two errors every result of the reference is reported in (eval_ycb.py, eval_ycbineoat.py),

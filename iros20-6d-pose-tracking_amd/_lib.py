@@ -29,6 +29,8 @@ POSE_ALIGN_MAX_POSES = 4096        # as include/se3tracknet.h: the most poses on
 POSE_ALIGN_MAX_ITERS = 64          # as include/se3tracknet.h: the most iterations of one se3tn_align_poses call
 POSE_ALIGN_SUMS = 28               # as include/se3tracknet.h: int64 sums per pose (21 of S_A | 6 of S_b | S_e)
 ALIGN_ITERS, ALIGN_CONVERGED, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2, 3   # as include/se3tracknet.h: se3tn_align_rec.status
+SCENE_MAX_OBJECTS = 32             # as include/se3tracknet.h: the most layers / objects of one se3tn_scene_stats / se3tn_scene_fit call
+SCENE_MAX_PIXELS = 1 << 21         # as include/se3tracknet.h: the largest frame (H * W) of the scene calls
 MAX_BATCH_LIMIT = 1982             # as include/se3tracknet.h: the largest max_batch se3tn_create accepts
 RES = 176
 
@@ -79,6 +81,17 @@ class PointFit(C.Structure):
                                           "_reserved")]
 
 
+class SceneFit(C.Structure):
+    """struct se3tn_scene_fit (include/se3tracknet.h): the record of one object of a frame composed with the others."""
+    _fields_ = [(k, C.c_uint32) for k in ("model_px", "visible_px", "hidden_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm",
+                                          "hidden_by", "tol_mm", "n_objects", "_reserved")]
+
+
+class SceneLayer(C.Structure):
+    """se3tn_scene_layer (include/se3tracknet.h): one depth layer of se3tn_scene_stats: a device sub-image and its rectangle."""
+    _fields_ = [("depth", C.c_void_p), ("rect", C.c_int32 * 4)]
+
+
 # the same record as a numpy dtype, for building many descriptors without a Python loop
 import numpy as _np
 CROP_DTYPE = _np.dtype([("rgb", "<u8"), ("depth", "<u8"), ("H", "<i4"), ("W", "<i4"), ("left", "<i4"), ("top", "<i4"),
@@ -93,6 +106,10 @@ assert COLOR_FIT_DTYPE.itemsize == C.sizeof(ColorFit) == 80
 POINT_FIT_FIELDS = ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm")   # the seven that carry data
 POINT_FIT_DTYPE = _np.dtype([(k, "<u4") for k in POINT_FIT_FIELDS + ("_reserved",)])
 assert POINT_FIT_DTYPE.itemsize == C.sizeof(PointFit) == 32
+SCENE_FIT_FIELDS = ("model_px", "visible_px", "hidden_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm", "hidden_by", "tol_mm",
+                    "n_objects")   # the eleven that carry data
+SCENE_FIT_DTYPE = _np.dtype([(k, "<u4") for k in SCENE_FIT_FIELDS + ("_reserved",)])
+assert SCENE_FIT_DTYPE.itemsize == C.sizeof(SceneFit) == 48 and C.sizeof(SceneLayer) == 24
 ALIGN_REC_DTYPE = _np.dtype([("iterations", "<u4"), ("status", "<u4"), ("pairs", "<u4"), ("facing_pts", "<u4"), ("sum_r2", "<i8"),
                              ("pairs0", "<u4"), ("_reserved", "<u4"), ("sum_r2_0", "<i8")])
 assert ALIGN_REC_DTYPE.itemsize == C.sizeof(AlignRec) == 40 and C.sizeof(AlignParams) == 32
@@ -178,6 +195,12 @@ _SIGS = {
     "se3tn_color_score": (C.c_double, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "se3tn_verify_poses_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_scene_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneLayer), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "se3tn_scene_fit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Object), C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_scene_fit_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Object), C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_points_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "se3tn_points_destroy": (None, [C.c_void_p]),
     "se3tn_points_count": (C.c_int, [C.c_void_p]),

@@ -18,6 +18,7 @@
 #include "pose_errors_plan.h"
 #include "pose_grid_plan.h"
 #include "pose_search_plan.h"
+#include "scene_fit_plan.h"
 #include "se3tn_internal.h"
 #include "tex_pyramid.h"
 #include "track_plan.h"
@@ -143,6 +144,20 @@ struct se3tn_ctx {
   PinnedBuf<se3tn_fit> fit_host;
   // se3tn_color_stats / se3tn_verify_poses_host: per-pair counters [max_batch][ColorFitArgs::WORDS] (se3tn_create; zero between launches)
   DeviceBuf<unsigned> color_counters;
+  // the scene stage.  se3tn_scene_stats: the counters [SCENE_COUNTER_WORDS] (se3tn_create; zero between launches).  se3tn_scene_fit:
+  // buffers of the stage's OWN, so that no tracking call reads what a scene call wrote and the other way round -- the pinned instance
+  // table and its device mirror ([cap RasterInstance | cap RasterMaterial]), rasteriser scratch for sc_cap instances of up to sc_V
+  // vertices / sc_F triangles, the rendered rectangles ([64 bytes | rgb | depth], fr_sub's layout) and their z-buffers for sc_px
+  // pixels in all; grown at need (scene_reserve).  sc_table_event: recorded behind the table's upload, waited for before the next
+  // call rewrites the pinned table (the call itself is stream-ordered)
+  DeviceBuf<unsigned> sc_counters;
+  int sc_cap = 0, sc_V = 0, sc_F = 0;
+  RasterScratch sc_mo;
+  PinnedBuf<uint8_t> sc_inst_host; DeviceBuf<uint8_t> sc_inst_dev;
+  size_t sc_px = 0;
+  DeviceBuf<uint8_t> sc_sub;
+  DeviceBuf<unsigned long long> sc_zbuf;
+  hipEvent_t sc_table_event = nullptr; bool sc_table_busy = false;
   // the synchronous _host entry points of the pose family (StagedCall): pinned staging of ps_cap bytes and its device mirror, laid out
   // per call (pose_errors_plan.h: pe_stage_*, pose_search_plan.h: PsStage, pose_grid_plan.h: PgStage, pose_align_plan.h: PaStage)
   PinnedBuf<unsigned char> ps_host; DeviceBuf<unsigned char> ps_dev; size_t ps_cap = 0;
@@ -177,6 +192,7 @@ struct se3tn_ctx {
     for (auto& g : graphs)
       if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (trk_copy_event) (void)hipEventDestroy(trk_copy_event);
+    if (sc_table_event) (void)hipEventDestroy(sc_table_event);
     if (trk_copy_stream) (void)hipStreamDestroy(trk_copy_stream);
     for (int s = 0; s < slots; ++s)
       for (auto& e : evs[s]) (void)hipEventDestroy(e);
@@ -501,6 +517,7 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
     if (e == hipSuccess) e = c->tail_arrive.alloc(c->max_batch, true);
     if (e == hipSuccess) e = c->fit_counters.alloc((size_t)FitArgs::WORDS * c->max_batch, true);
     if (e == hipSuccess) e = c->color_counters.alloc((size_t)ColorFitArgs::WORDS * c->max_batch, true);
+    if (e == hipSuccess) e = c->sc_counters.alloc((size_t)SCENE_COUNTER_WORDS, true);
     if (const char* sk = std::getenv("SE3TN_SMALL_KERNELS")) c->small_kernels = std::atoi(sk) != 0;
     if (const char* tp = std::getenv("SE3TN_TAIL_PARTS")) { c->tail_parts = std::atoi(tp) != 0; c->tail_parts_ch = std::atoi(tp) == 2 ? 32 : 16; }
     if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(split-K workspace)"); }
@@ -1955,9 +1972,16 @@ int se3tn_align_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const dou
 }
 
 static int reserve_objects_raster(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes);
+// where raster_instances keeps its scratch, its instance table and (frame route) its sub-images and z-buffers: the context's
+// (nullptr), or the scene stage's own
+struct RasterHome {
+  const RasterScratch* mo;
+  uint8_t *inst_host, *inst_dev, *sub;
+  unsigned long long* zbuf;
+};
 static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* poses, const double K[9], int H, int W,
                             const TrackWindow* windows, bool frame_route, uint8_t* rgb, uint16_t* depth, size_t maxpx, size_t fr_d_off,
-                            hipStream_t st, int* singular);
+                            hipStream_t st, int* singular, const RasterHome* home = nullptr);
 
 // se3tn_set_fit_check's stage of the three bodies, after their pose read-back (so `st` is idle and the instance table, the rasteriser
 // scratch and, on the frame route, the rectangles' sub-images and z-buffers of image A are free again): every pair's mesh rendered at
@@ -2149,24 +2173,26 @@ static int reserve_objects_raster(se3tn_ctx* c, int n, const se3tn_mesh* const* 
 // n instances in the rasteriser's FOUR launches (grid.y = instance), every one with its own mesh, pose and window and, on the frame
 // route, its own material: the instance table (the materials behind the n instance records) goes up in one copy on `st`.  Window
 // route: the 176 x 176 renders land in the stacks rgb / depth; frame route: every rectangle in c->fr_sub (maxpx, fr_d_off:
-// reserve_frame_rects).  The scratch, the table and the z-buffers are reserved.  A singular pose: SE3TN_E_ARG with *singular = its
+// reserve_frame_rects) -- or all of these where `home` says.  The scratch, the table and the z-buffers are reserved.  A singular pose: SE3TN_E_ARG with *singular = its
 // index and no text (the refusal is the caller's)
 static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const double* poses, const double K[9], int H, int W,
                             const TrackWindow* windows, bool frame_route, uint8_t* rgb, uint16_t* depth, size_t maxpx, size_t fr_d_off,
-                            hipStream_t st, int* singular) {
+                            hipStream_t st, int* singular, const RasterHome* home) {
+  const RasterHome ctx_home{&c->mo, c->tb_inst_host.get(), c->tb_inst_dev.get(), c->fr_sub.get(), c->fr_zbuf.get()};
+  if (!home) home = &ctx_home;
   RasterArgs ra{};
   raster_common(ra, c, const_cast<se3tn_mesh*>(meshes[0]), rgb, depth);
   ra.rw = RES; ra.rh = RES; ra.mode = 0;
-  raster_scratch(ra, c->mo);
+  raster_scratch(ra, *home->mo);
   ra.zbuf = c->tb_zbuf.get();
   largest_mesh(meshes, n, &ra.V, &ra.F);
   ra.inst_mesh = 1;
-  RasterInstance* inst_host = (RasterInstance*)c->tb_inst_host.get();
+  RasterInstance* inst_host = (RasterInstance*)home->inst_host;
   RasterMaterial* mat_host = (RasterMaterial*)(inst_host + n);
   if (frame_route) {
     ra.rw = W; ra.rh = H; ra.mode = 1;   // (matrix, mesh, material and rectangle come from the tables)
-    ra.rgb = c->fr_sub.get() + 64; ra.depth = (uint16_t*)(c->fr_sub.get() + fr_d_off);
-    ra.zbuf = c->fr_zbuf.get();
+    ra.rgb = home->sub + 64; ra.depth = (uint16_t*)(home->sub + fr_d_off);
+    ra.zbuf = home->zbuf;
     ra.scissor = 1; ra.spx = (int)maxpx;
     ra.inst_mesh = 2;   // every instance with its own material: the table behind the n instance records
   }
@@ -2187,8 +2213,8 @@ static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes
   }
   if (frame_route && maxpx == 0) return SE3TN_OK;   // (every window off the frame: nothing to render)
   const size_t tab_bytes = sizeof(RasterInstance) * n + (frame_route ? sizeof(RasterMaterial) * n : 0);
-  HIPCHK(hipMemcpyAsync(c->tb_inst_dev.get(), inst_host, tab_bytes, hipMemcpyHostToDevice, st));
-  ra.inst = (const RasterInstance*)c->tb_inst_dev.get();
+  HIPCHK(hipMemcpyAsync(home->inst_dev, inst_host, tab_bytes, hipMemcpyHostToDevice, st));
+  ra.inst = (const RasterInstance*)home->inst_dev;
   HIPCHK(launch_raster(ra, st, n));
   return SE3TN_OK;
 }
@@ -2270,6 +2296,177 @@ int se3tn_verify_poses_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, in
   std::memcpy(color_out, hp + L.color_off, sizeof(se3tn_color_fit) * (size_t)n);
   if (bbox_out)
     for (int i = 0; i < n; ++i) std::memcpy(bbox_out + 8 * (size_t)i, windows[i].vu, sizeof(windows[i].vu));
+  return SE3TN_OK;
+}
+
+// ---- the objects of one frame as one scene -------------------------------------------------------------------------------------------
+// what the three entry points refuse alike, before anything is allocated or written
+static int scene_args_check(const char* who, const se3tn_ctx* c, int n, int tol_mm, int H, int W, bool rendering) {
+  if (int rc = frame_check(who, H, W)) return rc;
+  if (int rc = mm_check(who, "tol_mm", tol_mm)) return rc;
+  if (int rc = refuse_if(rendering && H > 2048, SE3TN_E_ARG, who, "frames of more than 2048 rows are not supported (as se3tn_render_frame)")) return rc;
+  if (int rc = refuse_if(!scene_frame_ok(H, W), SE3TN_E_ARG, who, "H * W > 2^21 pixels: sum_abs_mm could overflow its word")) return rc;
+  const int most = c->max_batch < SE3TN_SCENE_MAX_OBJECTS ? c->max_batch : SE3TN_SCENE_MAX_OBJECTS;
+  if (int rc = count_check(who, n, most, "min(SE3TN_SCENE_MAX_OBJECTS, se3tn_max_batch)")) return rc;
+  return device_check(who, c, "compose the scene");
+}
+
+// the kernel on n checked layers
+static int scene_enqueue(se3tn_ctx* c, int n, const se3tn_scene_layer* layers, const uint16_t* observed, int H, int W, int tol_mm,
+                         struct se3tn_scene_fit* out, uint8_t* ids, uint16_t* scene, hipStream_t st) {
+  SceneArgs a{};
+  int32_t rects[4 * SceneArgs::MAX];
+  for (int i = 0; i < n; ++i) {
+    std::memcpy(rects + 4 * i, layers[i].rect, sizeof(layers[i].rect));
+    const bool empty = scene_rect_empty(layers[i].rect);
+    a.l[i].depth = empty ? nullptr : layers[i].depth;
+    a.l[i].x0 = empty ? 0 : layers[i].rect[0]; a.l[i].y0 = empty ? 0 : layers[i].rect[1];
+    a.l[i].x1 = empty ? 0 : layers[i].rect[2]; a.l[i].y1 = empty ? 0 : layers[i].rect[3];
+  }
+  a.observed = observed; a.H = H; a.W = W; a.n = n; a.tol = tol_mm;
+  a.plan = plan_scene(n, rects, H, W, ids != nullptr || scene != nullptr);
+  a.counters = c->sc_counters.get();
+  a.out = out; a.ids = ids; a.scene = scene;
+  HIPCHK(launch_scene_fit(a, st));
+  return SE3TN_OK;
+}
+
+int se3tn_scene_stats(se3tn_ctx* c, int n, const se3tn_scene_layer* layers, const uint16_t* observed_dev, int H, int W, int tol_mm,
+                      struct se3tn_scene_fit* out_dev, uint8_t* ids_dev, uint16_t* scene_dev, void* stream) {
+  const char* who = "se3tn_scene_stats";
+  if (!c || !layers || !observed_dev || !out_dev) return null_argument(who);
+  if (int rc = scene_args_check(who, c, n, tol_mm, H, W, false)) return rc;
+  for (int i = 0; i < n; ++i) {
+    if (int rc = refuse_if(!scene_rect_ok(layers[i].rect, H, W), SE3TN_E_ARG, who,
+                           "layer " + std::to_string(i) + ": its rectangle is not empty and not inside the frame")) return rc;
+    if (int rc = refuse_if(!scene_rect_empty(layers[i].rect) && !layers[i].depth, SE3TN_E_ARG, who,
+                           "layer " + std::to_string(i) + ": NULL depth")) return rc;
+  }
+  return scene_enqueue(c, n, layers, observed_dev, H, W, tol_mm, out_dev, ids_dev, scene_dev, (hipStream_t)stream);
+}
+
+// the refusals of se3tn_scene_fit / _host that concern the objects, and per object the window of its pose (plan_window: x0, y0, sw,
+// sh = se3tn_frame_rect's rectangle, miss = a window off the frame)
+static int scene_windows(const char* who, int n, const se3tn_object* objs, const double* poses, const double K[9], int H, int W,
+                         std::vector<TrackWindow>& windows, std::vector<const se3tn_mesh*>& meshes) {
+  const std::string w(who);
+  if (int rc = finite_K_check(who, K)) return rc;
+  if (int rc = finite_check(who, "pose", poses, nullptr, (size_t)n, 16, 12)) return rc;
+  windows.resize(n);
+  meshes.resize(n);
+  size_t bytes = 0;   // (nothing is staged: the offsets plan_window hands out are not used)
+  for (int i = 0; i < n; ++i) {
+    if (int rc = refuse_if(!objs[i].mesh, SE3TN_E_ARG, who, "object " + std::to_string(i) + " has no mesh")) return rc;
+    if (int rc = refuse_if(!(objs[i].object_width_mm > 0), SE3TN_E_ARG, who, "object " + std::to_string(i) + ": object_width_mm must be > 0")) return rc;
+    const PlanStatus ps = plan_window(poses + 16 * (size_t)i, K, objs[i].object_width_mm, H, W, bytes, windows[i]);
+    if (ps == PlanStatus::NOT_IN_FRONT) return fail(SE3TN_E_ARG, w + ": pose " + std::to_string(i) + " is not in front of the camera (z <= 0 or not finite)");
+    if (ps == PlanStatus::EMPTY_WINDOW) return fail(SE3TN_E_ARG, w + ": pose " + std::to_string(i) + ": empty crop window");
+    meshes[i] = objs[i].mesh;
+  }
+  return SE3TN_OK;
+}
+
+// the scene stage's own buffers for n instances of these meshes and these rectangles (sized as reserve_frame_rects sizes fr_sub:
+// n x the largest rectangle of the call, half as much again in hand, never past n whole frames)
+static int scene_reserve(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes, const TrackWindow* windows, int H, int W, size_t* maxpx,
+                         size_t* d_off) {
+  int V, F;
+  largest_mesh(meshes, n, &V, &F);
+  size_t mx = 0;
+  for (int i = 0; i < n; ++i)
+    if (!windows[i].miss) mx = std::max(mx, (size_t)windows[i].sw * (size_t)windows[i].sh);
+  const size_t need = mx ? (size_t)n * mx : 1, most = (size_t)n * H * W;
+  *maxpx = mx;
+  *d_off = 64 + (((size_t)n * mx * 3 + 63) & ~(size_t)63);
+  if (n <= c->sc_cap && V <= c->sc_V && F <= c->sc_F && need <= c->sc_px) return SE3TN_OK;
+  DeviceGuard dg(c->device);
+  if (int rc = begin_growth(dg)) return rc;
+  c->sc_table_busy = false;   // (the device has been drained)
+  if (!c->sc_table_event) HIPCHK(hipEventCreateWithFlags(&c->sc_table_event, hipEventDisableTiming));
+  if (n > c->sc_cap || V > c->sc_V || F > c->sc_F) {
+    const int cap = n > c->max_batch ? n : c->max_batch;
+    V = V > c->sc_V ? V : c->sc_V;
+    F = F > c->sc_F ? F : c->sc_F;
+    c->sc_cap = 0; c->sc_V = 0; c->sc_F = 0;
+    HIPCHK(c->sc_inst_host.alloc((sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap));
+    HIPCHK(c->sc_inst_dev.alloc((sizeof(RasterInstance) + sizeof(RasterMaterial)) * cap));
+    HIPCHK(c->sc_mo.alloc(V, F, cap));
+    c->sc_cap = cap; c->sc_V = V; c->sc_F = F;
+  }
+  if (need > c->sc_px) {
+    const size_t px = std::max(need, std::min(need + need / 2, most));
+    c->sc_px = 0;
+    HIPCHK(c->sc_sub.alloc(64 + ((px * 3 + 63) & ~(size_t)63) + px * 2 + 64));
+    HIPCHK(c->sc_zbuf.alloc(px));
+    c->sc_px = px;
+  }
+  return SE3TN_OK;
+}
+
+// render + kernel on `st`; everything has been checked
+static int scene_fit_enqueue(se3tn_ctx* c, int n, const std::vector<const se3tn_mesh*>& meshes, const std::vector<TrackWindow>& windows,
+                             const double* poses, const double K[9], const uint16_t* depth_dev, int H, int W, int tol_mm,
+                             struct se3tn_scene_fit* out, uint8_t* ids, uint16_t* scene, hipStream_t st) {
+  size_t maxpx = 0, d_off = 0;
+  if (int rc = scene_reserve(c, n, meshes.data(), windows.data(), H, W, &maxpx, &d_off)) return rc;
+  if (c->sc_table_busy) {   // the previous call's table may still be on its way up: wait for that copy (not for its launches)
+    HIPCHK(hipEventSynchronize(c->sc_table_event));
+    c->sc_table_busy = false;
+  }
+  const RasterHome home{&c->sc_mo, c->sc_inst_host.get(), c->sc_inst_dev.get(), c->sc_sub.get(), c->sc_zbuf.get()};
+  int singular = -1;   // (never set in frame mode)
+  const int rr = raster_instances(c, n, meshes.data(), poses, K, H, W, windows.data(), true, nullptr, nullptr, maxpx, d_off, st, &singular, &home);
+  if (maxpx != 0) {
+    HIPCHK(hipEventRecord(c->sc_table_event, st));
+    c->sc_table_busy = true;
+  }
+  if (rr) return rr;
+  se3tn_scene_layer layers[SE3TN_SCENE_MAX_OBJECTS];
+  for (int i = 0; i < n; ++i) {
+    const TrackWindow& t = windows[i];
+    layers[i].depth = t.miss ? nullptr : (const uint16_t*)(c->sc_sub.get() + d_off) + (size_t)i * maxpx;
+    const int32_t r[4] = {t.x0, t.y0, t.x0 + t.sw, t.y0 + t.sh};
+    for (int k = 0; k < 4; ++k) layers[i].rect[k] = t.miss ? 0 : r[k];
+  }
+  return scene_enqueue(c, n, layers, depth_dev, H, W, tol_mm, out, ids, scene, st);
+}
+
+int se3tn_scene_fit(se3tn_ctx* c, int n, const se3tn_object* objs, const double* poses, const double K[9], const uint16_t* depth_dev, int H,
+                    int W, int tol_mm, struct se3tn_scene_fit* out_dev, uint8_t* ids_dev, uint16_t* scene_dev, void* stream) {
+  const char* who = "se3tn_scene_fit";
+  if (!c || !objs || !poses || !K || !depth_dev || !out_dev) return null_argument(who);
+  if (int rc = scene_args_check(who, c, n, tol_mm, H, W, true)) return rc;
+  std::vector<TrackWindow> windows;
+  std::vector<const se3tn_mesh*> meshes;
+  if (int rc = scene_windows(who, n, objs, poses, K, H, W, windows, meshes)) return rc;
+  if (int rc = refuse_if(stream_is_capturing((hipStream_t)stream), SE3TN_E_STATE, who,
+                         "the poses are host arguments, a captured call could not carry new ones: capture se3tn_scene_stats instead")) return rc;
+  return scene_fit_enqueue(c, n, meshes, windows, poses, K, depth_dev, H, W, tol_mm, out_dev, ids_dev, scene_dev, (hipStream_t)stream);
+}
+
+int se3tn_scene_fit_host(se3tn_ctx* c, int n, const se3tn_object* objs, const double* poses, const double K[9], const uint16_t* depth, int H,
+                         int W, int tol_mm, struct se3tn_scene_fit* out, uint8_t* ids, uint16_t* scene, void* stream) {
+  const char* who = "se3tn_scene_fit_host";
+  if (!c || !objs || !poses || !K || !depth || !out) return null_argument(who);
+  if (int rc = scene_args_check(who, c, n, tol_mm, H, W, true)) return rc;
+  std::vector<TrackWindow> windows;
+  std::vector<const se3tn_mesh*> meshes;
+  if (int rc = scene_windows(who, n, objs, poses, K, H, W, windows, meshes)) return rc;
+  StagedCall sc{c, who, (hipStream_t)stream};
+  if (int rc = sc.refuse_capture()) return rc;
+  const SceneStage L = plan_scene_stage(n, H, W, ids != nullptr, scene != nullptr);
+  if (int rc = sc.grow(L.total)) return rc;
+  std::memcpy(sc.h, depth, L.up_bytes);
+  if (int rc = sc.upload(L.up_bytes)) return rc;
+  if (int rc = scene_fit_enqueue(c, n, meshes, windows, poses, K, sc.dev<uint16_t>(0), H, W, tol_mm, sc.dev<struct se3tn_scene_fit>(L.rec_off),
+                                 ids ? sc.dev<uint8_t>(L.ids_off) : nullptr, scene ? sc.dev<uint16_t>(L.scene_off) : nullptr, sc.st)) {
+    (void)hipStreamSynchronize(sc.st);   // (the upload reads the pinned staging: let it end before the next call writes there)
+    return rc;
+  }
+  if (int rc = sc.finish(L.rec_off, L.total - L.rec_off)) return rc;
+  std::memcpy(out, sc.h + L.rec_off, sizeof(struct se3tn_scene_fit) * (size_t)n);
+  if (ids) std::memcpy(ids, sc.h + L.ids_off, (size_t)H * W);
+  if (scene) std::memcpy(scene, sc.h + L.scene_off, (size_t)H * W * 2);
   return SE3TN_OK;
 }
 

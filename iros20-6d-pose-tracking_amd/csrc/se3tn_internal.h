@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/se3tracknet.h"
+#include "scene_fit_plan.h"   // the scene kernel's rule, tiles and counter words
 #include "infer_plan.h"   // network geometry, ConvId / conv_specs, the planned steps the conv launchers execute
 
 namespace se3tn {
@@ -228,6 +229,23 @@ struct ColorFitArgs {
 static_assert(sizeof(ColorFitArgs) <= 4096, "ColorFitArgs travels as kernel arguments: HIP's limit is 4 KB");
 static_assert(sizeof(se3tn_color_fit) == 80 && sizeof(se3tn_fit) == 32, "the records are 20 / 8 words");
 hipError_t launch_color_fit(const ColorFitArgs& a, int n, hipStream_t st);
+
+// n depth layers of one frame through a shared depth test (scene_fit.hip; the rule: scene_fit_rule.h, tiles and counters: scene_fit_plan.h);
+// the layers travel as kernel arguments
+struct SceneArgs {
+  static constexpr int MAX = SCENE_MAX_LAYERS;   // 32 x 24 B + constants = 0.9 KB of kernel arguments
+  SceneLayer l[MAX];          // layer i: device depth sub-image and its rectangle (empty: no pixels)
+  const uint16_t* observed;   // [H,W] millimetres
+  int H, W, n, tol;
+  ScenePlan plan;             // the area the tiles cover
+  unsigned* counters;         // [SCENE_COUNTER_WORDS], zero between launches (the last workgroup to arrive re-arms them)
+  struct se3tn_scene_fit* out;       // [n] records: device memory, or mapped pinned host memory (each word stored once)
+  uint8_t* ids;               // [H,W] or nullptr (then plan must cover the whole frame)
+  uint16_t* scene;            // [H,W] or nullptr
+};
+static_assert(sizeof(SceneArgs) <= 4096 && SceneArgs::MAX == SE3TN_SCENE_MAX_OBJECTS, "SceneArgs travels as kernel arguments: HIP's limit is 4 KB");
+static_assert(sizeof(struct se3tn_scene_fit) == 4 * SCENE_RECORD_WORDS, "the record is 12 words");
+hipError_t launch_scene_fit(const SceneArgs& a, hipStream_t st);
 
 // ADD / ADD-S of one chunk of pose pairs (pose_errors.hip; the index arithmetic is pose_errors_plan.h)
 struct PoseErrArgs {

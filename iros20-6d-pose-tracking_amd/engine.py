@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, SCENE_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -402,6 +402,96 @@ class Engine:
         check(self.lib.se3tn_memcpy_d2d(C.c_void_p(rgb.data_ptr()), rgb_p, n * RES * RES * 3, _stream_ptr()), "se3tn_memcpy_d2d")
         check(self.lib.se3tn_memcpy_d2d(C.c_void_p(dep.data_ptr()), dep_p, n * RES * RES * 2, _stream_ptr()), "se3tn_memcpy_d2d")
         return rgb, dep
+
+    # ---- the objects of one frame as one scene ---------------------------------------------------
+    def scene_stats(self, layers, rects, observed, tol_mm, ids=True, scene=True, out=None):
+        """se3tn_scene_stats: n depth layers of one frame composed through a shared depth test (the rule: utils.scene_stats).
+        layers: n cuda 16-bit tensors, layer i of rects[i][3]-rects[i][1] rows x rects[i][2]-rects[i][0] columns, contiguous (None for
+        an empty rectangle); rects [n,4] (x0, y0, x1, y1); observed: cuda 16-bit [H,W].  ids / scene: also compute the id image (cuda
+        uint8 [H,W]) / the composed depth (cuda int16 [H,W]).  Returns (records, ids, scene): records a structured array
+        (_lib.SCENE_FIT_DTYPE), the images as numpy arrays (uint8, uint16) or None; synchronises on the current stream.
+        out: where the n records go -- a cuda uint8 tensor of >= 48 n bytes, or the DEVICE address (int) of mapped pinned host memory;
+        the call is then only enqueued (capturable), records is None and the images stay device tensors."""
+        r = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(-1, 4))
+        n = len(r)
+        if len(layers) != n:
+            raise ValueError("scene_stats: %d layers and %d rectangles" % (len(layers), n))
+        assert observed.is_cuda and observed.element_size() == 2 and observed.is_contiguous() and observed.dim() == 2
+        H, W = int(observed.shape[0]), int(observed.shape[1])
+        arr = (_lib.SceneLayer * max(n, 1))()
+        for i in range(n):
+            w, h = int(r[i, 2] - r[i, 0]), int(r[i, 3] - r[i, 1])
+            arr[i].rect[:] = [int(v) for v in r[i]]
+            if w > 0 and h > 0 and layers[i] is not None:
+                d = layers[i]
+                assert d.is_cuda and d.element_size() == 2 and d.is_contiguous() and d.numel() == w * h
+                arr[i].depth = d.data_ptr()
+        dev = "cuda:%d" % self.device
+        ids_t = torch.empty((H, W), dtype=torch.uint8, device=dev) if ids else None
+        scene_t = torch.empty((H, W), dtype=torch.int16, device=dev) if scene else None
+        rec_t = None
+        if out is None:
+            rec_t = torch.empty((max(n, 1), 48), dtype=torch.uint8, device=dev)
+            out_p = rec_t.data_ptr()
+        else:
+            out_p = out.data_ptr() if torch.is_tensor(out) else int(out)
+        check(self.lib.se3tn_scene_stats(self._h, n, arr, C.c_void_p(observed.data_ptr()), H, W, int(tol_mm), C.c_void_p(out_p),
+                                         C.c_void_p(ids_t.data_ptr()) if ids else None, C.c_void_p(scene_t.data_ptr()) if scene else None,
+                                         _stream_ptr()), "se3tn_scene_stats")
+        if rec_t is None:
+            return None, ids_t, scene_t
+        rec = rec_t.cpu().numpy().reshape(-1).view(SCENE_FIT_DTYPE)[:n].copy()
+        return rec, (ids_t.cpu().numpy() if ids else None), (scene_t.cpu().numpy().view(np.uint16) if scene else None)
+
+    @staticmethod
+    def _scene_objects(objects):
+        """an se3tn_object array from a ctypes array of them, or from (mesh | HipRenderer, object_width_mm) pairs; model stays NULL
+        (the scene calls do not read it)"""
+        if isinstance(objects, C.Array):
+            return objects, len(objects)
+        objs = (_lib.Object * max(len(objects), 1))()
+        for i, (mesh, width) in enumerate(objects):
+            m = getattr(mesh, "_m", mesh)
+            objs[i].mesh = m.value if isinstance(m, C.c_void_p) else m
+            objs[i].object_width_mm = float(width)
+        return objs, len(objects)
+
+    def scene_fit(self, objects, poses, depth, K, tol_mm=10, ids=False, scene=False):
+        """se3tn_scene_fit / se3tn_scene_fit_host: render the objects' meshes at `poses` ([n,4,4]) into their se3tn_frame_rect
+        rectangles (full-frame mode, whatever a mesh's route or material), compose them through a shared depth test and score every
+        object over the pixels where it is the nearest tracked surface.  objects: a ctypes array of _lib.Object, or (mesh | HipRenderer,
+        object_width_mm) pairs.  depth: a numpy uint16 [H,W] frame -> the host entry (one upload, one read-back, synchronous; refused
+        while the current stream is being captured) with numpy results; a cuda 16-bit [H,W] tensor -> the device entry on the current
+        stream with ids / scene as device tensors (uint8 / int16) and the records read back (which synchronises).
+        Returns (records [n] of _lib.SCENE_FIT_DTYPE, ids | None, scene | None)."""
+        objs, n = self._scene_objects(objects)
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        if len(p) != n:
+            raise ValueError("scene_fit: %d poses for %d objects" % (len(p), n))
+        Kp = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9)).ctypes.data_as(C.POINTER(C.c_double))
+        if torch.is_tensor(depth):
+            assert depth.is_cuda and depth.element_size() == 2 and depth.is_contiguous() and depth.dim() == 2
+            H, W = int(depth.shape[0]), int(depth.shape[1])
+            rec_t = torch.empty((max(n, 1), 48), dtype=torch.uint8, device=depth.device)
+            ids_t = torch.empty((H, W), dtype=torch.uint8, device=depth.device) if ids else None
+            scene_t = torch.empty((H, W), dtype=torch.int16, device=depth.device) if scene else None
+            check(self.lib.se3tn_scene_fit(self._h, n, objs, C.c_void_p(p.ctypes.data), Kp, C.c_void_p(depth.data_ptr()), H, W, int(tol_mm),
+                                           C.c_void_p(rec_t.data_ptr()), C.c_void_p(ids_t.data_ptr()) if ids else None,
+                                           C.c_void_p(scene_t.data_ptr()) if scene else None, _stream_ptr()), "se3tn_scene_fit")
+            return rec_t.cpu().numpy().reshape(-1).view(SCENE_FIT_DTYPE)[:n].copy(), ids_t, scene_t
+        if self.device >= 0 and torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
+            raise Se3tnError("se3tn_scene_fit_host refused (rc=-2): the call is synchronous, it cannot be captured")
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("scene_fit: depth must be [H,W]")
+        H, W = int(d.shape[0]), int(d.shape[1])
+        rec = np.zeros(max(n, 1), SCENE_FIT_DTYPE)
+        ids_a = np.zeros((H, W), np.uint8) if ids else None
+        scene_a = np.zeros((H, W), np.uint16) if scene else None
+        check(self.lib.se3tn_scene_fit_host(self._h, n, objs, C.c_void_p(p.ctypes.data), Kp, C.c_void_p(d.ctypes.data), H, W, int(tol_mm),
+                                            C.c_void_p(rec.ctypes.data), C.c_void_p(ids_a.ctypes.data) if ids else None,
+                                            C.c_void_p(scene_a.ctypes.data) if scene else None, _stream_ptr()), "se3tn_scene_fit_host")
+        return rec[:n], ids_a, scene_a
 
     # ---- ADD / ADD-S of n pose pairs -------------------------------------------------------------
     def model_points(self, pts, normals=None):

@@ -179,6 +179,28 @@ class LiveMultiTracker:
     def last_fit_ratio(self):
         return self.tracker.last_fit_ratio
 
+    @property
+    def scene_check(self):
+        """The tracker's scene_check (None | tol_mm): with it set every on_track is followed by one scene call at the estimates, in
+        which the tracked objects explain each other's occlusions; tracker.last_prediction["scene_fit"], last_scene_ratio and
+        scene_status() carry the result.  (Acting on "lost" is left to the caller.)"""
+        return self.tracker.scene_check
+
+    @scene_check.setter
+    def scene_check(self, tol_mm):
+        self.tracker.scene_check = tol_mm
+
+    @property
+    def last_scene_ratio(self):
+        return self.tracker.last_scene_ratio
+
+    def scene_status(self, lost_below=0.5, min_visible=0.2):
+        """"tracked" | "lost" | "occluded" per object from the last on_track's scene records (utils.scene_status); None when
+        scene_check is off or no frame has been tracked."""
+        from . import utils as U
+        rec = (self.tracker.last_prediction or {}).get("scene_fit") if self.tracker.scene_check else None
+        return None if rec is None else U.scene_status(rec, lost_below, min_visible)
+
     def reset(self, poses_init):
         self.color = None
         self._depth = None

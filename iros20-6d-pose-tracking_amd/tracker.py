@@ -835,7 +835,24 @@ class MultiTracker:
         self.last_recover = None     # recover(): what the last search found (dict)
         self.last_fit_ratio = None   # fit_check set: inlier_px / model_px per object of the last call ([n] array)
         self._pred_rgb = self._pred_depth = None
+        # scene_check (extension): None (default) -- not one call more than before -- or tol_mm: every on_track / on_track_live is
+        # followed by ONE scene call at the estimates (scene_fit below)
+        self.scene_check = None
+        self.scene_ids = False           # scene_check set: also keep the id image of the frame in last_prediction["ids"]
+        self.last_scene_ratio = None     # scene_check set: inlier_px / visible_px per object ([n] array, NaN where nothing is visible)
+        self.last_visible_share = None   # scene_check set: visible_px / model_px per object ([n] array, NaN where model_px == 0)
+        self._filled = None              # scene_check on the live path: the filled frame, when the caller brought no depth_filled
         self.frame_cnt = 0
+
+    def scene_fit(self, poses, depth, tol_mm=10, ids=False):
+        """The tracked objects as ONE scene (Engine.scene_fit with this tracker's meshes, widths and camera): every object's mesh
+        rendered at poses[i] inside its frame rectangle, composed through a shared depth test and scored against `depth` (numpy uint16
+        [H,W]: the host entry; cuda 16-bit [H,W]: the device entry) over the pixels where it is the nearest TRACKED surface -- so an
+        object behind another tracked object is "hidden" there, not "lost".  Returns the [n] records (_lib.SCENE_FIT_DTYPE), or
+        (records, ids) with ids=True: the instance mask of the frame, uint8 [H,W], 0 = no tracked object, i + 1 = trackers[i].
+        utils.scene_status reads the records."""
+        rec, ids_img, _ = self.engine.scene_fit(self._objs, poses, depth, self.K, tol_mm=tol_mm, ids=ids)
+        return (rec, ids_img) if ids else rec
 
     @property
     def fit_check(self):
@@ -915,6 +932,10 @@ class MultiTracker:
             if filled is not None and not (filled.is_cuda and filled.element_size() == 2 and filled.is_contiguous()
                                            and tuple(filled.shape) == (H, W)):
                 raise ValueError("depth_filled must be a contiguous 16-bit device tensor [H,W]")
+            if filled is None and self.scene_check:   # the scene call reads the filled frame, which stays on the device
+                if self._filled is None or tuple(self._filled.shape) != (H, W):
+                    self._filled = torch.empty((H, W), dtype=torch.int16, device=self._dev)
+                filled = self._filled
             check(self.engine.lib.se3tn_on_track_objects_live(
                 self.engine._h, n, self._objs, C.c_void_p(poses.ctypes.data), self.K.ctypes.data_as(C.POINTER(C.c_double)),
                 C.c_void_p(rgb.ctypes.data), order, C.c_void_p(dep.ctypes.data), H, W, C.c_double(max_depth), extrapolate, blur,
@@ -929,6 +950,15 @@ class MultiTracker:
             self.engine.last_fit_images(n, self._pred_rgb, self._pred_depth)
             self.last_prediction.update(fit=fit, pred_rgb=self._pred_rgb, pred_depth=self._pred_depth)
             self.last_fit_ratio = U.fit_ratio(fit)
+        self.last_scene_ratio = self.last_visible_share = None
+        if self.scene_check:   # ONE scene call at the estimates: against the frame as given, or (live) the filled frame on the device
+            rec, ids_img, _ = self.engine.scene_fit(self._objs, out, dep if live is None else filled, self.K, tol_mm=int(self.scene_check),
+                                                    ids=bool(self.scene_ids))
+            self.last_prediction["scene_fit"] = rec
+            if self.scene_ids:
+                self.last_prediction["ids"] = ids_img
+            self.last_scene_ratio = U.scene_ratio(rec)
+            self.last_visible_share = U.visible_share(rec)
         self.frame_cnt += 1
         return out.reshape(n, 4, 4)
 

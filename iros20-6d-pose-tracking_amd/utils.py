@@ -512,3 +512,79 @@ def fit_ratio(rec):
     rec = np.asarray(rec)
     r = np.where(rec["model_px"] > 0, rec["inlier_px"] / np.maximum(rec["model_px"], 1), 0.0)
     return float(r) if r.ndim == 0 else r
+
+
+def scene_stats(layers, rects, observed, tol_mm):
+    """The rule of se3tn_scene_stats (include/se3tracknet.h, csrc/scene_fit_rule.h) in NumPy: n depth layers of one frame composed
+    through a shared depth test.  layers: n uint16 millimetre sub-images, layer i of shape [y1-y0, x1-x0] of rects[i] = (x0, y0, x1,
+    y1) (None or anything for an empty rectangle, x1 <= x0 or y1 <= y0); observed: uint16 [H,W].  Returns (records [n] of
+    _lib.SCENE_FIT_DTYPE, ids uint8 [H,W], scene uint16 [H,W]): owner(p) = the layer with the smallest valid depth at p, ties to the
+    lowest index; ids = owner + 1 or 0; every count of layer i over the frame, inlier .. behind over the pixels it owns."""
+    from ._lib import SCENE_FIT_DTYPE, SCENE_MAX_OBJECTS, SCENE_MAX_PIXELS
+    o = np.asarray(observed).astype(np.int64)
+    if o.ndim != 2 or o.size < 1 or o.size > SCENE_MAX_PIXELS:
+        raise ValueError("scene_stats: observed must be [H,W] with 1 <= H * W <= 2^21")
+    H, W = o.shape
+    rects = np.asarray(rects, np.int64).reshape(-1, 4)
+    n, tol = len(rects), int(tol_mm)
+    if not 1 <= n <= SCENE_MAX_OBJECTS or len(layers) != n or not 1 <= tol <= 65535:
+        raise ValueError("scene_stats: 1 .. %d layers with one rectangle each, tol_mm in [1, 65535]" % SCENE_MAX_OBJECTS)
+    M = np.zeros((n, H, W), np.int64)
+    for i, (x0, y0, x1, y1) in enumerate(rects):
+        if x1 <= x0 or y1 <= y0:
+            continue
+        if x0 < 0 or y0 < 0 or x1 > W or y1 > H:
+            raise ValueError("scene_stats: rectangle %d is not empty and not inside the frame" % i)
+        M[i, y0:y1, x0:x1] = np.asarray(layers[i]).astype(np.int64).reshape(y1 - y0, x1 - x0)
+    valid = (M > 100) & (M < 2000)
+    key = np.where(valid, M, 1 << 30)
+    owner = key.argmin(0)                       # the first minimum: ties go to the lowest index
+    owned = valid.any(0)
+    ids = np.where(owned, owner + 1, 0).astype(np.uint8)
+    scene = np.where(owned, key.min(0), 0).astype(np.uint16)
+    valid_o = (o > 100) & (o < 2000)
+    rec = np.zeros(n, SCENE_FIT_DTYPE)
+    for i in range(n):
+        visible = valid[i] & (owner == i)
+        hidden = valid[i] & ~visible
+        seen = visible & valid_o
+        d = o - M[i]
+        inlier = seen & (np.abs(d) <= tol)
+        for k, mask in (("model_px", valid[i]), ("visible_px", visible), ("hidden_px", hidden), ("seen_px", seen), ("inlier_px", inlier),
+                        ("front_px", seen & (d < -tol)), ("behind_px", seen & (d > tol))):
+            rec[k][i] = mask.sum()
+        rec["sum_abs_mm"][i] = np.abs(d)[inlier].sum()
+        rec["hidden_by"][i] = np.bitwise_or.reduce(np.left_shift(1, np.unique(owner[hidden])), initial=0)
+    rec["tol_mm"] = tol
+    rec["n_objects"] = n
+    return rec, ids, scene
+
+
+def scene_ratio(rec):
+    """inlier_px / visible_px of scene records, NaN where visible_px == 0 (float64 array)."""
+    rec = np.asarray(rec)
+    v = rec["visible_px"].astype(np.float64)
+    return np.where(v > 0, rec["inlier_px"] / np.maximum(v, 1.0), np.nan)
+
+
+def visible_share(rec):
+    """visible_px / model_px of scene records, NaN where model_px == 0 (float64 array)."""
+    rec = np.asarray(rec)
+    m = rec["model_px"].astype(np.float64)
+    return np.where(m > 0, rec["visible_px"] / np.maximum(m, 1.0), np.nan)
+
+
+def scene_status(records, lost_below, min_visible):
+    """What scene records say about each object, pure host: "occluded" when visible_px < min_visible * model_px or model_px == 0 (too
+    little of it is the nearest tracked surface to judge; nothing visible at all counts as occluded whatever min_visible is), else
+    "lost" when inlier_px / visible_px < lost_below, else "tracked".  A list of n strings."""
+    out = []
+    for r in np.atleast_1d(np.asarray(records)):
+        model, visible, inlier = int(r["model_px"]), int(r["visible_px"]), int(r["inlier_px"])
+        if model == 0 or visible == 0 or visible < float(min_visible) * model:
+            out.append("occluded")
+        elif inlier / visible < float(lost_below):
+            out.append("lost")
+        else:
+            out.append("tracked")
+    return out
