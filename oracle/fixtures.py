@@ -461,6 +461,169 @@ def soup_frame_pose():
     return pose(4, (0.01, -0.02, 0.28))
 
 
+# ---- large frames: where the rasteriser's float32 set-up arithmetic stops being exact --------------------------------------------------
+# (tests/test_raster_large_frames_oracle.py proves on the CPU what the two soups reach at these sizes and holds the rules to the live GL
+# library on them; tests/test_gpu_raster_large_frames.py holds the HIP kernels to the rules.)  (H, W): the size include/se3tracknet.h
+# names; the row limit and the 2^21-pixel limit at once; the row limit in a cheap frame.
+LARGE_FRAMES = [(1080, 1920), (2048, 1024), (2048, 96)]
+SLIVER_Z = (0.2, 1.8, 1.9)               # camera depth (m) of the nearest and the farthest sliver band, and of the backdrop
+SLIVER_LATTICE = 12                      # near-collinear lattice triangles per sliver soup
+SLIVER_MARGIN = 2.0                      # pixels between every sliver vertex and the frame's edge
+
+
+def large_frame_K(hw):
+    """SOUP_FRAME_K scaled to an H x W frame: the frame soup keeps its layout across every edge and the near plane under soup_frame_pose()"""
+    K = SOUP_FRAME_K.copy()
+    K[0] *= hw[1] / float(SOUP_FRAME_HW[1])
+    K[1] *= hw[0] / float(SOUP_FRAME_HW[0])
+    return K
+
+
+def float_area(X, Y):
+    """the sign-deciding sum of oracle/ss_rules.setup_triangle on snapped coordinates X, Y [n,3], in its float32 operation order"""
+    x, y = np.asarray(X).astype(np.float32), np.asarray(Y).astype(np.float32)
+    return ((y[:, 2] - y[:, 0]) * x[:, 1] + (y[:, 1] - y[:, 2]) * x[:, 0]) + (y[:, 0] - y[:, 1]) * x[:, 2]
+
+
+def exact_area(X, Y):
+    """the same sum in integers"""
+    x, y = np.asarray(X).astype(np.int64), np.asarray(Y).astype(np.int64)
+    return (y[:, 2] - y[:, 0]) * x[:, 1] + (y[:, 1] - y[:, 2]) * x[:, 0] + (y[:, 0] - y[:, 1]) * x[:, 2]
+
+
+def _bezout(p, q):
+    """(ex, ey) with p ey - q ex = 1 for coprime p, q"""
+    r0, r1, s0, s1, t0, t1 = p, q, 1, 0, 0, 1
+    while r1:
+        k = r0 // r1
+        r0, r1, s0, s1, t0, t1 = r1, r0 - k * r1, s1, s0 - k * s1, t1, t0 - k * t1
+    assert abs(r0) == 1                                   # s0 p + t0 q = r0
+    return -t0 * r0, s0 * r0
+
+
+def _near_collinear(rng, hw, n, misjudged):
+    """n triangles in snapped coordinates (1/16 pixel), two vertices on one lattice line v0 + k (p, q), the third one lattice step e off
+    it with p e_y - q e_x = 1: twice the area is the number of steps between the first two, at most 64 units where the products of the
+    float32 sum reach 2^30.  Up to `misjudged` of them are chosen so that the float sum is zero or has the wrong sign."""
+    H, W = hw
+    lo, hi = int(16 * SLIVER_MARGIN), np.array([16 * (W - SLIVER_MARGIN) - 16, 16 * (H - SLIVER_MARGIN) - 16])
+    bad, good = [], []
+    for _ in range(6000):
+        if len(bad) >= misjudged and len(bad) + len(good) >= n:
+            break
+        p, q = int(rng.integers(50, 8 * W)) * int(rng.choice([-1, 1])), int(rng.integers(50, 8 * H))
+        if np.gcd(p, q) != 1:
+            continue
+        e = np.array(_bezout(p, q))
+        assert p * e[1] - q * e[0] == 1
+        v0 = rng.integers(lo, hi + 1)
+        reach = min(int(min((hi[0] - v0[0]) // p if p > 0 else (v0[0] - lo) // -p, (hi[1] - v0[1]) // q)), 64)
+        if reach < 2:
+            continue
+        m = int(rng.integers(2, reach + 1))
+        k = int(rng.integers(0, m + 1))
+        tri = np.stack([v0, v0 + m * np.array([p, q]), v0 + k * np.array([p, q]) + int(rng.choice([-1, 1])) * e])[rng.permutation(3)]
+        if (tri < lo).any() or (tri > hi).any():
+            continue
+        fa, ea = float(float_area(tri[None, :, 0], tri[None, :, 1])[0]), int(exact_area(tri[None, :, 0], tri[None, :, 1])[0])
+        assert abs(ea) == m
+        (bad if (fa == 0 or (fa < 0) != (ea < 0)) else good).append(tri)
+    out = bad[:misjudged] + good
+    out = (out + bad[misjudged:])[:n]
+    assert len(out) == n, "near-collinear lattice triangles"
+    return np.array(out)
+
+
+def soup_slivers(hw, seed=0):
+    """The soup that makes the float32 set-up of a triangle inexact at large frames, for the frame hw = (H, W) under large_frame_K(hw)
+    and soup_frame_pose(): 480 thin triangles, both windings, three strongly different vertex colours each -- 456 with a long edge of a
+    quarter to the whole of the frame's diagonal and a width of 1 to 20 pixels (bounding boxes far above RASTER_BIG_PX: the wave-per-
+    triangle path), 24 upright ones, up to 110 pixels long and 1 to 2 wide, in the corner farthest from the window's origin (the
+    thread-per-triangle path); SLIVER_LATTICE near-collinear lattice triangles
+    (_near_collinear); behind them one backdrop quad.  Everything lies inside the frustum (the unclipped small and big paths).  Every
+    triangle has a band of camera depth of its own (sliver_owner_from_depth reads the owner back from a depth buffer).  All vertices
+    are chosen in snapped window coordinates and inverted through the projection in float64; the generator asserts with
+    oracle/ss_rules.project that the float32 projection snaps the lattice triangles where targeted.  Dict as soup_frame()'s, no texture,
+    plus `target` int64 [n,3,2]: the snapped (X, Y) aimed at, `lattice` / `short`: the indices of the near-collinear and of the short
+    triangles, `band`: each triangle's depth band."""
+    from . import ss_rules as S
+    H, W = hw
+    rng = np.random.default_rng(5000 + 7 * H + W + seed)
+    n_sl, n_short = 480, 24
+    lo, hi = np.array([SLIVER_MARGIN, SLIVER_MARGIN]), np.array([W - SLIVER_MARGIN, H - SLIVER_MARGIN])
+    diag = float(np.hypot(H, W))
+    tris = []
+    while len(tris) < n_sl:
+        a, b = rng.uniform(lo, hi), rng.uniform(lo, hi)
+        L = np.linalg.norm(b - a)
+        if not diag / 4 <= L <= diag:
+            continue
+        nrm = np.array([-(b - a)[1], (b - a)[0]]) / L
+        c = a + rng.uniform(0.1, 0.9) * (b - a) + rng.choice([-1, 1]) * rng.uniform(1, 20) * nrm
+        if (c < lo).any() or (c > hi).any():
+            continue
+        tris.append(np.stack([a, b, c])[rng.permutation(3)])
+    for k in range(n_short):                             # the last n_short: along an axis and short, a bounding box of under 256 pixels
+        ax = 1                                           # upright (the sum's products are row differences times columns), in the corner
+                                                         # farthest from the window's origin
+        L, wd, t = rng.uniform(0.55, 1.0) * min(110.0, 0.6 * (hi - lo)[ax]), rng.uniform(1.0, 2.0), rng.uniform(0.1, 0.9)
+        tri, ext = np.array([[0, 0], [L, 0], [t * L, wd]]), np.array([L + 1, wd + 1])
+        if ax:
+            tri, ext = tri[:, ::-1], ext[::-1]
+        corner = np.array([hi[0], lo[1]])                # (image coordinates: the largest X, and the largest GL Y = the smallest v)
+        base = corner + [-1, 1] * (rng.uniform(0, 0.2, 2) * (hi - lo)) - [ext[0], 0]
+        tris[n_sl - n_short + k] = (base + tri)[rng.permutation(3)]
+    target = np.rint((np.array(tris) - 0.5) * 16).astype(np.int64)                    # pixel i's centre (i + 0.5) is 16 i
+    lattice = _near_collinear(rng, hw, SLIVER_LATTICE, 8)
+    m_px = SLIVER_MARGIN + 1.3125
+    back = np.rint((np.array([[m_px, m_px], [W - m_px, m_px], [W - m_px, H - m_px], [m_px, H - m_px]]) - 0.5) * 16).astype(np.int64)
+    order = rng.permutation(n_sl + SLIVER_LATTICE)                                    # draw order; the depth bands follow the index before it
+    target = np.concatenate([np.concatenate([target, lattice])[order], back[[0, 1, 2]][None], back[[0, 2, 3]][None]])
+    n = len(target)
+    band = (SLIVER_Z[1] - SLIVER_Z[0]) / (n_sl + SLIVER_LATTICE)
+    z = SLIVER_Z[0] + band * (order[:, None] + rng.uniform(0.0, 0.3, (len(order), 3)))
+    is_lat = order >= n_sl
+    z[is_lat] = z[is_lat, :1]                            # (a near-collinear triangle's depth plane means nothing: one depth on all three)
+    z = np.concatenate([z, np.full((2, 3), SLIVER_Z[2])])
+    # snapped window coordinates -> continuous image coordinates (GL rows count bottom-up) -> camera -> object, in float64
+    K, P = large_frame_K(hw), soup_frame_pose()
+    u, v = target[..., 0] / 16.0 + 0.5, H - (target[..., 1] / 16.0 + 0.5)
+    cam = np.stack([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z], -1)
+    obj = (cam - P[:3, 3]) @ P[:3, :3]
+    m = _soup_pack(obj, rng)
+    base = np.array([[250, 30, 30], [30, 250, 30], [30, 30, 250]])
+    m["colors"] = np.concatenate([base[rng.permutation(3)] + rng.integers(-25, 6, (3, 3)) for _ in range(n)]).astype(np.uint8)
+    m["kd"] = np.array([0.9, 1.0, 0.8])
+    m["target"], m["lattice"] = target, np.nonzero(np.r_[is_lat, False, False])[0]
+    m["band"] = np.r_[order, n - 2, n - 2].astype(np.int64)
+    m["short"] = np.nonzero(np.r_[(order >= n_sl - n_short) & (order < n_sl), False, False])[0]
+    pv = S.project(S.clip_positions(m["vertices"], S.frame_pv(P, K, W, H)), W, H)
+    got = np.stack([pv["X"], pv["Y"]], -1).reshape(n, 3, 2)
+    assert np.array_equal(got[m["lattice"]], target[m["lattice"]]), "the near-collinear triangles snap where targeted"
+    assert not pv["flags"].any(), "the sliver soup stays inside the frustum"
+    return m
+
+
+def sliver_owner_from_depth(zbuf, m):
+    """the triangle each pixel of a float32 depth buffer (1.0 = cleared) of the sliver soup m shows, read from the depth alone: every
+    triangle lies in a band of camera depth of its own (vertex depths fill the lower 30 % of the band).  int32 [H,W], -1 = none; the two
+    triangles of the backdrop share one depth and both read as the first of them, len(faces) - 2."""
+    n = len(m["faces"])
+    zb = np.asarray(zbuf, np.float64)
+    near, far = 0.1, 2.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cam = 2.0 * near * far / ((far + near) - (2.0 * zb - 1.0) * (far - near))
+    band = (SLIVER_Z[1] - SLIVER_Z[0]) / (n - 2)
+    k = np.floor((cam - SLIVER_Z[0]) / band + 0.35)
+    k = np.where(np.isfinite(k), np.clip(k, -1, n - 2), -1).astype(np.int64)
+    of_band = np.full(n, -1, np.int32)                  # band -> triangle; the last entry serves band n - 2 and beyond: the backdrop
+    of_band[m["band"][:n - 2]] = np.arange(n - 2)
+    of_band[n - 2] = n - 2
+    owner = of_band[k]
+    owner[~(zb < 1.0)] = -1
+    return owner
+
+
 def soup_composite_poses():
     """two ordinary views and a close-up that puts much of the model before the near plane and some of it behind the camera"""
     return [pose(32, (0.02, -0.01, 0.5)), pose(33, (-0.03, 0.02, 0.62)), pose(34, (0.01, 0.0, 0.16))]

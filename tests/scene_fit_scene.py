@@ -115,14 +115,15 @@ def oracle_depth(mesh, G, hw=None, k=None):
                           K if k is None else k, w, h)[1]
 
 
-def oracle_layers(se3, meshes, poses, widths, hw=None):
+def oracle_layers(se3, meshes, poses, widths, hw=None, k=None):
     """per object (layer, rect): the oracle's render cut to se3tn_frame_rect's rectangle of the pose"""
     h, w = hw or HW
+    k = K if k is None else k
     layers, rects = [], []
     for mesh, G, width in zip(meshes, poses, widths):
-        x0, y0, x1, y1 = se3.frame_rect(G, K, width, h, w) or (0, 0, 0, 0)        # (None: the window misses the frame)
+        x0, y0, x1, y1 = se3.frame_rect(G, k, width, h, w) or (0, 0, 0, 0)        # (None: the window misses the frame)
         rects.append((x0, y0, x1, y1))
-        layers.append(np.ascontiguousarray(oracle_depth(mesh, G, (h, w))[y0:y1, x0:x1]) if (x1 > x0 and y1 > y0) else None)
+        layers.append(np.ascontiguousarray(oracle_depth(mesh, G, (h, w), k)[y0:y1, x0:x1]) if (x1 > x0 and y1 > y0) else None)
     return layers, rects
 
 

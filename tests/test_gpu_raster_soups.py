@@ -113,8 +113,10 @@ def test_window_route_under_the_numpy2_offset_rule(se3, eng2, fam, i):
         eng2.set_offset_rule("numpy1")
 
 
-@pytest.mark.parametrize("fam,i", RULE_CASES)
+@pytest.mark.parametrize("fam,i", CASES)
 def test_window_route_under_the_8_bit_subpixel_rule(se3, eng2, fam, i):
+    """every family: under the finer snap the float area of most triangles of `small`, `big` and `far` is inexact
+    (tests/test_raster_large_frames_oracle.py counts them)"""
     m, P, want = family_case(fam, i, sub_bits=8)
     try:
         eng2.set_raster_rule(8)
