@@ -56,8 +56,10 @@ const char* se3tn_last_error(void);
  * 1 <= max_batch <= SE3TN_MAX_BATCH_LIMIT, else SE3TN_E_ARG before anything is allocated.  The limit is where a 32-bit BYTE offset
  * from the base of a whole activation tensor would pass 2^31: the stride-2 gather kernel's DMA offsets into the 46 x 46 x 128 trunk
  * map (1,083,392 bytes per pair; conv3x3_gather_s2_kernel) are formed in `int`; every other per-batch index of the network kernels is
- * either 64-bit or reaches 2^31 later ("Routes and transitions").  Derived by reading the kernels, not by running there:
- * the tests run up to 256 pairs. */
+ * either 64-bit or reaches 2^31 later ("The largest batch").  Derived by reading the kernels -- tests/test_largest_batch_plan.py
+ * restates every 32-bit expression that grows with the batch and evaluates it at every size up to here -- and run:
+ * tests/test_gpu_largest_batch.py holds every pair of calls of 541 .. 1982 pairs to float64 (where `stem` passes 2^31 and 2^32 bytes, the
+ * F(4x4) planes 2^31, and at the limit itself) in six configurations on contexts of max_batch 1982.  Nothing was found. */
 #define SE3TN_MAX_BATCH_LIMIT 1982
 int se3tn_create(int device, int max_batch, se3tn_ctx** out);
 void se3tn_destroy(se3tn_ctx* ctx);

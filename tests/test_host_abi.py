@@ -366,7 +366,7 @@ def test_hip_buffers_ownership_under_sanitizers(tmp_path):
 
 def test_create_refuses_a_max_batch_above_the_limit(se3):
     """se3tn_create: SE3TN_E_ARG with a message above SE3TN_MAX_BATCH_LIMIT (the bound of the kernels' 32-bit byte offsets, derived by
-    reading them; nothing is run at or near it), before a context exists; a normal create works afterwards.  The constant is the
+    reading them: tests/test_largest_batch_plan.py; run up to it by tests/test_gpu_largest_batch.py), before a context exists; a normal create works afterwards.  The constant is the
     header's, mirrored in _lib, and is where the stride-2 gather's `int` offsets into the 46 x 46 x 128 map would pass 2^31."""
     L = se3._lib
     hdr = open(os.path.join(ROOT, "include", "se3tracknet.h")).read()
