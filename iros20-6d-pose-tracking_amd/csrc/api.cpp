@@ -142,7 +142,7 @@ struct se3tn_ctx {
   int fit_tol = 0, fit_last_n = 0, fit_cap = 0;
   DeviceBuf<uint8_t> fit_rgb; DeviceBuf<uint16_t> fit_depth;
   PinnedBuf<se3tn_fit> fit_host;
-  // se3tn_color_stats / se3tn_verify_poses_host: per-pair counters [max_batch][ColorFitArgs::WORDS] (se3tn_create; zero between launches)
+  // se3tn_color_stats / se3tn_verify_poses_host: per-pair counters [max_batch][FitArgs::COLOUR_WORDS] (se3tn_create; zero between launches)
   DeviceBuf<unsigned> color_counters;
   // the scene stage.  se3tn_scene_stats: the counters [SCENE_COUNTER_WORDS] (se3tn_create; zero between launches).  se3tn_scene_fit:
   // buffers of the stage's OWN, so that no tracking call reads what a scene call wrote and the other way round -- the pinned instance
@@ -461,6 +461,45 @@ struct StagedCall {
   template <class T> T* dev(size_t at) const { return reinterpret_cast<T*>(d + at); }
 };
 
+// ---- the crop records: what se3tn_fit_stats, the fit check, se3tn_color_stats and se3tn_verify_poses_host share ----------------------------
+// what se3tn_fit_stats and se3tn_color_stats refuse alike (rgb_read: the colour record reads rgb too)
+static int crops_check(const std::string& who, const se3tn_ctx* c, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm,
+                       const void* out_dev, bool rgb_read) {
+  if (!c || c->device < 0 || !model || !observed || !out_dev) return fail(SE3TN_E_ARG, who + ": bad argument");
+  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, who + ": n outside [1, max_batch]");
+  if (tol_mm < 1 || tol_mm > 65535) return fail(SE3TN_E_ARG, who + ": tol_mm outside [1, 65535]");
+  for (int i = 0; i < n; ++i)
+    for (const se3tn_crop* k : {model + i, observed + i})
+      if ((rgb_read && !k->rgb) || !k->depth || k->H < 1 || k->W < 1 || k->right <= k->left || k->bottom <= k->top)
+        return fail(SE3TN_E_ARG, who + ": descriptor " + std::to_string(i) + (rgb_read ? ": NULL rgb or depth" : ": NULL depth") + ", empty image or empty window");
+  return SE3TN_OK;
+}
+
+// The crop records of n pairs, FitArgs::MAX pairs per launch (the descriptors travel as kernel arguments): pair(j, m, o) fills
+// pair j's descriptors.  `colour` asks for the colour records too and picks the context's counters (fit launches and colour
+// launches on two streams of one context do not touch each other's words); raw_depth: the raw crop stacks (FitArgs)
+template <class Pair>
+static int fit_launches(se3tn_ctx* c, int n, Pair pair, se3tn_fit* fit, se3tn_color_fit* colour, int tol, uint8_t* raw_rgb, uint16_t* raw_depth,
+                        hipStream_t st) {
+  unsigned* const counters = colour ? c->color_counters.get() : c->fit_counters.get();
+  const size_t words = colour ? FitArgs::COLOUR_WORDS : FitArgs::WORDS;
+  for (int g0 = 0; g0 < n; g0 += FitArgs::MAX) {
+    const int k = n - g0 < FitArgs::MAX ? n - g0 : FitArgs::MAX;
+    FitArgs a;
+    for (int j = 0; j < k; ++j) pair(g0 + j, a.m[j], a.o[j]);
+    a.counters = counters + words * g0;
+    a.fit = fit ? fit + g0 : nullptr;
+    a.colour = colour ? colour + g0 : nullptr;
+    a.tol = tol;
+    if (raw_depth) {
+      a.raw_rgb = raw_rgb + (size_t)g0 * RES * RES * 3;
+      a.raw_depth = raw_depth + (size_t)g0 * RES * RES;
+    }
+    HIPCHK(launch_fit_stats(a, k, st));
+  }
+  return SE3TN_OK;
+}
+
 extern "C" {
 
 const char* se3tn_version(void) { return "se3tracknet-gfx950 0.6.0 (blob v7)"; }
@@ -516,7 +555,7 @@ int se3tn_create(int device, int max_batch, se3tn_ctx** out) {
     e = c->part.alloc((size_t)16 * 1024 * 121 * 16);
     if (e == hipSuccess) e = c->tail_arrive.alloc(c->max_batch, true);
     if (e == hipSuccess) e = c->fit_counters.alloc((size_t)FitArgs::WORDS * c->max_batch, true);
-    if (e == hipSuccess) e = c->color_counters.alloc((size_t)ColorFitArgs::WORDS * c->max_batch, true);
+    if (e == hipSuccess) e = c->color_counters.alloc((size_t)FitArgs::COLOUR_WORDS * c->max_batch, true);
     if (e == hipSuccess) e = c->sc_counters.alloc((size_t)SCENE_COUNTER_WORDS, true);
     if (const char* sk = std::getenv("SE3TN_SMALL_KERNELS")) c->small_kernels = std::atoi(sk) != 0;
     if (const char* tp = std::getenv("SE3TN_TAIL_PARTS")) { c->tail_parts = std::atoi(tp) != 0; c->tail_parts_ch = std::atoi(tp) == 2 ? 32 : 16; }
@@ -1596,24 +1635,9 @@ static int read_back_tracks(se3tn_ctx* c, int n, hipStream_t st, double* pose_ou
 
 // ---- the fit record ---------------------------------------------------------------------------------------------------------------
 int se3tn_fit_stats(se3tn_ctx* c, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm, se3tn_fit* out_dev, void* stream) {
-  if (!c || c->device < 0 || !model || !observed || !out_dev) return fail(SE3TN_E_ARG, "se3tn_fit_stats: bad argument");
-  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_fit_stats: n outside [1, max_batch]");
-  if (tol_mm < 1 || tol_mm > 65535) return fail(SE3TN_E_ARG, "se3tn_fit_stats: tol_mm outside [1, 65535]");
-  for (int i = 0; i < n; ++i)
-    for (const se3tn_crop* k : {model + i, observed + i})
-      if (!k->depth || k->H < 1 || k->W < 1 || k->right <= k->left || k->bottom <= k->top)
-        return fail(SE3TN_E_ARG, "se3tn_fit_stats: descriptor " + std::to_string(i) + ": NULL depth, empty image or empty window");
-  for (int g0 = 0; g0 < n; g0 += FitArgs::MAX) {   // the descriptors travel as kernel arguments, FitArgs::MAX pairs per launch
-    const int k = n - g0 < FitArgs::MAX ? n - g0 : FitArgs::MAX;
-    FitArgs a;
-    std::memcpy(a.m, model + g0, sizeof(se3tn_crop) * k);
-    std::memcpy(a.o, observed + g0, sizeof(se3tn_crop) * k);
-    a.counters = c->fit_counters.get() + (size_t)FitArgs::WORDS * g0;
-    a.out = out_dev + g0;
-    a.tol = tol_mm;
-    HIPCHK(launch_fit_stats(a, k, (hipStream_t)stream));
-  }
-  return SE3TN_OK;
+  if (int rc = crops_check("se3tn_fit_stats", c, model, observed, n, tol_mm, out_dev, false)) return rc;
+  return fit_launches(c, n, [&](int j, se3tn_crop& m, se3tn_crop& o) { m = model[j]; o = observed[j]; }, out_dev, nullptr, tol_mm, nullptr, nullptr,
+                      (hipStream_t)stream);
 }
 
 int se3tn_set_fit_check(se3tn_ctx* c, int tol_mm) {
@@ -1642,25 +1666,9 @@ int se3tn_last_fit_images(se3tn_ctx* c, const uint8_t** rgb_dev, const uint16_t*
 // ---- the colour record --------------------------------------------------------------------------------------------------------------
 int se3tn_color_stats(se3tn_ctx* c, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm, se3tn_fit* fit_out_dev,
                       se3tn_color_fit* out_dev, void* stream) {
-  if (!c || c->device < 0 || !model || !observed || !out_dev) return fail(SE3TN_E_ARG, "se3tn_color_stats: bad argument");
-  if (n < 1 || n > c->max_batch) return fail(SE3TN_E_ARG, "se3tn_color_stats: n outside [1, max_batch]");
-  if (tol_mm < 1 || tol_mm > 65535) return fail(SE3TN_E_ARG, "se3tn_color_stats: tol_mm outside [1, 65535]");
-  for (int i = 0; i < n; ++i)
-    for (const se3tn_crop* k : {model + i, observed + i})
-      if (!k->rgb || !k->depth || k->H < 1 || k->W < 1 || k->right <= k->left || k->bottom <= k->top)
-        return fail(SE3TN_E_ARG, "se3tn_color_stats: descriptor " + std::to_string(i) + ": NULL rgb or depth, empty image or empty window");
-  for (int g0 = 0; g0 < n; g0 += ColorFitArgs::MAX) {   // the descriptors travel as kernel arguments, ColorFitArgs::MAX pairs per launch
-    const int k = n - g0 < ColorFitArgs::MAX ? n - g0 : ColorFitArgs::MAX;
-    ColorFitArgs a;
-    std::memcpy(a.m, model + g0, sizeof(se3tn_crop) * k);
-    std::memcpy(a.o, observed + g0, sizeof(se3tn_crop) * k);
-    a.counters = c->color_counters.get() + (size_t)ColorFitArgs::WORDS * g0;
-    a.fit_out = fit_out_dev ? fit_out_dev + g0 : nullptr;
-    a.out = out_dev + g0;
-    a.tol = tol_mm;
-    HIPCHK(launch_color_fit(a, k, (hipStream_t)stream));
-  }
-  return SE3TN_OK;
+  if (int rc = crops_check("se3tn_color_stats", c, model, observed, n, tol_mm, out_dev, true)) return rc;
+  return fit_launches(c, n, [&](int j, se3tn_crop& m, se3tn_crop& o) { m = model[j]; o = observed[j]; }, fit_out_dev, out_dev, tol_mm, nullptr, nullptr,
+                      (hipStream_t)stream);
 }
 
 // the operation order is the header's; utils.color_score states it again in NumPy
@@ -2012,20 +2020,12 @@ static int fit_check_stage(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes,
   if (int rc = raster_instances(c, n, meshes, est, K, H, W, windows, frame_route, c->fit_rgb.get(), c->fit_depth.get(), maxpx, fr_d_off, st,
                                 &singular))
     return singular >= 0 ? fail(SE3TN_E_ARG, who + ": fit check: singular pose estimate") : rc;
-  for (int g0 = 0; g0 < n; g0 += FitArgs::MAX) {
-    const int k = n - g0 < FitArgs::MAX ? n - g0 : FitArgs::MAX;
-    FitArgs a;
-    for (int j = 0; j < k; ++j)
-      crop_pair(windows[g0 + j], 0.0, image_a(c, frame_route, g0 + j, c->fit_rgb.get(), c->fit_depth.get(), maxpx, fr_d_off), b_base, a.m[j], a.o[j]);
-    a.counters = c->fit_counters.get() + (size_t)FitArgs::WORDS * g0;
-    a.out = c->fit_host.dev() + g0;
-    a.tol = c->fit_tol;
-    if (frame_route) {
-      a.raw_rgb = c->fit_rgb.get() + (size_t)g0 * RES * RES * 3;
-      a.raw_depth = c->fit_depth.get() + (size_t)g0 * RES * RES;
-    }
-    HIPCHK(launch_fit_stats(a, k, st));
-  }
+  auto pair = [&](int j, se3tn_crop& m, se3tn_crop& o) {
+    crop_pair(windows[j], 0.0, image_a(c, frame_route, j, c->fit_rgb.get(), c->fit_depth.get(), maxpx, fr_d_off), b_base, m, o);
+  };
+  if (int rc = fit_launches(c, n, pair, c->fit_host.dev(), nullptr, c->fit_tol, frame_route ? c->fit_rgb.get() : nullptr,
+                            frame_route ? c->fit_depth.get() : nullptr, st))
+    return rc;
   HIPCHK(hipStreamSynchronize(st));
   c->fit_last_n = n;
   return SE3TN_OK;
@@ -2278,17 +2278,10 @@ int se3tn_verify_poses_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, in
   if (int rc = upload_staged(c, c->tb_stage_dev.get() + L.begin, hp + L.begin, bytes - L.begin, st)) return rc;   // (every window stages >= 64 bytes)
   se3tn_fit* fit_dev = (se3tn_fit*)(c->tb_stage_dev.get() + L.fit_off);
   se3tn_color_fit* col_dev = (se3tn_color_fit*)(c->tb_stage_dev.get() + L.color_off);
-  for (int g0 = 0; g0 < n; g0 += ColorFitArgs::MAX) {
-    const int k = n - g0 < ColorFitArgs::MAX ? n - g0 : ColorFitArgs::MAX;
-    ColorFitArgs a;
-    for (int j = 0; j < k; ++j)
-      crop_pair(windows[g0 + j], 0.0, image_a(c, frame_route, g0 + j, rA, dA, maxpx, fr_d_off), c->tb_stage_dev.get(), a.m[j], a.o[j]);
-    a.counters = c->color_counters.get() + (size_t)ColorFitArgs::WORDS * g0;
-    a.fit_out = fit_dev + g0;
-    a.out = col_dev + g0;
-    a.tol = tol_mm;
-    HIPCHK(launch_color_fit(a, k, st));
-  }
+  auto pair = [&](int j, se3tn_crop& m, se3tn_crop& o) {
+    crop_pair(windows[j], 0.0, image_a(c, frame_route, j, rA, dA, maxpx, fr_d_off), c->tb_stage_dev.get(), m, o);
+  };
+  if (int rc = fit_launches(c, n, pair, fit_dev, col_dev, tol_mm, nullptr, nullptr, st)) return rc;
   HIPCHK(hipMemcpyAsync(hp, c->tb_stage_dev.get(), L.rec_bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   up.done();

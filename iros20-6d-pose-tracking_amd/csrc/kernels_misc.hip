@@ -163,12 +163,6 @@ hipError_t launch_crop_raw(const se3tn_crop& c, uint8_t* rgb_out, uint16_t* dept
 // 512-1023): summing all 169 rows equals summing the 121 interior pixels.
 // Thread t averages channels 4t..4t+3 (coalesced 4 KB rows), multiplies by
 // its 3x4 slice of the head's FC matrix; wave-shuffle + LDS reduction over the head's 128 threads.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // AdaptiveAvgPool2d(1) + Linear(512, 3) + tanh of both heads + the float64 pose update (se3_tracknet.py:100-110, datasets.py:159-175)
 // for the configurations whose last conv stores the head map (small batches; large ones fuse this into wino_tail_kernel).
 // 16 workgroups per pair, one per 64-channel slice: a single workgroup reading the whole 692 KB map is bound by what ONE compute

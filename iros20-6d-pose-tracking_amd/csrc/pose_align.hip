@@ -14,15 +14,10 @@
 // nothing allocated, no traffic between workgroups: a pose's output depends on (points, normals, pose, depth, K, params) alone.
 #include "pose_align_math.h"
 #include "pose_align_plan.h"
+#include "record_reduce.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
-
-__device__ __forceinline__ long long pa_wave_sum(long long v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(PA_THREADS) void pose_align_kernel(const PoseAlignArgs a) {
   __shared__ long long red[(PA_WAVES + 1) * PA_ROW_WORDS];   // pa_lds_words(): the waves' rows, then the totals
@@ -56,9 +51,9 @@ __global__ __launch_bounds__(PA_THREADS) void pose_align_kernel(const PoseAlignA
       }
     }
 #pragma unroll
-    for (int w = 0; w < PA_SUMS; ++w) S[w] = pa_wave_sum(S[w]);
-    pairs = pa_wave_sum(pairs);
-    facing = pa_wave_sum(facing);
+    for (int w = 0; w < PA_SUMS; ++w) S[w] = wave_sum(S[w]);
+    pairs = wave_sum(pairs);
+    facing = wave_sum(facing);
     if (lane == 0) {
       long long* row = red + pa_lds_row(wave);
 #pragma unroll

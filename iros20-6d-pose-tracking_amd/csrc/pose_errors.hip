@@ -19,17 +19,12 @@
 // The inner loop keeps the minimum SQUARED distance; one sqrt per query point at the end (sqrt is monotone).
 #include "pose_errors_plan.h"
 #include "pose_transform.h"
+#include "record_reduce.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
 
 // Rigid, load_pose and THE transform of both clouds (pose_transform.h: shared with pose_search.hip, one operation order)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 template <bool ADDS>
 __global__ __launch_bounds__(PE_THREADS) void pose_errors_kernel(const PoseErrArgs a) {

@@ -14,6 +14,7 @@
 // the n records, no scratch, the same result on every run because keys are unique.
 #include "pose_point_rule.h"
 #include "pose_search_plan.h"
+#include "record_reduce.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
@@ -34,15 +35,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_kernel(const PoseScoreA
     transform(T, a.pts[3 * (size_t)j], a.pts[3 * (size_t)j + 1], a.pts[3 * (size_t)j + 2], cx, cy, cz);
     count_point(f, tol, cx, cy, cz, v);
   }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_xor(v[k], s, 64);
-  }
-  if ((t & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) part[t >> 6][k] = v[k];
-  }
+  wave_sums_to_lds(v, part);
   __syncthreads();
   if (t < PS_FIT_WORDS) {   // the record's eight words, one lane each: points | in frame, seen, inlier, front, behind | tol | 0
     unsigned r = 0u;

@@ -5,10 +5,10 @@
 // One thread per frame pixel of a 32 x 8 tile, a 1-D grid of plan.tiles_x * plan.tiles_y tiles over the plan's area.  A thread finds
 // its pixel's owner in one loop over the n layers (rectangle test, two-byte load), stores ids / scene, then walks the layers again:
 // per layer the six counts are ballots + popcounts of the wave, sum |o - m| a wave64 shuffle sum and hidden_by a shuffle OR (both
-// skipped when the ballot says no lane has anything to add) -> LDS across the four waves -> thread (layer, word) adds its word with
-// ONE vector atomic (add, or OR for hidden_by; device scope: the workgroups run on several XCDs; zeros are skipped) into the context's
-// counters.  The last workgroup to arrive (a ticket, as fit_stats_kernel) reads the sums, stores the finished records once with plain
-// vector stores and zeroes the counters and the ticket for the next launch.
+// skipped when the ballot says no lane has anything to add) -> LDS across the four waves -> the protocol of record_reduce.h in its
+// second shape: thread (layer, word) adds its word (OR for hidden_by; zeros are skipped), so every wave waits for its atomics and
+// thread 0 takes the ticket behind a barrier; the last workgroup stores the finished records.
+#include "record_reduce.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
@@ -37,11 +37,7 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_fit_kernel(const SceneArg
     for (int k = 0; k < SC_COUNTS; ++k) w[k] = (unsigned)__popcll(__ballot((bits >> k) & 1u));
     w[SCENE_SUM] = 0u;
     w[SCENE_BY] = 0u;
-    if (w[SC_INLIER] != 0u) {   // (uniform over the wave)
-#pragma unroll
-      for (int s = 32; s > 0; s >>= 1) ad += __shfl_xor(ad, s, 64);
-      w[SCENE_SUM] = ad;
-    }
+    if (w[SC_INLIER] != 0u) w[SCENE_SUM] = wave_sum(ad);   // (uniform over the wave)
     if (w[SC_MODEL] != w[SC_VISIBLE]) {   // some lane's pixel of this layer is hidden
 #pragma unroll
       for (int s = 32; s > 0; s >>= 1) by |= __shfl_xor(by, s, 64);
@@ -59,29 +55,23 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_fit_kernel(const SceneArg
       unsigned* cnt = a.counters + (size_t)li * SCENE_WORDS + k;
       if (k == SCENE_BY) {
         const unsigned s = part[0][li][k] | part[1][li][k] | part[2][li][k] | part[3][li][k];
-        if (s != 0u) {
-          const unsigned old = __hip_atomic_fetch_or(cnt, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          asm volatile("" ::"v"(old));   // (the returning form: the OR has been performed where the other XCDs' are)
-        }
+        if (s != 0u) counter_or(cnt, s);
       } else {
         const unsigned s = part[0][li][k] + part[1][li][k] + part[2][li][k] + part[3][li][k];
-        if (s != 0u) {
-          const unsigned old = __hip_atomic_fetch_add(cnt, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          asm volatile("" ::"v"(old));
-        }
+        if (s != 0u) counter_add(cnt, s);
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave: its atomics have returned ...
+  counters_returned();                                 // every wave: its atomics have returned ...
   __syncthreads();                                     // ... before thread 0 takes the workgroup's ticket
-  if (t == 0) last = __hip_atomic_fetch_add(a.counters + SCENE_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  if (t == 0) last = take_ticket(a.counters + SCENE_TICKET);
   __syncthreads();
   if (!last) return;                                   // (uniform: `last` is a shared word)
   // the records' words, one lane each: stored once, plain vector stores
   for (int q = t; q < a.n * SCENE_RECORD_WORDS; q += SCENE_THREADS) {
     const int li = q / SCENE_RECORD_WORDS, k = q - li * SCENE_RECORD_WORDS;
     const unsigned* cnt = a.counters + (size_t)li * SCENE_WORDS;
-    auto sum = [&](int j) { return __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto sum = [&](int j) { return counter_read(cnt + j); };
     unsigned r = 0u;
     switch (k) {   // se3tn_scene_fit: model, visible, hidden, seen, inlier, front, behind, sum_abs_mm, hidden_by, tol_mm, n_objects, 0
       case 0: r = sum(SC_MODEL); break;
@@ -100,8 +90,8 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_fit_kernel(const SceneArg
     reinterpret_cast<unsigned*>(a.out)[q] = r;
   }
   __syncthreads();                                     // every sum has been read: re-arm
-  if (t < a.n * SCENE_WORDS) __hip_atomic_store(a.counters + t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (t == 0) __hip_atomic_store(a.counters + SCENE_TICKET, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (t < a.n * SCENE_WORDS) counter_rearm(a.counters + t);
+  if (t == 0) counter_rearm(a.counters + SCENE_TICKET);
   __threadfence_system();                              // (the records may live in mapped host memory)
 }
 

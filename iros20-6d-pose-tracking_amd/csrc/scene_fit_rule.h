@@ -6,7 +6,7 @@
 // Layer i (i < n) is a uint16 millimetre sub-image of the rectangle {x0, y0, x1, y1} of the frame, tightly packed [y1 - y0, x1 - x0];
 // x1 <= x0 or y1 <= y0: a layer with no pixels.  For a frame pixel p = (x, y), with o(p) the observed depth:
 //     m_i(p)     the layer's value if p is inside its rectangle, else 0
-//     valid(d)   100 < d < 2000                                      the rule of se3tn_fit_stats
+//     valid(d)   100 < d < 2000                                      depth_valid() of fit_rule.h
 //     owner(p)   the i with the smallest valid m_i(p), ties to the lowest i; none if no layer is valid at p
 //     ids(p)     owner + 1, or 0;        scene(p) = m_owner(p), or 0
 // and layer i counts, over the frame,
@@ -21,6 +21,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include "fit_rule.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define SE3TN_SC_HD __host__ __device__
@@ -43,8 +45,6 @@ struct SceneLayer {   // one layer as the kernel reads it
   int x0, y0, x1, y1;
 };
 
-SE3TN_SC_HD inline bool scene_valid(int d) { return d > 100 && d < 2000; }
-
 // m_i(p)
 SE3TN_SC_HD inline int scene_layer_at(const SceneLayer& l, int x, int y) {
   if (x < l.x0 || x >= l.x1 || y < l.y0 || y >= l.y1) return 0;
@@ -54,24 +54,19 @@ SE3TN_SC_HD inline int scene_layer_at(const SceneLayer& l, int x, int y) {
 // the depth test: layers are offered in ascending i, a later one wins only when strictly nearer (ties to the lowest i).
 // owner = -1 and best = 0 before the first offer
 SE3TN_SC_HD inline void scene_offer(int i, int m, int& owner, int& best) {
-  if (scene_valid(m) && (owner < 0 || m < best)) { owner = i; best = m; }
+  if (depth_valid(m) && (owner < 0 || m < best)) { owner = i; best = m; }
 }
 
 // layer i at a pixel whose owner is known: the bits (1 << SC_*) of the counters the pixel enters, |o - m| of an inlier in `ad` (else 0)
 // and the hidden_by bit it sets in `by` (else 0)
 SE3TN_SC_HD inline unsigned scene_classify(int i, int m, int owner, int o, int tol, unsigned& ad, unsigned& by) {
+  static_assert(SC_MODEL == 0 && SC_VISIBLE == 1 && (int)SC_SEEN == (int)FC_SEEN + 1 && (int)SC_BEHIND == (int)FC_BEHIND + 1,
+                "the SC_* bits are the FC_* bits with visible inserted after model");
   ad = 0u; by = 0u;
-  if (!scene_valid(m)) return 0u;
+  if (!depth_valid(m)) return 0u;
   if (owner != i) { by = 1u << owner; return 1u << SC_MODEL; }
-  unsigned bits = (1u << SC_MODEL) | (1u << SC_VISIBLE);
-  if (!scene_valid(o)) return bits;
-  bits |= 1u << SC_SEEN;
-  const int d = o - m;
-  const int a = d < 0 ? -d : d;
-  if (a <= tol) { bits |= 1u << SC_INLIER; ad = (unsigned)a; }
-  else if (d < 0) bits |= 1u << SC_FRONT;
-  else bits |= 1u << SC_BEHIND;
-  return bits;
+  const unsigned f = fit_classify(m, o, tol, ad);   // a visible pixel: exactly se3tn_fit's counts, model set
+  return (1u << SC_MODEL) | (1u << SC_VISIBLE) | ((f >> FC_SEEN) << SC_SEEN);
 }
 
 }  // namespace se3tn

@@ -199,36 +199,25 @@ struct CropArgs {  // one launch handles up to MAX crops
 
 static_assert(sizeof(CropArgs) <= 4096, "CropArgs travels as kernel arguments: HIP's limit is 4 KB");
 
-// fit record of up to MAX (model, observed) pairs per launch (fit_stats.hip); the descriptors travel as kernel arguments
+// depth record, or depth AND colour record in one pass, of up to MAX (model, observed) pairs per launch (fit_stats.hip); the
+// descriptors travel as kernel arguments
 struct FitArgs {
   static constexpr int MAX = SE3TN_FIT_MAX_PAIRS;   // 2 x 32 x 56 B + constants = 3.6 KB of kernel arguments (limit 4 KB, asserted below)
-  static constexpr int WORDS = 8;                    // counter words per pair: the six sums | the arrival counter | unused
-  se3tn_crop m[MAX], o[MAX];  // model / observed image of pair i: depth, H, W, left .. bottom are read (rgb: with raw_rgb only)
-  unsigned* counters;         // [n][WORDS], zero between launches (the last workgroup of a pair to arrive re-arms them)
-  se3tn_fit* out;             // [n] records: device memory, or mapped pinned host memory (each word stored once)
+  static constexpr int SUMS = 6, WORDS = 8;          // depth only: the six sums of se3tn_fit; counter words per pair: the SUMS | the arrival counter | unused
+  static constexpr int COLOUR_SUMS = 24, COLOUR_WORDS = 32;   // with colour: + sum_m .. sum_abs of se3tn_color_fit (px = inlier_px); the same layout
+  se3tn_crop m[MAX], o[MAX];  // model / observed image of pair i: depth, H, W, left .. bottom are read (rgb: with colour or raw_rgb only)
+  unsigned* counters;         // [n][WORDS] or (colour) [n][COLOUR_WORDS], zero between launches (the last workgroup of a pair to arrive re-arms them)
+  se3tn_fit* fit;             // [n] depth records: device memory, or mapped pinned host memory (each word stored once); with colour: or nullptr
   int tol;
-  // non-null: pair i also stores the raw crop of its MODEL image (crop_bbox alone, what launch_crop_raw writes) as image i of
-  // raw_rgb [n,176,176,3] / raw_depth [n,176,176] -- the estimate render of the full-frame route, in the launch that scores it
+  // non-null (depth only): pair i also stores the raw crop of its MODEL image (crop_bbox alone, what launch_crop_raw writes) as image
+  // i of raw_rgb [n,176,176,3] / raw_depth [n,176,176] -- the estimate render of the full-frame route, in the launch that scores it
   uint8_t* raw_rgb = nullptr;
   uint16_t* raw_depth = nullptr;
+  se3tn_color_fit* colour = nullptr;   // non-null: [n] colour records as well (the COLOUR instantiation, its own counters)
 };
 static_assert(sizeof(FitArgs) <= 4096, "FitArgs travels as kernel arguments: HIP's limit is 4 KB");
-hipError_t launch_fit_stats(const FitArgs& a, int n, hipStream_t st);
-
-// depth AND colour record of up to MAX (model, observed) pairs per launch (color_fit.hip): one pass, both records
-struct ColorFitArgs {
-  static constexpr int MAX = SE3TN_FIT_MAX_PAIRS;
-  static constexpr int SUMS = 24;                    // the six sums of se3tn_fit | sum_m .. sum_abs of se3tn_color_fit (px = inlier_px)
-  static constexpr int WORDS = 32;                   // counter words per pair: the SUMS | the arrival counter | unused
-  se3tn_crop m[MAX], o[MAX];  // model / observed image of pair i: rgb, depth, H, W, left .. bottom are read
-  unsigned* counters;         // [n][WORDS], zero between launches (the last workgroup of a pair to arrive re-arms them)
-  se3tn_fit* fit_out;         // [n] depth records or nullptr
-  se3tn_color_fit* out;       // [n] colour records: device memory, or mapped pinned host memory (each word stored once)
-  int tol;
-};
-static_assert(sizeof(ColorFitArgs) <= 4096, "ColorFitArgs travels as kernel arguments: HIP's limit is 4 KB");
 static_assert(sizeof(se3tn_color_fit) == 80 && sizeof(se3tn_fit) == 32, "the records are 20 / 8 words");
-hipError_t launch_color_fit(const ColorFitArgs& a, int n, hipStream_t st);
+hipError_t launch_fit_stats(const FitArgs& a, int n, hipStream_t st);
 
 // n depth layers of one frame through a shared depth test (scene_fit.hip; the rule: scene_fit_rule.h, tiles and counters: scene_fit_plan.h);
 // the layers travel as kernel arguments

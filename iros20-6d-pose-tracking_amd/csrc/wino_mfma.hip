@@ -800,12 +800,6 @@ __global__ __launch_bounds__(((TH * TH * (CS / VEC) + 63) / 64) * 64) void wino_
   }
 }
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // grid (n, 512 / CS channel slices, 2 heads); thread = (tile, channel pair) like wino_output_kernel, so the pass has the
 // same parallelism; the per-channel sums over the map are reduced through LDS in a fixed order, each workgroup
 // contributes the partial dot products of its CS channels with the head's three FC rows:

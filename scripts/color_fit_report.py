@@ -11,7 +11,7 @@ another rotation altogether).
                  process, alternating with the one call;
   for scale      Tracker.on_track_batch of the same poses (random-init weights): verify is its front half, so this is the natural ceiling;
   kernel alone   --trace DIR: a child process of --reps one calls under `rocprofv3 --kernel-trace --stats` (a run of its own: tracing slows the
-                 host), color_fit_kernel's durations read from the kernel trace it leaves in DIR: median [min, max] of ALL its launches.
+                 host), the colour kernel's durations read from the kernel trace it leaves in DIR: median [min, max] of ALL its launches.
                  A child that ends with a non-zero status ends the script: nothing more is started on the device after it.
 
 The one call's records are held to the step-by-step path's, bytes.  Each figure: median [min, max] of --windows timings after a warm-up;
@@ -75,11 +75,12 @@ def setup(n, device):
 
 
 def kernel_from_trace(trace_dir):
-    """durations (us) of color_fit_kernel in the kernel-trace CSVs under trace_dir, by number of pairs (grid y)"""
+    """durations (us) of the colour kernel (fit_stats_kernel<true>; color_fit_kernel in builds before the two crop-record kernels became
+    one) in the kernel-trace CSVs under trace_dir, by number of pairs (grid y)"""
     out = {}
     for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
         for r in csv.DictReader(open(path)):
-            if "color_fit_kernel" in r["Kernel_Name"]:
+            if "color_fit_kernel" in r["Kernel_Name"] or "fit_stats_kernel<true>" in r["Kernel_Name"]:
                 out.setdefault(int(r["Grid_Size_Y"]), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     return out
 
@@ -162,7 +163,7 @@ def main():
                     sys.exit("color_fit_report: the traced child process of %d poses ended with status %d -- stopping here" % (n, r.returncode))
                 v = kernel_from_trace(d).get(n if n <= 32 else 32, [])
                 if not v:
-                    line["kernel_us"] = "no color_fit_kernel launch in the trace under %s: not measured" % d
+                    line["kernel_us"] = "no colour-kernel launch in the trace under %s: not measured" % d
                 else:                     # every launch of the child counts, its first ones (the clock still ramping up) included
                     line.update(kernel_us=round(med(v), 2), kernel_us_min=round(min(v), 2), kernel_us_max=round(max(v), 2), kernel_launches=len(v))
         print(json.dumps(line), flush=True)

@@ -1,10 +1,11 @@
-// Stand-alone host check of csrc/scene_fit_rule.h and csrc/scene_fit_plan.h (built with -fsanitize=address,undefined by
+// Stand-alone host check of csrc/fit_rule.h, csrc/scene_fit_rule.h and csrc/scene_fit_plan.h (built with -fsanitize=address,undefined by
 // tests/test_scene_fit_host.py).  The scene kernel is replayed on the host exactly as it is laid out -- the plan's tiles, 256 threads
 // per tile, every thread's pixel through the rule's statements -- on frames, layers and outputs malloc'ed with EXACTLY their bytes, so
 // an index past a layer, a frame or an output is a sanitizer report.  Checked: the records of synthetic cases equal numbers written
 // here; every pixel of the union of the rectangles is visited exactly once and no tile beyond the planned ones is needed; the
 // multiply-and-shift that finds a tile's row equals the division for every tile of the extreme frames; the staging regions of
-// se3tn_scene_fit_host do not overlap.
+// se3tn_scene_fit_host do not overlap; fit_classify (the depth rule of a pixel) gives the counts written here, and scene_classify on
+// an owned pixel is fit_classify with the visible bit inserted.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -234,8 +235,58 @@ static int tiles_and_stage() {
   return 0;
 }
 
+// csrc/fit_rule.h against numbers written here
+static int fit_rule() {
+  const unsigned M = 1u << FC_MODEL, S = 1u << FC_SEEN, I = 1u << FC_INLIER, F = 1u << FC_FRONT, B = 1u << FC_BEHIND;
+  CHECK(M == 1u && S == 2u && I == 4u && F == 8u && B == 16u && FC_COUNTS == 5);   // the order of se3tn_fit's fields
+  // the eleven rows of literal_pair() of tests/test_fit_check_host.py (TOL = 7) as runs of {m, o, pixels}
+  const int T = 7;
+  const int rows[][3] = {{0, 500, 176}, {100, 500, 88}, {2000, 500, 88}, {65535, 500, 176}, {500, 0, 44}, {500, 100, 44}, {500, 2000, 44},
+                         {500, 65535, 44}, {500, 500 + T, 176}, {500, 500 - T, 176}, {500, 500, 100}, {500, 499, 76}, {500, 500 - T - 1, 176},
+                         {500, 500 + T + 1, 50}, {500, 1999, 126}, {101, 1999, 176}, {1999, 101, 176}};
+  const unsigned want[2][6] = {{8 * 176, 7 * 176, 3 * 176, 2 * 176, 2 * 176, 2 * 176 * 7 + 76},                      // LITERAL
+                               {8 * 176, 7 * 176, 4 * 176 + 50, 176, 126 + 176, 2 * 176 * 7 + 76 + (176 + 50) * 8}};   // at TOL + 1
+  for (int w = 0; w < 2; ++w) {
+    unsigned got[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    for (const auto& r : rows) {
+      unsigned ad = 77u;
+      const unsigned bits = fit_classify(r[0], r[1], T + w, ad);
+      for (int k = 0; k < FC_COUNTS; ++k) got[k] += ((bits >> k) & 1u) * (unsigned)r[2];
+      got[5] += ad * (unsigned)r[2];
+    }
+    CHECK(std::memcmp(got, want[w], sizeof(got)) == 0);
+  }
+  // the edges alone: {m, o, tol, bits, ad}.  Two valid depths differ by at most 1999 - 101 = 1898, so at tol = 65535 every seen
+  // pixel is an inlier; 1898 and 1897 are the largest tolerances that |o - m| = tol and tol + 1 can meet
+  const unsigned edges[][5] = {
+      {100, 500, 65535, 0, 0}, {101, 500, 65535, M | S | I, 399}, {1999, 500, 65535, M | S | I, 1499}, {2000, 500, 65535, 0, 0}, {65535, 500, 65535, 0, 0},
+      {500, 100, 65535, M, 0}, {500, 101, 65535, M | S | I, 399}, {500, 1999, 65535, M | S | I, 1499}, {500, 2000, 65535, M, 0}, {500, 65535, 65535, M, 0},
+      {100, 500, 1, 0, 0},     {101, 500, 1, M | S | B, 0},       {1999, 500, 1, M | S | F, 0},        {2000, 500, 1, 0, 0},     {65535, 500, 1, 0, 0},
+      {500, 100, 1, M, 0},     {500, 101, 1, M | S | F, 0},       {500, 1999, 1, M | S | B, 0},        {500, 2000, 1, M, 0},     {500, 65535, 1, M, 0},
+      {500, 501, 1, M | S | I, 1}, {500, 499, 1, M | S | I, 1}, {500, 502, 1, M | S | B, 0}, {500, 498, 1, M | S | F, 0}, {500, 500, 1, M | S | I, 0},
+      {101, 1999, 65535, M | S | I, 1898}, {1999, 101, 65535, M | S | I, 1898}, {101, 1999, 1898, M | S | I, 1898}, {1999, 101, 1898, M | S | I, 1898},
+      {101, 1999, 1897, M | S | B, 0}, {1999, 101, 1897, M | S | F, 0}, {0, 0, 65535, 0, 0}, {65535, 65535, 65535, 0, 0}};
+  for (const auto& e : edges) {
+    unsigned ad = 77u;
+    CHECK(fit_classify((int)e[0], (int)e[1], (int)e[2], ad) == e[3] && ad == e[4]);
+    CHECK(depth_valid((int)e[0]) == ((e[3] & M) != 0u));
+  }
+  // scene_classify on an owned pixel: fit_classify with the visible bit inserted after model; a pixel of another owner: model and by
+  const int d[6] = {0, 100, 101, 500, 1999, 2000}, tols[2] = {10, 1898};
+  for (int tol : tols)
+    for (int m : d)
+      for (int o : d) {
+        unsigned fa = 77u, sa = 77u, by = 77u;
+        const unsigned f = fit_classify(m, o, tol, fa);
+        const unsigned want_sc = f ? (f & 1u) | (1u << SC_VISIBLE) | ((f & ~1u) << 1) : 0u;
+        CHECK(scene_classify(3, m, 3, o, tol, sa, by) == want_sc && sa == fa && by == 0u);
+        CHECK(scene_classify(3, m, 5, o, tol, sa, by) == (f & 1u) && sa == 0u && by == (f ? 1u << 5 : 0u));
+      }
+  return 0;
+}
+
 int main() {
-  if (thresholds() || ties() || rectangles() || many_and_none() || tiles_and_stage()) return 1;
+  if (thresholds() || ties() || rectangles() || many_and_none() || tiles_and_stage() || fit_rule()) return 1;
   std::puts("scene_fit_check: ok");
   return 0;
 }

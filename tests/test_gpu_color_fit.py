@@ -1,4 +1,4 @@
-"""GPU: the colour check -- se3tn_color_stats (csrc/color_fit.hip) against the per-pixel loop of tests/color_fit_oracle.py,
+"""GPU: the colour check -- se3tn_color_stats (csrc/fit_stats.hip, the colour instantiation) against the per-pixel loop of tests/color_fit_oracle.py,
 se3tn_verify_poses_host against the step-by-step path (render_window per pose + Engine.color_stats), and the scene of
 tests/color_fit_scene.py on the device: Tracker.verify, and Tracker.acquire with and without the colour switch.
 
@@ -84,7 +84,7 @@ def crop_array(se3, group):
 
 
 # ---- se3tn_color_stats -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 3, 33])
+@pytest.mark.parametrize("n", [1, 3, 32, 33])
 def test_color_stats_equals_the_oracle_and_fit_stats(se3, eng, pairs, n):
     assert se3._lib.FIT_MAX_PAIRS == 32 and eng.max_batch == 33                 # 33 pairs: two launches
     names = [pairs.names[(5 * i + n) % len(pairs.names)] for i in range(n)] if n < len(pairs.names) else \

@@ -1,6 +1,6 @@
 """GPU: the device's three copies of crop_bbox's NEAREST index rule, at the window sizes that decide it.
 
-preprocess_kernel<TAB> and crop_raw_kernel (csrc/kernels_misc.hip) and crop_source() (csrc/crop_rule.h, read by fit_stats_kernel) each
+preprocess_kernel<TAB> and crop_raw_kernel (csrc/kernels_misc.hip) and crop_source() (csrc/crop_rule.h, read by fit_stats_kernel<COLOUR>) each
 state  sx = min(floor(x * (1.0 / (176.0 / src))), src - 1)  in float64.  Where x * src / 176 is an exact integer the order of those
 three operations decides the index, and tests/crop_rule_cases.py lists the 239 sizes up to 2000 at which another evaluation gives
 another crop.  Here every one of them (and every size 1..352) goes through se3tn_preprocess and se3tn_crop_raw, 40 pairs of them
