@@ -741,6 +741,67 @@ int se3tn_search_pose_grid_host(se3tn_ctx* ctx, const se3tn_points* points, int 
                                 const double* trans, const uint16_t* depth, int H, int W, const double K[9], int tol_mm, int facing,
                                 int k, int32_t* idx_out, se3tn_point_fit* fit_out, void* stream);
 
+/* ---- re-acquiring a lost object AMONG tracked ones: the lattice search against the frame and the composed scene ---------------- */
+/* The searches above score a candidate against the observed frame alone.  With other tracked objects in the frame that fails twice:
+ * a candidate that lays the lost model onto the visible face of a tracked object collects that object's pixels as inliers (the
+ * surface is already CLAIMED), and where a tracked object stands in front of a candidate the point counts as `front`, the verdict
+ * of "something unknown is in the way", so a correct but half-hidden candidate cannot be compared with an unoccluded wrong one.
+ * se3tn_scene_fit(..., scene_dev) writes what the search lacks, the composed depth of any set of tracked objects: scene [H,W] uint16
+ * millimetres, 0 where there is none.  For rotation R, translation t, model point x (and normal n), all in float64, in this order,
+ * without fused multiply-add:
+ *     q, c, facing, in front, uf, vf, in frame, m = rint(c.z * 1000.0)     exactly as se3tn_score_pose_grid states them
+ *     s = scene[vf, uf]
+ *     hidden     in frame && 100 < s < 2000 && s <= m + tol_mm              a tracked surface at or in front of the point: the point
+ *                                                                          is occluded by it, or claimed by it
+ *                a hidden point enters hidden_pts and NOTHING else past in_frame_pts -- not seen, inlier, front or behind --
+ *                whatever d is
+ *     otherwise  d = depth[vf, uf]; seen, inlier, front, behind             exactly as se3tn_score_pose_grid states them
+ * The comparisons are made on doubles (s, m and tol_mm are integers in doubles: exact); only the pixel index is cast.
+ * The record keeps the 32 bytes and the field order of se3tn_point_fit; word 7, _reserved there, is hidden_pts.  se3tn_rank_poses
+ * reads inlier_pts and behind_pts only, so it may be given these records through a cast: (const se3tn_point_fit*)fit_dev.
+ * Always seen = inlier + front + behind and hidden + seen <= in_frame <= points; with an all-zero scene every word equals the word
+ * se3tn_score_pose_grid writes (hidden_pts = 0 = _reserved).  inlier_pts / (points - hidden_pts) is the share of the surface that is
+ * neither hidden nor claimed which the sensor confirms.  Guarantees (a)-(c) of se3tn_score_pose_grid hold with `scene` among what a
+ * record depends on (tests/scene_search_oracle.py).  Cost: the work split of se3tn_score_pose_grid, a seventh counter per
+ * translation and a second 2-byte gather per point at the pixel the first one reads. */
+typedef struct se3tn_scene_point_fit {   /* all uint32, 32 bytes: se3tn_point_fit with word 7 in use */
+  uint32_t points;        /* P, or with facing the number of facing points */
+  uint32_t in_frame_pts;  /* #{in frame}                                  */
+  uint32_t seen_pts;      /* #{in frame && !hidden && valid(d)}           */
+  uint32_t inlier_pts;    /* #{seen && |d - m| <= tol_mm}                 */
+  uint32_t front_pts;     /* #{seen && d <  m - tol_mm}                   */
+  uint32_t behind_pts;    /* #{seen && d >  m + tol_mm}                   */
+  uint32_t tol_mm;        /* echoed                                       */
+  uint32_t hidden_pts;    /* #{in frame && valid(s) && s <= m + tol_mm}   */
+} se3tn_scene_point_fit;  /* seen = inlier + front + behind;  hidden + seen <= in_frame <= points */
+/* The device entry: the arguments of se3tn_score_pose_grid and scene_dev, device uint16 [H,W]; fit_dev: n_rot * n_trans records in
+ * device memory or mapped pinned host memory (every word stored once with a plain store).  Stream-ordered, capturable, allocates
+ * nothing, no atomics on global memory.  Refusals as se3tn_score_pose_grid, a NULL scene_dev among the NULL pointers. */
+int se3tn_score_pose_grid_scene(se3tn_ctx* ctx, const se3tn_points* points, int n_rot, const double* rots_dev, int n_trans,
+                                const double* trans_dev, const uint16_t* depth_dev, const uint16_t* scene_dev, int H, int W,
+                                const double K[9], int tol_mm, int facing, se3tn_scene_point_fit* fit_dev, void* stream);
+/* The whole search as one call from HOST memory: rots, trans, depth, k, idx_out as se3tn_search_pose_grid_host, fit_out [k] the
+ * winners' scene-aware records; the occluders are n_occ objects (mesh and object_width_mm are read, as se3tn_scene_fit reads them)
+ * at occ_poses (HOST float64 [n_occ,16]).  The staging is [rots | trans | depth | pad | scene | pad | fit n | occ_fit n_occ | top_fit
+ * k | idx k]: one upload of [rots | trans | depth]; se3tn_scene_fit's render of the occluders and its kernel against the staged
+ * frame, composing the scene frame, which stays on the device; the scene-aware grid kernel; se3tn_rank_poses' kernel; one read-back of
+ * [occ_fit | top_fit | idx].  occ_fit_out (may be NULL) receives the occluders' own records, those se3tn_scene_fit writes for them.
+ * SYNCHRONOUS on `stream`, refused inside a stream capture (SE3TN_E_STATE); the pinned staging and the scene stage's buffers grow
+ * on a first or larger call.  Refusals: those of se3tn_search_pose_grid_host and those of se3tn_scene_fit_host (n_occ outside
+ * [1, min(SE3TN_SCENE_MAX_OBJECTS, se3tn_max_batch)] among them: a search with no occluders is se3tn_search_pose_grid_host), all
+ * before anything is allocated or written, each with its own message.  The context stays usable after a refusal. */
+int se3tn_search_pose_grid_scene_host(se3tn_ctx* ctx, const se3tn_points* points, int n_rot, const double* rots, int n_trans,
+                                      const double* trans, const uint16_t* depth, int H, int W, const double K[9], int tol_mm,
+                                      int facing, int k, int n_occ, const se3tn_object* occluders,
+                                      const double* occ_poses /* host [n_occ,16] */, int32_t* idx_out,
+                                      se3tn_scene_point_fit* fit_out, struct se3tn_scene_fit* occ_fit_out /* [n_occ], may be NULL */,
+                                      void* stream);
+/* The scene frame the last successful se3tn_search_pose_grid_scene_host composed: device uint16 [H,W] inside the context's staging
+ * mirror, for scoring further candidates with se3tn_score_pose_grid_scene without composing it again.  Valid until the next _host
+ * call of the pose family or the scene stage on this context, which lays the staging out anew: copy it (se3tn_memcpy_d2d) to keep it
+ * longer.  SE3TN_E_STATE when there is none.  No launch, no sync. */
+int se3tn_last_search_scene(se3tn_ctx* ctx, const uint16_t** scene_dev, int* H, int* W);
+
 /* ---- from a lattice node to a pose: point-to-plane steps of n hypotheses against one depth frame (ICP) ------------------------- */
 /* The two searches above end at the resolution of their lattices (10 mm, 15 degrees); the network's reach is its normalisers (30 mm,
  * 5 degrees by default), and it needs weights that track.  In between stands a depth-only refinement: a few damped Gauss-Newton steps

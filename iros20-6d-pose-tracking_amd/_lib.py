@@ -106,6 +106,10 @@ assert COLOR_FIT_DTYPE.itemsize == C.sizeof(ColorFit) == 80
 POINT_FIT_FIELDS = ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm")   # the seven that carry data
 POINT_FIT_DTYPE = _np.dtype([(k, "<u4") for k in POINT_FIT_FIELDS + ("_reserved",)])
 assert POINT_FIT_DTYPE.itemsize == C.sizeof(PointFit) == 32
+# se3tn_scene_point_fit: the same 32 bytes with word 7 in use (hidden_pts); se3tn_rank_poses and recover.pose_key read both alike
+SCENE_POINT_FIT_FIELDS = POINT_FIT_FIELDS + ("hidden_pts",)
+SCENE_POINT_FIT_DTYPE = _np.dtype([(k, "<u4") for k in SCENE_POINT_FIT_FIELDS])
+assert SCENE_POINT_FIT_DTYPE.itemsize == 32
 SCENE_FIT_FIELDS = ("model_px", "visible_px", "hidden_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm", "hidden_by", "tol_mm",
                     "n_objects")   # the eleven that carry data
 SCENE_FIT_DTYPE = _np.dtype([(k, "<u4") for k in SCENE_FIT_FIELDS + ("_reserved",)])
@@ -217,6 +221,12 @@ _SIGS = {
                                         C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "se3tn_search_pose_grid_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                               C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_score_pose_grid_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "se3tn_search_pose_grid_scene_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                    C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Object), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_last_search_scene": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "se3tn_align_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                     C.POINTER(AlignParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_align_poses_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),

@@ -161,6 +161,9 @@ struct se3tn_ctx {
   // the synchronous _host entry points of the pose family (StagedCall): pinned staging of ps_cap bytes and its device mirror, laid out
   // per call (pose_errors_plan.h: pe_stage_*, pose_search_plan.h: PsStage, pose_grid_plan.h: PgStage, pose_align_plan.h: PaStage)
   PinnedBuf<unsigned char> ps_host; DeviceBuf<unsigned char> ps_dev; size_t ps_cap = 0;
+  // where the last se3tn_search_pose_grid_scene_host left its scene frame in ps_dev (se3tn_last_search_scene); H = 0: nowhere -- the
+  // next staged call lays the buffer out anew
+  size_t ps_scene_off = 0; int ps_scene_H = 0, ps_scene_W = 0;
   bool rearm_counters = false;                  // a failed launch sequence: clear tail_arrive before the next one
   DeviceBuf<int> tail_arrive;                   // [max_batch] arrival counters of tail_kernel's 16 workgroups per pair (zero between launches)
   int* tail_flag = nullptr; int tail_seq = 0;   // set around se3tn_on_track's infer: the tail kernel stores tail_seq to this (mapped) word
@@ -437,6 +440,7 @@ struct StagedCall {
   unsigned char* d = nullptr;   // its device mirror
   int refuse_capture() const { return refuse_if(stream_is_capturing(st), SE3TN_E_STATE, who, "the call is synchronous, it cannot be captured"); }
   int grow(size_t bytes) {
+    c->ps_scene_H = c->ps_scene_W = 0;   // (this call's layout replaces whatever a scene search left)
     if (bytes > c->ps_cap) {   // first / larger call: the staging belongs to the context's device
       DeviceGuard dg(c->device);
       if (int rc = begin_growth(dg)) return rc;
@@ -1861,23 +1865,29 @@ int se3tn_search_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const do
 // ---- n_rot x n_trans candidate poses [R_r | t_t] against one depth frame, the best k ----------------------------------------------
 // NULL pointers first, then the numbers, then the context and the handle (which is not read before the context is known to have a
 // device): every refusal has its own message, on a host-only context too
-static int pose_grid_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, int n_rot, int n_trans, int H, int W,
-                           int tol_mm, int facing) {
-  if (!c || !ok_ptrs || !p) return null_argument(who);
+static int pose_grid_numbers_check(const char* who, int n_rot, int n_trans, int H, int W, int tol_mm, int facing) {
   if (n_rot < 1 || n_trans < 1 || (long long)n_rot * (long long)n_trans > (long long)PS_MAX_POSES)
     return fail(SE3TN_E_ARG, std::string(who) + ": n_rot = " + std::to_string(n_rot) + ", n_trans = " + std::to_string(n_trans) +
                                  ": both must be >= 1 and their product <= SE3TN_POSE_SEARCH_MAX_POSES = " + std::to_string(PS_MAX_POSES));
   if (int rc = pose_score_check(who, H, W, tol_mm)) return rc;
-  if (facing != 0 && facing != 1) return fail(SE3TN_E_ARG, std::string(who) + ": facing = " + std::to_string(facing) + " is neither 0 nor 1");
+  return refuse_if(facing != 0 && facing != 1, SE3TN_E_ARG, who, "facing = " + std::to_string(facing) + " is neither 0 nor 1");
+}
+static int pose_grid_context_check(const char* who, const se3tn_ctx* c, const se3tn_points* p, int facing) {
   if (int rc = device_check(who, c, "search")) return rc;
   if (int rc = same_device_check(who, c, p)) return rc;
   return facing ? normals_check(who, p, "facing = 1 but ") : SE3TN_OK;
 }
+static int pose_grid_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, int n_rot, int n_trans, int H, int W,
+                           int tol_mm, int facing) {
+  if (!c || !ok_ptrs || !p) return null_argument(who);
+  if (int rc = pose_grid_numbers_check(who, n_rot, n_trans, H, W, tol_mm, facing)) return rc;
+  return pose_grid_context_check(who, c, p, facing);
+}
 static PoseGridArgs pose_grid_args(const se3tn_points* p, const double* rots, int n_trans, const double* trans, const uint16_t* depth, int H,
-                                   int W, const double K[9], int tol_mm, int facing, se3tn_point_fit* out) {
+                                   int W, const double K[9], int tol_mm, int facing, se3tn_point_fit* out, const uint16_t* scene = nullptr) {
   PoseGridArgs a;
   a.pts = p->xyz.get(); a.nrm = p->nrm.get(); a.P = p->P; a.rots = rots; a.trans = trans; a.n_trans = n_trans;
-  a.depth = depth; a.H = H; a.W = W; a.tol = tol_mm; a.facing = facing; a.out = out;
+  a.depth = depth; a.H = H; a.W = W; a.tol = tol_mm; a.facing = facing; a.out = out; a.scene = scene;
   for (int i = 0; i < 9; ++i) a.K[i] = K[i];
   return a;
 }
@@ -2294,13 +2304,16 @@ int se3tn_verify_poses_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, in
 
 // ---- the objects of one frame as one scene -------------------------------------------------------------------------------------------
 // what the three entry points refuse alike, before anything is allocated or written
-static int scene_args_check(const char* who, const se3tn_ctx* c, int n, int tol_mm, int H, int W, bool rendering) {
-  if (int rc = frame_check(who, H, W)) return rc;
-  if (int rc = mm_check(who, "tol_mm", tol_mm)) return rc;
+static int scene_numbers_check(const char* who, const se3tn_ctx* c, int n, int H, int W, bool rendering) {
   if (int rc = refuse_if(rendering && H > 2048, SE3TN_E_ARG, who, "frames of more than 2048 rows are not supported (as se3tn_render_frame)")) return rc;
   if (int rc = refuse_if(!scene_frame_ok(H, W), SE3TN_E_ARG, who, "H * W > 2^21 pixels: sum_abs_mm could overflow its word")) return rc;
   const int most = c->max_batch < SE3TN_SCENE_MAX_OBJECTS ? c->max_batch : SE3TN_SCENE_MAX_OBJECTS;
-  if (int rc = count_check(who, n, most, "min(SE3TN_SCENE_MAX_OBJECTS, se3tn_max_batch)")) return rc;
+  return count_check(who, n, most, "min(SE3TN_SCENE_MAX_OBJECTS, se3tn_max_batch)");
+}
+static int scene_args_check(const char* who, const se3tn_ctx* c, int n, int tol_mm, int H, int W, bool rendering) {
+  if (int rc = frame_check(who, H, W)) return rc;
+  if (int rc = mm_check(who, "tol_mm", tol_mm)) return rc;
+  if (int rc = scene_numbers_check(who, c, n, H, W, rendering)) return rc;
   return device_check(who, c, "compose the scene");
 }
 
@@ -2460,6 +2473,76 @@ int se3tn_scene_fit_host(se3tn_ctx* c, int n, const se3tn_object* objs, const do
   std::memcpy(out, sc.h + L.rec_off, sizeof(struct se3tn_scene_fit) * (size_t)n);
   if (ids) std::memcpy(ids, sc.h + L.ids_off, (size_t)H * W);
   if (scene) std::memcpy(scene, sc.h + L.scene_off, (size_t)H * W * 2);
+  return SE3TN_OK;
+}
+
+// ---- the lattice search among tracked objects: the scene-aware rule -----------------------------------------------------------------------
+static_assert(sizeof(se3tn_scene_point_fit) == sizeof(se3tn_point_fit) && offsetof(se3tn_scene_point_fit, inlier_pts) == offsetof(se3tn_point_fit, inlier_pts) &&
+                  offsetof(se3tn_scene_point_fit, behind_pts) == offsetof(se3tn_point_fit, behind_pts) &&
+                  offsetof(se3tn_scene_point_fit, hidden_pts) == offsetof(se3tn_point_fit, _reserved),
+              "the ranking reads scene-aware records through a cast");
+static_assert(sizeof(struct se3tn_scene_fit) == PG_OCC_FIT_BYTES, "pose_grid_plan.h lays the occluders' records out");
+
+int se3tn_score_pose_grid_scene(se3tn_ctx* c, const se3tn_points* p, int n_rot, const double* rots_dev, int n_trans, const double* trans_dev,
+                                const uint16_t* depth_dev, const uint16_t* scene_dev, int H, int W, const double K[9], int tol_mm, int facing,
+                                se3tn_scene_point_fit* fit_dev, void* stream) {
+  const char* who = "se3tn_score_pose_grid_scene";
+  if (int rc = pose_grid_check(who, c, rots_dev && trans_dev && depth_dev && scene_dev && K && fit_dev, p, n_rot, n_trans, H, W, tol_mm, facing))
+    return rc;
+  HIPCHK(launch_pose_grid(pose_grid_args(p, rots_dev, n_trans, trans_dev, depth_dev, H, W, K, tol_mm, facing,
+                                         reinterpret_cast<se3tn_point_fit*>(fit_dev), scene_dev), n_rot, (hipStream_t)stream));
+  return SE3TN_OK;
+}
+
+int se3tn_search_pose_grid_scene_host(se3tn_ctx* c, const se3tn_points* p, int n_rot, const double* rots, int n_trans, const double* trans,
+                                      const uint16_t* depth, int H, int W, const double K[9], int tol_mm, int facing, int k, int n_occ,
+                                      const se3tn_object* occluders, const double* occ_poses, int32_t* idx_out, se3tn_scene_point_fit* fit_out,
+                                      struct se3tn_scene_fit* occ_fit_out, void* stream) {
+  const char* who = "se3tn_search_pose_grid_scene_host";
+  // the numbers and the occluders first, then the context and the handle, then what is read from the caller's arrays
+  if (!c || !p || !rots || !trans || !depth || !K || !idx_out || !fit_out || !occluders || !occ_poses) return null_argument(who);
+  if (int rc = pose_grid_numbers_check(who, n_rot, n_trans, H, W, tol_mm, facing)) return rc;
+  const int n = n_rot * n_trans;
+  if (int rc = pose_rank_check(who, n, k)) return rc;
+  if (int rc = scene_numbers_check(who, c, n_occ, H, W, true)) return rc;
+  std::vector<TrackWindow> windows;
+  std::vector<const se3tn_mesh*> meshes;
+  if (int rc = scene_windows(who, n_occ, occluders, occ_poses, K, H, W, windows, meshes)) return rc;
+  if (int rc = pose_grid_context_check(who, c, p, facing)) return rc;
+  StagedCall sc{c, who, (hipStream_t)stream};
+  if (int rc = sc.refuse_capture()) return rc;
+  if (int rc = finite_check(who, "rotation", rots, nullptr, (size_t)n_rot, 9, 9)) return rc;
+  if (int rc = finite_check(who, "translation", trans, nullptr, (size_t)n_trans, 3, 3)) return rc;
+  const PgSceneStage s = pg_scene_stage(n_rot, n_trans, H, W, k, n_occ);
+  if (int rc = sc.grow(s.bytes)) return rc;
+  std::memcpy(sc.h + s.rots, rots, sizeof(double) * 9 * (size_t)n_rot);
+  std::memcpy(sc.h + s.trans, trans, sizeof(double) * 3 * (size_t)n_trans);
+  std::memcpy(sc.h + s.depth, depth, sizeof(uint16_t) * (size_t)H * (size_t)W);
+  if (int rc = sc.upload(s.upload_bytes)) return rc;
+  // the occluders rendered and composed against the staged frame: their records, and the scene frame the search reads
+  if (int rc = scene_fit_enqueue(c, n_occ, meshes, windows, occ_poses, K, sc.dev<uint16_t>(s.depth), H, W, tol_mm,
+                                 sc.dev<struct se3tn_scene_fit>(s.occ_fit), nullptr, sc.dev<uint16_t>(s.scene), sc.st)) {
+    (void)hipStreamSynchronize(sc.st);   // (the upload reads the pinned staging: let it end before the next call writes there)
+    return rc;
+  }
+  HIPCHK(launch_pose_grid(pose_grid_args(p, sc.dev<double>(s.rots), n_trans, sc.dev<double>(s.trans), sc.dev<uint16_t>(s.depth), H, W, K,
+                                         tol_mm, facing, sc.dev<se3tn_point_fit>(s.fit), sc.dev<uint16_t>(s.scene)), n_rot, sc.st));
+  HIPCHK(launch_pose_rank(sc.dev<se3tn_point_fit>(s.fit), n, k, sc.dev<int32_t>(s.idx), sc.dev<se3tn_point_fit>(s.top_fit), sc.st));
+  if (int rc = sc.finish(s.readback_at, s.readback_bytes)) return rc;
+  std::memcpy(fit_out, sc.h + s.top_fit, sizeof(se3tn_scene_point_fit) * (size_t)k);
+  std::memcpy(idx_out, sc.h + s.idx, sizeof(int32_t) * (size_t)k);
+  if (occ_fit_out) std::memcpy(occ_fit_out, sc.h + s.occ_fit, sizeof(struct se3tn_scene_fit) * (size_t)n_occ);
+  c->ps_scene_off = s.scene; c->ps_scene_H = H; c->ps_scene_W = W;
+  return SE3TN_OK;
+}
+
+int se3tn_last_search_scene(se3tn_ctx* c, const uint16_t** scene_dev, int* H, int* W) {
+  const char* who = "se3tn_last_search_scene";
+  if (!c || !scene_dev || !H || !W) return null_argument(who);
+  if (int rc = refuse_if(c->ps_scene_H < 1, SE3TN_E_STATE, who,
+                         "no scene frame: se3tn_search_pose_grid_scene_host has not succeeded, or another _host call has used the staging since")) return rc;
+  *scene_dev = reinterpret_cast<const uint16_t*>(c->ps_dev.get() + c->ps_scene_off);
+  *H = c->ps_scene_H; *W = c->ps_scene_W;
   return SE3TN_OK;
 }
 

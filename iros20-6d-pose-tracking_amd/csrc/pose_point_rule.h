@@ -11,6 +11,7 @@
 //     d = depth[vf, uf],  m = rint(c.z * 1000.0)
 //     seen       in frame && 100 < d < 2000
 //     inlier |d - m| <= tol      front d < m - tol      behind d > m + tol             (of the seen ones; exact: integers in doubles)
+// count_point_scene (below, se3tn_score_pose_grid_scene) puts one verdict in front of `seen`: hidden by a tracked surface.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -66,6 +67,32 @@ SE3TN_PS_HD inline void count_point(const DepthFrame& f, double tol, double cx, 
   if (fabs(d - m) <= tol) v[2] += 1u;
   if (d < m - tol) v[3] += 1u;
   if (d > m + tol) v[4] += 1u;
+}
+
+// The scene-aware rule (se3tn_score_pose_grid_scene): `scene` [H,W] is the composed depth of the tracked objects in millimetres, 0
+// where there is none.
+//     s = scene[vf, uf]
+//     hidden     in frame && 100 < s < 2000 && s <= m + tol       a tracked surface at or in front of the point: occluded by it, or
+//                                                                 claimed by it.  The point enters hidden and nothing else past in frame
+//     otherwise  d = depth[vf, uf]; seen, inlier, front, behind exactly as count_point
+// the point c added to the six counters v: in frame, seen, inlier, front, behind, hidden
+SE3TN_PS_HD inline void count_point_scene(const DepthFrame& f, const uint16_t* scene, double tol, double cx, double cy, double cz,
+                                          unsigned v[6]) {
+  double uf, vf;
+  size_t q;
+  if (!pixel_of(f, cx, cy, cz, uf, vf, q)) return;
+  v[0] += 1u;
+  const double s = (double)scene[q];
+  const double d = (double)f.depth[q];   // (read beside s, not after the verdict on it: on the device the two gathers travel together)
+  const double m = model_mm(cz);
+  // every counter is added to by name, without a branch that picks one: the device keeps the seven sums in registers only then
+  const bool hid = seen(s) && s <= m + tol;
+  const bool sn = !hid && seen(d);
+  v[5] += hid ? 1u : 0u;
+  v[1] += sn ? 1u : 0u;
+  v[2] += (sn && fabs(d - m) <= tol) ? 1u : 0u;
+  v[3] += (sn && d < m - tol) ? 1u : 0u;
+  v[4] += (sn && d > m + tol) ? 1u : 0u;
 }
 
 }  // namespace se3tn

@@ -277,6 +277,8 @@ struct PoseGridArgs {
   int tol;                 // millimetres
   int facing;              // 0 | 1
   se3tn_point_fit* out;    // [n_rot * n_trans] records, every word stored once
+  const uint16_t* scene;   // NULL, or [H,W] millimetres, the composed depth of the tracked objects: the scene-aware rule, and `out`
+                           // holds se3tn_scene_point_fit records (word 7 = hidden_pts).  Last: the plain kernels' arguments stay put
 };
 hipError_t launch_pose_grid(const PoseGridArgs& a, int n_rot, hipStream_t st);
 

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, SCENE_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, SCENE_FIT_DTYPE, SCENE_POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -581,19 +581,26 @@ class Engine:
               "se3tn_rank_poses")
         return idx, fit[idx.long()]
 
-    def score_pose_grid(self, points, rots, trans, depth, K, tol_mm, facing=False, top=None):
+    def score_pose_grid(self, points, rots, trans, depth, K, tol_mm, facing=False, top=None, scene=None):
         """se3tn_score_pose_grid (+ se3tn_rank_poses): the n_rot x n_trans candidates [R_r | t_t] (candidate r * n_trans + t) of the
         rotations `rots` ([n_rot,3,3] or [n_rot,9]) and translations `trans` ([n_trans,3]) scored as score_poses scores composed
         poses, without materialising them.  facing=True counts only the points whose normal faces the camera (the handle must carry
         normals: Engine.model_points(pts, normals)); a record's ``points`` is then the number of facing points.  facing=False gives
         the words of score_poses on the composed poses.  Inputs and return values as score_poses: numpy in -> a structured array of
         n_rot * n_trans records, or with top=k (idx[k] int32, records[k]) from ONE synchronous call (se3tn_search_pose_grid_host);
-        cuda tensors in (float64 rots / trans, 16-bit depth) -> int32 tensors, stream-ordered, nothing allocated by the library."""
+        cuda tensors in (float64 rots / trans, 16-bit depth) -> int32 tensors, stream-ordered, nothing allocated by the library.
+        scene (a cuda 16-bit [H,W] tensor, or a host uint16 array beside host inputs): the composed depth of the tracked objects
+        (Engine.scene_fit(..., scene=True)) -> the scene-aware rule of se3tn_score_pose_grid_scene: a point at or behind a tracked
+        surface is hidden_pts and nothing else.  The records then have dtype _lib.SCENE_POINT_FIT_DTYPE (word 7 = hidden_pts); with
+        host inputs everything is uploaded and the device entry runs, top=k included (the one-call host search takes the occluders,
+        not their scene: search_pose_grid_scene).  Without it nothing changes."""
         if not isinstance(points, ModelPoints) or not points._h:
             raise Se3tnError("score_pose_grid: points must be an open ModelPoints handle (Engine.model_points)")
         Kh = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
         Kp = Kh.ctypes.data_as(C.POINTER(C.c_double))
         fc = 1 if facing else 0
+        if scene is not None:
+            return self._score_pose_grid_scene(points, rots, trans, depth, Kp, tol_mm, fc, top, scene)
         tensors = [torch.is_tensor(x) for x in (rots, trans, depth)]
         if any(tensors):
             if not all(tensors):
@@ -619,16 +626,85 @@ class Engine:
               "se3tn_search_pose_grid_host")
         return idx, fit
 
-    def _score_pose_grid_device(self, points, rots, trans, depth, Kp, tol_mm, facing, top):
+    def _score_pose_grid_scene(self, points, rots, trans, depth, Kp, tol_mm, facing, top, scene):
+        """score_pose_grid with a scene: tensors in -> tensors out; arrays in -> uploaded, the device entry, numpy out"""
+        tensors = [torch.is_tensor(x) for x in (rots, trans, depth)]
+        if any(tensors):
+            if not (all(tensors) and torch.is_tensor(scene)):
+                raise Se3tnError("score_pose_grid: rots, trans, depth and scene must all be tensors or all be arrays")
+            return self._score_pose_grid_device(points, rots, trans, depth, Kp, tol_mm, facing, top, scene)
+        dev = "cuda:%d" % self.device
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("score_pose_grid: depth must be [H,W]")
+        if torch.is_tensor(scene):   # (a scene kept on the device beside host candidates: MultiTracker.recover's rescoring)
+            sc = scene
+        else:
+            sc = np.ascontiguousarray(scene, dtype=np.uint16)
+            if sc.shape != d.shape:
+                raise ValueError("score_pose_grid: scene must have the frame's shape")
+            sc = torch.from_numpy(sc.view(np.int16)).to(dev)
+        r = torch.from_numpy(np.ascontiguousarray(np.asarray(rots, np.float64).reshape(-1, 9))).to(dev)
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(trans, np.float64).reshape(-1, 3))).to(dev)
+        out = self._score_pose_grid_device(points, r, t, torch.from_numpy(d.view(np.int16)).to(dev), Kp, tol_mm, facing, top, sc)
+        if top is None:
+            return out.cpu().numpy().view(SCENE_POINT_FIT_DTYPE).reshape(-1)
+        return out[0].cpu().numpy(), out[1].cpu().numpy().view(SCENE_POINT_FIT_DTYPE).reshape(-1)
+
+    def search_pose_grid_scene(self, points, rots, trans, depth, K, occluders, occ_poses, tol_mm=10, facing=True, top=8, keep_scene=False):
+        """se3tn_search_pose_grid_scene_host: the lattice search among tracked objects as ONE synchronous call from host arrays --
+        one upload of [rots | trans | depth], the occluders (as scene_fit's `objects`: a ctypes array of _lib.Object, or (mesh |
+        HipRenderer, object_width_mm) pairs) rendered at occ_poses ([n_occ,4,4]) and composed into a scene frame that stays on the
+        device, the scene-aware grid kernel, the ranking, one read-back.  Returns (idx[top] int32, records[top] of
+        _lib.SCENE_POINT_FIT_DTYPE, the occluders' records [n_occ] of _lib.SCENE_FIT_DTYPE); with keep_scene=True a fourth value, a
+        cuda int16 [H,W] tensor holding a copy of the composed scene (se3tn_last_search_scene) for score_pose_grid(scene=...)."""
+        if not isinstance(points, ModelPoints) or not points._h:
+            raise Se3tnError("search_pose_grid_scene: points must be an open ModelPoints handle (Engine.model_points)")
+        objs, n_occ = self._scene_objects(occluders)
+        op = np.ascontiguousarray(np.asarray(occ_poses, np.float64).reshape(-1, 16))
+        if len(op) != n_occ:
+            raise ValueError("search_pose_grid_scene: %d poses for %d occluders" % (len(op), n_occ))
+        Kp = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9)).ctypes.data_as(C.POINTER(C.c_double))
+        r = np.ascontiguousarray(np.asarray(rots, np.float64).reshape(-1, 9))
+        t = np.ascontiguousarray(np.asarray(trans, np.float64).reshape(-1, 3))
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("search_pose_grid_scene: depth must be [H,W]")
+        H, W = int(d.shape[0]), int(d.shape[1])
+        k = int(top)
+        idx = np.empty(max(k, 0), np.int32)
+        fit = np.zeros(max(k, 0), SCENE_POINT_FIT_DTYPE)
+        occ = np.zeros(max(n_occ, 1), SCENE_FIT_DTYPE)
+        check(self.lib.se3tn_search_pose_grid_scene_host(self._h, points._h, int(r.shape[0]), C.c_void_p(r.ctypes.data), int(t.shape[0]),
+                                                         C.c_void_p(t.ctypes.data), C.c_void_p(d.ctypes.data), H, W, Kp, int(tol_mm),
+                                                         1 if facing else 0, k, n_occ, objs, C.c_void_p(op.ctypes.data),
+                                                         C.c_void_p(idx.ctypes.data), C.c_void_p(fit.ctypes.data), C.c_void_p(occ.ctypes.data),
+                                                         _stream_ptr()), "se3tn_search_pose_grid_scene_host")
+        if not keep_scene:
+            return idx, fit, occ[:n_occ]
+        ptr, h, w = C.c_void_p(), C.c_int(), C.c_int()
+        check(self.lib.se3tn_last_search_scene(self._h, C.byref(ptr), C.byref(h), C.byref(w)), "se3tn_last_search_scene")
+        scene_t = torch.empty((H, W), dtype=torch.int16, device="cuda:%d" % self.device)
+        check(self.lib.se3tn_memcpy_d2d(C.c_void_p(scene_t.data_ptr()), ptr, H * W * 2, _stream_ptr()), "se3tn_memcpy_d2d")
+        return idx, fit, occ[:n_occ], scene_t
+
+    def _score_pose_grid_device(self, points, rots, trans, depth, Kp, tol_mm, facing, top, scene=None):
         assert rots.is_cuda and rots.dtype == torch.float64 and rots.is_contiguous() and rots.numel() % 9 == 0
         assert trans.is_cuda and trans.dtype == torch.float64 and trans.is_contiguous() and trans.numel() % 3 == 0
         assert depth.is_cuda and depth.element_size() == 2 and depth.dim() == 2 and depth.is_contiguous()
         n_rot, n_trans = rots.numel() // 9, trans.numel() // 3
         n = n_rot * n_trans
         fit = torch.empty((n, 8), dtype=torch.int32, device=rots.device)
-        check(self.lib.se3tn_score_pose_grid(self._h, points._h, n_rot, C.c_void_p(rots.data_ptr()), n_trans, C.c_void_p(trans.data_ptr()),
-                                             C.c_void_p(depth.data_ptr()), int(depth.shape[0]), int(depth.shape[1]), Kp, int(tol_mm),
-                                             int(facing), C.c_void_p(fit.data_ptr()), _stream_ptr()), "se3tn_score_pose_grid")
+        if scene is not None:
+            assert scene.is_cuda and scene.element_size() == 2 and scene.is_contiguous() and scene.shape == depth.shape
+            check(self.lib.se3tn_score_pose_grid_scene(self._h, points._h, n_rot, C.c_void_p(rots.data_ptr()), n_trans,
+                                                       C.c_void_p(trans.data_ptr()), C.c_void_p(depth.data_ptr()), C.c_void_p(scene.data_ptr()),
+                                                       int(depth.shape[0]), int(depth.shape[1]), Kp, int(tol_mm), int(facing),
+                                                       C.c_void_p(fit.data_ptr()), _stream_ptr()), "se3tn_score_pose_grid_scene")
+        else:
+            check(self.lib.se3tn_score_pose_grid(self._h, points._h, n_rot, C.c_void_p(rots.data_ptr()), n_trans, C.c_void_p(trans.data_ptr()),
+                                                 C.c_void_p(depth.data_ptr()), int(depth.shape[0]), int(depth.shape[1]), Kp, int(tol_mm),
+                                                 int(facing), C.c_void_p(fit.data_ptr()), _stream_ptr()), "se3tn_score_pose_grid")
         if top is None:
             return fit
         idx = torch.empty((max(int(top), 0),), dtype=torch.int32, device=rots.device)

@@ -145,10 +145,15 @@ class LiveMultiTracker:
     """`TrackerRos` for several objects seen by one camera: a ``MultiTracker`` instead of a ``Tracker``, n poses instead of one.
     The surface of ``LiveTracker``; on_track() returns a list of n (translation [3], quaternion x,y,z,w, stamp) and feeds the n
     poses back.  one_call=False composes engine.fill_depth + the channel swap + MultiTracker.on_track; one_call=True is ONE library
-    call per frame (opt-in, as LiveTracker's; measured in profiles/EXPERIMENTS.md item 73)."""
+    call per frame (opt-in, as LiveTracker's; measured in profiles/EXPERIMENTS.md item 73).
+    recover_lost: None (default; then not one call more is made) or a dict of utils.scene_status thresholds (lost_below,
+    min_visible; further keys are MultiTracker.recover's keywords): after each frame the objects the scene records call "lost" go
+    through MultiTracker.recover around the poses the frame started from, and the poses it finds are adopted.  Needs scene_check."""
 
-    def __init__(self, multi_tracker, poses_init, max_depth=2.0, extrapolate=False, blur_type="bilateral", one_call=False):
+    def __init__(self, multi_tracker, poses_init, max_depth=2.0, extrapolate=False, blur_type="bilateral", one_call=False,
+                 recover_lost=None):
         self.tracker = multi_tracker
+        self.recover_lost = None if recover_lost is None else dict(recover_lost)
         self.color = None
         self._depth = None
         self.cur_time = None
@@ -183,7 +188,7 @@ class LiveMultiTracker:
     def scene_check(self):
         """The tracker's scene_check (None | tol_mm): with it set every on_track is followed by one scene call at the estimates, in
         which the tracked objects explain each other's occlusions; tracker.last_prediction["scene_fit"], last_scene_ratio and
-        scene_status() carry the result.  (Acting on "lost" is left to the caller.)"""
+        scene_status() carry the result.  (Acting on "lost": recover_lost, or MultiTracker.recover.)"""
         return self.tracker.scene_check
 
     @scene_check.setter
@@ -247,6 +252,21 @@ class LiveMultiTracker:
         self._filled_valid = True
         return poses
 
+    def _recover_lost(self, obs_in_cam):
+        """recover_lost: the objects of this frame the scene records call "lost" searched among the tracked ones.  The lost objects
+        are searched around the poses the frame started from, the occluders stand at this frame's estimates."""
+        if not self.tracker.scene_check:
+            raise ValueError("LiveMultiTracker: recover_lost needs scene_check (the scene records say which objects are lost)")
+        kw = dict(self.recover_lost)
+        status = self.scene_status(kw.get("lost_below", 0.5), kw.get("min_visible", 0.2))
+        lost = [i for i, s in enumerate(status) if s == "lost"]
+        if not lost:
+            return obs_in_cam
+        around = np.asarray(obs_in_cam, np.float64).copy()
+        around[lost] = self.A_in_cam[lost]
+        rgb = np.ascontiguousarray(self.color[:, :, ::-1]) if self.one_call else self.color.astype(np.uint8)
+        return self.tracker.recover(around, rgb, self.depth, lost=lost, **kw)
+
     def on_track(self):
         if self.color is None or (self._raw if self.one_call else self._depth) is None or self.cur_time is None:
             return None
@@ -254,6 +274,8 @@ class LiveMultiTracker:
             obs_in_cam = self._on_track_one_call()
         else:
             obs_in_cam = self.tracker.on_track(self.A_in_cam, self.color.astype(np.uint8), self._depth)
+        if self.recover_lost is not None:
+            obs_in_cam = self._recover_lost(obs_in_cam)
         self.A_in_cam = obs_in_cam.copy()
         out = []
         for ob_in_cam in obs_in_cam:

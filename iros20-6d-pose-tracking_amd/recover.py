@@ -17,7 +17,8 @@ KEY_FIELD_MAX = (1 << 20) - 1   # as csrc/pose_search_plan.h: the two 20-bit fie
 def pose_key(fit, index=None):
     """The 64-bit key se3tn_rank_poses orders records by (csrc/pose_search_plan.h ps_key), as Python ints in an object array:
     inlier_pts * 2^40 + (2^20 - 1 - min(behind_pts, 2^20 - 1)) * 2^20 + (2^20 - 1 - index); index defaults to the record's place.
-    More inliers first, then fewer seen-through points, then the lower index."""
+    More inliers first, then fewer seen-through points, then the lower index.  Reads inlier_pts and behind_pts only: records of
+    _lib.POINT_FIT_DTYPE and of _lib.SCENE_POINT_FIT_DTYPE (the scene-aware searches) alike."""
     fit = np.atleast_1d(fit)
     idx = np.arange(len(fit)) if index is None else np.atleast_1d(index)
     return np.array([(min(int(f["inlier_pts"]), KEY_FIELD_MAX + 1) << 40) + ((KEY_FIELD_MAX - min(int(f["behind_pts"]), KEY_FIELD_MAX)) << 20)

@@ -854,6 +854,90 @@ class MultiTracker:
         rec, ids_img, _ = self.engine.scene_fit(self._objs, poses, depth, self.K, tol_mm=tol_mm, ids=ids)
         return (rec, ids_img) if ids else rec
 
+    def recover(self, prev_poses, rgb, depth, lost=None, lost_below=0.5, min_visible=0.2, trans_radius=0.05, trans_step=0.01,
+                rot_deg=(15.0,), tol_mm=10, top=None, refine=1, align=0):
+        """Extension: re-acquire the lost objects of a frame AMONG the tracked ones.  Tracker.recover scores a candidate against the
+        depth frame alone: it lays a lost model onto the visible face of a neighbour, and counts a tracked object in front of a
+        candidate as an unknown obstacle.  Here the objects that are "tracked" explain their pixels (the rule of
+        se3tn_score_pose_grid_scene): a point at or behind a tracked surface is hidden_pts and nothing else.
+        prev_poses: [n,4,4], the poses to search around (lost objects) and to render at (occluders); rgb, depth: the frame.
+        lost: a list of object indices; default: the objects utils.scene_status(last_prediction["scene_fit"], lost_below,
+        min_visible) calls "lost" -- scene_check must have run (ValueError otherwise, also when `lost` is given: the occluders
+        are chosen by the same records).  Occluders are the objects with status "tracked" that are not being searched, at their
+        prev_poses; "occluded" and lost objects explain nothing.  With no occluder at all every lost object falls back to
+        trackers[i].recover(..., facing=True) and last_recover[i]["fallback"] says so.
+        Per lost object i, in index order: (1) recover.lattice_factors around prev_poses[i]; (2) ONE call,
+        Engine.search_pose_grid_scene with facing=True on trackers[i]'s facing handle, whose composed scene is kept on the device;
+        (3) align > 0: Engine.align_poses of the top nodes, refine >= 1: trackers[i].on_track_batch on them, as Tracker.recover
+        does; (4) the pool [refined, aligned, unrefined] rescored under the scene-aware rule as the diagonal of a grid against the
+        kept scene, and the largest recover.pose_key wins.  So the result never scores below the lattice's best under the scene
+        rule.  The alignment and the network stay scene-unaware; the choice is not.  A recovered object does NOT become an
+        occluder for the next lost one within the same call: every search of a call sees the same occluders.
+        Returns [n,4,4]: rows of objects that were not searched are prev_poses' rows.  last_recover: {i: dict} per searched object
+        -- what Tracker.last_recover keeps (n, top_idx, top_fit, refined, final_fit, chosen, inlier_frac = inlier_pts / points;
+        aligned, align_rec) plus occluders (indices), occ_fit (their scene records), hidden_pts and visible_frac = inlier_pts /
+        (points - hidden_pts), NaN when that is 0."""
+        from .recover import lattice_factors, pose_key
+        poses = np.asarray(prev_poses, np.float64).reshape(-1, 4, 4)
+        if poses.shape[0] != self.n:
+            raise ValueError("MultiTracker.recover: %d poses for %d objects" % (poses.shape[0], self.n))
+        rec = (self.last_prediction or {}).get("scene_fit")
+        if rec is None:
+            raise ValueError("MultiTracker.recover: no scene records -- set scene_check (tol_mm) and track a frame first: they say which "
+                             "objects are lost and which are tracked and explain their pixels")
+        status = U.scene_status(rec, lost_below, min_visible)
+        lost = [i for i, s in enumerate(status) if s == "lost"] if lost is None else sorted(set(int(i) for i in lost))
+        if any(i < 0 or i >= self.n for i in lost):
+            raise ValueError("MultiTracker.recover: lost = %s names an object outside [0, %d)" % (lost, self.n))
+        out = poses.copy()
+        self.last_recover = {}
+        if not lost:
+            return out
+        occ = [i for i, s in enumerate(status) if s == "tracked" and i not in lost]
+        dep = np.ascontiguousarray(depth, dtype=np.uint16)
+        if not occ:   # nothing explains anything: the single-object search
+            for i in lost:
+                out[i] = self.trackers[i].recover(poses[i], rgb, dep, trans_radius=trans_radius, trans_step=trans_step, rot_deg=rot_deg,
+                                                  tol_mm=tol_mm, top=top, refine=refine, facing=True, align=align)
+                self.last_recover[i] = dict(self.trackers[i].last_recover, occluders=[], fallback=True)
+            return out
+        occ_objs = (type(self._objs[0]) * len(occ))(*[self._objs[j] for j in occ])
+        for i in lost:
+            t = self.trackers[i]
+            handle = t._facing_handle(None, "MultiTracker.recover")
+            k = min(8, t.engine.max_batch) if top is None else int(top)
+            rots, trans = lattice_factors(poses[i], trans_radius, trans_step, rot_deg)
+            top_idx, top_fit, occ_fit, scene = self.engine.search_pose_grid_scene(handle, rots, trans, dep, self.K, occ_objs, poses[occ],
+                                                                                  tol_mm=tol_mm, facing=True, top=k, keep_scene=True)
+            unrefined = t._compose(rots, trans, top_idx)
+            info = dict(n=len(rots) * len(trans), top_idx=top_idx, top_fit=top_fit, refined=None, facing=True, occluders=list(occ),
+                        occ_fit=occ_fit, fallback=False)
+            aligned = None
+            if int(align) > 0:
+                aligned, align_rec = t.engine.align_poses(handle, unrefined, dep, self.K, iters=int(align))
+                info.update(aligned=aligned, align_rec=align_rec)
+            if int(refine) < 1 and aligned is None:
+                final, final_fit, chosen = unrefined, top_fit[:1].copy(), 0
+            else:
+                refined = unrefined if aligned is None else aligned
+                for _ in range(int(refine)):
+                    refined = np.asarray(t.on_track_batch(list(refined), [rgb] * k, [dep] * k), np.float64)
+                if int(refine) < 1:
+                    refined = None
+                final = np.concatenate(([] if refined is None else [refined]) + ([] if aligned is None else [aligned]) + [unrefined])
+                m = len(final)
+                grid = self.engine.score_pose_grid(handle, final[:, :3, :3], final[:, :3, 3], dep, self.K, tol_mm, facing=True, scene=scene)
+                final_fit = grid[np.arange(m) * m + np.arange(m)]
+                chosen = int(np.argmax(pose_key(final_fit)))   # ties prefer the earlier part of the pool: the lower index
+                info.update(refined=refined)
+            win = final_fit[chosen]
+            shown = int(win["points"]) - int(win["hidden_pts"])
+            info.update(final_fit=final_fit, chosen=chosen, inlier_frac=t._frac(win), hidden_pts=int(win["hidden_pts"]),
+                        visible_frac=float(win["inlier_pts"]) / shown if shown > 0 else float("nan"))
+            self.last_recover[i] = info
+            out[i] = final[chosen]
+        return out
+
     @property
     def fit_check(self):
         """None (default) | tol_mm, as Tracker.fit_check: every call also scores each object's estimate against the observed depth
