@@ -96,8 +96,22 @@ int se3tn_set_normalization(se3tn_ctx* ctx, const double mean[8], const double s
  *   SE3TN_PREC_F16X3 operands split into f16 hi + f16 lo (22 significant bits), products formed as
  *                    hi*hi + hi*lo + lo*hi on the f16 matrix cores with float32 accumulation:
  *                    float32-class error (measured ~1e-6 on the outputs) at 16/3 the MFMA rate.
- *                    Activations of those layers must stay inside the f16 range (|x| < 65000);
- *                    se3tn_overflow reports (and clears) a violation -- rerun in SE3TN_PREC_F32 then. */
+ *                    Range: every value STORED in this mode -- the network inputs, the pooled stems, every activation between
+ *                    two convolutions, and where the heads run as the fused F(4x4) block (se3tn_set_winograd, n >= min_batch)
+ *                    the F(4x4) input planes B^T d B of the heads' stride-2 map and of the map between their two convolutions
+ *                    -- must satisfy |x| <= 65000.  A store that does not raises a per-context flag; se3tn_overflow reports
+ *                    and clears it (it outlives later calls and precision switches until read, and a replayed graph raises
+ *                    it too) -- rerun in SE3TN_PREC_F32 then.  Inf and NaN count as violations.
+ *                    What that means per route (measured against float64, tests/test_gpu_f16x3_range.py, seed 31):
+ *                      high side, heads conv by conv: maps up to 65000 (a map with maximum 4.3e4: no flag, |d logit| 4e-7);
+ *                      high side, fused F(4x4) heads: the planes run above the map (up to 49 x: the rows of B^T have absolute
+ *                        sums up to 7; 10.3 x on that network), so the flag already rises for a map maximum between 5.4e3
+ *                        (planes 5.6e4, no flag) and 1.1e4 (planes 1.1e5, flag): conservative, never silent;
+ *                      low side, both routes: only the weights are scaled per row, so the lo half of a small activation falls
+ *                        into f16 subnormals (2^-24 absolute) and NO flag is raised.  With a whole stored map scaled down (its
+ *                        reader's weights up), |d logit| is float32-class (<= 1e-6, PREC_F32: 4e-7) down to a map maximum of
+ *                        4e-2, 1e-5 at 2e-3, 3e-4 at 1.5e-4 and 5e-3 at 1e-5.  A network whose stored maps peak below ~1e-2
+ *                        (a small BN gamma ahead of large weights) belongs in SE3TN_PREC_F32. */
 #define SE3TN_PREC_F32 0
 #define SE3TN_PREC_F16X3 1
 /* Init-time call: the first selection of SE3TN_PREC_F16X3 (and a later change of weights while it is selected) derives the

@@ -986,7 +986,7 @@ static int run_plan(se3tn_ctx* c, const InferConfig& cfg, const InferPlan& p, co
     else
       HIPCHK(launch_stem(A, B, W + L.stem_w, W + L.stem_b, nullptr, c->stem.get(), n, st));
     HIPCHK((hipError_t)mark(stem_label(p, 0), false));
-    HIPCHK(launch_maxpool(c->stem.get(), c->pool.get(), n, fast ? 1 : 0, st));
+    HIPCHK(launch_maxpool(c->stem.get(), c->pool.get(), n, fast ? 1 : 0, c->overflow.get(), st));
     HIPCHK((hipError_t)mark(stem_label(p, 1), false));
   }
   struct MarkCtx { se3tn_ctx* c; hipStream_t st; const char* name; };

@@ -325,7 +325,7 @@ hipError_t launch_crop_raw(const se3tn_crop& c, uint8_t* rgb_out, uint16_t* dept
 hipError_t launch_stem(const float* inA, const float* inB, const float* w, const float* bias,
                        const float* wscale, float* out, int n, hipStream_t st);
 // split_out != 0: write split rows (f16 hi | f16 lo) for the f16x3 mode
-hipError_t launch_maxpool(const float* in, float* out, int n, int split_out, hipStream_t st);
+hipError_t launch_maxpool(const float* in, float* out, int n, int split_out, int* overflow, hipStream_t st);
 // conv3x3: executes the planned step (SMALL64 .. GATHER; its slice count, whether it reduces them); cin/cout/stride select the
 // instantiation; epi: 0 bias+relu, 1 bias+res+relu, 2 bias+selu.  hipErrorInvalidValue: no kernel of that algorithm for the shape
 hipError_t launch_conv3x3(const ConvArgs& a, const ConvStep& step, int cin, int cout, int stride, int epi, hipStream_t st);

@@ -297,7 +297,7 @@ __device__ __forceinline__ void pool_row(const float* __restrict__ src, int y, i
 }
 
 __global__ __launch_bounds__(POOL_THREADS) void maxpool3x3s2_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                     int n, int rows, int split_out) {
+                                                                     int n, int rows, int split_out, int* overflow) {
   // workgroup -> (image, strip).  Consecutive workgroup ids land on different XCDs (id % 8); strips s and s + 1 share
   // one input row, so an XCD gets whole images (image = 8 k + xcd) and the shared row comes from its own L2
   const int strips = S2 / rows;
@@ -327,16 +327,22 @@ __global__ __launch_bounds__(POOL_THREADS) void maxpool3x3s2_kernel(const float*
     for (int k = 0; k < 4; ++k) {
       const float4 m = max4(max4(carry[k], a[k]), b[k]);
       carry[k] = b[k];
-      if (split_out) {  // f16x3 mode: 32-channel chunk = 32 f16 hi | 32 f16 lo (SELU output is bounded below, finite)
+      if (split_out) {  // f16x3 mode: 32-channel chunk = 32 f16 hi | 32 f16 lo (SELU output is bounded below, not above)
         typedef _Float16 half4 __attribute__((ext_vector_type(4)));
         const int c = c4 * 4;
         unsigned char* p_ = reinterpret_cast<unsigned char*>(dst + k * 128) + (c >> 5) * 128 + (c & 31) * 2;
         const float f[4] = {m.x, m.y, m.z, m.w};
         half4 h, l;
+        bool bad = false;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { h[e] = (_Float16)f[e]; l[e] = (_Float16)(f[e] - (float)h[e]); }
+        for (int e = 0; e < 4; ++e) {
+          h[e] = (_Float16)f[e];
+          l[e] = (_Float16)(f[e] - (float)h[e]);
+          bad |= !(fabsf(f[e]) <= 65000.f);
+        }
         *reinterpret_cast<half4*>(p_) = h;
         *reinterpret_cast<half4*>(p_ + 64) = l;
+        if (bad) atomicOr(overflow, 1);
       } else {
         *reinterpret_cast<float4*>(dst + k * 128 + c4 * 4) = m;
       }
@@ -357,9 +363,9 @@ static int pool_rows(int n) {
   return 1;
 }
 
-hipError_t launch_maxpool(const float* in, float* out, int n, int split_out, hipStream_t st) {
+hipError_t launch_maxpool(const float* in, float* out, int n, int split_out, int* overflow, hipStream_t st) {
   const int rows = pool_rows(n);
-  hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(n * (S2 / rows)), dim3(POOL_THREADS), 0, st, in, out, n, rows, split_out);
+  hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(n * (S2 / rows)), dim3(POOL_THREADS), 0, st, in, out, n, rows, split_out, overflow);
   return hipGetLastError();
 }
 
