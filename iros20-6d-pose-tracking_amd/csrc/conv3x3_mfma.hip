@@ -15,8 +15,7 @@
 //  * operand tiles are DMA'd global -> LDS with global_load_lds_dwordx4 (no staging VGPRs, no
 //    ds_write pass).  A DMA's LDS image is lane-linear, so LDS rows are unpadded 128-byte runs
 //    (32 floats) and ds_read_b128 bank conflicts are removed by an XOR swizzle applied on the SOURCE
-//    side (which 16-byte slot a lane fetches) and again on the read address:
-//        physical slot = logical slot ^ ((row >> 1) & 7);
+//    side (which 16-byte slot a lane fetches) and again on the read address: lds_rows.h states it;
 //  * the DMA is issued from inline asm: for the builtin hipcc (ROCm 7.2) cannot prove that the DMA
 //    destination (the other buffer) does not alias the ds_reads of the current buffer and puts
 //    `s_waitcnt vmcnt(0)` in front of the first ds_read of every K-step.  The one wait needed
@@ -129,7 +128,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_slab_kernel(const ConvArgs a) 
   // ---- DMA geometry ---------------------------------------------------------------------------
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
   // slab piece j = 8 pixels: lane l -> pixel 8 j + (l >> 3), LDS slot l & 7 holds channel block
-  // (l & 7) ^ f(pixel), f(i) = (i >> 1) & 7 = (4 j + (l >> 4)) & 7: two lane patterns (j even / odd)
+  // lds_rows::slot_block(pixel, l & 7).  Lane form: row_key(8 j + (l >> 3)) = (4 j + (l >> 4)) & 7, two patterns (j even / odd);
+  // written out because the compiler folds slot_block((l >> 3) [+ 8], l & 7) into other instructions here
+  // (tests/c_abi/lds_rows_check.cpp holds the two spellings together)
   const unsigned sv_even = (unsigned)((lane >> 3) * a.in_ld * 4 + (((lane & 7) ^ ((lane >> 4) & 7)) << 4));
   const unsigned sv_odd = (unsigned)((lane >> 3) * a.in_ld * 4 + (((lane & 7) ^ ((4 + (lane >> 4)) & 7)) << 4));
   // weight piece q = 8 cout rows of the contiguous [BN][32] tile; same swizzle with row = 8 q + (l >> 3)
@@ -159,10 +160,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_slab_kernel(const ConvArgs a) 
   }
 
   // weight fragment offsets (floats): lane (l31, hh) reads logical slot 2 kg + hh of row base + l31
-  const int X = (l31 >> 1) & 7;
-  const int wlo = (hh ^ (X & 1)) * 4, xk = X >> 1;
-  const int fo0 = ((0 ^ xk) << 3) + wlo, fo1 = ((1 ^ xk) << 3) + wlo, fo2 = ((2 ^ xk) << 3) + wlo,
-            fo3 = ((3 ^ xk) << 3) + wlo;
+  const lds_rows::LaneFrag fo = lds_rows::lane_frag(l31, hh);
 
   // prologue of the first tile: whole slab of chunk 0 + first weight tile
 #pragma unroll
@@ -190,12 +188,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_slab_kernel(const ConvArgs a) 
     if (more) TILE_GEOMETRY(tnext / panels, nlo, nnp)
 
     f32x16 acc[PT][CT];
-#pragma unroll
-    for (int i = 0; i < PT; ++i)
-#pragma unroll
-      for (int j = 0; j < CT; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
     // residual + ReLU epilogue of the short-K (64-channel) tiles: the residual values are fetched while the last
     // chunk's MFMAs run instead of after them (an L2 / HBM round trip per tile otherwise sits in the epilogue)
@@ -235,28 +228,19 @@ __global__ __launch_bounds__(512, 2) void conv3x3_slab_kernel(const ConvArgs a) 
 
         const int r = tap / 3, s = tap - r * 3;
         const int tapoff = (r - 1) * Wp + (s - 1);
-        // pixel fragment addresses: slab row idx = ibase + tapoff, slot (2 kg + hh) ^ ((idx >> 1) & 7),
-        // i.e. float offset (8 kg) ^ py with py = (hh ^ ((idx >> 1) & 7)) * 4
+        // pixel fragment addresses: slab rows are keyed per pixel: row idx = ibase + tapoff, float offset
+        // lds_rows::frag_off(idx, kg, hh) = (8 kg) ^ py with py = slot_off(idx, hh)
         int prow[PT], py[PT];
 #pragma unroll
         for (int i = 0; i < PT; ++i) {
           const int idx = ibase[i] + tapoff;
           prow[i] = sb * SLAB + idx * 32;
-          py[i] = (hh ^ ((idx >> 1) & 7)) << 2;
+          py[i] = lds_rows::slot_off(idx, hh);
         }
         const float* pW = smem + 2 * SLAB + wb * WT + (wn * CT * 32 + l31) * 32;
-#define PXF(G) *reinterpret_cast<const float4*>(smem + prow[i] + ((8 * (G)) ^ py[i]))
-#define WTF(G) *reinterpret_cast<const float4*>(pW + j * 1024 + ((G) == 0 ? fo0 : (G) == 1 ? fo1 : (G) == 2 ? fo2 : fo3))
-        if (MM == MM_F16X3) {
-          SE3TN_MMA_SPLIT(PT, CT, PXF, WTF)
-        } else {
-          SE3TN_MMA_GROUP(PT, CT, PXF(0), WTF(0))
-          SE3TN_MMA_GROUP(PT, CT, PXF(1), WTF(1))
-          SE3TN_MMA_GROUP(PT, CT, PXF(2), WTF(2))
-          SE3TN_MMA_GROUP(PT, CT, PXF(3), WTF(3))
-        }
-#undef PXF
-#undef WTF
+#define SLAB_PXF(G) *reinterpret_cast<const float4*>(smem + prow[i] + ((8 * (G)) ^ py[i]))
+        SE3TN_MMA_KSTEP(MM, PT, CT, SLAB_PXF, SE3TN_ROWS_WTF)
+#undef SLAB_PXF
         if (kt + 1 < NCH * 9 || more) wait_dma_and_barrier();
       }
     }
@@ -301,72 +285,32 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_gather_s2_kernel(const Con
   const int Wp = a.W + 2, Hp = a.H + 2, HoWo = a.Ho * a.Wo;
   const int mlast = a.M - 1;
 
-  // staging: thread t fills LDS slot (t & 7) of rows (t >> 3) + 32 j with channel block
-  // (t & 7) ^ ((row >> 1) & 7); in padded coordinates tap (r,s) of output (ho,wo) is input (2ho+r, 2wo+s)
+  // staging (lds_rows.h, mfma_common.h): thread t fills LDS slot (t & 7) of rows (t >> 3) + RS j
   const int r0 = tid >> 3;
-  const int c4 = (tid & 7) ^ ((r0 >> 1) & 7);
+  const int c4 = lds_rows::slot_block(r0, tid & 7);
   unsigned pvoff[PJ];
-#pragma unroll
-  for (int j = 0; j < PJ; ++j) {
-    const int m = min(m0 + r0 + RS * j, mlast);
-    const int n = m / HoWo, rem = m - n * HoWo;
-    const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-    pvoff[j] = (unsigned)((((n * Hp + 2 * ho) * Wp + 2 * wo) * a.in_ld + c4 * 4) * 4);
-  }
-  const unsigned wvoff = (unsigned)((r0 * 32 + c4 * 4) * 4);
+  SE3TN_GATHER_PVOFF(2)
+  const unsigned wvoff = (unsigned)(lds_rows::stage_src(r0, tid & 7) * 4);
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
 
-#define ISSUE_TILE(CH, TAP, BUFI)                                                                    \
-  {                                                                                                  \
-    const int r_ = (TAP) / 3, s_ = (TAP) - r_ * 3;                                                   \
-    const float* pb_ = in + (size_t)(r_ * Wp + s_) * a.in_ld + (CH) * 32;                            \
-    const unsigned lb_ = lds0 + (unsigned)(((BUFI) * BUF + wid * 256) * 4);                          \
-    _Pragma("unroll") for (int j_ = 0; j_ < PJ; ++j_) glds16<0>(pb_, pvoff[j_], lb_ + j_ * RS * 128);  \
-    const float* tb_ = wgt + (size_t)((CH) * 9 + (TAP)) * (a.tiles_n * BN) * 32;                     \
-    _Pragma("unroll") for (int j_ = 0; j_ < WJ; ++j_)                                                \
-        glds16<0>(tb_ + j_ * RS * 32, wvoff, lb_ + BM * 128 + j_ * RS * 128);                        \
-  }
-
-  const int X = (l31 >> 1) & 7;
-  const int lo = (hh ^ (X & 1)) * 4, xk = X >> 1;
-  const int fo0 = ((0 ^ xk) << 3) + lo, fo1 = ((1 ^ xk) << 3) + lo, fo2 = ((2 ^ xk) << 3) + lo,
-            fo3 = ((3 ^ xk) << 3) + lo;
+  const lds_rows::LaneFrag fo = lds_rows::lane_frag(l31, hh);
 
   f32x16 acc[PT][CT];
-#pragma unroll
-  for (int i = 0; i < PT; ++i)
-#pragma unroll
-    for (int j = 0; j < CT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
-  ISSUE_TILE(0, 0, 0)
+  SE3TN_GATHER_ISSUE_TILE(0, 0, 0)
   wait_dma_and_barrier();
 
   int ch = 0, tap = 0;
   for (int kt = 0; kt < KT; ++kt) {
     const int buf = kt & 1;
     if (++tap == 9) { tap = 0; ++ch; }
-    if (kt + 1 < KT) ISSUE_TILE(ch, tap, buf ^ 1)
+    if (kt + 1 < KT) SE3TN_GATHER_ISSUE_TILE(ch, tap, buf ^ 1)
     const float* pP = smem + buf * BUF + (wm * PT * 32 + l31) * 32;
     const float* pW = smem + buf * BUF + (BM + wn * CT * 32 + l31) * 32;
-#define FOG(G) ((G) == 0 ? fo0 : (G) == 1 ? fo1 : (G) == 2 ? fo2 : fo3)
-#define PXF(G) *reinterpret_cast<const float4*>(pP + i * 1024 + FOG(G))
-#define WTF(G) *reinterpret_cast<const float4*>(pW + j * 1024 + FOG(G))
-    if (MM == MM_F16X3) {
-      SE3TN_MMA_SPLIT(PT, CT, PXF, WTF)
-    } else {
-      SE3TN_MMA_GROUP(PT, CT, PXF(0), WTF(0))
-      SE3TN_MMA_GROUP(PT, CT, PXF(1), WTF(1))
-      SE3TN_MMA_GROUP(PT, CT, PXF(2), WTF(2))
-      SE3TN_MMA_GROUP(PT, CT, PXF(3), WTF(3))
-    }
-#undef PXF
-#undef WTF
-#undef FOG
+    SE3TN_MMA_KSTEP_ROWS(MM, PT, CT)
     if (kt + 1 < KT) wait_dma_and_barrier();
   }
-#undef ISSUE_TILE
 
   int opix[PT];
   bool ok[PT];
@@ -442,7 +386,7 @@ template <int CIN, int STRIDE, int CT, int MM>
 __global__ __launch_bounds__(256, 2) void conv3x3_splitk_kernel(const ConvArgs a) {
   constexpr int BM = 128, BN = 64 * CT, PT = 2;
   constexpr int NCH = CIN / 32;
-  constexpr int WR = BN / 32;  // weight rows per staging thread
+  constexpr int RS = 32, PJ = BM / RS, WJ = BN / RS;  // rows staged per DMA step; pixel / weight rows per staging thread
   constexpr int BUF = (BM + BN) * 32;
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -464,73 +408,32 @@ __global__ __launch_bounds__(256, 2) void conv3x3_splitk_kernel(const ConvArgs a
   // K-steps (32-channel chunk, tap) are numbered ch * 9 + tap; slice sl takes KT consecutive ones (a.slices divides NCH * 9)
   const int KT = NCH * 9 / a.slices, ks0 = sl * KT;
 
+  // staging (lds_rows.h, mfma_common.h): thread t fills LDS slot (t & 7) of rows (t >> 3) + 32 j
   const int r0 = tid >> 3;
-  const int c4 = (tid & 7) ^ ((r0 >> 1) & 7);
-  unsigned pvoff[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int m = min(m0 + r0 + 32 * j, mlast);
-    const int n = m / HoWo, rem = m - n * HoWo;
-    const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-    pvoff[j] = (unsigned)((((n * Hp + STRIDE * ho) * Wp + STRIDE * wo) * a.in_ld + c4 * 4) * 4);
-  }
-  const unsigned wvoff = (unsigned)((r0 * 32 + c4 * 4) * 4);
+  const int c4 = lds_rows::slot_block(r0, tid & 7);
+  unsigned pvoff[PJ];
+  SE3TN_GATHER_PVOFF(STRIDE)
+  const unsigned wvoff = (unsigned)(lds_rows::stage_src(r0, tid & 7) * 4);
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
 
-#define ISSUE_TILE(CH, TAP, BUFI)                                                                    \
-  {                                                                                                  \
-    const int r_ = (TAP) / 3, s_ = (TAP) - r_ * 3;                                                   \
-    const float* pb_ = in + (size_t)(r_ * Wp + s_) * a.in_ld + (CH) * 32;                            \
-    const unsigned lb_ = lds0 + (unsigned)(((BUFI) * BUF + wid * 256) * 4);                          \
-    glds16<0>(pb_, pvoff[0], lb_);                                                                   \
-    glds16<0>(pb_, pvoff[1], lb_ + 4096);                                                            \
-    glds16<0>(pb_, pvoff[2], lb_ + 8192);                                                            \
-    glds16<0>(pb_, pvoff[3], lb_ + 12288);                                                           \
-    const float* tb_ = wgt + (size_t)((CH) * 9 + (TAP)) * (a.tiles_n * BN) * 32;                     \
-    _Pragma("unroll") for (int j = 0; j < WR; ++j)                                                   \
-        glds16<0>(tb_ + j * 1024, wvoff, lb_ + BM * 128 + j * 4096);                                 \
-  }
-
-  const int X = (l31 >> 1) & 7;
-  const int lo = (hh ^ (X & 1)) * 4, xk = X >> 1;
-  const int fo0 = ((0 ^ xk) << 3) + lo, fo1 = ((1 ^ xk) << 3) + lo, fo2 = ((2 ^ xk) << 3) + lo,
-            fo3 = ((3 ^ xk) << 3) + lo;
+  const lds_rows::LaneFrag fo = lds_rows::lane_frag(l31, hh);
 
   f32x16 acc[PT][CT];
-#pragma unroll
-  for (int i = 0; i < PT; ++i)
-#pragma unroll
-    for (int j = 0; j < CT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   int ch = ks0 / 9, tap = ks0 - ch * 9;
-  ISSUE_TILE(ch, tap, 0)
+  SE3TN_GATHER_ISSUE_TILE(ch, tap, 0)
   wait_dma_and_barrier();
 
   for (int kt = 0; kt < KT; ++kt) {
     const int buf = kt & 1;
     if (++tap == 9) { tap = 0; ++ch; }
-    if (kt + 1 < KT) ISSUE_TILE(ch, tap, buf ^ 1)
+    if (kt + 1 < KT) SE3TN_GATHER_ISSUE_TILE(ch, tap, buf ^ 1)
     const float* pP = smem + buf * BUF + (wm * PT * 32 + l31) * 32;
     const float* pW = smem + buf * BUF + (BM + wn * CT * 32 + l31) * 32;
-#define FOG(G) ((G) == 0 ? fo0 : (G) == 1 ? fo1 : (G) == 2 ? fo2 : fo3)
-#define PXF(G) *reinterpret_cast<const float4*>(pP + i * 1024 + FOG(G))
-#define WTF(G) *reinterpret_cast<const float4*>(pW + j * 1024 + FOG(G))
-    if (MM == MM_F16X3) {
-      SE3TN_MMA_SPLIT(PT, CT, PXF, WTF)
-    } else {
-      SE3TN_MMA_GROUP(PT, CT, PXF(0), WTF(0))
-      SE3TN_MMA_GROUP(PT, CT, PXF(1), WTF(1))
-      SE3TN_MMA_GROUP(PT, CT, PXF(2), WTF(2))
-      SE3TN_MMA_GROUP(PT, CT, PXF(3), WTF(3))
-    }
-#undef PXF
-#undef WTF
-#undef FOG
+    SE3TN_MMA_KSTEP_ROWS(MM, PT, CT)
     if (kt + 1 < KT) wait_dma_and_barrier();
   }
-#undef ISSUE_TILE
 
   // raw partial sums: part[slice][group][m][cout] for conv_reduce_kernel
   const int cout = a.tiles_n * BN;
@@ -548,16 +451,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_splitk_kernel(const ConvArgs a
             make_float4(acc[i][j][4 * q + 0], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
       }
   }
-}
-
-template <typename K>
-static hipError_t set_lds(K kern, size_t lds, PerDeviceOnce& once) {
-  bool* done = once.current();
-  if (done && *done) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess && done) *done = true;
-  return e;
 }
 
 template <int CIN, int WM, int WN, int PT, int CT, int SLABPX, int EPI, int MM = MM_F32, int OUTF = FMT_F32,

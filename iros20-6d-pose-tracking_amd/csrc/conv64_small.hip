@@ -13,8 +13,8 @@
 //     ahead of their MFMAs;
 //   * a 16-byte LDS read feeds four MFMAs: the lane quarter q holds k = 4q..4q+3 of a 16-channel group, MFMA m takes element m of both
 //     operands (a permutation of k inside the group -- the same on both sides);
-//   * LDS images are XOR-swizzled like the other kernels' (weights: 16-byte column ^ ((row >> 1) & 7), applied on the DMA source
-//     address; patch: column ^ (patch pixel & 7)): a fragment read puts at most two lanes of a 16-lane group on one bank group;
+//   * LDS images are XOR-swizzled like the other kernels' (weights: the row tile of lds_rows.h; the patch is NOT that layout:
+//     16 slots per pixel, column ^ (patch pixel & 7)): a fragment read puts at most two lanes of a 16-lane group on one bank group;
 //   * two accumulators (the two 16-channel groups of a K-step) are added at the end: 144 dependent MFMAs would wait on each other;
 //   * stored padding: the input carries its zero border, the patch is read without bounds logic; only interiors are stored.
 // Float32 only; the f16x3 mode keeps the split-K kernels.  Results differ from the split-K path in the last bits (another summation
@@ -156,14 +156,12 @@ __global__ __launch_bounds__(256, 1) void conv64_small_kernel(const ConvArgs a) 
     const unsigned voff = (unsigned)(((py * Wp + pxx) * a.in_ld + col * 4) * 4);
     glds16<0>(in, voff, lds0 + (unsigned)((j * 256 + wid * 64) * 16));
   }
-  // ... then the first weight tiles (the packed panels [chunk][tap][64 couts][32]: 8 KB each, row r, column (tid & 7) ^ ((r >> 1) & 7));
-  // the rest are requested from inside the K-steps
+  // ... then the first weight tiles (the packed panels [chunk][tap][64 couts][32]: 8 KB each, staged as lds_rows.h row tiles: thread
+  // -> row tid >> 3, slot tid & 7); the rest are requested from inside the K-steps
   C64Dma dma;
   {
-    const int r0 = tid >> 3;
-    const int c4 = (tid & 7) ^ ((r0 >> 1) & 7);
     dma.wgt = wgt;
-    dma.wvoff = (unsigned)((r0 * 32 + c4 * 4) * 4);
+    dma.wvoff = (unsigned)(lds_rows::stage_src(tid >> 3, tid & 7) * 4);
     dma.wl = lds0 + (unsigned)(C64_PATCH_FLOATS * 4 + wid * 1024);
   }
   c64_request_tile<0>(dma); c64_request_tile<1>(dma); c64_request_tile<2>(dma); c64_request_tile<3>(dma);
@@ -174,9 +172,10 @@ __global__ __launch_bounds__(256, 1) void conv64_small_kernel(const ConvArgs a) 
   f.pix = lane & 15;
   f.q = lane >> 4;
   {
-    const int row = wid * 16 + (lane & 15), sw = (row >> 1) & 7;
-    f.wrow_off[0] = row * 32 + ((f.q ^ sw) << 2);
-    f.wrow_off[1] = row * 32 + (((4 + f.q) ^ sw) << 2);
+    const int row = wid * 16 + (lane & 15);   // the 16x16x4 form: lane quarter q reads logical blocks q and 4 + q of its row
+    const int sw = lds_rows::row_key(row);
+    f.wrow_off[0] = row * 32 + lds_rows::key_off(sw, f.q);
+    f.wrow_off[1] = row * 32 + lds_rows::key_off(sw, 4 + f.q);
   }
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   C64Ops o0, o1;
@@ -200,13 +199,8 @@ hipError_t launch_conv64_small(const ConvArgs& a, int n, int epi, hipStream_t st
   auto k0 = pi ? conv64_small_kernel<0, true> : conv64_small_kernel<0, false>;
   auto k1 = pi ? conv64_small_kernel<1, true> : conv64_small_kernel<1, false>;
   if (pi && n > SMALL_MAX_IMG) return hipErrorInvalidValue;
-  bool* done = attr[(epi == 1 ? 1 : 0) + (pi ? 2 : 0)].current();
-  if (!(done && *done)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(epi == 1 ? k1 : k0), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)C64_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    if (done) *done = true;
-  }
+  hipError_t e = set_lds(epi == 1 ? k1 : k0, C64_LDS_BYTES, attr[(epi == 1 ? 1 : 0) + (pi ? 2 : 0)]);
+  if (e != hipSuccess) return e;
   const dim3 grid(121, n, a.groups);
   if (epi == 1) hipLaunchKernelGGL(k1, grid, dim3(256), C64_LDS_BYTES, st, a);
   else hipLaunchKernelGGL(k0, grid, dim3(256), C64_LDS_BYTES, st, a);

@@ -23,7 +23,7 @@
 //   * v_mfma_f32_32x32x2_f32, A operand = weights, B operand = pixels: wave w = pixels 32 w .. 32 w + 31 of the tile x the 32 couts;
 //     a 16-byte LDS read feeds four MFMAs (lane half h holds channels 8 g + 4 h .. + 3 of an 8-channel group, MFMA e takes element e
 //     of both operands); two accumulators (even / odd groups) are added at the end;
-//   * LDS images XOR-swizzled like the other kernels' (16-byte column ^ ((row >> 1) & 7), applied on the DMA source address).
+//   * LDS images are the swizzled row tiles of lds_rows.h (patch rows keyed by their pixel index, weight rows by their cout).
 // Float32 only (f16x3 keeps conv3x3_splitk_kernel).
 #include "mfma_common.h"
 
@@ -96,10 +96,10 @@ __device__ __forceinline__ void cs_request(const CsDma& x) {
       // patch: slot = 16-byte column (slot & 7) of patch pixel (slot >> 3); slots past the patch re-read its last pixel
       const int slot = r * 256 + x.tid;
       const int p = min(slot >> 3, x.PP - 1);
-      const int col = (slot & 7) ^ ((p >> 1) & 7);
+      const int col = (slot & 7) ^ SE3TN_ROW_KEY(p);   // = lds_rows::slot_block(p, slot & 7), as tokens (lds_rows.h)
       glds16<0>(x.in + c * 32, (unsigned)((p * x.in_ld + col * 4) * 4), x.lds0 + (unsigned)((c * G::CHUNK_FLOATS + (r * 256 + x.wid * 64) * 4) * 4));
     } else {
-      // weight tile: row tid >> 3, column (tid & 7) ^ ((row >> 1) & 7)
+      // weight tile: row tid >> 3, slot tid & 7 (x.wvoff)
       constexpr int tap = r - G::NB;
       glds16<0>(x.wgt + ((size_t)c * 9 + tap) * x.cout * 32, x.wvoff,
                 x.lds0 + (unsigned)((c * G::CHUNK_FLOATS + G::PATCH_FLOATS + tap * 1024 + x.wid * 256) * 4));
@@ -132,11 +132,11 @@ __device__ __forceinline__ void cs_load(const CsLane& f, CsFrag& fr) {
   const int pp = f.ppb + r * f.Wp + s;
   const float* px = f.smem + c * G::CHUNK_FLOATS + pp * 32;
   const float* wt = f.smem + c * G::CHUNK_FLOATS + G::PATCH_FLOATS + tap * 1024 + f.row * 32;
-  const int swp = (pp >> 1) & 7, sww = (f.row >> 1) & 7;
+  const int swp = lds_rows::row_key(pp), sww = lds_rows::row_key(f.row);   // lds_rows::frag_off(row, g, kh) of both rows
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
-    fr.x[g] = *reinterpret_cast<const float4*>(px + (((2 * g + f.kh) ^ swp) << 2));
-    fr.w[g] = *reinterpret_cast<const float4*>(wt + (((2 * g + f.kh) ^ sww) << 2));
+    fr.x[g] = *reinterpret_cast<const float4*>(px + lds_rows::key_off(swp, 2 * g + f.kh));
+    fr.w[g] = *reinterpret_cast<const float4*>(wt + lds_rows::key_off(sww, 2 * g + f.kh));
   }
 }
 
@@ -215,10 +215,7 @@ __global__ __launch_bounds__(256, 1) void conv_slices_small_kernel(const ConvArg
   CsDma dma;
   dma.in = in; dma.wgt = wgt; dma.lds0 = lds0;
   dma.tid = tid; dma.wid = wid; dma.PP = PP; dma.in_ld = a.in_ld; dma.cout = cout;
-  {
-    const int r0 = tid >> 3;
-    dma.wvoff = (unsigned)((r0 * 32 + (((tid & 7) ^ ((r0 >> 1) & 7)) << 2)) * 4);
-  }
+  dma.wvoff = (unsigned)(lds_rows::stage_src(tid >> 3, tid & 7) * 4);
   CsRequestRange<G, 0, G::AHEAD>::go(dma);
 
   CS_TRACE(1)
@@ -277,12 +274,8 @@ static hipError_t launch_cs(const ConvArgs& a, hipStream_t st) {
   if (pi && a.M / HW > SMALL_MAX_IMG) return hipErrorInvalidValue;
   auto kern = pi ? conv_slices_small_kernel<CHUNKS, STRIDE, PPMAX, WO, SLICES, NT, true>
                  : conv_slices_small_kernel<CHUNKS, STRIDE, PPMAX, WO, SLICES, NT, false>;
-  bool* done = attr[pi ? 1 : 0].current();
-  if (!(done && *done)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
-    if (e != hipSuccess) return e;
-    if (done) *done = true;
-  }
+  hipError_t e = set_lds(kern, G::LDS, attr[pi ? 1 : 0]);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(SLICES * NT, TPI * (a.M / HW), a.groups), dim3(256), G::LDS, st, a);
   return hipGetLastError();
 }

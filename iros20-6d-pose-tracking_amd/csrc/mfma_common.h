@@ -1,6 +1,7 @@
 // Device-side building blocks shared by the MFMA kernels (conv3x3_mfma.hip, wino_mfma.hip):
-// LDS-DMA issue, the f32 / f16x3 MFMA K-step macros, split-row access, epilogue math.
+// LDS-DMA issue, the f32 / f16x3 MFMA K-step macros on the swizzled row tiles of lds_rows.h, split-row access, epilogue math.
 #pragma once
+#include "lds_rows.h"
 #include "se3tn_internal.h"
 
 namespace se3tn {
@@ -15,10 +16,8 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 //            32 x f16 hi | 32 x f16 lo with x = hi + lo to 22 significant bits; the product is formed
 //            as hi*hi + hi*lo + lo*hi with three v_mfma_f32_32x32x16_f16 (f32 accumulate): 16/3 = 5.3x
 //            the f32 MFMA rate at f32-class error (the dropped lo*lo term is 2^-22 relative).
-//            A split row has the SAME size, 16-byte slot structure and swizzle as a float32 row:
-//            slots 0-3 = hi channels 0-31, slots 4-7 = lo, and slot 2 kb + hh (+4) is exactly the
-//            8-half MFMA operand of lane-half hh for 16-channel block kb -- i.e. the four 8-k groups
-//            of the f32 kernel ARE (hi kb0, hi kb1, lo kb0, lo kb1).
+//            A split row has the SAME size, 16-byte slot structure and swizzle as a float32 row (lds_rows.h):
+//            slot 2 kb + hh (+4) is exactly the 8-half MFMA operand of lane-half hh for 16-channel block kb.
 enum { MM_F32 = 0, MM_F16X3 = 1 };
 // tensor element formats of the epilogue (template parameters OUTF / RESF)
 enum { FMT_F32 = 0, FMT_SPLIT = 1 };
@@ -110,6 +109,65 @@ __device__ __forceinline__ void wait_dma_and_barrier() {
       _Pragma("unroll") for (int j = 0; j < CTN; ++j) _Pragma("unroll") for (int i = 0; i < PTN; ++i) \
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[kb + 2][j], ph_[kb][i], acc[i][j], 0, 0, 0); \
     }                                                                                                \
+  }
+
+// ---- the K-step on row tiles (lds_rows.h) ---------------------------------------------------------
+// One K-step (32 channels) in either arithmetic mode: PXF(G) / WTF(G) name the float4 fragment of 8-k group G (may use `i` / `j`).
+#define SE3TN_MMA_KSTEP(MM, PTN, CTN, PXF, WTF)                                                       \
+  if ((MM) == MM_F16X3) {                                                                            \
+    SE3TN_MMA_SPLIT(PTN, CTN, PXF, WTF)                                                              \
+  } else {                                                                                           \
+    SE3TN_MMA_GROUP(PTN, CTN, PXF(0), WTF(0))                                                        \
+    SE3TN_MMA_GROUP(PTN, CTN, PXF(1), WTF(1))                                                        \
+    SE3TN_MMA_GROUP(PTN, CTN, PXF(2), WTF(2))                                                        \
+    SE3TN_MMA_GROUP(PTN, CTN, PXF(3), WTF(3))                                                        \
+  }
+// The fragments of a wave's row tiles: `pP` / `pW` point at this lane's row (l31) of the wave's first 32-row pixel / weight block
+// (a multiple of 32 rows into the tile), blocks i / j follow 1024 floats apart, `fo` = lds_rows::lane_frag(l31, hh).
+#define SE3TN_ROWS_PXF(G) *reinterpret_cast<const float4*>(pP + i * 1024 + SE3TN_FRAG_OFF(fo, G))
+#define SE3TN_ROWS_WTF(G) *reinterpret_cast<const float4*>(pW + j * 1024 + SE3TN_FRAG_OFF(fo, G))
+// the whole K-step on pP / pW row tiles into acc[PTN][CTN]
+#define SE3TN_MMA_KSTEP_ROWS(MM, PTN, CTN) SE3TN_MMA_KSTEP(MM, PTN, CTN, SE3TN_ROWS_PXF, SE3TN_ROWS_WTF)
+
+template <int PT, int CT>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[PT][CT]) {
+#pragma unroll
+  for (int i = 0; i < PT; ++i)
+#pragma unroll
+    for (int j = 0; j < CT; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+
+// ---- per-tap gather of the 3x3 convs' row tiles (conv3x3_gather_s2_kernel, conv3x3_splitk_kernel) ----------------------
+// A workgroup stages RS rows per DMA step: thread t fills LDS slot (t & 7) of rows r0 + RS j, r0 = t >> 3, with channel block
+// c4 = lds_rows::slot_block(r0, t & 7) (RS % 16 == 0: one key for all of a thread's rows).  pvoff[j] = byte offset of that block
+// of pixel row m0 + r0 + RS j (clamped to the last row) under tap (0, 0): in padded coordinates tap (r, s) of output (ho, wo)
+// is input (STRIDE ho + r, STRIDE wo + s), so a tap is one scalar offset on the DMA base.
+// (A macro, like the K-step: as a function the compiler forms other address arithmetic.)  Names of the calling kernel: a, m0, r0,
+// c4, pvoff[PJ], Wp = a.W + 2, Hp = a.H + 2, HoWo = a.Ho * a.Wo, mlast = a.M - 1 and the constants RS, PJ.
+#define SE3TN_GATHER_PVOFF(STRIDE)                                                                   \
+  _Pragma("unroll") for (int j = 0; j < PJ; ++j) {                                                   \
+    const int m = min(m0 + r0 + RS * j, mlast);                                                      \
+    const int n = m / HoWo, rem = m - n * HoWo;                                                      \
+    const int ho = rem / a.Wo, wo = rem - ho * a.Wo;                                                 \
+    pvoff[j] = (unsigned)((((n * Hp + (STRIDE) * ho) * Wp + (STRIDE) * wo) * a.in_ld + c4 * 4) * 4); \
+  }
+// K-step (CH, TAP) into buffer BUFI = [BM pixel rows][BN weight rows]: PJ = 4 pixel pieces and WJ weight pieces of RS rows per
+// thread.  Names of the calling kernel: in, wgt, Wp, a, lds0, wid, pvoff[PJ], wvoff and the constants BM, BN, BUF, RS, PJ, WJ.
+#define SE3TN_GATHER_ISSUE_TILE(CH, TAP, BUFI)                                                       \
+  {                                                                                                  \
+    static_assert(PJ == 4 && PJ * RS == BM, "four pixel pieces per thread");                         \
+    const int r_ = (TAP) / 3, s_ = (TAP) - r_ * 3;                                                   \
+    const float* pb_ = in + (size_t)(r_ * Wp + s_) * a.in_ld + (CH) * 32;                            \
+    const unsigned lb_ = lds0 + (unsigned)(((BUFI) * BUF + wid * 256) * 4);                          \
+    glds16<0>(pb_, pvoff[0], lb_);                                                                   \
+    glds16<0>(pb_, pvoff[1], lb_ + RS * 128);                                                        \
+    glds16<0>(pb_, pvoff[2], lb_ + 2 * RS * 128);                                                    \
+    glds16<0>(pb_, pvoff[3], lb_ + 3 * RS * 128);                                                    \
+    const float* tb_ = wgt + (size_t)((CH) * 9 + (TAP)) * (a.tiles_n * BN) * 32;                     \
+    _Pragma("unroll") for (int j_ = 0; j_ < WJ; ++j_)                                                \
+        glds16<0>(tb_ + j_ * RS * 32, wvoff, lb_ + BM * 128 + j_ * RS * 128);                        \
   }
 
 // ---- split-row element access: 4 consecutive channels c..c+3 (c % 4 == 0) of pixel `pix` ---------

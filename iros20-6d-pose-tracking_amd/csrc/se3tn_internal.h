@@ -310,6 +310,16 @@ struct PerDeviceOnce {
     return &done[dev];
   }
 };
+// raises a kernel's dynamic-LDS limit to `lds` bytes, once per device; `once` belongs to that kernel (a function-local static)
+template <typename K>
+inline hipError_t set_lds(K kern, size_t lds, PerDeviceOnce& once) {
+  bool* done = once.current();
+  if (done && *done) return hipSuccess;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e == hipSuccess && done) *done = true;
+  return e;
+}
 
 // launchers (defined in the .hip files)
 // f16x3 split panels + per-cout scales of every conv / both stems from the bound float32 blob (kernels_misc.hip)

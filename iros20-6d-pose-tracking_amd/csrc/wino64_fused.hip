@@ -21,8 +21,8 @@
 //   at the end Y is staged through LDS: + bias (+ residual), ReLU, pixel-major float4 stores of the 2 x 2 outputs per tile.
 //
 // MFMA work: 16 x 2 x (128 x 64 x 32) MACs per workgroup = 2.13x less than direct (incl. the 7 unused rows).  Float32 throughout; rounding as
-// F(2x2) in wino_mfma.hip (1.5e-7 of the layer's largest activation).  Operand tiles use the same 128-byte rows, XOR swizzle and
-// fragment layout as conv3x3_mfma.hip / wino_mfma.hip.
+// F(2x2) in wino_mfma.hip (1.5e-7 of the layer's largest activation).  Operand tiles are the swizzled row tiles of lds_rows.h, as in
+// conv3x3_mfma.hip / wino_mfma.hip (here the V tile is written by the VALU, not by DMA: the staging side is a ds_write address).
 #include "mfma_common.h"
 
 namespace se3tn {
@@ -119,9 +119,9 @@ __global__ __launch_bounds__(512) void wino64_fused_kernel(const Wino64Args a) {
 
   // ---- DMA geometry ------------------------------------------------------------------------------------------------------
   // patch piece id = tid + 512 j (j < 9): pixel id >> 3 (row-major in the 24 x 24 patch), 16-byte slot id & 7 -> LDS linear
-  // U tile: thread -> row tid >> 3 (cout), LDS slot tid & 7 holds channel block (tid & 7) ^ ((row >> 1) & 7)
+  // U tile: thread -> row tid >> 3 (cout), LDS slot tid & 7 (staging side of lds_rows.h)
   const int ur = tid >> 3;
-  const unsigned uvoff = (unsigned)((ur * 32 + (((tid & 7) ^ ((ur >> 1) & 7)) << 2)) * 4);
+  const unsigned uvoff = (unsigned)(lds_rows::stage_src(ur, tid & 7) * 4);
 
 #define W64_ISSUE_PATCH(CH)                                                                                     \
   {                                                                                                            \
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(512) void wino64_fused_kernel(const Wino64Args a) {
     const int ttr = tt < W64_TILES * W64_TILES ? tt : W64_TILES * W64_TILES - 1;
     const int tty = ttr / W64_TILES, ttx = ttr - tty * W64_TILES;
     tpix[j] = ((2 * tty) * W64_PATCH + ttx) * 32 + tcb * 4;                 // float index of window pixel (0,0), this channel block
-    tdst[j] = tt * 32 + ((tcb ^ ((tt >> 1) & 7)) << 2);                       // swizzled operand row t
+    tdst[j] = tt * 32 + lds_rows::slot_off(tt, tcb);                          // swizzled operand row t: block tcb
   }
   // offsets / coefficients of frequency F's B^T entries (uniform: scalar registers)
 #define W64_BT(F)                                                                                               \
@@ -183,9 +183,7 @@ __global__ __launch_bounds__(512) void wino64_fused_kernel(const Wino64Args a) {
   }
 
   // ---- fragment offsets of the four 8-k groups of a step (as wino_gemm_kernel) ------------------------------------------------------
-  const int X = (l31 >> 1) & 7;
-  const int lo = (hh ^ (X & 1)) * 4, xk = X >> 1;
-  const int fo0 = ((0 ^ xk) << 3) + lo, fo1 = ((1 ^ xk) << 3) + lo, fo2 = ((2 ^ xk) << 3) + lo, fo3 = ((3 ^ xk) << 3) + lo;
+  const lds_rows::LaneFrag fo = lds_rows::lane_frag(l31, hh);
 
   float Y[16][4];   // Y[e][o]: accumulator element e (cout 8 (e >> 2) + 4 hh + (e & 3)) of output pixel o = 2 y + x of the tile
 #pragma unroll
@@ -238,14 +236,14 @@ __global__ __launch_bounds__(512) void wino64_fused_kernel(const Wino64Args a) {
       const float* pW = Ub + buf * W64_U_FLOATS + (cbk * 32 + l31) * 32;                                       \
       float pv_[16], wv_[16];                                                                                  \
       float d_[2][4][4], v_[2][4];   /* [task][window pixel | -][channel] */                                    \
-      *reinterpret_cast<float4*>(pv_ + 0) = *reinterpret_cast<const float4*>(pP + fo0);                         \
-      *reinterpret_cast<float4*>(wv_ + 0) = *reinterpret_cast<const float4*>(pW + fo0);                         \
-      *reinterpret_cast<float4*>(pv_ + 4) = *reinterpret_cast<const float4*>(pP + fo1);                         \
-      *reinterpret_cast<float4*>(wv_ + 4) = *reinterpret_cast<const float4*>(pW + fo1);                         \
-      *reinterpret_cast<float4*>(pv_ + 8) = *reinterpret_cast<const float4*>(pP + fo2);                         \
-      *reinterpret_cast<float4*>(wv_ + 8) = *reinterpret_cast<const float4*>(pW + fo2);                         \
-      *reinterpret_cast<float4*>(pv_ + 12) = *reinterpret_cast<const float4*>(pP + fo3);                        \
-      *reinterpret_cast<float4*>(wv_ + 12) = *reinterpret_cast<const float4*>(pW + fo3);                        \
+      *reinterpret_cast<float4*>(pv_ + 0) = *reinterpret_cast<const float4*>(pP + fo.o0);                         \
+      *reinterpret_cast<float4*>(wv_ + 0) = *reinterpret_cast<const float4*>(pW + fo.o0);                         \
+      *reinterpret_cast<float4*>(pv_ + 4) = *reinterpret_cast<const float4*>(pP + fo.o1);                         \
+      *reinterpret_cast<float4*>(wv_ + 4) = *reinterpret_cast<const float4*>(pW + fo.o1);                         \
+      *reinterpret_cast<float4*>(pv_ + 8) = *reinterpret_cast<const float4*>(pP + fo.o2);                         \
+      *reinterpret_cast<float4*>(wv_ + 8) = *reinterpret_cast<const float4*>(pW + fo.o2);                         \
+      *reinterpret_cast<float4*>(pv_ + 12) = *reinterpret_cast<const float4*>(pP + fo.o3);                        \
+      *reinterpret_cast<float4*>(wv_ + 12) = *reinterpret_cast<const float4*>(pW + fo.o3);                        \
       /* window pixels of frequency fn_ = (i, j): rows bt_r0/1(i), columns bt_r0/1(j) */                        \
       /* (step 15 of chunk 0 transforms a patch that is being replaced and the last step one nobody reads: harmless, branch-free) */ \
       constexpr int i_ = fn_ >> 2, j_ = fn_ & 3;                                                               \
@@ -359,14 +357,9 @@ hipError_t launch_wino64(const float* in, int in_ld, int in_gs, const float* U, 
   a.in_gs = in_gs; a.res_gs = res_gs; a.out_gs = out_gs; a.bias_gs = bias_gs; a.u_gs = u_gs;
   a.n = n; a.groups = groups;
   static PerDeviceOnce attr[2];
-  const void* kern = epi == 1 ? reinterpret_cast<const void*>(wino64_fused_kernel<1>) : reinterpret_cast<const void*>(wino64_fused_kernel<0>);
   const size_t lds = W64_LDS_BYTES;
-  bool* done = attr[epi == 1 ? 1 : 0].current();
-  if (!done || !*done) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (done) *done = true;
-  }
+  hipError_t e = epi == 1 ? set_lds(wino64_fused_kernel<1>, lds, attr[1]) : set_lds(wino64_fused_kernel<0>, lds, attr[0]);
+  if (e != hipSuccess) return e;
   const dim3 grid(n * 4 * groups);
   if (epi == 1) hipLaunchKernelGGL(wino64_fused_kernel<1>, grid, dim3(512), lds, st, a);
   else hipLaunchKernelGGL(wino64_fused_kernel<0>, grid, dim3(512), lds, st, a);

@@ -14,7 +14,7 @@
 // Three launches per convolution:
 //   wino_input_kernel   d ((m+2)^2 windows of the zero-bordered NHWC tensor) -> V[g][f][T][C]
 //   wino_gemm_kernel    (m+2)^2 x groups independent GEMMs; {128|96} x 128 tiles, 4 waves, 2 workgroups
-//                       per CU, operands LDS-DMA'd with the XOR swizzle / fragment layout of conv3x3_mfma.hip
+//                       per CU, operands LDS-DMA'd into the swizzled row tiles of lds_rows.h (as conv3x3_mfma.hip)
 //   wino_output_kernel  A^T M A + folded-BN bias (+ residual) + ReLU -> interior of the padded output
 // U = G g G^T is derived on the device in float64 (rounded once) from the packed direct weights when the
 // blob is uploaded / bound (wino_weight_kernel): the blob format and the host packer do not change.
@@ -414,13 +414,13 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs a) {
   const float* __restrict__ Ub = a.U + (size_t)g * a.u_gs + ((size_t)f * a.Cout + n0) * 32;
   const int mlast = a.T - 1;
 
-  // staging: thread t fills LDS slot (t & 7) of rows (t >> 3) + 32 j with channel block (t & 7) ^ ((row >> 1) & 7)
+  // staging (lds_rows.h): thread t fills LDS slot (t & 7) of rows (t >> 3) + 32 j
   const int r0 = tid >> 3;
-  const int c4 = (tid & 7) ^ ((r0 >> 1) & 7);
+  const int c4 = lds_rows::slot_block(r0, tid & 7);
   unsigned pvoff[BM / 32];
 #pragma unroll
   for (int j = 0; j < BM / 32; ++j) pvoff[j] = (unsigned)((min(m0 + r0 + 32 * j, mlast) * CIN + c4 * 4) * 4);
-  const unsigned wvoff = (unsigned)((r0 * 32 + c4 * 4) * 4);
+  const unsigned wvoff = (unsigned)(lds_rows::stage_src(r0, tid & 7) * 4);
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
 
 #define ISSUE_TILE(CH, BUFI)                                                                         \
@@ -433,18 +433,10 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs a) {
         glds16<0>(tb_ + 1024 * j_, wvoff, lb_ + BM * 128 + j_ * 4096);                               \
   }
 
-  const int X = (l31 >> 1) & 7;
-  const int lo = (hh ^ (X & 1)) * 4, xk = X >> 1;
-  const int fo0 = ((0 ^ xk) << 3) + lo, fo1 = ((1 ^ xk) << 3) + lo, fo2 = ((2 ^ xk) << 3) + lo,
-            fo3 = ((3 ^ xk) << 3) + lo;
+  const lds_rows::LaneFrag fo = lds_rows::lane_frag(l31, hh);
 
   f32x16 acc[PT][CT];
-#pragma unroll
-  for (int i = 0; i < PT; ++i)
-#pragma unroll
-    for (int j = 0; j < CT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
 #ifdef SE3TN_WG_TRACE
   unsigned long long t_start_ = 0;
@@ -467,20 +459,7 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(const WinoArgs a) {
     if (ch + 1 < NCH) ISSUE_TILE(ch + 1, buf ^ 1)
     const float* pP = smem + buf * BUF + (wm * PT * 32 + l31) * 32;
     const float* pW = smem + buf * BUF + (BM + wn * CT * 32 + l31) * 32;
-#define FOG(G) ((G) == 0 ? fo0 : (G) == 1 ? fo1 : (G) == 2 ? fo2 : fo3)
-#define PXF(G) *reinterpret_cast<const float4*>(pP + i * 1024 + FOG(G))
-#define WTF(G) *reinterpret_cast<const float4*>(pW + j * 1024 + FOG(G))
-    if (MM == MM_F16X3) {   // V and U are split rows (f16 hi | lo): hi*hi + hi*lo + lo*hi on the f16 matrix cores
-      SE3TN_MMA_SPLIT(PT, CT, PXF, WTF)
-    } else {
-      SE3TN_MMA_GROUP(PT, CT, PXF(0), WTF(0))
-      SE3TN_MMA_GROUP(PT, CT, PXF(1), WTF(1))
-      SE3TN_MMA_GROUP(PT, CT, PXF(2), WTF(2))
-      SE3TN_MMA_GROUP(PT, CT, PXF(3), WTF(3))
-    }
-#undef PXF
-#undef WTF
-#undef FOG
+    SE3TN_MMA_KSTEP_ROWS(MM, PT, CT)   // MM_F16X3: V and U are split rows (f16 hi | lo)
     if (ch + 1 < NCH) wait_dma_and_barrier();
   }
 #undef ISSUE_TILE
@@ -547,10 +526,10 @@ __global__ __launch_bounds__(512, 2) void wino_gemmp_kernel(const WinoArgs a, in
   const int panels = a.Cout / BN, mtiles = (a.T + BM - 1) / BM, tpp = panels * mtiles;
   const int mlast = a.T - 1;
 
-  // staging: thread t fills LDS slot (t & 7) of rows (t >> 3) + 64 j with channel block (t & 7) ^ ((row >> 1) & 7)
+  // staging (lds_rows.h): thread t fills LDS slot (t & 7) of rows (t >> 3) + 64 j
   const int r0 = tid >> 3;
-  const int c4 = (tid & 7) ^ ((r0 >> 1) & 7);
-  const unsigned wvoff = (unsigned)((r0 * 32 + c4 * 4) * 4);
+  const int c4 = lds_rows::slot_block(r0, tid & 7);
+  const unsigned wvoff = (unsigned)(lds_rows::stage_src(r0, tid & 7) * 4);
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
 
   // virtual tile -> (plane b, row tile, cout panel)
@@ -580,17 +559,10 @@ __global__ __launch_bounds__(512, 2) void wino_gemmp_kernel(const WinoArgs a, in
     _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) glds16<0>(tb_ + 2048 * j_, wvoff, lb_ + BM * 128 + j_ * 8192); \
   }
 
-  const int X = (l31 >> 1) & 7;
-  const int lo = (hh ^ (X & 1)) * 4, xk = X >> 1;
-  const int fo0 = ((0 ^ xk) << 3) + lo, fo1 = ((1 ^ xk) << 3) + lo, fo2 = ((2 ^ xk) << 3) + lo, fo3 = ((3 ^ xk) << 3) + lo;
+  const lds_rows::LaneFrag fo = lds_rows::lane_frag(l31, hh);
 
   f32x16 acc[PT][CT];
-#pragma unroll
-  for (int i = 0; i < PT; ++i)
-#pragma unroll
-    for (int j = 0; j < CT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   int v = blockIdx.x;
   if (v >= total_tiles) return;
@@ -623,16 +595,7 @@ __global__ __launch_bounds__(512, 2) void wino_gemmp_kernel(const WinoArgs a, in
       GP_STAMP(kstep_, 1)
       const float* pP = smem + buf * BUF + (wm * PT * 32 + l31) * 32;
       const float* pW = smem + buf * BUF + (BM + wn * CT * 32 + l31) * 32;
-#define FOG(G) ((G) == 0 ? fo0 : (G) == 1 ? fo1 : (G) == 2 ? fo2 : fo3)
-#define PXF(G) *reinterpret_cast<const float4*>(pP + i * 1024 + FOG(G))
-#define WTF(G) *reinterpret_cast<const float4*>(pW + j * 1024 + FOG(G))
-      SE3TN_MMA_GROUP(PT, CT, PXF(0), WTF(0))
-      SE3TN_MMA_GROUP(PT, CT, PXF(1), WTF(1))
-      SE3TN_MMA_GROUP(PT, CT, PXF(2), WTF(2))
-      SE3TN_MMA_GROUP(PT, CT, PXF(3), WTF(3))
-#undef PXF
-#undef WTF
-#undef FOG
+      SE3TN_MMA_KSTEP_ROWS(MM_F32, PT, CT)
       GP_STAMP(kstep_, 2)
       if (ch + 1 < NCH || more) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -950,13 +913,8 @@ static hipError_t launch_gemm(const WinoArgs& a, hipStream_t st) {
   auto kern = wino_gemm_kernel<CIN, WM, WN, PT, CT, MM>;
   constexpr int BM = WM * PT * 32, BN = WN * CT * 32;
   const size_t lds = 2 * (BM + BN) * 32 * sizeof(float);
-  bool* done = attr.current();
-  if (!done || !*done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (done) *done = true;
-  }
+  hipError_t e = set_lds(kern, lds, attr);
+  if (e != hipSuccess) return e;
   const int grid = (a.Cout / BN) * ((a.T + BM - 1) / BM) * a.groups * a.nf;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
@@ -967,12 +925,8 @@ static hipError_t launch_gemmp(const WinoArgs& a, int total_tiles, int grid, hip
   static PerDeviceOnce attr;
   auto kern = wino_gemmp_kernel<CIN>;
   const size_t lds = 2 * (128 + 256) * 32 * sizeof(float);
-  bool* done = attr.current();
-  if (!done || !*done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (done) *done = true;
-  }
+  hipError_t e = set_lds(kern, lds, attr);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, total_tiles);
   return hipGetLastError();
 }
@@ -1014,12 +968,8 @@ static hipError_t launch_mid(const WinoArgs& a, float* keep, hipStream_t st) {
   constexpr size_t lds = (size_t)HP * HP * CS * sizeof(float);
   static PerDeviceOnce attr;
   auto kern = wino_mid_kernel<M, TH, CS, VEC, SP>;
-  bool* done = attr.current();
-  if (!done || !*done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (done) *done = true;
-  }
+  hipError_t e = set_lds(kern, lds, attr);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(a.n, a.C / CS, a.groups), dim3(THREADS), lds, st, a, keep);
   return hipGetLastError();
 }

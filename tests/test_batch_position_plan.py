@@ -27,7 +27,7 @@ def cdiv(a, b):
 
 # ---- the selection rules -----------------------------------------------------------------------------------------------------------
 def pool_rows(n):
-    """csrc/stem7x7_mfma.hip:362 pool_rows: the longest strip that still gives 256 workgroups"""
+    """csrc/stem7x7_mfma.hip:355 pool_rows: the longest strip that still gives 256 workgroups"""
     for r in (44, 22, 11, 4, 2, 1):
         if n * (S2 // r) >= 256:
             return r
@@ -35,12 +35,12 @@ def pool_rows(n):
 
 
 def pool_remap(n):
-    """csrc/stem7x7_mfma.hip:316 maxpool3x3s2_kernel: images below n / 8 * 8 are remapped image = 8 k + xcd, the n % 8 behind them not"""
+    """csrc/stem7x7_mfma.hip:309 maxpool3x3s2_kernel: images below n / 8 * 8 are remapped image = 8 k + xcd, the n % 8 behind them not"""
     return "tail images" if n % 8 else "all remapped"
 
 
 def stem_grid(n):
-    """csrc/stem7x7_mfma.hip:276 launch_stem: min(31 n, 128) persistent workgroups per branch"""
+    """csrc/stem7x7_mfma.hip:269 launch_stem: min(31 n, 128) persistent workgroups per branch"""
     return min(31 * n, 128)
 
 
@@ -120,7 +120,7 @@ def wino_gemm(cfg, n, which):
 
 
 def ragged(cfg, n, which):
-    """the last row tile of a Winograd GEMM is cut (csrc/wino_mfma.hip:670 mlast) | fits"""
+    """the last row tile of a Winograd GEMM is cut (csrc/wino_mfma.hip:633 mlast) | fits"""
     t = tile(cfg, n, which)
     th = cdiv((S3, S4)[which], t)
     rows = 96 if wino_gemm(cfg, n, which).endswith("96 rows") else 128

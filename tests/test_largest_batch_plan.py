@@ -132,7 +132,7 @@ def gemm_kind(cfg, n, which):
 
 
 def gemm_grid(cfg, n, which):
-    """csrc/wino_mfma.hip:966 (Cout / 128) ceil(T / BM) groups nf | csrc/infer_plan.h:268 the persistent kernel's (cus / 8) 8"""
+    """csrc/wino_mfma.hip:924 (Cout / 128) ceil(T / BM) groups nf | csrc/infer_plan.h:268 the persistent kernel's (cus / 8) 8"""
     t, kind = block_tile(cfg, n, which), gemm_kind(cfg, n, which)
     if "persistent" in kind:
         return 256
@@ -166,9 +166,9 @@ gather4 = lambda name: lambda cfg, n: rule(cfg, name)(n) == "gather 4"
 # (sv_even / sv_odd, wvoff, lvoff, uvoff, the fused trunk's patch offsets) are relative to a tile and do not grow with n: no entry.
 AUDIT = [
     # the one the limit comes from
-    ("gather pvoff[] on q64 (convAB1)", "csrc/conv3x3_mfma.hip:314", "int", always, lambda cfg, n: gather_pvoff(n, S2, 128)),
-    ("gather pvoff[] on ab (heads conv1)", "csrc/conv3x3_mfma.hip:314", "int", always, lambda cfg, n: gather_pvoff(n, S3, 256)),
-    ("split-K pvoff[] / conv_reduce total", "csrc/conv3x3_mfma.hip:475, :606", "never", any_split_k, lambda cfg, n: n),
+    ("gather pvoff[] on q64 (convAB1)", "csrc/mfma_common.h:154", "int", always, lambda cfg, n: gather_pvoff(n, S2, 128)),
+    ("gather pvoff[] on ab (heads conv1)", "csrc/mfma_common.h:154", "int", always, lambda cfg, n: gather_pvoff(n, S3, 256)),
+    ("split-K pvoff[] / conv_reduce total", "csrc/mfma_common.h:154; csrc/conv3x3_mfma.hip:499", "never", any_split_k, lambda cfg, n: n),
     # host: the counts the argument blocks carry as int
     ("ConvArgs.M, trunk", "csrc/api.cpp:820", "int", always, lambda cfg, n: n * S2 * S2),
     ("WinoArgs.T, 256-channel block", "csrc/api.cpp:840", "int", fused_block(0), lambda cfg, n: gemm_T(cfg, n, 0)),
@@ -176,21 +176,21 @@ AUDIT = [
     ("plan_gemm tiles, 256-channel block", "csrc/infer_plan.h:260", "int", fused_block(0), lambda cfg, n: gemm_tiles(cfg, n, 0)),
     ("plan_gemm tiles, heads", "csrc/infer_plan.h:260", "int", fused_block(1), lambda cfg, n: gemm_tiles(cfg, n, 1)),
     # pixel indices formed in int (multiplied by the row length in size_t afterwards)
-    ("padded_index, 46 x 46 maps", "csrc/mfma_common.h:144-147", "int", always, lambda cfg, n: n * (S2 + 2) ** 2),
-    ("slab lo + 8 j pixels / ntiles", "csrc/conv3x3_mfma.hip:109, :122-123", "int", trunk_slab, lambda cfg, n: n * (S2 + 2) ** 2 + 8 * 58),
-    ("stem ntiles", "csrc/stem7x7_mfma.hip:88, :264", "int", always, lambda cfg, n: n * 31),
-    ("max-pool padded row (img 46 + po + 1)", "csrc/stem7x7_mfma.hip:325", "int", always, lambda cfg, n: n * (S2 + 2)),
-    ("wino64 patch row (img 46 + y0)", "csrc/wino64_fused.hip:116, :339", "int", trunk_fused, lambda cfg, n: n * (S2 + 2)),
-    ("Winograd pixel (n Hp + Y) Wp + X, 24 x 24", "csrc/wino_mfma.hip:191, :219, :288, :329, :750", "int", fused_block(0),
+    ("padded_index, 46 x 46 maps", "csrc/mfma_common.h:202-205", "int", always, lambda cfg, n: n * (S2 + 2) ** 2),
+    ("slab lo + 8 j pixels / ntiles", "csrc/conv3x3_mfma.hip:108, :121-122", "int", trunk_slab, lambda cfg, n: n * (S2 + 2) ** 2 + 8 * 58),
+    ("stem ntiles", "csrc/stem7x7_mfma.hip:88, :257", "int", always, lambda cfg, n: n * 31),
+    ("max-pool padded row (img 46 + po + 1)", "csrc/stem7x7_mfma.hip:318", "int", always, lambda cfg, n: n * (S2 + 2)),
+    ("wino64 patch row (img 46 + y0)", "csrc/wino64_fused.hip:116, :337", "int", trunk_fused, lambda cfg, n: n * (S2 + 2)),
+    ("Winograd pixel (n Hp + Y) Wp + X, 24 x 24", "csrc/wino_mfma.hip:191, :219, :288, :329, :713", "int", fused_block(0),
      lambda cfg, n: n * (S3 + 2) ** 2 + 8 * (S3 + 2)),
-    ("Winograd pixel (n Hp + Y) Wp + X, 13 x 13", "csrc/wino_mfma.hip:191, :219, :841, :871", "int", fused_block(1),
+    ("Winograd pixel (n Hp + Y) Wp + X, 13 x 13", "csrc/wino_mfma.hip:191, :219, :804, :834", "int", fused_block(1),
      lambda cfg, n: n * (S4 + 2) ** 2 + 8 * (S4 + 2)),
-    ("mid / tail tile t = n NT + tile", "csrc/wino_mfma.hip:700, :828", "int", fused_block(0), lambda cfg, n: gemm_T(cfg, n, 0)),
-    ("fc_finish logits i 6 + k", "csrc/wino_mfma.hip:925, :935", "int", fused_block(1), lambda cfg, n: 6 * (cdiv(n, 10) * 10)),
+    ("mid / tail tile t = n NT + tile", "csrc/wino_mfma.hip:663, :791", "int", fused_block(0), lambda cfg, n: gemm_T(cfg, n, 0)),
+    ("fc_finish logits i 6 + k", "csrc/wino_mfma.hip:888, :898", "int", fused_block(1), lambda cfg, n: 6 * (cdiv(n, 10) * 10)),
     # DMA byte offsets from the base of ONE plane of V
-    ("GEMM pvoff[], 256-channel block", "csrc/wino_mfma.hip:422, :572", "int", fused_block(0),
+    ("GEMM pvoff[], 256-channel block", "csrc/wino_mfma.hip:422, :551", "int", fused_block(0),
      lambda cfg, n: ((gemm_T(cfg, n, 0) - 1) * 256 + 7 * 4) * 4),
-    ("GEMM pvoff[], heads", "csrc/wino_mfma.hip:422, :572", "int", fused_block(1), lambda cfg, n: ((gemm_T(cfg, n, 1) - 1) * 512 + 7 * 4) * 4),
+    ("GEMM pvoff[], heads", "csrc/wino_mfma.hip:422, :551", "int", fused_block(1), lambda cfg, n: ((gemm_T(cfg, n, 1) - 1) * 512 + 7 * 4) * 4),
     # element counts of the one-thread-per-element passes
     ("to_padded_input total / idx", "csrc/kernels_misc.hip:33, :55", "int", always, lambda cfg, n: cdiv(n * 176 * 176, 256) * 256),
     ("padded_nhwc_to_nchw total / idx (se3tn_get_feature)", "csrc/kernels_misc.hip:414, :430; csrc/api.cpp:1048", "int", always,
@@ -199,23 +199,23 @@ AUDIT = [
      lambda cfg, n: transform_threads(cfg, n, 0)),
     ("Winograd transform idx, heads", "csrc/wino_mfma.hip:170-171, :269-270", "int", fused_block(1), lambda cfg, n: transform_threads(cfg, n, 1)),
     # grids
-    ("stem grid", "csrc/stem7x7_mfma.hip:265-267", "grid x", always, lambda cfg, n: 2 * min(31 * n, 128)),
-    ("max-pool grid", "csrc/stem7x7_mfma.hip:362", "grid x", always, lambda cfg, n: n * (S2 // PLAN.pool_rows(n))),
-    ("fused trunk grid", "csrc/wino64_fused.hip:370", "grid x", trunk_fused, lambda cfg, n: n * 4 * 2),
-    ("slab grid", "csrc/conv3x3_mfma.hip:573-577", "grid x", trunk_slab, lambda cfg, n: min(cdiv(n * S2 * S2, 256) * 2, 256)),
-    ("gather grid, convAB1", "csrc/conv3x3_mfma.hip:589-590", "grid x", always,
+    ("stem grid", "csrc/stem7x7_mfma.hip:258-260", "grid x", always, lambda cfg, n: 2 * min(31 * n, 128)),
+    ("max-pool grid", "csrc/stem7x7_mfma.hip:355", "grid x", always, lambda cfg, n: n * (S2 // PLAN.pool_rows(n))),
+    ("fused trunk grid", "csrc/wino64_fused.hip:363", "grid x", trunk_fused, lambda cfg, n: n * 4 * 2),
+    ("slab grid", "csrc/conv3x3_mfma.hip:466-470", "grid x", trunk_slab, lambda cfg, n: min(cdiv(n * S2 * S2, 256) * 2, 256)),
+    ("gather grid, convAB1", "csrc/conv3x3_mfma.hip:482-483", "grid x", always,
      lambda cfg, n: cdiv(n * S3 * S3, 128 if gather4("convAB1 s2")(cfg, n) else 256) * 2),
-    ("gather grid, heads conv1", "csrc/conv3x3_mfma.hip:589-590", "grid x", always,
+    ("gather grid, heads conv1", "csrc/conv3x3_mfma.hip:482-483", "grid x", always,
      lambda cfg, n: cdiv(n * S4 * S4, 128 if gather4("heads conv1 s2")(cfg, n) else 256) * 8),
-    ("GEMM grid, 256-channel block", "csrc/wino_mfma.hip:966; csrc/infer_plan.h:268", "grid x", fused_block(0), lambda cfg, n: gemm_grid(cfg, n, 0)),
-    ("GEMM grid, heads", "csrc/wino_mfma.hip:966; csrc/infer_plan.h:268", "grid x", fused_block(1), lambda cfg, n: gemm_grid(cfg, n, 1)),
-    ("Winograd transform grid x", "csrc/wino_mfma.hip:1052-1056, :1084-1088", "grid x", fused_block(1),
+    ("GEMM grid, 256-channel block", "csrc/wino_mfma.hip:924; csrc/infer_plan.h:268", "grid x", fused_block(0), lambda cfg, n: gemm_grid(cfg, n, 0)),
+    ("GEMM grid, heads", "csrc/wino_mfma.hip:924; csrc/infer_plan.h:268", "grid x", fused_block(1), lambda cfg, n: gemm_grid(cfg, n, 1)),
+    ("Winograd transform grid x", "csrc/wino_mfma.hip:1002-1006, :1034-1038", "grid x", fused_block(1),
      lambda cfg, n: max(transform_threads(cfg, n, 0), transform_threads(cfg, n, 1)) // 256),
-    ("Winograd transform threads", "csrc/wino_mfma.hip:1052-1056, :1084-1088", "threads", fused_block(1),
+    ("Winograd transform threads", "csrc/wino_mfma.hip:1002-1006, :1034-1038", "threads", fused_block(1),
      lambda cfg, n: max(transform_threads(cfg, n, 0), transform_threads(cfg, n, 1))),
-    ("mid / tail grid x = n", "csrc/wino_mfma.hip:1029, :1075", "grid x", fused_block(1), lambda cfg, n: n),
-    ("mid grid y = C / CS, z = groups", "csrc/wino_mfma.hip:1029 (CS >= 16)", "grid yz", fused_block(1), lambda cfg, n: 512 // 16),
-    ("fc_finish grid", "csrc/wino_mfma.hip:1081", "grid x", fused_block(1), lambda cfg, n: cdiv(n, 10)),
+    ("mid / tail grid x = n", "csrc/wino_mfma.hip:979, :1025", "grid x", fused_block(1), lambda cfg, n: n),
+    ("mid grid y = C / CS, z = groups", "csrc/wino_mfma.hip:979 (CS >= 16)", "grid yz", fused_block(1), lambda cfg, n: 512 // 16),
+    ("fc_finish grid", "csrc/wino_mfma.hip:1031", "grid x", fused_block(1), lambda cfg, n: cdiv(n, 10)),
     ("tail grid", "csrc/kernels_misc.hip:261", "grid x", plain_tail, lambda cfg, n: n * 16),
     ("to_padded_input grid", "csrc/kernels_misc.hip:56", "grid x", always, lambda cfg, n: cdiv(n * 176 * 176, 256)),
     ("padded_nhwc_to_nchw grid", "csrc/kernels_misc.hip:431", "grid x", always, lambda cfg, n: cdiv(n * S3 * S3 * 256, 256)),
