@@ -900,6 +900,50 @@ int se3tn_align_poses_host(se3tn_ctx* ctx, const se3tn_points* points, int n, co
                            const double K[9], const se3tn_align_params* params, double* poses_out, se3tn_align_rec* rec_out,
                            int64_t* sums_out, void* stream);
 
+/* ---- the alignment AMONG tracked objects: points hidden by the composed scene are not paired ------------------------------------ */
+/* se3tn_align_poses pairs every facing point with whatever the sensor saw within gate_mm of it.  Among other objects that pulls a
+ * hypothesis onto a neighbour's face (the surface is already CLAIMED by a tracked object) or tilts it onto an object lying on the
+ * lost one.  With `scene` [H,W] uint16 millimetres, the composed depth of the tracked objects as se3tn_scene_fit(..., scene_dev)
+ * writes it (0 where there is none), the rule of se3tn_align_poses gains ONE step, for a FACING point whose pixel is in frame,
+ * before d is looked at (q, c, n', f, uf, vf, m = rint(c.z * 1000.0) exactly as stated there):
+ *     s = scene[vf, uf]
+ *     hidden     100 < s < 2000 && s <= m + scene_tol_mm                   the predicate of se3tn_score_pose_grid_scene, on doubles
+ *                a hidden point enters hidden_pts and NOTHING else past facing_pts: it is not paired whatever d is and adds to none
+ *                of the 28 sums
+ *     otherwise  d = depth[vf, uf]; seen, paired, o, r, J, fx                exactly as se3tn_align_poses states them
+ * scene_tol_mm, [1, 65535], is the tolerance of the hidden verdict -- the tol_mm of se3tn_score_pose_grid_scene -- and independent
+ * of params->gate_mm.  Sums, solve, update and stop rules are those of se3tn_align_poses.
+ * The record keeps the 40 bytes and the field order of se3tn_align_rec; the word at offset 28, _reserved there, is hidden_pts: the
+ * hidden points at the last evaluated pose.  Always pairs + hidden_pts <= facing_pts.  With an all-zero scene every byte of pose,
+ * record and sums equals what se3tn_align_poses writes (hidden_pts = 0 = _reserved).  Guarantees (a)-(c) of se3tn_align_poses hold
+ * with (scene, scene_tol_mm) among what a pose's output depends on (tests/scene_align_oracle.py;
+ * tests/c_abi/pose_align_scene_check.cpp runs the statements on the host).  Cost: that of se3tn_align_poses, a third count and a
+ * second 2-byte gather per facing in-frame point, at the pixel the first one reads. */
+typedef struct se3tn_scene_align_rec {   /* 40 bytes: se3tn_align_rec with the word at offset 28 in use */
+  uint32_t iterations;   /* iterations evaluated                                       */
+  uint32_t status;       /* SE3TN_ALIGN_*                                              */
+  uint32_t pairs;        /* paired points at the last evaluated pose                   */
+  uint32_t facing_pts;   /* facing points at the last evaluated pose                   */
+  int64_t sum_r2;        /* S_e of the last evaluated pose (metres^2 * 2^32)           */
+  uint32_t pairs0;       /* paired points at the first evaluated pose                  */
+  uint32_t hidden_pts;   /* hidden points at the last evaluated pose                   */
+  int64_t sum_r2_0;      /* S_e of the first evaluated pose                            */
+} se3tn_scene_align_rec; /* pairs + hidden_pts <= facing_pts                           */
+/* The device entry: the arguments of se3tn_align_poses, scene_dev (device uint16 [H,W]: what se3tn_scene_fit(..., scene_dev) and
+ * se3tn_last_search_scene hand out) and scene_tol_mm.  Stream-ordered, capturable, allocates nothing, no atomics on global memory.
+ * Refusals as se3tn_align_poses, in the same order, a NULL scene_dev among the NULL pointers, and scene_tol_mm outside [1, 65535]
+ * (SE3TN_E_ARG, the message names scene_tol_mm). */
+int se3tn_align_poses_scene(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses_dev, const uint16_t* depth_dev,
+                            const uint16_t* scene_dev, int H, int W, const double K[9], const se3tn_align_params* params,
+                            int scene_tol_mm, double* poses_out_dev, se3tn_scene_align_rec* rec_dev, int64_t* sums_dev, void* stream);
+/* The same from HOST memory: poses, depth, poses_out, rec_out, sums_out as se3tn_align_poses_host, scene HOST uint16 [H,W].  The
+ * staging is [poses | depth | pad | scene | pad | poses_out | rec | sums]: one upload of [poses | depth | pad | scene], one launch, one
+ * read-back.  SYNCHRONOUS on `stream`, refused inside a stream capture (SE3TN_E_STATE); it shares the pinned staging of the pose
+ * family.  Refusals as se3tn_align_poses_host and those above. */
+int se3tn_align_poses_scene_host(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses, const uint16_t* depth,
+                                 const uint16_t* scene, int H, int W, const double K[9], const se3tn_align_params* params,
+                                 int scene_tol_mm, double* poses_out, se3tn_scene_align_rec* rec_out, int64_t* sums_out, void* stream);
+
 /* ---- host-side pieces of the path (pure CPU, float64, as the reference computes them) ----- */
 /* Utils.py:302-316 compute_bbox with scale (1000,1000,1000): pose row-major 4x4 (metres), K
  * row-major 3x3, width in mm; out_vu[8] = 4 x (v,u) int32, np.round (half-to-even). */

@@ -75,6 +75,12 @@ class AlignRec(C.Structure):
                 ("sum_r2", C.c_int64), ("pairs0", C.c_uint32), ("_reserved", C.c_uint32), ("sum_r2_0", C.c_int64)]
 
 
+class SceneAlignRec(C.Structure):
+    """se3tn_scene_align_rec (include/se3tracknet.h): what became of one pose of se3tn_align_poses_scene."""
+    _fields_ = [("iterations", C.c_uint32), ("status", C.c_uint32), ("pairs", C.c_uint32), ("facing_pts", C.c_uint32),
+                ("sum_r2", C.c_int64), ("pairs0", C.c_uint32), ("hidden_pts", C.c_uint32), ("sum_r2_0", C.c_int64)]
+
+
 class PointFit(C.Structure):
     """se3tn_point_fit (include/se3tracknet.h): the record of one candidate pose of se3tn_score_poses."""
     _fields_ = [(k, C.c_uint32) for k in ("points", "in_frame_pts", "seen_pts", "inlier_pts", "front_pts", "behind_pts", "tol_mm",
@@ -117,6 +123,9 @@ assert SCENE_FIT_DTYPE.itemsize == C.sizeof(SceneFit) == 48 and C.sizeof(SceneLa
 ALIGN_REC_DTYPE = _np.dtype([("iterations", "<u4"), ("status", "<u4"), ("pairs", "<u4"), ("facing_pts", "<u4"), ("sum_r2", "<i8"),
                              ("pairs0", "<u4"), ("_reserved", "<u4"), ("sum_r2_0", "<i8")])
 assert ALIGN_REC_DTYPE.itemsize == C.sizeof(AlignRec) == 40 and C.sizeof(AlignParams) == 32
+# se3tn_scene_align_rec: the same 40 bytes with the word at offset 28 in use (hidden_pts)
+SCENE_ALIGN_REC_DTYPE = _np.dtype([(k if k != "_reserved" else "hidden_pts", ALIGN_REC_DTYPE.fields[k][0]) for k in ALIGN_REC_DTYPE.names])
+assert SCENE_ALIGN_REC_DTYPE.itemsize == C.sizeof(SceneAlignRec) == 40 and SCENE_ALIGN_REC_DTYPE.fields["hidden_pts"][1] == 28
 
 
 _SIGS = {
@@ -231,6 +240,11 @@ _SIGS = {
                                     C.POINTER(AlignParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_align_poses_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                          C.POINTER(AlignParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_align_poses_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.POINTER(C.c_double), C.POINTER(AlignParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_align_poses_scene_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                               C.POINTER(C.c_double), C.POINTER(AlignParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     "se3tn_compute_bbox": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(C.c_int32)]),
     "se3tn_pose_update_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float),

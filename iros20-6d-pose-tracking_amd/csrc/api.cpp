@@ -1928,8 +1928,9 @@ int se3tn_search_pose_grid_host(se3tn_ctx* c, const se3tn_points* p, int n_rot, 
 // ---- n pose hypotheses aligned to one depth frame: point-to-plane steps, all iterations in one launch ----------------------------------
 // NULL pointers first, then the numbers, then the context and the handle (which is not read before the context is known to have a
 // device): every refusal has its own message, on a host-only context too
+// scene_tol_mm: NULL for the plain entry points, the hidden verdict's tolerance for the scene-aware ones
 static int pose_align_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, const se3tn_points* p, int n, int H, int W,
-                            const se3tn_align_params* q) {
+                            const se3tn_align_params* q, const int* scene_tol_mm = nullptr) {
   const std::string w(who);
   if (!c || !ok_ptrs || !p || !q) return null_argument(who);
   if (int rc = count_check(who, n, PA_MAX_POSES, "SE3TN_POSE_ALIGN_MAX_POSES")) return rc;
@@ -1942,16 +1943,19 @@ static int pose_align_check(const char* who, const se3tn_ctx* c, bool ok_ptrs, c
   if (q->_reserved != 0) return fail(SE3TN_E_ARG, w + ": params._reserved = " + std::to_string(q->_reserved) + " is not 0");
   if (!(q->damping >= 0.0) || !std::isfinite(q->damping)) return fail(SE3TN_E_ARG, w + ": damping is negative or not finite");
   if (!(q->stop >= 0.0) || !std::isfinite(q->stop)) return fail(SE3TN_E_ARG, w + ": stop is negative or not finite");
+  if (scene_tol_mm)
+    if (int rc = mm_check(who, "scene_tol_mm", *scene_tol_mm)) return rc;
   if (int rc = frame_check(who, H, W)) return rc;
   if (int rc = device_check(who, c, "align")) return rc;
   if (int rc = same_device_check(who, c, p)) return rc;
   return normals_check(who, p, "");
 }
 static PoseAlignArgs pose_align_args(const se3tn_points* p, const double* poses, const uint16_t* depth, int H, int W, const double K[9],
-                                     const se3tn_align_params* q, double* poses_out, se3tn_align_rec* rec, int64_t* sums) {
+                                     const se3tn_align_params* q, double* poses_out, se3tn_align_rec* rec, int64_t* sums,
+                                     const uint16_t* scene = nullptr, int scene_tol_mm = 0) {
   PoseAlignArgs a;
   a.pts = p->xyz.get(); a.nrm = p->nrm.get(); a.P = p->P; a.poses = poses; a.depth = depth; a.H = H; a.W = W; a.p = *q;
-  a.poses_out = poses_out; a.rec = rec; a.sums = sums;
+  a.poses_out = poses_out; a.rec = rec; a.sums = sums; a.scene = scene; a.scene_tol = scene_tol_mm;
   for (int i = 0; i < 9; ++i) a.K[i] = K[i];
   return a;
 }
@@ -1985,6 +1989,45 @@ int se3tn_align_poses_host(se3tn_ctx* c, const se3tn_points* p, int n, const dou
   if (int rc = sc.finish(s.poses_out, s.readback_bytes)) return rc;
   std::memcpy(poses_out, sc.h + s.poses_out, sizeof(double) * 16 * (size_t)n);
   std::memcpy(rec_out, sc.h + s.rec, sizeof(se3tn_align_rec) * (size_t)n);
+  if (sums_out) std::memcpy(sums_out, sc.h + s.sums, sizeof(int64_t) * SE3TN_POSE_ALIGN_SUMS * (size_t)n);
+  return SE3TN_OK;
+}
+
+// ---- the alignment among tracked objects: points hidden by the composed scene are not paired --------------------------------------------
+// (the kernel writes se3tn_scene_align_rec records through PoseAlignArgs::rec: pose_align_math.h holds the two layouts equal)
+int se3tn_align_poses_scene(se3tn_ctx* c, const se3tn_points* p, int n, const double* poses_dev, const uint16_t* depth_dev,
+                            const uint16_t* scene_dev, int H, int W, const double K[9], const se3tn_align_params* params, int scene_tol_mm,
+                            double* poses_out_dev, se3tn_scene_align_rec* rec_dev, int64_t* sums_dev, void* stream) {
+  const char* who = "se3tn_align_poses_scene";
+  if (int rc = pose_align_check(who, c, poses_dev && depth_dev && scene_dev && K && poses_out_dev && rec_dev, p, n, H, W, params, &scene_tol_mm))
+    return rc;
+  HIPCHK(launch_pose_align(pose_align_args(p, poses_dev, depth_dev, H, W, K, params, poses_out_dev, reinterpret_cast<se3tn_align_rec*>(rec_dev),
+                                           sums_dev, scene_dev, scene_tol_mm), n, (hipStream_t)stream));
+  return SE3TN_OK;
+}
+
+int se3tn_align_poses_scene_host(se3tn_ctx* c, const se3tn_points* p, int n, const double* poses, const uint16_t* depth, const uint16_t* scene,
+                                 int H, int W, const double K[9], const se3tn_align_params* params, int scene_tol_mm, double* poses_out,
+                                 se3tn_scene_align_rec* rec_out, int64_t* sums_out, void* stream) {
+  const char* who = "se3tn_align_poses_scene_host";
+  if (int rc = pose_align_check(who, c, poses && depth && scene && K && poses_out && rec_out, p, n, H, W, params, &scene_tol_mm)) return rc;
+  StagedCall sc{c, who, (hipStream_t)stream};
+  if (int rc = sc.refuse_capture()) return rc;
+  if (int rc = finite_K_check(who, K)) return rc;
+  if (int rc = finite_check(who, "pose", poses, nullptr, (size_t)n, 16, 12)) return rc;   // row 3 is not read
+  const PaSceneStage s = pa_stage_scene(n, H, W, sums_out ? 1 : 0);
+  if (int rc = sc.grow(s.bytes)) return rc;
+  const size_t frame_bytes = sizeof(uint16_t) * (size_t)H * (size_t)W;
+  std::memcpy(sc.h + s.poses, poses, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(sc.h + s.depth, depth, frame_bytes);
+  std::memcpy(sc.h + s.scene, scene, frame_bytes);
+  if (int rc = sc.upload(s.upload_bytes)) return rc;
+  HIPCHK(launch_pose_align(pose_align_args(p, sc.dev<double>(s.poses), sc.dev<uint16_t>(s.depth), H, W, K, params, sc.dev<double>(s.poses_out),
+                                           sc.dev<se3tn_align_rec>(s.rec), sums_out ? sc.dev<int64_t>(s.sums) : nullptr,
+                                           sc.dev<uint16_t>(s.scene), scene_tol_mm), n, sc.st));
+  if (int rc = sc.finish(s.poses_out, s.readback_bytes)) return rc;
+  std::memcpy(poses_out, sc.h + s.poses_out, sizeof(double) * 16 * (size_t)n);
+  std::memcpy(rec_out, sc.h + s.rec, sizeof(se3tn_scene_align_rec) * (size_t)n);
   if (sums_out) std::memcpy(sums_out, sc.h + s.sums, sizeof(int64_t) * SE3TN_POSE_ALIGN_SUMS * (size_t)n);
   return SE3TN_OK;
 }

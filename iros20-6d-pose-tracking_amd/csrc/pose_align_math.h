@@ -1,8 +1,9 @@
 // The arithmetic of se3tn_align_poses (include/se3tracknet.h states the rule), host and device: the terms of one model point (which
 // pixel it pairs with is the rule of pose_point_rule.h), their quantisation, the 6 x 6 solve and the Cayley update.  pose_align.hip
 // runs these statements on the device and
-// tests/c_abi/pose_align_check.cpp runs the very same ones on the host, so the two can be held to each other and to the numpy oracle
-// (tests/pose_align_oracle.py) word for word.  Whoever includes this compiles with -ffp-contract=off: every operation below is
+// tests/c_abi/pose_align_check.cpp (and pose_align_scene_check.cpp for the scene-aware rule of se3tn_align_poses_scene) runs the very
+// same ones on the host, so the two can be held to each other and to the numpy oracles (tests/pose_align_oracle.py,
+// tests/scene_align_oracle.py) word for word.  Whoever includes this compiles with -ffp-contract=off: every operation below is
 // rounded once, in the order written.  No HIP header is needed to read it.
 #pragma once
 #include <math.h>
@@ -29,8 +30,14 @@ SE3TN_PS_HD inline int64_t pa_fx(double v) { return (int64_t)rint(fmin(fmax(v, -
 // One model point x with normal n under pose T, paired when it faces, its pixel is seen and |d - m| <= gate (millimetres).  Returns
 // bit 0: facing, bit 1: paired; with bit 1 set J[6] and r are the point's row of the Jacobian and its residual (metres), otherwise
 // they are not written.
-SE3TN_PS_HD inline int pa_point(const Rigid& T, const DepthFrame& f, double gate, double x, double y, double z, double nx, double ny,
-                                double nz, double J[6], double& r) {
+//
+// The scene-aware rule (SCENE, se3tn_align_poses_scene) puts one verdict in front of `seen`: with s = scene[vf, uf] (read beside d,
+// not after the verdict on d: on the device the two gathers travel together) a point that is hidden(s, m, scene_tol) of
+// pose_point_rule.h returns bits 0 and 2 and is not paired whatever d is.  The statements are written once for both rules; without
+// SCENE `scene` and `scene_tol` are not read.
+template <bool SCENE>
+SE3TN_PS_HD inline int pa_point_rule(const Rigid& T, const DepthFrame& f, const uint16_t* scene, double scene_tol, double gate, double x,
+                                     double y, double z, double nx, double ny, double nz, double J[6], double& r) {
   double qx, qy, qz, mx, my, mz, uf, vf;
   size_t q;
   rotate(T.r, x, y, z, qx, qy, qz);
@@ -39,6 +46,10 @@ SE3TN_PS_HD inline int pa_point(const Rigid& T, const DepthFrame& f, double gate
   if (!faces(mx, my, mz, cx, cy, cz)) return 0;
   if (!pixel_of(f, cx, cy, cz, uf, vf, q)) return 1;
   const double d = (double)f.depth[q];
+  if (SCENE) {
+    const double s = (double)scene[q];
+    if (hidden(s, model_mm(cz), scene_tol)) return 5;
+  }
   if (!(seen(d) && fabs(d - model_mm(cz)) <= gate)) return 1;
   const double oz = d / 1000.0;
   const double ox = ((uf - f.k2) * oz) / f.k0;
@@ -49,6 +60,15 @@ SE3TN_PS_HD inline int pa_point(const Rigid& T, const DepthFrame& f, double gate
   J[2] = qx * my - qy * mx;
   J[3] = mx; J[4] = my; J[5] = mz;
   return 3;
+}
+SE3TN_PS_HD inline int pa_point(const Rigid& T, const DepthFrame& f, double gate, double x, double y, double z, double nx, double ny,
+                                double nz, double J[6], double& r) {
+  return pa_point_rule<false>(T, f, nullptr, 0.0, gate, x, y, z, nx, ny, nz, J, r);
+}
+// bit 0: facing, bit 1: paired, bit 2: hidden (never with bit 1)
+SE3TN_PS_HD inline int pa_point_scene(const Rigid& T, const DepthFrame& f, const uint16_t* scene, double scene_tol, double gate, double x,
+                                      double y, double z, double nx, double ny, double nz, double J[6], double& r) {
+  return pa_point_rule<true>(T, f, scene, scene_tol, gate, x, y, z, nx, ny, nz, J, r);
 }
 
 // the 28 quantised terms of a paired point added to S
@@ -168,6 +188,17 @@ SE3TN_PS_HD inline bool pa_step(Rigid& T, const int64_t S[PA_SUMS], uint32_t pai
   pa_update(T, delta);
   if (pa_small(delta, p.stop)) { rec.status = SE3TN_ALIGN_CONVERGED; return true; }
   return it + 1 >= p.iters;
+}
+
+// The scene-aware record: the fields pa_step left, and the hidden points of the pose it last evaluated in the place of _reserved
+static_assert(sizeof(se3tn_scene_align_rec) == sizeof(se3tn_align_rec) && offsetof(se3tn_scene_align_rec, hidden_pts) == 28 &&
+                  offsetof(se3tn_align_rec, _reserved) == 28 && offsetof(se3tn_scene_align_rec, sum_r2_0) == offsetof(se3tn_align_rec, sum_r2_0),
+              "se3tn_scene_align_rec is se3tn_align_rec with the word at offset 28 in use");
+SE3TN_PS_HD inline se3tn_scene_align_rec pa_scene_rec(const se3tn_align_rec& rec, uint32_t hidden_pts) {
+  se3tn_scene_align_rec s;
+  s.iterations = rec.iterations; s.status = rec.status; s.pairs = rec.pairs; s.facing_pts = rec.facing_pts; s.sum_r2 = rec.sum_r2;
+  s.pairs0 = rec.pairs0; s.hidden_pts = hidden_pts; s.sum_r2_0 = rec.sum_r2_0;
+  return s;
 }
 
 }  // namespace se3tn

@@ -1,5 +1,6 @@
 // Launch geometry, LDS layout and staging layout of the pose alignment (pose_align.hip, api.cpp: se3tn_align_poses,
-// se3tn_align_poses_host).  Host and device; no HIP header is needed to read it (tests/c_abi/pose_align_check.cpp runs it on the host
+// se3tn_align_poses_host, and their scene-aware counterparts se3tn_align_poses_scene, se3tn_align_poses_scene_host).  Host and
+// device; no HIP header is needed to read it (tests/c_abi/pose_align_check.cpp and pose_align_scene_check.cpp run it on the host
 // under sanitizers).
 //
 // One workgroup of PA_THREADS threads serves one pose through ALL its iterations (grid.x = n <= PA_MAX_POSES): thread t takes the
@@ -42,6 +43,17 @@ SE3TN_PS_HD inline int pa_lds_row(int wave) { return wave * PA_ROW_WORDS; }
 SE3TN_PS_HD inline int pa_lds_total() { return PA_WAVES * PA_ROW_WORDS; }
 SE3TN_PS_HD inline int pa_lds_words() { return (PA_WAVES + 1) * PA_ROW_WORDS; }
 
+// The scene-aware instantiation (se3tn_align_poses_scene) keeps a third count, hidden, behind the two: a wave hands over
+// PA_SCENE_ROW_WORDS words, and the rows and the totals are laid out as above with that width (1,240 bytes instead of 1,200).
+constexpr int PA_SCENE_ROW_WORDS = SE3TN_POSE_ALIGN_SUMS + 3;   // the 28 sums | pairs | facing points | hidden points
+constexpr int PA_W_HIDDEN = SE3TN_POSE_ALIGN_SUMS + 2;
+static_assert(PA_SCENE_ROW_WORDS <= PA_THREADS, "one thread per word of the cross-wave sum");
+static_assert(sizeof(se3tn_scene_align_rec) == 40, "the record of include/se3tracknet.h");
+SE3TN_PS_HD inline int pa_row_words(int scene) { return scene ? PA_SCENE_ROW_WORDS : PA_ROW_WORDS; }
+SE3TN_PS_HD inline int pa_scene_lds_row(int wave) { return wave * PA_SCENE_ROW_WORDS; }
+SE3TN_PS_HD inline int pa_scene_lds_total() { return PA_WAVES * PA_SCENE_ROW_WORDS; }
+SE3TN_PS_HD inline int pa_scene_lds_words() { return (PA_WAVES + 1) * PA_SCENE_ROW_WORDS; }
+
 // Staging of se3tn_align_poses_host (pose_search_plan.h has the head):
 //   [poses n x 16 doubles | frame | poses_out n x 16 doubles | rec n x 40 | sums n x 28 int64]
 // One read-back covers [poses_out, poses_out + readback_bytes): the poses and the records, and the sums when they were asked for.
@@ -56,6 +68,25 @@ SE3TN_PS_HD inline PaStage pa_stage(int n, int H, int W, int with_sums) {
   s.poses_out = ps_head(s, (size_t)n * 16 * sizeof(double), H, W);
   s.rec = s.poses_out + (size_t)n * 16 * sizeof(double);
   s.sums = s.rec + (size_t)n * sizeof(se3tn_align_rec);
+  s.readback_bytes = (s.sums - s.poses_out) + (with_sums ? (size_t)n * SE3TN_POSE_ALIGN_SUMS * sizeof(int64_t) : 0);
+  s.bytes = s.sums + (size_t)n * SE3TN_POSE_ALIGN_SUMS * sizeof(int64_t);
+  return s;
+}
+
+// Staging of se3tn_align_poses_scene_host:
+//   [poses n x 16 doubles | frame | pad to 8 | scene H x W uint16 | pad to 8 | poses_out n x 16 doubles | rec n x 40 | sums n x 28 int64]
+// The scene frame is an input here: ONE upload covers [0, upload_bytes), the poses, the frame and the scene; the read-back is as above.
+struct PaSceneStage : PaStage {
+  size_t scene;   // byte offset
+};
+SE3TN_PS_HD inline PaSceneStage pa_stage_scene(int n, int H, int W, int with_sums) {
+  PaSceneStage s;
+  s.poses = 0;
+  s.scene = ps_head(s, (size_t)n * 16 * sizeof(double), H, W);
+  s.upload_bytes = s.scene + (size_t)H * (size_t)W * sizeof(uint16_t);
+  s.poses_out = ps_align8(s.upload_bytes);
+  s.rec = s.poses_out + (size_t)n * 16 * sizeof(double);
+  s.sums = s.rec + (size_t)n * sizeof(se3tn_scene_align_rec);
   s.readback_bytes = (s.sums - s.poses_out) + (with_sums ? (size_t)n * SE3TN_POSE_ALIGN_SUMS * sizeof(int64_t) : 0);
   s.bytes = s.sums + (size_t)n * SE3TN_POSE_ALIGN_SUMS * sizeof(int64_t);
   return s;

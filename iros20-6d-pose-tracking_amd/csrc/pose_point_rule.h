@@ -11,7 +11,8 @@
 //     d = depth[vf, uf],  m = rint(c.z * 1000.0)
 //     seen       in frame && 100 < d < 2000
 //     inlier |d - m| <= tol      front d < m - tol      behind d > m + tol             (of the seen ones; exact: integers in doubles)
-// count_point_scene (below, se3tn_score_pose_grid_scene) puts one verdict in front of `seen`: hidden by a tracked surface.
+// count_point_scene (below, se3tn_score_pose_grid_scene) and pa_point_scene (pose_align_math.h, se3tn_align_poses_scene) put one verdict
+// in front of `seen`: hidden by a tracked surface -- hidden() below, stated once for both.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -54,6 +55,10 @@ SE3TN_PS_HD inline bool pixel_of(const DepthFrame& f, double cx, double cy, doub
 SE3TN_PS_HD inline bool seen(double d) { return d > 100.0 && d < 2000.0; }       // a depth the sensor measured, millimetres
 SE3TN_PS_HD inline double model_mm(double cz) { return rint(cz * 1000.0); }       // m: the model's depth at the point
 
+// the hidden verdict of the scene-aware rules on an in-frame point: s = scene[vf, uf], m = model_mm(c.z), tol in millimetres --
+// a tracked surface the sensor could have measured, at or in front of the point
+SE3TN_PS_HD inline bool hidden(double s, double m, double tol) { return seen(s) && s <= m + tol; }
+
 // the point c added to the five counters v: in frame, seen, inlier, front, behind
 SE3TN_PS_HD inline void count_point(const DepthFrame& f, double tol, double cx, double cy, double cz, unsigned v[5]) {
   double uf, vf;
@@ -86,7 +91,7 @@ SE3TN_PS_HD inline void count_point_scene(const DepthFrame& f, const uint16_t* s
   const double d = (double)f.depth[q];   // (read beside s, not after the verdict on it: on the device the two gathers travel together)
   const double m = model_mm(cz);
   // every counter is added to by name, without a branch that picks one: the device keeps the seven sums in registers only then
-  const bool hid = seen(s) && s <= m + tol;
+  const bool hid = hidden(s, m, tol);
   const bool sn = !hid && seen(d);
   v[5] += hid ? 1u : 0u;
   v[1] += sn ? 1u : 0u;

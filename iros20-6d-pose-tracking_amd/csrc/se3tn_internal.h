@@ -296,6 +296,8 @@ struct PoseAlignArgs {
   double* poses_out;       // [n,16]; may be `poses`
   se3tn_align_rec* rec;    // [n]
   int64_t* sums;           // [n,28] or nullptr
+  const uint16_t* scene;   // NULL, or [H,W] millimetres, the composed depth of the tracked objects: the scene-aware rule, and `rec`
+  int scene_tol;           // holds se3tn_scene_align_rec records (hidden_pts at offset 28).  Last: the plain kernel's arguments stay put
 };
 hipError_t launch_pose_align(const PoseAlignArgs& a, int n, hipStream_t st);
 

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, SCENE_FIT_DTYPE, SCENE_POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import ALIGN_REC_DTYPE, SCENE_ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, SCENE_FIT_DTYPE, SCENE_POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -713,7 +713,8 @@ class Engine:
         return idx, fit[idx.long()]
 
     # ---- n pose hypotheses aligned to one depth frame ------------------------------------------------
-    def align_poses(self, points, poses, depth, K, gate_mm=20, iters=20, min_pairs=12, damping=1e-6, stop=1e-6, sums=False):
+    def align_poses(self, points, poses, depth, K, gate_mm=20, iters=20, min_pairs=12, damping=1e-6, stop=1e-6, sums=False, scene=None,
+                    scene_tol_mm=10):
         """se3tn_align_poses: up to `iters` damped point-to-plane steps of the facing points of the model `points` (a ModelPoints
         handle WITH normals) against the depth frame (uint16 mm [H,W]), for each of n poses, in ONE launch -- the rule of
         include/se3tracknet.h: points pair with the pixel they project to when it lies within gate_mm of them, every sum is an
@@ -723,12 +724,20 @@ class Engine:
         numpy in ([n,4,4] or [n,16] poses, [H,W] depth) -> (poses [n,4,4] float64, records [n] of _lib.ALIGN_REC_DTYPE), ONE synchronous
         call (se3tn_align_poses_host: one upload, one launch, one read-back); cuda tensors in (float64 poses, 16-bit depth) -> (poses
         [n,4,4] float64 tensor, records uint8 tensor [n,40]: ``.cpu().numpy().view(ALIGN_REC_DTYPE)``), stream-ordered on the current
-        stream, nothing allocated by the library.  sums=True appends the int64 [n,28] sums of each pose's last evaluated iteration."""
+        stream, nothing allocated by the library.  sums=True appends the int64 [n,28] sums of each pose's last evaluated iteration.
+        scene (default None: exactly the calls above) is the composed depth of the tracked objects, uint16 mm [H,W], 0 where there is
+        none -- what scene_fit(..., scene=True) and search_pose_grid_scene(keep_scene=True) return: se3tn_align_poses_scene, under
+        which a facing point with a tracked surface at or in front of it (100 < s < 2000 and s <= m + scene_tol_mm) is hidden: not
+        paired, and counted in hidden_pts.  The records then have _lib.SCENE_ALIGN_REC_DTYPE (hidden_pts in the place of _reserved).
+        numpy poses and depth with a numpy scene: the host entry, one call; cuda tensors with a cuda 16-bit scene: the device entry on
+        the current stream; numpy poses and depth with a cuda scene: poses and depth are uploaded, the device entry runs, numpy out."""
         if not isinstance(points, ModelPoints) or not points._h:
             raise Se3tnError("align_poses: points must be an open ModelPoints handle (Engine.model_points)")
         Kh = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
         Kp = Kh.ctypes.data_as(C.POINTER(C.c_double))
         prm = _lib.AlignParams(int(gate_mm), int(iters), int(min_pairs), 0, float(damping), float(stop))
+        if scene is not None:
+            return self._align_poses_scene(points, poses, depth, Kp, prm, sums, scene, int(scene_tol_mm))
         if torch.is_tensor(poses) or torch.is_tensor(depth):
             if not (torch.is_tensor(poses) and torch.is_tensor(depth)):
                 raise Se3tnError("align_poses: poses and depth must both be tensors or both be arrays")
@@ -754,6 +763,52 @@ class Engine:
         check(self.lib.se3tn_align_poses_host(self._h, points._h, n, C.c_void_p(p.ctypes.data), C.c_void_p(d.ctypes.data), int(d.shape[0]),
                                               int(d.shape[1]), Kp, C.byref(prm), C.c_void_p(out.ctypes.data), C.c_void_p(rec.ctypes.data),
                                               C.c_void_p(sm.ctypes.data) if sums else None, _stream_ptr()), "se3tn_align_poses_host")
+        return (out, rec, sm) if sums else (out, rec)
+
+    def _align_poses_scene(self, points, poses, depth, Kp, prm, sums, scene, scene_tol_mm):
+        """align_poses with a scene: tensors in -> tensors out; arrays in -> the host entry, or with a cuda scene uploaded, the device
+        entry, numpy out"""
+        tensors = [torch.is_tensor(poses), torch.is_tensor(depth)]
+        if any(tensors):
+            if not (all(tensors) and torch.is_tensor(scene)):
+                raise Se3tnError("align_poses: poses, depth and scene must all be tensors or all be arrays")
+            return self._align_poses_scene_device(points, poses, depth, Kp, prm, sums, scene, scene_tol_mm)
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("align_poses: depth must be [H,W]")
+        if torch.is_tensor(scene):   # (a scene kept on the device beside host hypotheses: MultiTracker.recover's alignment)
+            dev = "cuda:%d" % self.device
+            out = self._align_poses_scene_device(points, torch.from_numpy(p).to(dev), torch.from_numpy(d.view(np.int16)).to(dev), Kp, prm,
+                                                 sums, scene, scene_tol_mm)
+            res = (out[0].cpu().numpy(), out[1].cpu().numpy().view(SCENE_ALIGN_REC_DTYPE).reshape(-1))
+            return res + (out[2].cpu().numpy(),) if sums else res
+        sc = np.ascontiguousarray(scene, dtype=np.uint16)
+        if sc.shape != d.shape:
+            raise ValueError("align_poses: scene must have the frame's shape")
+        n = int(p.shape[0])
+        out = np.empty((max(n, 0), 4, 4), np.float64)
+        rec = np.zeros(max(n, 0), SCENE_ALIGN_REC_DTYPE)
+        sm = np.zeros((max(n, 0), _lib.POSE_ALIGN_SUMS), np.int64) if sums else None
+        check(self.lib.se3tn_align_poses_scene_host(self._h, points._h, n, C.c_void_p(p.ctypes.data), C.c_void_p(d.ctypes.data),
+                                                    C.c_void_p(sc.ctypes.data), int(d.shape[0]), int(d.shape[1]), Kp, C.byref(prm),
+                                                    scene_tol_mm, C.c_void_p(out.ctypes.data), C.c_void_p(rec.ctypes.data),
+                                                    C.c_void_p(sm.ctypes.data) if sums else None, _stream_ptr()),
+              "se3tn_align_poses_scene_host")
+        return (out, rec, sm) if sums else (out, rec)
+
+    def _align_poses_scene_device(self, points, poses, depth, Kp, prm, sums, scene, scene_tol_mm):
+        assert poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous() and poses.numel() % 16 == 0
+        assert depth.is_cuda and depth.element_size() == 2 and depth.dim() == 2 and depth.is_contiguous()
+        assert scene.is_cuda and scene.element_size() == 2 and scene.is_contiguous() and scene.shape == depth.shape
+        n = poses.numel() // 16
+        out = torch.empty((n, 4, 4), dtype=torch.float64, device=poses.device)
+        rec = torch.empty((n, SCENE_ALIGN_REC_DTYPE.itemsize), dtype=torch.uint8, device=poses.device)
+        sm = torch.empty((n, _lib.POSE_ALIGN_SUMS), dtype=torch.int64, device=poses.device) if sums else None
+        check(self.lib.se3tn_align_poses_scene(self._h, points._h, n, C.c_void_p(poses.data_ptr()), C.c_void_p(depth.data_ptr()),
+                                               C.c_void_p(scene.data_ptr()), int(depth.shape[0]), int(depth.shape[1]), Kp, C.byref(prm),
+                                               scene_tol_mm, C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()),
+                                               C.c_void_p(sm.data_ptr()) if sums else None, _stream_ptr()), "se3tn_align_poses_scene")
         return (out, rec, sm) if sums else (out, rec)
 
     def fill_depth(self, depth_mm, max_depth=2.0, extrapolate=False, blur_type="bilateral", return_metres=False):

@@ -342,7 +342,10 @@ class Tracker:
     def align(self, poses, depth, **kw):
         """Align n pose hypotheses ([n,4,4]) to the depth frame (HxW uint16 mm): Engine.align_poses on ``object_cloud`` with
         ``object_normals`` (uploaded at first use and kept) and this tracker's K -> (poses [n,4,4], records [n]); the keywords
-        (gate_mm, iters, min_pairs, damping, stop, sums) are Engine.align_poses'.  Needs ``object_normals``: ValueError otherwise."""
+        (gate_mm, iters, min_pairs, damping, stop, sums) are Engine.align_poses'.  Needs ``object_normals``: ValueError otherwise.
+        scene=..., scene_tol_mm=10 (Engine.align_poses'): the composed depth of the tracked objects, uint16 [H,W] as an array or a cuda
+        16-bit tensor -- points hidden by it are not paired and the records are _lib.SCENE_ALIGN_REC_DTYPE (MultiTracker.align
+        composes that scene from its own objects)."""
         handle = self._facing_handle(None, "align")
         dep = depth if torch.is_tensor(depth) else np.ascontiguousarray(depth, dtype=np.uint16)
         return self.engine.align_poses(handle, poses, dep, self.K, **kw)
@@ -854,8 +857,30 @@ class MultiTracker:
         rec, ids_img, _ = self.engine.scene_fit(self._objs, poses, depth, self.K, tol_mm=tol_mm, ids=ids)
         return (rec, ids_img) if ids else rec
 
+    def align(self, i, poses, depth, occ_poses, occluders=None, scene_tol_mm=10, **kw):
+        """Extension: align hypotheses of object i ([k,4,4]) to the depth frame AMONG the other objects.  The occluders (indices;
+        default: every other object) are rendered at occ_poses ([len(occluders),4,4], in that order) and composed into a scene frame
+        on the device (Engine.scene_fit(..., scene=True) on the uploaded frame, with scene_tol_mm as its tolerance); then
+        Engine.align_poses(scene=...) runs on trackers[i]'s model: a facing point with a tracked surface at or in front of it is
+        hidden, not paired.  depth: numpy uint16 [H,W] or a cuda 16-bit tensor.  Returns (poses [k,4,4], records [k] of
+        _lib.SCENE_ALIGN_REC_DTYPE) as numpy; the further keywords are Engine.align_poses'."""
+        i = int(i)
+        occ = [j for j in range(self.n) if j != i] if occluders is None else [int(j) for j in occluders]
+        if not 0 <= i < self.n or any(j < 0 or j >= self.n or j == i for j in occ) or not occ:
+            raise ValueError("MultiTracker.align: object %d among occluders %s of %d objects" % (i, occ, self.n))
+        t = self.trackers[i]
+        handle = t._facing_handle(None, "MultiTracker.align")
+        dep = depth if torch.is_tensor(depth) else torch.from_numpy(np.ascontiguousarray(depth, dtype=np.uint16).view(np.int16)).to(self._dev)
+        occ_objs = (type(self._objs[0]) * len(occ))(*[self._objs[j] for j in occ])
+        _, _, scene = self.engine.scene_fit(occ_objs, occ_poses, dep, self.K, tol_mm=scene_tol_mm, scene=True)
+        p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))).to(self._dev)
+        out = t.engine.align_poses(handle, p, dep, self.K, scene=scene, scene_tol_mm=scene_tol_mm, **kw)
+        from ._lib import SCENE_ALIGN_REC_DTYPE
+        res = (out[0].cpu().numpy(), out[1].cpu().numpy().view(SCENE_ALIGN_REC_DTYPE).reshape(-1))
+        return res + tuple(x.cpu().numpy() for x in out[2:])
+
     def recover(self, prev_poses, rgb, depth, lost=None, lost_below=0.5, min_visible=0.2, trans_radius=0.05, trans_step=0.01,
-                rot_deg=(15.0,), tol_mm=10, top=None, refine=1, align=0):
+                rot_deg=(15.0,), tol_mm=10, top=None, refine=1, align=0, scene_align=False):
         """Extension: re-acquire the lost objects of a frame AMONG the tracked ones.  Tracker.recover scores a candidate against the
         depth frame alone: it lays a lost model onto the visible face of a neighbour, and counts a tracked object in front of a
         candidate as an unknown obstacle.  Here the objects that are "tracked" explain their pixels (the rule of
@@ -871,7 +896,11 @@ class MultiTracker:
         (3) align > 0: Engine.align_poses of the top nodes, refine >= 1: trackers[i].on_track_batch on them, as Tracker.recover
         does; (4) the pool [refined, aligned, unrefined] rescored under the scene-aware rule as the diagonal of a grid against the
         kept scene, and the largest recover.pose_key wins.  So the result never scores below the lattice's best under the scene
-        rule.  The alignment and the network stay scene-unaware; the choice is not.  A recovered object does NOT become an
+        rule.  The network stays scene-unaware, and so does the alignment by default; the choice is not.  scene_align=True (with
+        align > 0): step (3) aligns the top nodes against the kept scene of step (2) (Engine.align_poses(scene=..., scene_tol_mm =
+        tol_mm)): points hidden by a tracked object are not paired, so a neighbour's face or an object lying on the lost one no longer
+        drags the hypotheses away; align_rec then has _lib.SCENE_ALIGN_REC_DTYPE (hidden_pts) and last_recover[i]["scene_align"]
+        says which rule ran (False on the no-occluder fallback).  A recovered object does NOT become an
         occluder for the next lost one within the same call: every search of a call sees the same occluders.
         Returns [n,4,4]: rows of objects that were not searched are prev_poses' rows.  last_recover: {i: dict} per searched object
         -- what Tracker.last_recover keeps (n, top_idx, top_fit, refined, final_fit, chosen, inlier_frac = inlier_pts / points;
@@ -899,7 +928,7 @@ class MultiTracker:
             for i in lost:
                 out[i] = self.trackers[i].recover(poses[i], rgb, dep, trans_radius=trans_radius, trans_step=trans_step, rot_deg=rot_deg,
                                                   tol_mm=tol_mm, top=top, refine=refine, facing=True, align=align)
-                self.last_recover[i] = dict(self.trackers[i].last_recover, occluders=[], fallback=True)
+                self.last_recover[i] = dict(self.trackers[i].last_recover, occluders=[], fallback=True, scene_align=False)
             return out
         occ_objs = (type(self._objs[0]) * len(occ))(*[self._objs[j] for j in occ])
         for i in lost:
@@ -911,10 +940,14 @@ class MultiTracker:
                                                                                   tol_mm=tol_mm, facing=True, top=k, keep_scene=True)
             unrefined = t._compose(rots, trans, top_idx)
             info = dict(n=len(rots) * len(trans), top_idx=top_idx, top_fit=top_fit, refined=None, facing=True, occluders=list(occ),
-                        occ_fit=occ_fit, fallback=False)
+                        occ_fit=occ_fit, fallback=False, scene_align=bool(scene_align) and int(align) > 0)
             aligned = None
             if int(align) > 0:
-                aligned, align_rec = t.engine.align_poses(handle, unrefined, dep, self.K, iters=int(align))
+                if scene_align:
+                    aligned, align_rec = t.engine.align_poses(handle, unrefined, dep, self.K, iters=int(align), scene=scene,
+                                                              scene_tol_mm=tol_mm)
+                else:
+                    aligned, align_rec = t.engine.align_poses(handle, unrefined, dep, self.K, iters=int(align))
                 info.update(aligned=aligned, align_rec=align_rec)
             if int(refine) < 1 and aligned is None:
                 final, final_fit, chosen = unrefined, top_fit[:1].copy(), 0
