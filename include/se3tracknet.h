@@ -691,7 +691,7 @@ typedef struct se3tn_point_fit {   /* all uint32, 32 bytes */
 int se3tn_score_poses(se3tn_ctx* ctx, const se3tn_points* points, int n, const double* poses_dev, const uint16_t* depth_dev,
                       int H, int W, const double K[9], int tol_mm, se3tn_point_fit* fit_dev, void* stream);
 /* The indices of the k best of n records, best first, into idx_dev (device or mapped pinned host int32 [k]).  Record i has the key
- *     inlier_pts * 2^40 + (2^20 - 1 - min(behind_pts, 2^20 - 1)) * 2^20 + (2^20 - 1 - i)
+ *     min(inlier_pts, 2^20) * 2^40 + (2^20 - 1 - min(behind_pts, 2^20 - 1)) * 2^20 + (2^20 - 1 - i)
  * -- more inliers, then fewer seen-through points, then the lower index; unique within a call -- and the k largest keys are written
  * in descending order.  Selection without state: round r takes the largest key below round r - 1's winner (k passes over the n
  * records by one workgroup), so the result is deterministic.  Stream-ordered, capturable.  SE3TN_E_ARG: a NULL pointer, a host-only

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import scene_fit_scene as SS
+from mapped_memory import Mapped   # noqa: F401  (tests/test_gpu_scene_search.py imports it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,23 +32,6 @@ def eng(se3):
 
 def dev16(a):
     return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).cuda()
-
-
-class Mapped:
-    """mapped pinned host memory from the HIP runtime the library runs on: .d is the address the device reaches it by"""
-
-    def __init__(self, nbytes):
-        self.hip, self.nbytes = C.CDLL(None), nbytes
-        self.h, self.d = C.c_void_p(), C.c_void_p()
-        assert self.hip.hipHostMalloc(C.byref(self.h), C.c_size_t(nbytes), C.c_uint(2)) == 0          # hipHostMallocMapped
-        assert self.hip.hipHostGetDevicePointer(C.byref(self.d), self.h, C.c_uint(0)) == 0
-        C.memset(self.h, 0xEE, nbytes)
-
-    def read(self):
-        return np.frombuffer(C.string_at(self.h, self.nbytes), np.uint8).copy()
-
-    def close(self):
-        self.hip.hipHostFree(self.h)
 
 
 def run_stats(se3, eng, c, **kw):
