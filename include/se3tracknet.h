@@ -8,7 +8,7 @@
  * Conventions
  *   - plain C types only; device pointers are caller-owned (e.g. torch tensors' data_ptr());
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream);
- *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth, fit_stats, color_stats, scene_stats) is stream-ordered and
+ *   - every se3tn_* compute call (preprocess, crop_raw, infer, render, render_frame, fill_depth, fit_stats, color_stats, color_stats_scene, scene_stats) is stream-ordered and
  *     asynchronous: no hipMalloc, no hipDeviceSynchronize, no host<->device copy of results => hipGraph-capturable.
  *     All device memory is allocated by the init-time calls: se3tn_create (activations, 176x176 z-buffer),
  *     se3tn_upload_weights / se3tn_bind_weights / se3tn_set_winograd (Winograd planes), se3tn_set_precision (f16x3 split
@@ -507,6 +507,25 @@ typedef struct se3tn_color_fit {   /* all uint32, 20 words, 80 bytes */
  * NULL pointer (a descriptor without rgb or depth included), an empty window or image. */
 int se3tn_color_stats(se3tn_ctx* ctx, const se3tn_crop* model, const se3tn_crop* observed, int n, int tol_mm,
                       se3tn_fit* fit_out_dev /* may be NULL */, se3tn_color_fit* out_dev, void* stream);
+/* The same pass AMONG tracked objects.  se3tn_color_stats compares at every depth inlier; a tracked object that lies on the model's
+ * surface, or touches it, within tol_mm is a depth inlier too, and its colours would enter the correlation as if they were the
+ * model's.  `scene` is a third HOST array of n descriptors: the composed depth of the tracked objects (what se3tn_scene_fit writes as
+ * `scene`, 0 where there is none), read through its own descriptor with the same index rule, zero outside the image; only depth, H,
+ * W and left .. bottom are read.  The caller makes the scene pixel the one at the frame position the observed pixel came from (the
+ * same window on a frame-sized image: what se3tn_verify_poses_scene_host does).  With s the scene depth of the crop pixel:
+ *     hidden   valid(m) && valid(s) && s <= m + tol_mm    a tracked surface at or in front of the pixel: occluded by it, or claimed by it
+ * A hidden pixel enters model_px and hidden_px and nothing else; every other pixel is classified exactly as in se3tn_fit
+ * (csrc/fit_rule.h states both; the verdict is the one of se3tn_score_pose_grid_scene and se3tn_align_poses_scene on a model point).
+ * A pixel is COMPARED exactly when it is an inlier under this rule.  The depth record keeps se3tn_fit's 32 bytes with `_reserved`
+ * holding hidden_px: model_px == hidden_px + (the pixels classified as before), seen_px == inlier_px + front_px + behind_px; the
+ * colour record is se3tn_color_fit unchanged, px == inlier_px.  With an all-zero scene every byte of both records is
+ * se3tn_color_stats'.  A launch takes SE3TN_FIT_SCENE_MAX_PAIRS pairs (three descriptors per pair travel as kernel arguments); larger
+ * n are chunked.  Contract and refusals as se3tn_color_stats (stream-ordered, capturable, allocates nothing, the same counters:
+ * as every compute call of a context, one stream); also SE3TN_E_ARG, before anything is written, for a scene descriptor without
+ * depth and for an empty scene image or window. */
+#define SE3TN_FIT_SCENE_MAX_PAIRS 16
+int se3tn_color_stats_scene(se3tn_ctx* ctx, const se3tn_crop* model, const se3tn_crop* observed, const se3tn_crop* scene, int n,
+                            int tol_mm, se3tn_fit* fit_out_dev /* may be NULL */, se3tn_color_fit* out_dev, void* stream);
 /* The score of a record: the mean over the channels of the zero-mean normalised cross-correlation, in [-1, 1]; it does not change
  * under a gain or an offset of either image, which is what makes a Lambert-shaded render comparable with a camera image.  Host-only,
  * pure, needs no context.  Operation order (utils.color_score returns the same double): per channel c, with n = px, in int64
@@ -532,6 +551,17 @@ double se3tn_color_score(const se3tn_color_fit* rec, int min_px, double per_chan
 int se3tn_verify_poses_host(se3tn_ctx* ctx, se3tn_mesh* mesh, const double* poses, int n, const double K[9], double object_width_mm,
                             const uint8_t* rgb, const uint16_t* depth, int H, int W, int tol_mm, se3tn_fit* fit_out,
                             se3tn_color_fit* color_out, int32_t* bbox_out /* [n,4,2], may be NULL */);
+/* se3tn_verify_poses_host with the scene of the frame: scene_dev is the composed depth of the tracked objects, DEVICE uint16 [H,W]
+ * -- what se3tn_scene_fit writes as `scene`, or what se3tn_search_pose_grid_scene_host leaves on the device
+ * (se3tn_last_search_scene); this call renders no occluder itself.  Per pose the scene descriptor is that frame-sized image under the
+ * pose's own un-shifted crop window, so the scene pixel is the one at the frame position the observed pixel came from, and the records
+ * are se3tn_color_stats_scene's: fit_out[i]._reserved carries hidden_px.  Everything else as se3tn_verify_poses_host: staging, layout,
+ * one upload, the rasteriser path, one read-back, the refusals (SE3TN_E_ARG for a NULL scene_dev, before anything is written);
+ * SYNCHRONOUS on the default stream (the scene must be complete there: a caller who wrote it on another stream waits for that stream
+ * first), and it leaves no state behind. */
+int se3tn_verify_poses_scene_host(se3tn_ctx* ctx, se3tn_mesh* mesh, const double* poses, int n, const double K[9], double object_width_mm,
+                                  const uint8_t* rgb, const uint16_t* depth, const uint16_t* scene_dev /* device [H,W] */, int H, int W,
+                                  int tol_mm, se3tn_fit* fit_out, se3tn_color_fit* color_out, int32_t* bbox_out /* [n,4,2], may be NULL */);
 
 /* ---- the objects of one frame as ONE scene: tracked objects explain each other's occlusions -------------------------------- */
 /* se3tn_set_fit_check scores every object alone: where something stands in front of it the pixel is front_px, whatever that

@@ -21,6 +21,7 @@ BLUR_NONE, BLUR_BILATERAL, BLUR_GAUSSIAN = 0, 1, 2
 COLOR_RGB, COLOR_BGR = 0, 1        # se3tn_on_track_live's / se3tn_on_track_objects_live's color_order
 ROUTE_WINDOW, ROUTE_FRAME = 0, 1   # as include/se3tracknet.h: the renderer se3tn_on_track uses for a mesh's image A
 FIT_MAX_PAIRS = 32                 # as include/se3tracknet.h: pairs per launch of se3tn_fit_stats (larger n are chunked)
+FIT_SCENE_MAX_PAIRS = 16           # as include/se3tracknet.h: pairs per launch of se3tn_color_stats_scene (three descriptors per pair)
 POSE_ERRORS_CHUNK = 256            # as include/se3tracknet.h: pose pairs per launch of se3tn_pose_errors (larger n are chunked)
 POSE_ERRORS_MAX_POINTS = 1 << 20   # as include/se3tracknet.h: the largest model se3tn_points_create accepts
 POSE_SEARCH_MAX_POSES = 1 << 20   # as include/se3tracknet.h: the most candidate poses one se3tn_score_poses / se3tn_rank_poses call takes
@@ -106,6 +107,9 @@ assert CROP_DTYPE.itemsize == C.sizeof(Crop)
 FIT_FIELDS = ("model_px", "seen_px", "inlier_px", "front_px", "behind_px", "sum_abs_mm", "tol_mm")   # the seven that carry data
 FIT_DTYPE = _np.dtype([(k, "<u4") for k in FIT_FIELDS + ("_reserved",)])
 assert FIT_DTYPE.itemsize == C.sizeof(Fit) == 32
+# the depth record of the scene-aware crop rule (se3tn_color_stats_scene): the same 32 bytes with word 7 in use (hidden_px)
+SCENE_CROP_FIT_DTYPE = _np.dtype([(k, "<u4") for k in FIT_FIELDS + ("hidden_px",)])
+assert SCENE_CROP_FIT_DTYPE.itemsize == 32 and SCENE_CROP_FIT_DTYPE.fields["hidden_px"][1] == 28
 COLOR_FIT_SUMS = ("sum_m", "sum_o", "sum_mm", "sum_oo", "sum_mo", "sum_abs")   # three words each: R, G, B
 COLOR_FIT_DTYPE = _np.dtype([("px", "<u4"), ("tol_mm", "<u4")] + [(k, "<u4", (3,)) for k in COLOR_FIT_SUMS])
 assert COLOR_FIT_DTYPE.itemsize == C.sizeof(ColorFit) == 80
@@ -205,9 +209,13 @@ _SIGS = {
     "se3tn_last_fit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "se3tn_last_fit_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "se3tn_color_stats": (C.c_int, [C.c_void_p, C.POINTER(Crop), C.POINTER(Crop), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_color_stats_scene": (C.c_int, [C.c_void_p, C.POINTER(Crop), C.POINTER(Crop), C.POINTER(Crop), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "se3tn_color_score": (C.c_double, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "se3tn_verify_poses_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se3tn_verify_poses_scene_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se3tn_scene_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneLayer), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "se3tn_scene_fit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Object), C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -142,7 +142,7 @@ struct se3tn_ctx {
   int fit_tol = 0, fit_last_n = 0, fit_cap = 0;
   DeviceBuf<uint8_t> fit_rgb; DeviceBuf<uint16_t> fit_depth;
   PinnedBuf<se3tn_fit> fit_host;
-  // se3tn_color_stats / se3tn_verify_poses_host: per-pair counters [max_batch][FitArgs::COLOUR_WORDS] (se3tn_create; zero between launches)
+  // se3tn_color_stats(_scene) / se3tn_verify_poses(_scene)_host: per-pair counters [max_batch][FitArgs::COLOUR_WORDS] (se3tn_create; zero between launches)
   DeviceBuf<unsigned> color_counters;
   // the scene stage.  se3tn_scene_stats: the counters [SCENE_COUNTER_WORDS] (se3tn_create; zero between launches).  se3tn_scene_fit:
   // buffers of the stage's OWN, so that no tracking call reads what a scene call wrote and the other way round -- the pinned instance
@@ -479,23 +479,23 @@ static int crops_check(const std::string& who, const se3tn_ctx* c, const se3tn_c
   return SE3TN_OK;
 }
 
-// The crop records of n pairs, FitArgs::MAX pairs per launch (the descriptors travel as kernel arguments): pair(j, m, o) fills
-// pair j's descriptors.  `colour` asks for the colour records too and picks the context's counters (fit launches and colour
-// launches on two streams of one context do not touch each other's words); raw_depth: the raw crop stacks (FitArgs)
-template <class Pair>
+// The crop records of n pairs, Args::MAX pairs per launch (the descriptors travel as kernel arguments): pair(j, m, o) fills
+// pair j's descriptors -- Args = FitSceneArgs, the scene-aware rule: pair(j, m, o, s).  `colour` asks for the colour records too and picks the context's counters
+// (fit launches and colour launches on two streams of one context do not touch each other's words); raw_depth: the raw crop stacks (FitArgs)
+template <class Args = FitArgs, class Pair>
 static int fit_launches(se3tn_ctx* c, int n, Pair pair, se3tn_fit* fit, se3tn_color_fit* colour, int tol, uint8_t* raw_rgb, uint16_t* raw_depth,
                         hipStream_t st) {
   unsigned* const counters = colour ? c->color_counters.get() : c->fit_counters.get();
   const size_t words = colour ? FitArgs::COLOUR_WORDS : FitArgs::WORDS;
-  for (int g0 = 0; g0 < n; g0 += FitArgs::MAX) {
-    const int k = n - g0 < FitArgs::MAX ? n - g0 : FitArgs::MAX;
-    FitArgs a;
-    for (int j = 0; j < k; ++j) pair(g0 + j, a.m[j], a.o[j]);
+  for (int g0 = 0; g0 < n; g0 += Args::MAX) {
+    const int k = n - g0 < Args::MAX ? n - g0 : Args::MAX;
+    Args a;
+    for (int j = 0; j < k; ++j) { if constexpr (Args::SCENE) pair(g0 + j, a.m[j], a.o[j], a.s[j]); else pair(g0 + j, a.m[j], a.o[j]); }
     a.counters = counters + words * g0;
     a.fit = fit ? fit + g0 : nullptr;
     a.colour = colour ? colour + g0 : nullptr;
     a.tol = tol;
-    if (raw_depth) {
+    if constexpr (!Args::SCENE) if (raw_depth) {
       a.raw_rgb = raw_rgb + (size_t)g0 * RES * RES * 3;
       a.raw_depth = raw_depth + (size_t)g0 * RES * RES;
     }
@@ -2282,10 +2282,10 @@ static int raster_instances(se3tn_ctx* c, int n, const se3tn_mesh* const* meshes
 // bytes are those of that launch (tests/test_gpu_color_fit.py holds them equal).  What the call writes: c->mo, the instance table
 // (tb_inst_host / tb_inst_dev), tb_rgbA / tb_depthA / tb_zbuf or fr_sub / fr_zbuf, tb_stage_host / tb_stage_dev and the colour
 // counters (re-armed by the kernel) -- every one rewritten by a tracking call before it reads it
-int se3tn_verify_poses_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, int n, const double K[9], double object_width_mm,
-                            const uint8_t* rgb, const uint16_t* depth, int H, int W, int tol_mm, se3tn_fit* fit_out,
-                            se3tn_color_fit* color_out, int32_t* bbox_out) {
-  const char* who = "se3tn_verify_poses_host";
+// the body of se3tn_verify_poses_host and (scene_dev != NULL) se3tn_verify_poses_scene_host, the entry points at the end of this file
+static int verify_poses(const char* who, se3tn_ctx* c, se3tn_mesh* m, const double* poses, int n, const double K[9], double object_width_mm,
+                        const uint8_t* rgb, const uint16_t* depth, const uint16_t* scene_dev, int H, int W, int tol_mm, se3tn_fit* fit_out,
+                        se3tn_color_fit* color_out, int32_t* bbox_out) {
   if (!c || !m || !poses || !K || !rgb || !depth || !fit_out || !color_out) return null_argument(who);
   if (int rc = frame_check(who, H, W)) return rc;
   if (int rc = refuse_if(!(object_width_mm > 0), SE3TN_E_ARG, who, "object_width_mm must be > 0")) return rc;
@@ -2331,10 +2331,10 @@ int se3tn_verify_poses_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, in
   if (int rc = upload_staged(c, c->tb_stage_dev.get() + L.begin, hp + L.begin, bytes - L.begin, st)) return rc;   // (every window stages >= 64 bytes)
   se3tn_fit* fit_dev = (se3tn_fit*)(c->tb_stage_dev.get() + L.fit_off);
   se3tn_color_fit* col_dev = (se3tn_color_fit*)(c->tb_stage_dev.get() + L.color_off);
-  auto pair = [&](int j, se3tn_crop& m, se3tn_crop& o) {
-    crop_pair(windows[j], 0.0, image_a(c, frame_route, j, rA, dA, maxpx, fr_d_off), c->tb_stage_dev.get(), m, o);
-  };
-  if (int rc = fit_launches(c, n, pair, fit_dev, col_dev, tol_mm, nullptr, nullptr, st)) return rc;
+  auto pair = [&](int j, se3tn_crop& m, se3tn_crop& o) { crop_pair(windows[j], 0.0, image_a(c, frame_route, j, rA, dA, maxpx, fr_d_off), c->tb_stage_dev.get(), m, o); };
+  auto triple = [&](int j, se3tn_crop& m, se3tn_crop& o, se3tn_crop& s) { pair(j, m, o); crop_scene(windows[j], scene_dev, H, W, s); };
+  if (int rc = scene_dev ? fit_launches<FitSceneArgs>(c, n, triple, fit_dev, col_dev, tol_mm, nullptr, nullptr, st)
+                         : fit_launches(c, n, pair, fit_dev, col_dev, tol_mm, nullptr, nullptr, st)) return rc;
   HIPCHK(hipMemcpyAsync(hp, c->tb_stage_dev.get(), L.rec_bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   up.done();
@@ -2989,6 +2989,39 @@ int se3tn_pose_update_host(const double A[16], const float trans[3], const float
   B[12] = B[13] = B[14] = 0.0;
   B[15] = 1.0;
   return SE3TN_OK;
+}
+
+// ---- the colour record among tracked objects (the scene-aware rule of fit_rule.h) ---------------------------------------------------
+// (down here so that no line of the code above moves: tests/pose_family_limits.py names lines of it)
+int se3tn_color_stats_scene(se3tn_ctx* c, const se3tn_crop* model, const se3tn_crop* observed, const se3tn_crop* scene, int n, int tol_mm,
+                            se3tn_fit* fit_out_dev, se3tn_color_fit* out_dev, void* stream) {
+  const std::string who = "se3tn_color_stats_scene";
+  if (!scene) return fail(SE3TN_E_ARG, who + ": bad argument");
+  if (int rc = crops_check(who, c, model, observed, n, tol_mm, out_dev, true)) return rc;
+  for (int i = 0; i < n; ++i) {
+    const se3tn_crop& k = scene[i];
+    if (!k.depth) return fail(SE3TN_E_ARG, who + ": scene descriptor " + std::to_string(i) + ": NULL depth");
+    if (k.H < 1 || k.W < 1 || k.right <= k.left || k.bottom <= k.top)
+      return fail(SE3TN_E_ARG, who + ": scene descriptor " + std::to_string(i) + ": empty image or empty window");
+  }
+  auto triple = [&](int j, se3tn_crop& m, se3tn_crop& o, se3tn_crop& s) { m = model[j]; o = observed[j]; s = scene[j]; };
+  return fit_launches<FitSceneArgs>(c, n, triple, fit_out_dev, out_dev, tol_mm, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// the two entry points of verify_poses(): without a scene the plain rule (fit_launches on FitArgs), with one the scene-aware rule -- pose
+// j's scene descriptor is the frame-sized scene_dev under the un-shifted window winB of the pose (crop_scene, track_plan.h)
+int se3tn_verify_poses_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, int n, const double K[9], double object_width_mm,
+                            const uint8_t* rgb, const uint16_t* depth, int H, int W, int tol_mm, se3tn_fit* fit_out,
+                            se3tn_color_fit* color_out, int32_t* bbox_out) {
+  return verify_poses("se3tn_verify_poses_host", c, m, poses, n, K, object_width_mm, rgb, depth, nullptr, H, W, tol_mm, fit_out, color_out, bbox_out);
+}
+
+int se3tn_verify_poses_scene_host(se3tn_ctx* c, se3tn_mesh* m, const double* poses, int n, const double K[9], double object_width_mm,
+                                  const uint8_t* rgb, const uint16_t* depth, const uint16_t* scene_dev, int H, int W, int tol_mm,
+                                  se3tn_fit* fit_out, se3tn_color_fit* color_out, int32_t* bbox_out) {
+  const char* who = "se3tn_verify_poses_scene_host";
+  if (!scene_dev) return null_argument(who);
+  return verify_poses(who, c, m, poses, n, K, object_width_mm, rgb, depth, scene_dev, H, W, tol_mm, fit_out, color_out, bbox_out);
 }
 
 }  // extern "C"

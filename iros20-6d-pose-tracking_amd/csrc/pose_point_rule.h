@@ -56,7 +56,8 @@ SE3TN_PS_HD inline bool seen(double d) { return d > 100.0 && d < 2000.0; }      
 SE3TN_PS_HD inline double model_mm(double cz) { return rint(cz * 1000.0); }       // m: the model's depth at the point
 
 // the hidden verdict of the scene-aware rules on an in-frame point: s = scene[vf, uf], m = model_mm(c.z), tol in millimetres --
-// a tracked surface the sensor could have measured, at or in front of the point
+// a tracked surface the sensor could have measured, at or in front of the point.  fit_hidden() of fit_rule.h is the same verdict on
+// integers, for a crop pixel (se3tn_color_stats_scene)
 SE3TN_PS_HD inline bool hidden(double s, double m, double tol) { return seen(s) && s <= m + tol; }
 
 // the point c added to the five counters v: in frame, seen, inlier, front, behind

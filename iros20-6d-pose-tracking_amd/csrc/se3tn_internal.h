@@ -204,6 +204,7 @@ static_assert(sizeof(CropArgs) <= 4096, "CropArgs travels as kernel arguments: H
 struct FitArgs {
   static constexpr int MAX = SE3TN_FIT_MAX_PAIRS;   // 2 x 32 x 56 B + constants = 3.6 KB of kernel arguments (limit 4 KB, asserted below)
   static constexpr int SUMS = 6, WORDS = 8;          // depth only: the six sums of se3tn_fit; counter words per pair: the SUMS | the arrival counter | unused
+  static constexpr bool SCENE = false;              // (FitSceneArgs below: true -- what fit_launches in api.cpp branches on)
   static constexpr int COLOUR_SUMS = 24, COLOUR_WORDS = 32;   // with colour: + sum_m .. sum_abs of se3tn_color_fit (px = inlier_px); the same layout
   se3tn_crop m[MAX], o[MAX];  // model / observed image of pair i: depth, H, W, left .. bottom are read (rgb: with colour or raw_rgb only)
   unsigned* counters;         // [n][WORDS] or (colour) [n][COLOUR_WORDS], zero between launches (the last workgroup of a pair to arrive re-arms them)
@@ -218,6 +219,24 @@ struct FitArgs {
 static_assert(sizeof(FitArgs) <= 4096, "FitArgs travels as kernel arguments: HIP's limit is 4 KB");
 static_assert(sizeof(se3tn_color_fit) == 80 && sizeof(se3tn_fit) == 32, "the records are 20 / 8 words");
 hipError_t launch_fit_stats(const FitArgs& a, int n, hipStream_t st);
+
+// both records under the scene-aware rule (fit_rule.h: fit_classify_scene) of up to MAX (model, observed, scene) triples per launch:
+// fit_stats_kernel<true, true>.  A third descriptor per pair would push FitArgs past the 4 KB of kernel arguments at 32 pairs, so the
+// scene instantiation has its own arguments with SE3TN_FIT_SCENE_MAX_PAIRS pairs; the members the kernel body shares keep FitArgs' names
+struct FitSceneArgs {
+  static constexpr int MAX = SE3TN_FIT_SCENE_MAX_PAIRS;   // 3 x 16 x 56 B + constants = 2.7 KB of kernel arguments (limit 4 KB, asserted below)
+  static constexpr bool SCENE = true;
+  static constexpr int SUMS = FitArgs::COLOUR_SUMS + 1;   // the 24 of the colour instantiation | hidden; the ticket follows: 26 of COLOUR_WORDS
+  se3tn_crop m[MAX], o[MAX];  // as FitArgs (rgb and depth are read)
+  se3tn_crop s[MAX];          // the scene of pair i -- the composed depth of the tracked objects: depth, H, W, left .. bottom are read
+  unsigned* counters;         // [n][FitArgs::COLOUR_WORDS], the colour instantiation's own words: the layout is shared, word 24 is zero between launches
+  se3tn_fit* fit;             // [n] depth records, the last word = hidden_px; or nullptr
+  int tol;
+  se3tn_color_fit* colour;    // [n] colour records
+};
+static_assert(sizeof(FitSceneArgs) <= 4096, "FitSceneArgs travels as kernel arguments: HIP's limit is 4 KB");
+static_assert(FitSceneArgs::SUMS + 1 <= FitArgs::COLOUR_WORDS, "25 sums and the ticket fit the colour counters of a pair");
+hipError_t launch_fit_stats(const FitSceneArgs& a, int n, hipStream_t st);
 
 // n depth layers of one frame through a shared depth test (scene_fit.hip; the rule: scene_fit_rule.h, tiles and counters: scene_fit_plan.h);
 // the layers travel as kernel arguments

@@ -146,4 +146,12 @@ inline void crop_pair(const TrackWindow& t, double z_mm, const ImageA& A, const 
   ca.stats = 0;
 }
 
+// The scene descriptor of a pair (the scene-aware crop records, fit_rule.h): the frame-sized composed depth of the tracked objects,
+// device [H,W], under the UN-shifted winB -- the frame position image B's staged sub-image shows under the shifted one
+inline void crop_scene(const TrackWindow& t, const uint16_t* scene, int H, int W, se3tn_crop& cs) {
+  cs = se3tn_crop{};
+  cs.depth = scene; cs.H = H; cs.W = W;
+  cs.left = t.winB[0]; cs.top = t.winB[1]; cs.right = t.winB[2]; cs.bottom = t.winB[3];
+}
+
 }  // namespace se3tn

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ALIGN_REC_DTYPE, SCENE_ALIGN_REC_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, SCENE_FIT_DTYPE, SCENE_POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
+from ._lib import ALIGN_REC_DTYPE, SCENE_ALIGN_REC_DTYPE, SCENE_CROP_FIT_DTYPE, COLOR_FIT_DTYPE, CROP_DTYPE, FIT_DTYPE, POINT_FIT_DTYPE, SCENE_FIT_DTYPE, SCENE_POINT_FIT_DTYPE, NCHW, NHWC, RES, Crop, Se3tnError, check
 
 
 def _stream_ptr():
@@ -317,16 +317,22 @@ class Engine:
         return out.cpu().numpy().reshape(-1).view(FIT_DTYPE)[:n].copy()
 
     # ---- how well a hypothesis fits the observed colour ------------------------------------------
-    def color_stats(self, model, observed, tol_mm, out=None):
+    def color_stats(self, model, observed, tol_mm, out=None, scene=None):
         """se3tn_color_stats: model / observed = n descriptors each, dict(rgb=cuda uint8 [H,W,3], depth=cuda 16-bit [H,W],
         window=(left, top, right, bottom)); window defaults to the whole image.  ONE pass gives both records: returns (fit, color),
         structured arrays of n records (_lib.FIT_DTYPE as fit_stats, _lib.COLOR_FIT_DTYPE: px, tol_mm, sum_m, sum_o, sum_mm, sum_oo,
         sum_mo, sum_abs with three words each); synchronises on the current stream.  out: a cuda uint8 [>= n,112] tensor -- the call
         is then only enqueued (capturable) and returns None; row-wise the first n * 32 bytes are the fit records, the n * 80 behind
-        them the colour records (color_records reads them)."""
+        them the colour records (color_records reads them).
+        scene: n more descriptors, as the observed ones but with depth alone, dict(depth=cuda 16-bit [H,W], window=...) -- the composed
+        depth of the tracked objects under the window that shows the frame positions the observed crop shows
+        (se3tn_color_stats_scene, the rule: utils.fit_stats(scene=)): pixels hidden by a tracked surface are counted as hidden_px and
+        not compared; fit is then _lib.SCENE_CROP_FIT_DTYPE (color_records(..., scene=True) reads it so)."""
         n = len(model)
         if len(observed) != n:
             raise ValueError("color_stats: %d model and %d observed descriptors" % (n, len(observed)))
+        if scene is not None and len(scene) != n:
+            raise ValueError("color_stats: %d scene descriptors for %d pairs" % (len(scene), n))
         arrs = []
         for group in (model, observed):
             arr = (Crop * max(n, 1))()
@@ -341,23 +347,42 @@ class Engine:
             arrs.append(arr)
         buf = out if out is not None else torch.empty((max(n, 1), 112), dtype=torch.uint8, device="cuda:%d" % self.device)
         assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and buf.numel() >= 112 * n
-        check(self.lib.se3tn_color_stats(self._h, arrs[0], arrs[1], n, int(tol_mm), C.c_void_p(buf.data_ptr()),
-                                         C.c_void_p(buf.data_ptr() + 32 * n), _stream_ptr()), "se3tn_color_stats")
-        return None if out is not None else self.color_records(buf, n)
+        if scene is None:
+            check(self.lib.se3tn_color_stats(self._h, arrs[0], arrs[1], n, int(tol_mm), C.c_void_p(buf.data_ptr()),
+                                             C.c_void_p(buf.data_ptr() + 32 * n), _stream_ptr()), "se3tn_color_stats")
+            return None if out is not None else self.color_records(buf, n)
+        arr = (Crop * max(n, 1))()
+        for i, c in enumerate(scene):
+            if torch.is_tensor(c):
+                c = dict(depth=c)
+            depth = c["depth"]
+            assert depth.is_cuda and depth.element_size() == 2 and depth.is_contiguous() and depth.dim() == 2
+            arr[i].rgb = None; arr[i].depth = depth.data_ptr()
+            arr[i].H, arr[i].W = int(depth.shape[0]), int(depth.shape[1])
+            win = c.get("window") or (0, 0, int(depth.shape[1]), int(depth.shape[0]))
+            arr[i].left, arr[i].top, arr[i].right, arr[i].bottom = [int(v) for v in win]
+        check(self.lib.se3tn_color_stats_scene(self._h, arrs[0], arrs[1], arr, n, int(tol_mm), C.c_void_p(buf.data_ptr()),
+                                               C.c_void_p(buf.data_ptr() + 32 * n), _stream_ptr()), "se3tn_color_stats_scene")
+        return None if out is not None else self.color_records(buf, n, scene=True)
 
     @staticmethod
-    def color_records(buf, n):
-        """(fit, color) of the n pairs a color_stats(..., out=buf) call left in buf"""
+    def color_records(buf, n, scene=False):
+        """(fit, color) of the n pairs a color_stats(..., out=buf) call left in buf (scene=True: the call had a scene, fit reads as
+        _lib.SCENE_CROP_FIT_DTYPE)"""
         host = buf.cpu().numpy().reshape(-1)
-        return host[:32 * n].view(FIT_DTYPE).copy(), host[32 * n:112 * n].view(COLOR_FIT_DTYPE).copy()
+        return host[:32 * n].view(SCENE_CROP_FIT_DTYPE if scene else FIT_DTYPE).copy(), host[32 * n:112 * n].view(COLOR_FIT_DTYPE).copy()
 
-    def verify_poses(self, mesh, poses, rgb, depth, K, object_width_mm, tol_mm=10):
+    def verify_poses(self, mesh, poses, rgb, depth, K, object_width_mm, tol_mm=10, scene=None):
         """se3tn_verify_poses_host: "which of these n hypotheses does the frame confirm" in ONE call -- per pose its compute_bbox
         window, its own image A (the renderer of `mesh`: a HipRenderer or its se3tn_mesh handle) and the depth and colour records of
         that render against the frame's window.  poses [n,4,4]; rgb HxWx3 uint8, depth HxW uint16 mm (host arrays); K 3x3.
         Returns (fit [n], color [n], bbox [n,4,2]).  Synchronous on the default stream: refused (Se3tnError, rc = SE3TN_E_STATE) while
         the current stream is being captured -- here, since the library sees a capture only where the default stream takes part in it
-        (a blocking stream), and torch captures on non-blocking ones."""
+        (a blocking stream), and torch captures on non-blocking ones.
+        scene: the composed depth of the tracked objects of the frame, a cuda 16-bit [H,W] tensor (what scene_fit(..., scene=True) or
+        search_pose_grid_scene(..., keep_scene=True) return; torch's current stream is waited for before the call, which runs on the
+        default stream) or a host uint16 [H,W] array, which is uploaded -- se3tn_verify_poses_scene_host: pixels hidden by a tracked
+        surface are hidden_px and not compared, fit is _lib.SCENE_CROP_FIT_DTYPE."""
         if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
             raise Se3tnError("se3tn_verify_poses_host refused (rc=-2): the call is synchronous, it cannot be captured")
         p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
@@ -367,11 +392,27 @@ class Engine:
         if rgb.ndim != 3 or rgb.shape[2] != 3 or dep.shape != rgb.shape[:2]:
             raise ValueError("verify_poses: rgb must be HxWx3 uint8 and depth HxW")
         Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
-        fit, col, bb = np.zeros(max(n, 1), FIT_DTYPE), np.zeros(max(n, 1), COLOR_FIT_DTYPE), np.zeros((max(n, 1), 4, 2), np.int32)
-        check(self.lib.se3tn_verify_poses_host(
-            self._h, getattr(mesh, "_m", mesh), C.c_void_p(p.ctypes.data), n, Kc.ctypes.data_as(C.POINTER(C.c_double)),
-            C.c_double(float(object_width_mm)), C.c_void_p(rgb.ctypes.data), C.c_void_p(dep.ctypes.data), int(rgb.shape[0]), int(rgb.shape[1]),
-            int(tol_mm), C.c_void_p(fit.ctypes.data), C.c_void_p(col.ctypes.data), C.c_void_p(bb.ctypes.data)), "se3tn_verify_poses_host")
+        fit_dtype = FIT_DTYPE if scene is None else SCENE_CROP_FIT_DTYPE
+        fit, col, bb = np.zeros(max(n, 1), fit_dtype), np.zeros(max(n, 1), COLOR_FIT_DTYPE), np.zeros((max(n, 1), 4, 2), np.int32)
+        front = (self._h, getattr(mesh, "_m", mesh), C.c_void_p(p.ctypes.data), n, Kc.ctypes.data_as(C.POINTER(C.c_double)),
+                 C.c_double(float(object_width_mm)), C.c_void_p(rgb.ctypes.data), C.c_void_p(dep.ctypes.data))
+        back = (int(rgb.shape[0]), int(rgb.shape[1]), int(tol_mm), C.c_void_p(fit.ctypes.data), C.c_void_p(col.ctypes.data),
+                C.c_void_p(bb.ctypes.data))
+        if scene is None:
+            check(self.lib.se3tn_verify_poses_host(*front, *back), "se3tn_verify_poses_host")
+        else:
+            if torch.is_tensor(scene):
+                sc = scene
+                if not (sc.is_cuda and sc.element_size() == 2 and sc.is_contiguous() and tuple(sc.shape) == dep.shape):
+                    raise ValueError("verify_poses: scene must be a contiguous cuda 16-bit tensor of the frame's shape")
+                torch.cuda.current_stream(sc.device).synchronize()   # the scene is complete before the default stream reads it
+            else:
+                host = np.ascontiguousarray(scene, dtype=np.uint16)
+                if host.shape != dep.shape:
+                    raise ValueError("verify_poses: scene must have the frame's shape")
+                sc = torch.from_numpy(host.view(np.int16) if host.flags.writeable else host.view(np.int16).copy()).to("cuda:%d" % self.device)
+                torch.cuda.current_stream(sc.device).synchronize()
+            check(self.lib.se3tn_verify_poses_scene_host(*front, C.c_void_p(sc.data_ptr()), *back), "se3tn_verify_poses_scene_host")
         return fit[:n], col[:n], bb[:n]
 
     def set_fit_check(self, tol_mm):

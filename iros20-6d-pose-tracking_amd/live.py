@@ -147,7 +147,8 @@ class LiveMultiTracker:
     poses back.  one_call=False composes engine.fill_depth + the channel swap + MultiTracker.on_track; one_call=True is ONE library
     call per frame (opt-in, as LiveTracker's; measured in profiles/EXPERIMENTS.md item 73).
     recover_lost: None (default; then not one call more is made) or a dict of utils.scene_status thresholds (lost_below,
-    min_visible; further keys are MultiTracker.recover's keywords, align and scene_align among them): after each frame the objects the scene records call "lost" go
+    min_visible; further keys are MultiTracker.recover's keywords, align and scene_align among them, and "colour": True -- with colour_within / min_px -- for
+    the scene-aware colour choice among the depth-equal hypotheses, which reads the frame's RGB image): after each frame the objects the scene records call "lost" go
     through MultiTracker.recover around the poses the frame started from, and the poses it finds are adopted.  Needs scene_check."""
 
     def __init__(self, multi_tracker, poses_init, max_depth=2.0, extrapolate=False, blur_type="bilateral", one_call=False,

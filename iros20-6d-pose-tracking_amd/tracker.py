@@ -278,47 +278,57 @@ class Tracker:
         final_fit = self._score_diagonal(handle, final, dep, tol_mm)
         return final, refined, final_fit, int(np.argmax(pose_key(final_fit)))   # ties prefer the earlier part of the pool: the lower index
 
-    def verify(self, poses, rgb, depth, tol_mm=10, min_px=64):
+    def verify(self, poses, rgb, depth, tol_mm=10, min_px=64, scene=None):
         """Extension: which of these n pose hypotheses ([n,4,4]) does the frame (rgb HxWx3 uint8, depth HxW uint16 mm) confirm --
         by colour, where depth cannot tell: per pose the model rendered in its own compute_bbox window against that window of the
         frame, compared at the pixels where the two depths agree within tol_mm -> (fit [n], color [n], score [n]): the depth
         records (as fit_stats), the colour records (_lib.COLOR_FIT_DTYPE) and utils.color_score of each (the zero-mean normalised
         cross-correlation, mean of R, G, B; 0 below min_px compared pixels).  With the built-in HIP renderer ONE library call
-        (se3tn_verify_poses_host); with an injected renderer render_window per pose plus Engine.color_stats."""
+        (se3tn_verify_poses_host); with an injected renderer render_window per pose plus Engine.color_stats.
+        scene: the composed depth of the tracked objects of the frame, uint16 [H,W] as an array or a cuda 16-bit tensor
+        (Engine.scene_fit(..., scene=True); MultiTracker.verify composes it from its own objects) -- the scene-aware rule
+        (se3tn_verify_poses_scene_host, utils.fit_stats(scene=)): a pixel with a tracked surface at or in front of the model's is
+        hidden_px and not compared, so an object lying on this one does not lend it its colours; fit is then
+        _lib.SCENE_CROP_FIT_DTYPE."""
         from .renderer import HipRenderer
         poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
         n = len(poses)
         if n > self.engine.max_batch:
             raise ValueError("verify: %d poses > max_samples=%d given to Tracker()" % (n, self.engine.max_batch))
         if n == 0:
-            from ._lib import COLOR_FIT_DTYPE, FIT_DTYPE
-            return np.zeros(0, FIT_DTYPE), np.zeros(0, COLOR_FIT_DTYPE), np.zeros(0, np.float64)
+            from ._lib import COLOR_FIT_DTYPE, FIT_DTYPE, SCENE_CROP_FIT_DTYPE
+            return np.zeros(0, FIT_DTYPE if scene is None else SCENE_CROP_FIT_DTYPE), np.zeros(0, COLOR_FIT_DTYPE), np.zeros(0, np.float64)
         if self.one_call and isinstance(self.renderer, HipRenderer):
             dep = _depth_u16(depth, rgb).view(np.uint16)   # the shape check and the reference's cast; the host call takes the uint16 itself
-            fit, color, _ = self.engine.verify_poses(self.renderer, poses, rgb, dep, self.K, self.object_width, tol_mm)
+            fit, color, _ = self.engine.verify_poses(self.renderer, poses, rgb, dep, self.K, self.object_width, tol_mm, scene=scene)
         else:
-            fit, color = self._verify_stepwise(poses, rgb, depth, tol_mm)
+            fit, color = self._verify_stepwise(poses, rgb, depth, tol_mm, scene)
         return fit, color, np.atleast_1d(U.color_score(color, min_px))
 
-    def _verify_stepwise(self, poses, rgb, depth, tol_mm):
+    def _verify_stepwise(self, poses, rgb, depth, tol_mm, scene=None):
         """verify on the step-by-step path: per pose render_window against the uploaded frame under the pose's own crop window,
-        through Engine.color_stats -- the records the one-call path gets from the library"""
+        through Engine.color_stats -- the records the one-call path gets from the library (scene: the frame-sized scene under the
+        same window)"""
         rgb_d = torch.from_numpy(np.ascontiguousarray(rgb, dtype=np.uint8)).to(self._dev)
         dep_d = torch.from_numpy(_depth_u16(depth, rgb)).to(self._dev)
-        model, observed = [], []
+        if scene is not None and not torch.is_tensor(scene):
+            scene = torch.from_numpy(np.ascontiguousarray(scene, dtype=np.uint16).view(np.int16)).to(self._dev)
+        model, observed, hiding = [], [], []
         for pose in poses:
             rgbA, depA = self.render_window(pose)
             model.append(dict(rgb=torch.from_numpy(np.ascontiguousarray(rgbA, dtype=np.uint8)).to(self._dev),
                               depth=torch.from_numpy(np.ascontiguousarray(depA).astype(np.uint16).view(np.int16)).to(self._dev)))
             bb = U.compute_bbox(pose, self.K, self.object_width, scale=(1000, 1000, 1000))
             observed.append(dict(rgb=rgb_d, depth=dep_d, window=U.crop_window(bb)))
-        return self.engine.color_stats(model, observed, tol_mm)
+            hiding.append(dict(depth=scene, window=U.crop_window(bb)))
+        return self.engine.color_stats(model, observed, tol_mm, scene=None if scene is None else hiding)
 
-    def _choose_by_colour(self, info, final, final_fit, rgb, dep, tol_mm, within, min_px=64):
+    def _choose_by_colour(self, info, final, final_fit, rgb, dep, tol_mm, within, min_px=64, scene=None):
         """colour=True of acquire / recover: D = the depth winner (info['chosen']); the candidates are the pool members whose
         inlier_pts reach `within` times D's -- colour never buys a pose the depth frame does not support; among them the highest
         verify score wins, a tie goes to the larger depth key, and if every candidate scores 0, D stays.  `dep` is the uint16 frame
-        the depth stages of the caller read.  Updates info; returns the chosen index."""
+        the depth stages of the caller read; scene: verify's (MultiTracker.recover: the kept scene of its search).  Updates info;
+        returns the chosen index."""
         from ._lib import COLOR_FIT_DTYPE
         from .recover import pose_key
         d = int(info["chosen"])
@@ -329,7 +339,8 @@ class Tracker:
         mb = self.engine.max_batch
         for i0 in range(0, len(cand), mb):   # (a pool of 3 x top poses may exceed the engine's batch)
             part = cand[i0:i0 + mb]
-            _, col, sc = self.verify(final[part], rgb, dep, tol_mm, min_px)
+            _, col, sc = self.verify(final[part], rgb, dep, tol_mm, min_px) if scene is None else \
+                self.verify(final[part], rgb, dep, tol_mm, min_px, scene=scene)
             color[part], score[part] = col, sc
         chosen = d
         if np.any(score[cand] != 0.0):
@@ -879,8 +890,25 @@ class MultiTracker:
         res = (out[0].cpu().numpy(), out[1].cpu().numpy().view(SCENE_ALIGN_REC_DTYPE).reshape(-1))
         return res + tuple(x.cpu().numpy() for x in out[2:])
 
+    def verify(self, i, poses, rgb, depth, occ_poses, occluders=None, tol_mm=10, min_px=64):
+        """Extension: which of these hypotheses of object i ([k,4,4]) does the frame confirm by colour, AMONG the other objects.
+        The occluders (indices; default: every other object) are rendered at occ_poses ([len(occluders),4,4], in that order) and
+        composed into a scene frame on the device (Engine.scene_fit(..., scene=True) on the uploaded depth frame, tol_mm as its
+        tolerance); then trackers[i].verify(scene=...) runs: a pixel with a tracked surface at or in front of the model's is
+        hidden_px and its colours are not compared.  rgb HxWx3 uint8, depth HxW uint16 mm (host arrays).  Returns (fit [k] of
+        _lib.SCENE_CROP_FIT_DTYPE, color [k], score [k]) as Tracker.verify."""
+        i = int(i)
+        occ = [j for j in range(self.n) if j != i] if occluders is None else [int(j) for j in occluders]
+        if not 0 <= i < self.n or any(j < 0 or j >= self.n or j == i for j in occ) or not occ:
+            raise ValueError("MultiTracker.verify: object %d among occluders %s of %d objects" % (i, occ, self.n))
+        dep = np.ascontiguousarray(depth, dtype=np.uint16)
+        dep_d = torch.from_numpy(dep.view(np.int16)).to(self._dev)
+        occ_objs = (type(self._objs[0]) * len(occ))(*[self._objs[j] for j in occ])
+        _, _, scene = self.engine.scene_fit(occ_objs, occ_poses, dep_d, self.K, tol_mm=tol_mm, scene=True)
+        return self.trackers[i].verify(poses, rgb, dep, tol_mm=tol_mm, min_px=min_px, scene=scene)
+
     def recover(self, prev_poses, rgb, depth, lost=None, lost_below=0.5, min_visible=0.2, trans_radius=0.05, trans_step=0.01,
-                rot_deg=(15.0,), tol_mm=10, top=None, refine=1, align=0, scene_align=False):
+                rot_deg=(15.0,), tol_mm=10, top=None, refine=1, align=0, scene_align=False, colour=False, colour_within=0.9, min_px=64):
         """Extension: re-acquire the lost objects of a frame AMONG the tracked ones.  Tracker.recover scores a candidate against the
         depth frame alone: it lays a lost model onto the visible face of a neighbour, and counts a tracked object in front of a
         candidate as an unknown obstacle.  Here the objects that are "tracked" explain their pixels (the rule of
@@ -900,7 +928,14 @@ class MultiTracker:
         align > 0): step (3) aligns the top nodes against the kept scene of step (2) (Engine.align_poses(scene=..., scene_tol_mm =
         tol_mm)): points hidden by a tracked object are not paired, so a neighbour's face or an object lying on the lost one no longer
         drags the hypotheses away; align_rec then has _lib.SCENE_ALIGN_REC_DTYPE (hidden_pts) and last_recover[i]["scene_align"]
-        says which rule ran (False on the no-occluder fallback).  A recovered object does NOT become an
+        says which rule ran (False on the no-occluder fallback).  colour=True (off by default, and then not one call more is made
+        and every bit is as before): after step (4) the choice goes through trackers[i]._choose_by_colour over the pool and its
+        scene-rule records, against the kept scene of step (2) -- D is the depth winner, the candidates are the pool members with
+        inlier_pts >= colour_within * inlier_pts[D], each verified under the scene-aware colour rule (Tracker.verify(scene=...): the
+        pixels a tracked object hides or claims are not compared), the highest score wins, a tie goes to the larger depth key, and
+        if every score is 0, D stays (with refine=0 and no alignment the pool is the ranked top of the lattice, as in
+        Tracker.recover).  last_recover[i] then also keeps depth_chosen, color_fit, color_score and candidates; on the no-occluder
+        fallback the switch is passed to trackers[i].recover.  A recovered object does NOT become an
         occluder for the next lost one within the same call: every search of a call sees the same occluders.
         Returns [n,4,4]: rows of objects that were not searched are prev_poses' rows.  last_recover: {i: dict} per searched object
         -- what Tracker.last_recover keeps (n, top_idx, top_fit, refined, final_fit, chosen, inlier_frac = inlier_pts / points;
@@ -927,7 +962,8 @@ class MultiTracker:
         if not occ:   # nothing explains anything: the single-object search
             for i in lost:
                 out[i] = self.trackers[i].recover(poses[i], rgb, dep, trans_radius=trans_radius, trans_step=trans_step, rot_deg=rot_deg,
-                                                  tol_mm=tol_mm, top=top, refine=refine, facing=True, align=align)
+                                                  tol_mm=tol_mm, top=top, refine=refine, facing=True, align=align,
+                                                  **(dict(colour=True, colour_within=colour_within) if colour else {}))
                 self.last_recover[i] = dict(self.trackers[i].last_recover, occluders=[], fallback=True, scene_align=False)
             return out
         occ_objs = (type(self._objs[0]) * len(occ))(*[self._objs[j] for j in occ])
@@ -950,7 +986,7 @@ class MultiTracker:
                     aligned, align_rec = t.engine.align_poses(handle, unrefined, dep, self.K, iters=int(align))
                 info.update(aligned=aligned, align_rec=align_rec)
             if int(refine) < 1 and aligned is None:
-                final, final_fit, chosen = unrefined, top_fit[:1].copy(), 0
+                final, final_fit, chosen = unrefined, (top_fit.copy() if colour else top_fit[:1].copy()), 0   # (colour: the pool is the ranked top)
             else:
                 refined = unrefined if aligned is None else aligned
                 for _ in range(int(refine)):
@@ -967,6 +1003,11 @@ class MultiTracker:
             shown = int(win["points"]) - int(win["hidden_pts"])
             info.update(final_fit=final_fit, chosen=chosen, inlier_frac=t._frac(win), hidden_pts=int(win["hidden_pts"]),
                         visible_frac=float(win["inlier_pts"]) / shown if shown > 0 else float("nan"))
+            if colour:
+                chosen = t._choose_by_colour(info, final, final_fit, rgb, dep, tol_mm, colour_within, min_px, scene=scene)
+                win = final_fit[chosen]
+                shown = int(win["points"]) - int(win["hidden_pts"])
+                info.update(hidden_pts=int(win["hidden_pts"]), visible_frac=float(win["inlier_pts"]) / shown if shown > 0 else float("nan"))
             self.last_recover[i] = info
             out[i] = final[chosen]
         return out

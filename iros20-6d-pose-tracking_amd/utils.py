@@ -449,35 +449,53 @@ def quaternion_matrix(quaternion):
                      [0.0, 0.0, 0.0, 1.0]])
 
 
-def fit_stats(model_depth_u16, observed_depth_u16, tol_mm):
+def _hidden_mask(model_depth, scene_depth, tol):
+    """the hidden verdict of the scene-aware crop rule (csrc/fit_rule.h: fit_hidden): valid(m) && valid(s) && s <= m + tol"""
+    m = np.asarray(model_depth).astype(np.int64)
+    s = np.asarray(scene_depth).astype(np.int64)
+    return (m > 100) & (m < 2000) & (s > 100) & (s < 2000) & (s <= m + tol)
+
+
+def fit_stats(model_depth_u16, observed_depth_u16, tol_mm, scene=None):
     """The fit record of se3tn_fit_stats (include/se3tracknet.h) in NumPy, for callers without a device image: model / observed
     depth crops in millimetres, [..., 176, 176] (any shape whose last two axes are the image) -> a structured array of shape [...]
-    with the fields of se3tn_fit.  valid(d) = 100 < d < 2000; seen_px == inlier_px + front_px + behind_px."""
-    from ._lib import FIT_DTYPE
+    with the fields of se3tn_fit.  valid(d) = 100 < d < 2000; seen_px == inlier_px + front_px + behind_px.
+    scene: the crop of the composed depth of the tracked objects at the same pixels, [..., 176, 176] -- the scene-aware rule of
+    se3tn_color_stats_scene: a pixel with valid(m) && valid(s) && s <= m + tol_mm is hidden; it enters model_px and hidden_px and
+    nothing else, every other pixel is classified as without a scene.  The record is then _lib.SCENE_CROP_FIT_DTYPE (hidden_px in
+    the place of _reserved); model_px == hidden_px + (the pixels classified as before)."""
+    from ._lib import FIT_DTYPE, SCENE_CROP_FIT_DTYPE
     m = np.asarray(model_depth_u16).astype(np.int64)
     o = np.asarray(observed_depth_u16).astype(np.int64)
     d, tol = o - m, int(tol_mm)
     model = (m > 100) & (m < 2000)
-    seen = model & (o > 100) & (o < 2000)
+    shown = model if scene is None else model & ~_hidden_mask(m, scene, tol)
+    seen = shown & (o > 100) & (o < 2000)
     inlier = seen & (np.abs(d) <= tol)
-    rec = np.zeros(m.shape[:-2], FIT_DTYPE)
+    rec = np.zeros(m.shape[:-2], FIT_DTYPE if scene is None else SCENE_CROP_FIT_DTYPE)
     for key, mask in (("model_px", model), ("seen_px", seen), ("inlier_px", inlier), ("front_px", seen & (d < -tol)),
                       ("behind_px", seen & (d > tol))):
         rec[key] = mask.sum(axis=(-2, -1))
     rec["sum_abs_mm"] = (np.abs(d) * inlier).sum(axis=(-2, -1))
     rec["tol_mm"] = tol
+    if scene is not None:
+        rec["hidden_px"] = (model & ~shown).sum(axis=(-2, -1))
     return rec
 
 
-def color_stats(model_rgb, model_depth, observed_rgb, observed_depth, tol_mm):
+def color_stats(model_rgb, model_depth, observed_rgb, observed_depth, tol_mm, scene=None):
     """The colour record of se3tn_color_stats (include/se3tracknet.h) in NumPy: model / observed crops, rgb uint8 [..., 176, 176, 3]
     and depth uint16 mm [..., 176, 176] -> a structured array of shape [...] with the fields of se3tn_color_fit.  A pixel is compared
-    exactly when it is an inlier of fit_stats: both depths valid (100 < d < 2000) and |o - m| <= tol_mm."""
+    exactly when it is an inlier of fit_stats: both depths valid (100 < d < 2000) and |o - m| <= tol_mm.
+    scene: as fit_stats' -- the pixels hidden by a tracked surface are not compared (se3tn_color_stats_scene)."""
     from ._lib import COLOR_FIT_DTYPE
     m = np.asarray(model_depth).astype(np.int64)
     o = np.asarray(observed_depth).astype(np.int64)
     tol = int(tol_mm)
-    cmp_ = ((m > 100) & (m < 2000) & (o > 100) & (o < 2000) & (np.abs(o - m) <= tol))[..., None]
+    cmp_ = (m > 100) & (m < 2000) & (o > 100) & (o < 2000) & (np.abs(o - m) <= tol)
+    if scene is not None:
+        cmp_ = cmp_ & ~_hidden_mask(m, scene, tol)
+    cmp_ = cmp_[..., None]
     mc = np.asarray(model_rgb).astype(np.int64) * cmp_
     oc = np.asarray(observed_rgb).astype(np.int64) * cmp_
     rec = np.zeros(m.shape[:-2], COLOR_FIT_DTYPE)

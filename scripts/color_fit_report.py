@@ -80,7 +80,7 @@ def kernel_from_trace(trace_dir):
     out = {}
     for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
         for r in csv.DictReader(open(path)):
-            if "color_fit_kernel" in r["Kernel_Name"] or "fit_stats_kernel<true>" in r["Kernel_Name"]:
+            if "color_fit_kernel" in r["Kernel_Name"] or "fit_stats_kernel<true>" in r["Kernel_Name"] or "fit_stats_kernel<true, false>" in r["Kernel_Name"]:
                 out.setdefault(int(r["Grid_Size_Y"]), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     return out
 
