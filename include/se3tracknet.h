@@ -996,7 +996,10 @@ int se3tn_pose_update_host(const double poseA[16], const float trans[3], const f
  * dims = {H, W, C} as stored (borders included).  A stage the last se3tn_infer (or se3tn_on_track_objects, or the graph it
  * replayed) did NOT write is refused with SE3TN_E_STATE instead of handing out an older call's data: "stem" after the batch 1-5
  * stem + pool kernel, "ab_t" / "head_t" / "head" after the fused Winograd blocks, "head" when the tail added the last head conv's
- * partial sums itself (see se3tn_keep_intermediates).  "inA" / "inB" are always handed out (se3tn_preprocess fills them too). */
+ * partial sums itself (see se3tn_keep_intermediates).  "inA" / "inB" are always handed out (se3tn_preprocess fills them too).
+ * After a call under SE3TN_PREC_F16X3 the words of "pool" "t64" "q64" "ab" "ab_t" "head_t" are split rows -- per pixel and per 32
+ * channels 32 f16 hi halves, then their 32 f16 lo halves, value = hi + lo -- and "inA" / "inB" hold 4 hi | 4 lo per pixel; "stem"
+ * and "head" are float32, and so is the "head_t" the fused head block stores on request (it keeps that map on chip as float32). */
 int se3tn_debug_buffer(se3tn_ctx* ctx, const char* name, const float** ptr, int32_t dims[3]);
 /* The fused Winograd blocks (batches of n >= the se3tn_set_winograd threshold) keep the activation between a
  * residual block's two convolutions in LDS and reduce the heads' last activation in registers: "ab_t", "head_t"

@@ -19,7 +19,10 @@ other pool pairs in every slot.  Per (configuration, n), on one live context per
   (e) the first occurrence of each pool pair against its float64 stage maps (test_gpu_routes' _close and scales), borders zero --
       with (d) that holds every pixel of every slot to float64;
   (f) se3tn_get_feature equals the interior of `ab`, transposed, bit for bit, for every slot.
-f16x3: logits, poses and `head` only (every other map holds split rows), and the range guard stays silent.
+f16x3 keeps `pool`, `t64`, `q64`, `ab`, `ab_t` and (conv by conv) `head_t` as split rows (f16 hi | f16 lo, tests/split_rows.py).  (d) compares their raw
+words like any other map; (e) decodes the first occurrence of each pool pair and holds it to the same float64 maps with the same
+bounds, its raw border words zero bits, and every stored (hi, lo) pair of every slot must be one a split store writes; (f) holds the
+library's decode (se3tn_get_feature) to the test's decode of `ab`; and the range guard stays silent.
 check_every_slot_of_a_call holds the checks; tests/test_gpu_largest_batch.py runs it at 541 .. 1982 pairs on contexts of that size."""
 import time
 
@@ -31,6 +34,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import fixtures as Fx
 from oracle import se3_oracle as O
+import split_rows as SR
 import test_batch_position_plan as PLAN
 import test_gpu_routes as RT
 
@@ -124,8 +128,7 @@ def _call(se3, eng, buf, ref, idx, poses):
     eng.infer(buf.A, buf.B, n, se3.NCHW, buf.trans, buf.rot, buf.pA, buf.pB)
 
 
-def _words(t):
-    return t.contiguous().view(torch.int32)
+_words = RT._words
 
 
 def check_every_slot_of_a_call(se3, ref, live, cfg, n, worst, seconds, chunk=None):
@@ -182,7 +185,7 @@ def check_every_slot_of_a_call(se3, ref, live, cfg, n, worst, seconds, chunk=Non
         assert d < 1e-12, "%s slot %d: |d pose| vs processPredict of the device's own trans / rot %.3e" % (tag, j, d)
         assert (poseB[j, 3] == np.array([0, 0, 0, 1.0])).all(), (tag, j)
 
-    # (d) bit identity across the slots that hold the same pool pair (f16x3: `head` and the logits)
+    # (d) bit identity across the slots that hold the same pool pair (f16x3: the split rows as they are stored, raw)
     first = {}
     for j, k in enumerate(idx.tolist()):
         first.setdefault(k, j)
@@ -190,7 +193,7 @@ def check_every_slot_of_a_call(se3, ref, live, cfg, n, worst, seconds, chunk=Non
     assert len(first) == min(n, PLAN.POOL)
     assert torch.equal(_words(lg_d), _words(lg_d[src])), "%s: logits differ between slots of one pool pair: slots %s" % (
         tag, (_words(lg_d) != _words(lg_d[src])).any(1).nonzero().flatten().tolist())
-    checked = {s: t for s, t in maps.items() if t is not None and (not rec["f16"] or s == "head")}
+    checked = {s: t for s, t in maps.items() if t is not None}
     for s, t in checked.items():
         bad = []
         for lo, hi in spans:    # whole maps, borders included: every word of every slot
@@ -199,20 +202,26 @@ def check_every_slot_of_a_call(se3, ref, live, cfg, n, worst, seconds, chunk=Non
         assert not bad, "%s %s: slots %s differ from the first slot of their pool pair (%s)" % (
             tag, s, bad[:16], [(j, int(src[j])) for j in bad[:4]])
 
-    # (e) the first occurrence of each pool pair against float64, borders zero
+    # (e) the first occurrence of each pool pair against float64, borders zero (f16x3: that one slot of a split map decoded, at most
+    # 12 slots per map; the raw split rows of ALL slots checked span by span)
     sc = lambda keys: max(RT.STAGE_SCALE[want_r[k].replace(" block", "")] for k in keys)
     sc_trunk, sc_all = sc(("trunk1", "trunk2", "trunk3", "trunk4")), sc([k for k, _ in RT.LAYERS])
+    split = RT.split_stages(rec, want_r)
     for s, t in checked.items():
+        if s in split:
+            for lo, hi in spans:
+                RT._check_split_map("%s %s slots %d..%d" % (tag, s, lo, hi - 1), t[lo:hi])
         for k, j in first.items():
-            got = RT._nchw(t[j:j + 1], 0 if s == "stem" else 1)
+            got = RT._nchw(RT._stage_values(split, s, t[j:j + 1]), 0 if s == "stem" else 1)
             RT._close("%s %s slot %d (pool pair %d)" % (tag, s, j, k), got, ref["stages"][s][k:k + 1], RT.ACT_RTOL,
                       1e-5 if s in ("stem", "pool") else 0, sc_trunk if s in ("stem", "pool", "t64", "q64") else sc_all)
 
-    # (f) se3tn_get_feature: the interior of `ab`, transposed
-    if not rec["f16"]:
-        feat = eng.feature(n)
-        assert torch.equal(_words(feat), _words(maps["ab"][:, 1:-1, 1:-1, :].permute(0, 3, 1, 2))), tag
-    else:
+    # (f) se3tn_get_feature: the interior of `ab`, transposed (f16x3: the library's decode kernel against the test's, span by span)
+    feat = eng.feature(n)
+    for lo, hi in spans:
+        ab = RT._stage_values(split, "ab", maps["ab"][lo:hi])
+        assert torch.equal(_words(feat[lo:hi]), _words(ab[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2))), (tag, lo)
+    if rec["f16"]:
         assert not eng.overflow(), tag
     torch.cuda.synchronize()
     seconds[(cfg, n)] = time.time() - t_start

@@ -87,6 +87,57 @@ def test_preprocess_odd_frame_and_all_invalid_depth(se3):
         assert np.allclose(got[3], (2000.0 - mean[7]) / std[7])
 
 
+def test_preprocess_into_the_contexts_buffers_in_f16x3_is_the_split_of_the_float32_pixels(se3):
+    """se3tn_preprocess into se3tn_input_buffer (the zero-bordered [n,182,182,4] buffers the stem reads): under SE3TN_PREC_F32 the
+    float32 pixels, bit-exact against the oracle; under SE3TN_PREC_F16X3 the same pixels as 4 f16 hi | 4 f16 lo (split_pixel,
+    csrc/kernels_misc.hip) -- decoded, they must equal the split (tests/split_rows.py encode_pixels) of the float32 ones bit for bit.
+    Three crops: a window inside the frame, one leaving it (zero padding before normalisation), one with all-invalid depth (2000 ->
+    (2000 - mean) / std splits like any other value)."""
+    import split_rows as SR
+    rng = np.random.default_rng(12)
+    H, W = 480, 640
+    rgb = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    depth = rng.integers(0, 2500, (H, W)).astype(np.uint16)
+    mean, std = Fx.mean_std(3)
+    eng = se3.Engine(0, 3)
+    try:
+        eng.load_state_dict(O.make_state_dict(0))
+        eng.set_normalization(mean, std)
+        specs = [(depth, (213, 48, 546, 381), 812.5, 0), (depth, (-120, -90, 200, 230), -640.25, 1),
+                 (np.zeros((H, W), np.uint16), (300, 200, 476, 376), 700.0, 1)]
+        rgb_d = torch.from_numpy(rgb).cuda()
+        crops = [dict(rgb=rgb_d, depth=torch.from_numpy(d.view(np.int16)).cuda(), window=w, z_offset_mm=z, stats=st) for d, w, z, st in specs]
+        words = lambda t: t.contiguous().view(torch.int32)
+        for which, name in ((0, "inA"), (1, "inB")):
+            eng.set_precision(se3._lib.PREC_F32)
+            eng.preprocess(crops, eng.input_buffer_ptr(which))
+            f32 = eng.debug_buffer(name, 3).cpu()
+            assert tuple(f32.shape) == (3, 182, 182, 4)
+            for i, (d, w, z, st) in enumerate(specs):
+                want = _oracle_crop(rgb, d, w, z, mean, std, st)
+                assert (f32[i, 3:-3, 3:-3].permute(2, 0, 1).numpy() == want).all(), (name, i)
+            v = np.float32((2000.0 - mean[7]) / std[7])
+            assert (f32[2, 3:-3, 3:-3, 3].numpy() == v).all()
+            border = f32.clone(); border[:, 3:-3, 3:-3] = 0
+            assert not bool(words(border).any()), name
+            eng.set_precision(se3._lib.PREC_F16X3)
+            eng.preprocess(crops, eng.input_buffer_ptr(which))
+            assert not eng.overflow()
+            f16 = eng.debug_buffer(name, 3).cpu()
+            assert SR.well_formed(f16, pixels=True), name
+            want = SR.decode_pixels(torch.from_numpy(SR.encode_pixels(f32.numpy())))
+            got = SR.decode_pixels(f16)
+            assert torch.equal(words(got), words(want)), (name, int((words(got) != words(want)).any(-1).sum()))
+            border = f16.clone(); border[:, 3:-3, 3:-3] = 0
+            assert not bool(words(border).any()), name
+            # the all-invalid depth value: one pair of halves everywhere, the split of the float32 value
+            hi, lo = SR.split(np.array([v], np.float32))
+            dh, dl = SR.pixel_halves(f16[2:3, 3:-3, 3:-3].contiguous())
+            assert (dh[..., 3].numpy() == hi[0]).all() and (dl[..., 3].numpy() == lo[0]).all() and lo[0] != 0, (name, hi, lo)
+    finally:
+        eng.close()
+
+
 def test_more_crops_than_one_launch_holds(se3):
     """se3tn_preprocess chunks the descriptors into kernel-argument blocks of 64 (CropArgs::MAX)."""
     rng = np.random.default_rng(2)
